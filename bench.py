@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- rays/s of the fused render hot path at BASELINE.json's configuration.
 
-    python bench.py --gpus N --steps K --warmup W                 (driver contract; --precision fp32 | bf16x3, --workload c2 | c3)
+    python bench.py --gpus N --steps K --warmup W                 (driver contract; --precision fp32 | bf16x3, --workload c2 | c3,
+                                                                   --dump-outputs DIR: the timed path's last outputs as .npy files)
     (N > 1: one rank per GPU, either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` or --
      when WORLD_SIZE is not set -- by bench.py itself, which starts exactly that command as a child and relays rank 0's line)
 
@@ -80,6 +81,23 @@ def emit(obj):
     out = _JSON_OUT if _JSON_OUT is not None else sys.stdout
     out.write(json.dumps(obj) + "\n")
     out.flush()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step, one DIR/<name>.npy each, float32 (whole
+    arrays: the workloads' outputs are far below DUMP_MAX_BYTES).  The inputs are seeded, so two builds run with the same arguments can be
+    compared array for array."""
+    host = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    log(f"outputs of the last timed step -> {dirname}: " + ", ".join(f"{k} {tuple(a.shape)}" for k, a in host.items()))
 
 
 def self_launch(n_gpus):
@@ -206,9 +224,10 @@ def roofline(precision, kern_ms, which):
                     + ") / kernel time from device events; bf16x3 issues 3x that on the bf16 MFMA pipe (mfma_pipe_frac)"}
 
 
-def c3_leg(model, dev, rank, world, dist, clock, n_it, warm=True):
+def c3_leg(model, dev, rank, world, dist, clock, n_it, warm=True, warm_iters=2, outputs=None):
     """BASELINE config 3: 64 objects x 4096 x 64, object-sharded (driver.shard_slice), every rank optimises its slice in one launch per
-    iteration, then ONE all_gather of the metric rows (the only collective).  Returns (seconds for n_it iterations [max over ranks], rows)."""
+    iteration, then ONE all_gather of the metric rows (the only collective).  Returns (seconds for n_it iterations [max over ranks], rows).
+    ``outputs`` (optional dict) receives this rank's shape codes, texture codes and poses as optimize_objects_batched returned them."""
     from supnerf_amd import driver as D
     hp = D.load_hpams()
     hp["render_im_sz"] = IM_SZ
@@ -217,8 +236,8 @@ def c3_leg(model, dev, rank, world, dist, clock, n_it, warm=True):
     gl = torch.Generator().manual_seed(3)
     sc_all, tc_all = torch.randn(C3_OBJECTS, 256, generator=gl) * 0.3, torch.randn(C3_OBJECTS, 256, generator=gl) * 0.3
     sc_l, tc_l = sc_all[mine], tc_all[mine]
-    if warm and objs:
-        hp["optimize"]["num_opts"] = 2
+    if warm and warm_iters > 0 and objs:
+        hp["optimize"]["num_opts"] = warm_iters
         D.optimize_objects_batched(model, dev, objs[:2], hp, sc_l[:2], tc_l[:2], mine[:2], reg_iters=-1)
     hp["optimize"]["num_opts"] = n_it
     clock.barrier()
@@ -227,8 +246,10 @@ def c3_leg(model, dev, rank, world, dist, clock, n_it, warm=True):
         # reg_iters = -1: EVERY timed iteration is a full optimisation iteration (forward + backward + depth render + AdamW).  The loop's
         # first reg_iters + 1 iterations are render-only in the reference (src/optimizer_nuscenes.py:684-689,768-769) and since round 4 skip
         # the backward whose gradients the reference clears unread -- with the default reg_iters = 3 half of an 8-iteration leg would be cheap
-        m, *_ = D.optimize_objects_batched(model, dev, objs, hp, sc_l, tc_l, mine, reg_iters=-1)
+        m, sc_o, tc_o, pose_o = D.optimize_objects_batched(model, dev, objs, hp, sc_l, tc_l, mine, reg_iters=-1)
         local = m.reshape(len(objs), -1)
+        if outputs is not None:
+            outputs.update(shape_codes=sc_o, texture_codes=tc_o, poses=pose_o)
     else:
         local = torch.zeros(0, n_it * 4, device=dev)
     rows = D.gather_metric_rows(local.to(dev), torch.tensor(mine, device=dev, dtype=torch.float32), C3_OBJECTS)
@@ -256,7 +277,13 @@ def main():
     ap.add_argument("--workload", default="c2", choices=["c2", "c3"],
                     help="c2: fused forward of one object per GPU (BASELINE configs[1], weak scaling); c3: the optimise iteration over 64 objects "
                          "sharded across the GPUs (BASELINE configs[2], strong scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; rank 0): "
+                         "c2 -> rgb, depth, acc of the fused forward; c3 -> the all-gathered metric rows and rank 0's shape codes, texture "
+                         "codes and poses")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))            # (before anything touches the GPU: the ranks are fresh child processes)
     claim_stdout()
@@ -290,10 +317,13 @@ def main():
 
     if args.workload == "c3":
         model.precision = prec
-        n_it = max(2, min(args.steps, 8))
-        dt, rows, n_mine = c3_leg(model, dev, rank, world, dist, clock, n_it)
+        n_it = args.steps
+        c3_out = {}
+        dt, rows, n_mine = c3_leg(model, dev, rank, world, dist, clock, n_it, warm_iters=args.warmup, outputs=c3_out)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dict(metric_rows=rows, **c3_out))
         res = {"metric": "rays/sec, optimise iteration (fwd + bwd + depth render + AdamW) over 64 objects x 4096 rays x 64 samples, object-sharded",
-               "value": C3_OBJECTS * N_RAYS * n_it / dt, "unit": "rays/s", "n_gpus": world, "steps": n_it, "warmup": 2, "ms_per_step": dt / n_it * 1e3,
+               "value": C3_OBJECTS * N_RAYS * n_it / dt, "unit": "rays/s", "n_gpus": world, "steps": n_it, "warmup": args.warmup, "ms_per_step": dt / n_it * 1e3,
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": DTYPE[prec], "data": "synthetic",
                "config": {"workload": "BASELINE configs[2]: 64 synthetic nuScenes-like cars, 4096 rays x 64 samples each, contiguous object shards "
                                       "(driver.shard_slice), one launch per iteration and rank, one all_gather of the metric rows at the end",
@@ -327,6 +357,9 @@ def main():
     log(f"headline: {args.steps} fused forwards, {prec}")
     # ---- headline: the contract's wall clock around EXACTLY --steps launches, in the reference's arithmetic unless asked otherwise
     elapsed = clock.wall(lambda: step(prec), args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        rgb, depth, acc = outs[prec][:3]
+        dump_outputs(args.dump_outputs, dict(rgb=rgb, depth=depth, acc=acc))
     value = world * N_RAYS * args.steps / elapsed
     ranks = clock.rank_records(rank, N_RAYS * args.steps / clock.last_local)
     kern_ms = clock.events(lambda: step(prec), args.steps)

@@ -3,10 +3,10 @@ edited line -- src/optimizer_nuscenes.py:14-21 (``from utils import render_rays_
 (``SUPNeRF(**hpams['net_hyperparams'])``), :1796 (strict ``load_state_dict``), :603,617 (``encode_img``), :526 (``pose_update``),
 src/trainer_unified_nuscenes.py:227-229 (``nn.DataParallel``).
 
-Two module trees are used: the REAL reference (build container only: ``/root/reference`` with inert stand-ins for the absent ``cv2`` and
-``torchvision``, in a child interpreter so that the test session's ``sys.modules`` stay clean), and a stand-in tree written by the test
-itself (travels to the GPU box, where the reference does not exist): files named like the reference's, with the same public names and
-layer names but trivially small bodies -- enough to be recognised and rebound, nothing of the reference's text.
+The callers are a stand-in tree written by the test itself: files named like the reference's, with the same public names and layer names
+but trivially small bodies -- enough to be recognised and rebound, nothing of the reference's text.  What the reference's own classes build
+is pinned by the fixture ``tests/golden/supnerf_layout.json`` (recorded from the reference by ``tests/golden/gen_golden_install.py``): its
+nuScenes ``net_hyperparams`` and every state-dict entry of the ``SUPNeRF`` they make, which the stand-in encoder reproduces entry for entry.
 """
 import json
 import os
@@ -18,7 +18,6 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 # ---------------------------------------------------------------------------------------------------------------- stand-in tree
 STANDIN_MODEL = '''
@@ -245,103 +244,103 @@ def test_launcher_runs_an_unmodified_script(tmp_path):
     assert rec == {"argv": ["--gpu", "0"], "main": "__main__", "v2": True, "cls": True, "prec": "fp32", "gpu_touched": False}
 
 
-# ---------------------------------------------------------------------------------------------------------------- the real reference
-REAL_REFERENCE_CHILD = r'''
-import os, sys, types, json
-import torch, torch.nn as nn, torch.nn.functional as F
-sys.path.insert(0, sys.argv[1])                                   # this repository
-REF = "/root/reference"
-# inert stand-ins for the two packages the image lacks (SURVEY 8c; an ordinary ModuleNotFoundError otherwise)
-cv2 = types.ModuleType("cv2"); sys.modules["cv2"] = cv2
-tv = types.ModuleType("torchvision"); tvt = types.ModuleType("torchvision.transforms")
-tvm = types.ModuleType("torchvision.models"); tvr = types.ModuleType("torchvision.models.resnet")
-class Resize:
-    def __init__(self, size): self.size = size
-    def __call__(self, x): return F.interpolate(x, size=self.size, mode="bilinear", align_corners=False)
-def conv3x3(i, o, stride=1, groups=1, dilation=1): return nn.Conv2d(i, o, 3, stride, dilation, groups=groups, bias=False, dilation=dilation)
-def conv1x1(i, o, stride=1): return nn.Conv2d(i, o, 1, stride, bias=False)
-class BasicBlock(nn.Module):                                       # torchvision's residual block (public API), for ImgEncoder(BasicBlock, ...)
-    expansion = 1
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1, norm_layer=None):
+# ---------------------------------------------------------------------------------------------------------------- the reference's layout
+# fixture supnerf_layout.json (tests/golden/gen_golden_install.py): the reference's nuScenes net_hyperparams and every state-dict entry of
+# the SUPNeRF they build.  The stand-in encoder below carries exactly the recorded img_encoder.* entries, so a checkpoint of the recorded
+# layout loads strictly into the stand-in caller's class, the installed class and the package's own SUPNeRF.
+LAYOUT = os.path.join(ROOT, "tests", "golden", "supnerf_layout.json")
+STANDIN_LAYOUT_ENCODER = '''
+import json as _json
+import torch.nn.functional as _F
+_ENC = [e for e in _json.load(open(LAYOUT_PATH))["state_dict"] if e[0].startswith("img_encoder.")]
+class ImgEncoder(nn.Module):                      # the recorded encoder's entries; a forward through its four heads only
+    def __init__(self, block, layers, num_classes=128, norm_layer=None, pred_wlh=False):
         super().__init__()
-        norm_layer = norm_layer or nn.BatchNorm2d
-        self.conv1, self.bn1 = conv3x3(inplanes, planes, stride), norm_layer(planes)
-        self.relu = nn.ReLU(inplace=True)
-        self.conv2, self.bn2 = conv3x3(planes, planes), norm_layer(planes)
-        self.downsample, self.stride = downsample, stride
-    def forward(self, x):
-        idt = x if self.downsample is None else self.downsample(x)
-        return self.relu(self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x))))) + idt)
-class Bottleneck(BasicBlock):
-    expansion = 4
-tvt.Resize = Resize; tvr.BasicBlock, tvr.Bottleneck, tvr.conv1x1, tvr.conv3x3 = BasicBlock, Bottleneck, conv1x1, conv3x3
-tv.transforms, tv.models, tvm.resnet = tvt, tvm, tvr
-sys.modules.update({"torchvision": tv, "torchvision.transforms": tvt, "torchvision.models": tvm, "torchvision.models.resnet": tvr})
-sys.path.insert(0, os.path.join(REF, "src"))                      # optimize_nuscenes.py:1-3
-
-import supnerf_amd as A
-out = {}
-# (1) the caller's modules imported FIRST, like a script that imports supnerf_amd late
-import utils as RU, model_supnerf as MS, model_codenerf as MC, renderer as RR
-orig_v2, orig_cls = RU.render_rays_v2, MS.SUPNeRF
-hp = json.load(open(os.path.join(REF, "jsonfiles", "supnerf.nusc.vehicle.car.json")))
-torch.manual_seed(0)
-saved = {"model_params": orig_cls(**hp["net_hyperparams"]).state_dict()}          # what save_models writes
-rep = A.install()
-out["patched"] = rep["patched"]
-out["v2_is_ours"] = RU.render_rays_v2 is A.utils.render_rays_v2
-out["others"] = all(getattr(RU, n) is getattr(A.utils, n) for n in ("render_rays", "render_rays_specified", "render_full_img",
-                    "render_virtual_imgs", "prepare_pixel_samples", "volume_rendering_batch", "volume_rendering2"))
-out["renderer"] = RR.NeRFRenderer is A.renderer.NeRFRenderer and RR.render_rays_v3 is A.renderer.render_rays_v3 and RR.volume_rendering3 is A.renderer.volume_rendering3
-model = MS.SUPNeRF(**hp["net_hyperparams"])                          # src/optimizer_nuscenes.py:1785
-missing = model.load_state_dict(saved["model_params"])               # :1796, strict
-out["strict_ok"] = True
-out["n_keys"] = len(saved["model_params"]); out["enc_keys"] = sum(k.startswith("img_encoder.") for k in saved["model_params"])
-out["pose_keys"] = sum(k.startswith(("pose_layer_", "regress_layer_", "out_delta_layer")) for k in saved["model_params"])
-out["is_hip"] = isinstance(model, A.model._DecoderBase) and isinstance(model, orig_cls)
-out["encoder_cls"] = type(model.img_encoder).__module__ + "." + type(model.img_encoder).__name__
-model.eval()
-with torch.no_grad():
-    f = model.encode_img(torch.zeros(1, 3, 64, 64))                   # :603,617
-    out["encode_img"] = [None if t is None else list(t.shape) for t in f]
-    out["pose_update"] = list(model.pose_update(f[2], torch.zeros(1, 16)).shape)     # :526
-try:
-    model(torch.zeros(4, 2, 3), torch.zeros(4, 2, 3), torch.zeros(1, 256), torch.zeros(1, 256))
-    out["cpu_forward"] = "ran"
-except A.SnrError:
-    out["cpu_forward"] = "SnrError"
-# supnerf_amd.SUPNeRF itself resolves the caller's encoder and loads the same checkpoint strictly
-m2 = A.SUPNeRF(**hp["net_hyperparams"]); m2.load_state_dict(saved["model_params"])
-out["pkg_encoder_cls"] = type(m2.img_encoder).__module__ + "." + type(m2.img_encoder).__name__
-out["codenerf"] = issubclass(MC.CodeNeRF, A.model._DecoderBase)
-# nn.DataParallel wraps it like src/trainer_unified_nuscenes.py:227-229 (no GPU here: construction + state-dict only)
-out["dp_keys_equal"] = set(k[len("module."):] for k in nn.DataParallel(model).state_dict()) == set(saved["model_params"])
-A.uninstall()
-out["restored"] = RU.render_rays_v2 is orig_v2 and MS.SUPNeRF is orig_cls
-# (2) a module imported AFTER install() goes through the hook
-for n in ("utils", "renderer", "model_supnerf", "model_codenerf"):
-    sys.modules.pop(n, None)
-A.install()
-import utils as RU2
-from model_supnerf import SUPNeRF as S2
-out["hook"] = RU2.render_rays_v2 is A.utils.render_rays_v2 and issubclass(S2, A.model._DecoderBase) and RU2 is not RU
-print("RESULT " + json.dumps(out))
+        self.pred_wlh = pred_wlh
+        for name, shape, dtype, kind in _ENC:
+            *path, leaf = name[len("img_encoder."):].split(".")
+            mod = self
+            for p in path:
+                if p not in mod._modules:
+                    mod.add_module(p, nn.Module())
+                mod = mod._modules[p]
+            t = torch.randn(shape) * 0.01 if dtype == "float32" else torch.zeros(shape, dtype=getattr(torch, dtype))
+            if kind == "parameter":
+                mod.register_parameter(leaf, nn.Parameter(t))
+            else:
+                mod.register_buffer(leaf, t)
+    def forward(self, x, pose_shortcut=False):
+        head = lambda m, f: _F.linear(_F.pad(f, (0, m.weight.shape[1] - f.shape[1])), m.weight, m.bias)
+        f = x.mean((2, 3))
+        pose = head(self.fc_pose, f)
+        return head(self.fc_shape, f), head(self.fc_texture, f), pose, head(self.fc_uv, pose)
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference exists in the build container only")
-def test_real_reference_callers_run_with_zero_edits():
-    """Against the reference itself: install(), ``SUPNeRF(**hpams['net_hyperparams'])`` from its own json, strict load of a state-dict made
-    by ITS class (img_encoder.*, pose_layer_*, regress_layer_* keys), ``encode_img`` / ``pose_update`` through its stock modules."""
-    out = subprocess.run([sys.executable, "-c", REAL_REFERENCE_CHILD, ROOT], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
-    assert set(rec["patched"]) == {"utils", "renderer", "model_supnerf", "model_codenerf"}, rec
-    assert rec["v2_is_ours"] and rec["others"] and rec["renderer"] and rec["strict_ok"] and rec["is_hip"], rec
-    assert rec["enc_keys"] > 100 and rec["pose_keys"] >= 14 and rec["n_keys"] > rec["enc_keys"] + rec["pose_keys"], rec
-    assert rec["encoder_cls"] == "model_supnerf.ImgEncoder" and rec["pkg_encoder_cls"] == "model_supnerf.ImgEncoder", rec
-    assert rec["encode_img"][0] == [1, 256] and rec["encode_img"][4] is None and rec["pose_update"] == [1, 6], rec
-    assert rec["cpu_forward"] == "SnrError" and rec["codenerf"] and rec["dp_keys_equal"] and rec["restored"] and rec["hook"], rec
+def _checkpoint_of_the_recorded_layout(layout):
+    """What the reference's ``save_models`` writes for ``SUPNeRF(**net_hyperparams)``: every recorded entry, recorded shape and dtype."""
+    g = torch.Generator().manual_seed(5)
+    sd = {k: (torch.randn(shape, generator=g) * 0.05 if dtype == "float32" else torch.zeros(shape, dtype=getattr(torch, dtype)))
+          for k, shape, dtype, _ in layout["state_dict"]}
+    return {"model_params": sd}
+
+
+def test_reference_layout_callers_run_with_zero_edits(standin_tree):
+    """With the reference's own recorded configuration and checkpoint layout: install(), ``SUPNeRF(**hpams['net_hyperparams'])`` from its
+    nuScenes json, strict load of a state-dict of ITS layout (img_encoder.*, pose_layer_*, regress_layer_* keys) into the installed class and
+    into the package's own SUPNeRF, ``encode_img`` / ``pose_update`` through the caller's modules, and the import hook."""
+    import supnerf_amd as A
+    layout = json.load(open(LAYOUT))
+    hp = {"net_hyperparams": layout["net_hyperparams"]}
+    with open(os.path.join(standin_tree, "model_supnerf.py"), "w") as f:
+        f.write(STANDIN_MODEL + STANDIN_LAYOUT_ENCODER.replace("LAYOUT_PATH", repr(LAYOUT)))
+    saved = _checkpoint_of_the_recorded_layout(layout)
+    sd = saved["model_params"]
+    enc_keys = sum(k.startswith("img_encoder.") for k in sd)
+    pose_keys = sum(k.startswith(("pose_layer_", "regress_layer_", "out_delta_layer")) for k in sd)
+    assert enc_keys > 100 and pose_keys >= 14 and len(sd) > enc_keys + pose_keys
+    # (1) the caller's modules imported FIRST, like a script that imports supnerf_amd late
+    import utils as RU
+    import model_supnerf as MS
+    import model_codenerf as MC
+    import renderer as RR
+    orig_v2, orig_cls = RU.render_rays_v2, MS.SUPNeRF
+    orig_cls(**hp["net_hyperparams"]).load_state_dict(sd)          # strict: the stand-in caller builds exactly the recorded layout
+    rep = A.install()
+    assert set(rep["patched"]) == {"utils", "renderer", "model_supnerf", "model_codenerf"}, rep
+    assert RU.render_rays_v2 is A.utils.render_rays_v2
+    assert all(getattr(RU, n) is getattr(A.utils, n) for n in ("render_rays", "render_rays_specified", "render_full_img", "render_virtual_imgs",
+                                                                "prepare_pixel_samples", "volume_rendering_batch", "volume_rendering2"))
+    assert RR.NeRFRenderer is A.renderer.NeRFRenderer and RR.render_rays_v3 is A.renderer.render_rays_v3
+    assert RR.volume_rendering3 is A.renderer.volume_rendering3
+    model = MS.SUPNeRF(**hp["net_hyperparams"])                      # src/optimizer_nuscenes.py:1785
+    model.load_state_dict(sd)                                          # :1796, strict
+    assert isinstance(model, A.model._DecoderBase) and isinstance(model, orig_cls)
+    assert type(model.img_encoder).__module__ + "." + type(model.img_encoder).__name__ == "model_supnerf.ImgEncoder"
+    model.eval()
+    with torch.no_grad():
+        feats = model.encode_img(torch.zeros(*layout["encode_img_input"]))          # :603,617
+        assert [None if t is None else list(t.shape) for t in feats] == layout["encode_img_shapes"]
+        assert list(model.pose_update(feats[2], torch.zeros(1, 16)).shape) == layout["pose_update_shape"]      # :526
+    with pytest.raises(A.SnrError):                                    # the HIP forward: CPU tensors fail loudly
+        model(torch.zeros(4, 2, 3), torch.zeros(4, 2, 3), torch.zeros(1, 256), torch.zeros(1, 256))
+    # supnerf_amd.SUPNeRF itself resolves the caller's encoder and has the reference's layout entry for entry
+    m2 = A.SUPNeRF(**hp["net_hyperparams"])
+    m2.load_state_dict(sd)
+    assert type(m2.img_encoder) is MS.ImgEncoder
+    assert {k: list(v.shape) for k, v in m2.state_dict().items()} == {k: shape for k, shape, _, _ in layout["state_dict"]}
+    assert issubclass(MC.CodeNeRF, A.model._DecoderBase)
+    # nn.DataParallel wraps it like src/trainer_unified_nuscenes.py:227-229 (construction + state-dict only)
+    assert set(k[len("module."):] for k in torch.nn.DataParallel(model).state_dict()) == set(sd)
+    A.uninstall()
+    assert RU.render_rays_v2 is orig_v2 and MS.SUPNeRF is orig_cls
+    # (2) a module imported AFTER install() goes through the hook
+    for n in ("utils", "renderer", "model_supnerf", "model_codenerf"):
+        sys.modules.pop(n, None)
+    A.install()
+    import utils as RU2
+    from model_supnerf import SUPNeRF as S2
+    assert RU2.render_rays_v2 is A.utils.render_rays_v2 and issubclass(S2, A.model._DecoderBase) and RU2 is not RU
 
 
 # ---------------------------------------------------------------------------------------------------------------- on the GPU
