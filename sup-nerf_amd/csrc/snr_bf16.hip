@@ -1199,7 +1199,7 @@ bf16_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float
     // private to the wave from here on: LDS operations of one wave execute in order)
     if (lane < 32) {
         float* c = comp + (wave * 32 + p) * COMP_STRIDE;
-        c[0] = gs * (1.f - expf(-sig_gp)); c[1] = gr; c[2] = gg; c[3] = gb;
+        c[0] = gs * -expm1f(-sig_gp); c[1] = gr; c[2] = gg; c[3] = gb;      // softplus'(pre) = -expm1(-sigma) (snr_mlp_bwd.hip)
     }
     float dpre2[2], gr2[2], gg2[2], gb2[2];
 #pragma unroll

@@ -193,8 +193,10 @@ decoder_bwd_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const floa
             gs = c[0]; gr = c[1]; gg = c[2]; gb = c[3]; gzc = c[4];
         }
     }
-    // softplus'(pre) = sigmoid(pre) = 1 - exp(-sigma)   (sigma = softplus(pre); exact 1 in fp32 past the threshold)
-    const float dpre = gs * (1.f - expf(-io.sigmas[gp]));
+    // softplus'(pre) = sigmoid(pre) = 1 - exp(-sigma) with sigma = softplus(pre), formed as -expm1(-sigma): 1 - expf(-sigma) is exactly 0
+    // for sigma below ~6e-8 (pre below ~-16.6), where sigmoid(pre) ~ sigma still matters (the last, 1e10-wide interval turns sigma ~ 1e-10
+    // into an alpha of order 1); exact 1 in fp32 past the threshold
+    const float dpre = gs * -expm1f(-io.sigmas[gp]);
 
     float in[9][16];
     f32x16 acc[9];

@@ -744,6 +744,13 @@ def _packed_for(names, weights, shape_blocks, texture_blocks):
     return packed
 
 
+def sigma_pre_grad(d_sig, sig):
+    """Gradient wrt the density head's pre-activation from the upstream ``d_sig`` and the saved density sigma = softplus(pre):
+    softplus'(pre) = sigmoid(pre) = 1 - exp(-sigma), formed as -expm1(-sigma).  (1 - exp(-sigma) is exactly 0 in fp32 for sigma below ~6e-8,
+    where sigmoid(pre) ~ sigma still carries the gradient of the 1e10-wide last interval; past the softplus threshold it is 1.)"""
+    return d_sig * -torch.expm1(-sig)
+
+
 class DecoderPointsTrain(torch.autograd.Function):
     """Training-mode decoder (SURVEY 8a9 mode B): like DecoderPoints but the per-point decoder WEIGHTS are inputs too and
     receive gradients.  The layer-chain kernels additionally write every layer's input X_l (forward) and pre-activation
@@ -822,8 +829,8 @@ class DecoderPointsTrain(torch.autograd.Function):
                 by_layer[li] = (dW[:, :283].contiguous(), db)
             else:
                 by_layer[li] = weight_grad(G[li], n_out, act[li - 1], 256, ws=ws, precision=wprec)
-        # sigma head: pre = w . y4 + b with y4 = input of enc_viewdir; d pre = d_sig * sigmoid(pre) = d_sig * (1 - exp(-sigma))
-        dpre = (d_sig * (1 - torch.exp(-sig))).reshape(P, 1)
+        # sigma head: pre = w . y4 + b with y4 = input of enc_viewdir
+        dpre = sigma_pre_grad(d_sig, sig).reshape(P, 1)
         d_sigma_w, d_sigma_b = weight_grad(dpre, 1, act[li_view - 1], 256, ws=ws)
         d_rgb2_w, d_rgb2_b = weight_grad(d_rgb.reshape(P, 3), 3, act[n_slots - 1], 128, ws=ws)
         out = []
