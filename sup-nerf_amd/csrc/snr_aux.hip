@@ -318,11 +318,8 @@ __global__ void __launch_bounds__(256) scene_general_kernel(const float* __restr
 // NaN with a payload in rgb[3 pix] (a pixel whose true result carries those bits is recomputed to the same value).  Keeping the general
 // code out of this kernel keeps its registers low (6 waves per SIMD); the next pixel's 5 x 4 values per lane are requested one pixel ahead
 // so that the memory latency is off the per-pixel chain LDS -> search -> scatter -> composite.
-#ifndef SCENE_FAST_WAVES
-#define SCENE_FAST_WAVES 6
-#endif
 template <int RUN>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCENE_FAST_WAVES, 8))) scene_fast_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ zv,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) scene_fast_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ zv,
                                                          long long n_pixels, int n, int flags, float* __restrict__ rgb, float* __restrict__ depth,
                                                          float* __restrict__ acc) {
     extern __shared__ __attribute__((aligned(16))) float scene_lds[];
@@ -575,17 +572,18 @@ using namespace snr;
 // ============================================================================ C ABI
 int snr_bf16_pack_(const float* const* W, int sb, int tb, float* packed, void* stream_);   // snr_bf16.hip
 
-extern "C" {
-
-int snr_abi_version(void) { return SNR_ABI_VERSION; }
-
 static thread_local const char* g_last_err = "";
-const char* snr_last_hip_error(void) { return g_last_err; }
 int snr_check_launch_(void) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { g_last_err = hipGetErrorString(e); return SNR_E_LAUNCH; }
     return SNR_OK;
 }
+
+extern "C" {
+
+int snr_abi_version(void) { return SNR_ABI_VERSION; }
+
+const char* snr_last_hip_error(void) { return g_last_err; }
 
 size_t snr_packed_bytes(int sb, int tb) {
     if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS) return 0;

@@ -68,10 +68,8 @@ struct Ring {
 // global and the LDS address together, selects the KiB.  Nothing else in these kernels uses M0 (checked in the disassembly).
 template <int K>
 __device__ __forceinline__ void ring_piece(const Ring& r, unsigned voff) {
-#ifndef SNR_EXP_NODMA
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3"
                  :: "v"(voff), "s"(r.pg), "s"(r.pm0), "n"(1024 * K - 4096) : "memory");
-#endif
 }
 template <int K0, int N>
 __device__ __forceinline__ void ring_pieces(const Ring& r, unsigned voff) {
@@ -103,16 +101,10 @@ __device__ __forceinline__ void ring_start(Ring& r, const char* stream, int tota
 // acquire has nothing younger behind it, so no DMA is in flight when the layers are done.  (`last` only guards a miscounted stream.)
 template <bool LAST = false>      // LAST: the stream's final chunk, no younger DMA behind it
 __device__ __forceinline__ const char* ring_acquire(Ring& r, char* lds) {
-#ifndef SNR_EXP_NOSYNC
     if constexpr (LAST) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#endif
-#ifdef SNR_EXP_SAMECHUNK      /* timing experiment: every fetch re-reads the stream's last chunk (L2-hot) */
-    const char* nx = r.last;
-#else
     const char* nx = r.next < r.last ? r.next : r.last;
-#endif
     r.pg = nx + r.wave_lds;
     r.pm0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)lds) + r.fill * WB_BYTES + r.wave_lds + 4096u;
     r.next = nx + BF_CHUNK;
@@ -151,15 +143,8 @@ __device__ __forceinline__ void pin(XOp& o) { asm volatile("" : "+v"(o.hi), "+v"
 // pre-activation that lands on the other side of zero flips a ReLU).  Activations are clamped to the fp16 range (+-65504) in the same
 // v_med3 that applies the ReLU; what lies below 6e-8 in magnitude is lost (absolute, harmless beside biases of order 0.1).  The backward
 // chain and the weight-gradient products carry GRADIENTS, whose magnitudes need bf16's exponent range: they stay on bf16 pieces.
-// -DSNR_FWD_BF16 builds the bf16 forward of rounds 1-2 (A/B timing).
-#ifndef SNR_FWD_BF16
-#define SNR_FWD_F16 1
 typedef _Float16 fwd_t;
 #define SNR_MFMA16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, x, y, z)
-#else
-typedef __bf16 fwd_t;
-#define SNR_MFMA16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, x, y, z)
-#endif
 typedef fwd_t fwdx8 __attribute__((ext_vector_type(8)));
 struct FOp { fwdx8 hi, lo; };
 __device__ __forceinline__ void split_store_f(float v, FOp& o, int j) {
@@ -178,35 +163,22 @@ __device__ __forceinline__ void pin(FOp& o) { asm volatile("" : "+v"(o.hi), "+v"
 // interleave request of the forward's groups: 3 MFMAs, then 3 VALU ops (tools/ab_time.py, two boxes, interleaved rounds: 1:1 0.4940 /
 // 0.5289 ms forward / forward with ReLU bits, 3:3 0.4840 / 0.5162, 1:0 0.4937 / 0.5232, 2:2, 3:2, 3:4, 4:3, 4:4, 6:6, 8:8, 12:12 all slower
 // than 3:3 -- the solver's freedom inside a request matters as much as the ratio)
-#ifndef SNR_IL16_MFMA
-#define SNR_IL16_MFMA 3
-#endif
-#ifndef SNR_IL16_VALU
-#define SNR_IL16_VALU 3
-#endif
-#ifndef SNR_IL16_DS
-#define SNR_IL16_DS 0          // (an LDS-read request in the groups: 1 or 2 per 3 or 6 MFMAs measured 1.4 - 5 % slower)
-#endif
+// (an LDS-read request in the groups as well, 1 or 2 per 3 or 6 MFMAs, measured 1.4 - 5 % slower)
+constexpr int IL16_MFMA = 3, IL16_VALU = 3;
 #define SNR_INTERLEAVE16(N_MFMA)                                                         \
-    _Pragma("unroll") for (int g_ = 0; g_ < (N_MFMA) / SNR_IL16_MFMA; ++g_) {            \
-        __builtin_amdgcn_sched_group_barrier(0x008, SNR_IL16_MFMA, 0);                   \
-        if (SNR_IL16_DS) __builtin_amdgcn_sched_group_barrier(0x100, SNR_IL16_DS, 0);    \
-        if (SNR_IL16_VALU) __builtin_amdgcn_sched_group_barrier(0x002, SNR_IL16_VALU, 0);\
+    _Pragma("unroll") for (int g_ = 0; g_ < (N_MFMA) / IL16_MFMA; ++g_) {                \
+        __builtin_amdgcn_sched_group_barrier(0x008, IL16_MFMA, 0);                       \
+        __builtin_amdgcn_sched_group_barrier(0x002, IL16_VALU, 0);                       \
     }
 
 // the backward's groups (bf16_bwd16_kernel) take the same form of request; measured (tools/ab_time.py, two boxes, interleaved rounds, ms):
 // 1:1 0.5879 / 0.6029, 1:0 0.5882, 1:2 0.6036, 2:3 0.5926, 3:3 0.5960 / 0.6109, 1:3 0.5992, 2:2 0.6127, 3:2 0.6154, 4:4 0.6191, 1:4 0.6016,
 // 2:1 0.6024, 3:4 0.6209, 6:6 0.6250; the 32x32x16 kernel of rounds 1-3 on the same boxes: 0.6031 / 0.6198
-#ifndef SNR_IL16B_MFMA
-#define SNR_IL16B_MFMA 1
-#endif
-#ifndef SNR_IL16B_VALU
-#define SNR_IL16B_VALU 1
-#endif
+constexpr int IL16B_MFMA = 1, IL16B_VALU = 1;
 #define SNR_INTERLEAVE16B(N_MFMA)                                                        \
-    _Pragma("unroll") for (int g_ = 0; g_ < (N_MFMA) / SNR_IL16B_MFMA; ++g_) {           \
-        __builtin_amdgcn_sched_group_barrier(0x008, SNR_IL16B_MFMA, 0);                  \
-        if (SNR_IL16B_VALU) __builtin_amdgcn_sched_group_barrier(0x002, SNR_IL16B_VALU, 0);\
+    _Pragma("unroll") for (int g_ = 0; g_ < (N_MFMA) / IL16B_MFMA; ++g_) {               \
+        __builtin_amdgcn_sched_group_barrier(0x008, IL16B_MFMA, 0);                      \
+        __builtin_amdgcn_sched_group_barrier(0x002, IL16B_VALU, 0);                      \
     }
 
 struct Frag16 { fwdx8 hi[4], lo[4]; };        // A fragments of four 16-row tiles (one group): 8 KiB of the chunk, contiguous
@@ -278,18 +250,9 @@ struct Epi16 {
 // in arrival order (T ascending, e ascending; see store_masks16)
 template <int HALF, bool MASKS, bool ZADD, bool DUMP>
 __device__ __forceinline__ void epi16(const f32x4& acc, FOp& o, const Epi16& c, int T, int cblk, int g, uint32_t& mbits) {
-#ifdef SNR_EXP_NOEPI
-    return;
-#endif
-#ifdef SNR_EXP_EPI0      /* timing experiment: the operand step is a raw copy of accumulator bits (one move per two values) */
-    { uint32_t (&hw0)[4] = reinterpret_cast<uint32_t (&)[4]>(o.hi); uint32_t (&lw0)[4] = reinterpret_cast<uint32_t (&)[4]>(o.lo);
-      hw0[2 * HALF] = __float_as_uint(acc[0]); hw0[2 * HALF + 1] = __float_as_uint(acc[1]); lw0[2 * HALF] = __float_as_uint(acc[2]); lw0[2 * HALF + 1] = __float_as_uint(acc[3]);
-      if (HALF == 1) pin(o); return; }
-#endif
     f32x4 z;
     if (ZADD) z = *reinterpret_cast<const f32x4*>(c.zl + 16 * T + 4 * g);
     f32x4 dv;
-#ifdef SNR_FWD_F16
     // ReLU and the clamp to the fp16 range in one v_med3 (floor = -65504 for the layer without an activation); the pieces are packed two
     // at a time with v_cvt_pkrtz_f16_f32 (the remainder x - hi is exact in fp32 whichever way hi was rounded)
     const float lo_bound = c.floor == 0 ? 0.f : -65504.f;
@@ -314,30 +277,13 @@ __device__ __forceinline__ void epi16(const f32x4& acc, FOp& o, const Epi16& c, 
         const h2 hp = __builtin_amdgcn_cvt_pkrtz(xv[2 * k], xv[2 * k + 1]);
         // the remainder x - hi as ONE v_fma_mix_f32 (f32 x 1 - f16 piece; exact) instead of v_cvt_f32_f16 + v_sub_f32: three VALU
         // instructions per value in this epilogue where bf16 pieces took four (forward -1.5 %, forward with ReLU bits -2.7 %)
-#ifdef SNR_EXP_EPI1      /* timing experiment: no low piece (ReLU + one packed conversion per two values) */
-        const h2 lp = hp;
-        hw[2 * HALF + k] = __builtin_bit_cast(uint32_t, hp);
-        lw[2 * HALF + k] = __builtin_bit_cast(uint32_t, lp);
-#else
         const h2 lp = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf(xv[2 * k], one_, -(float)hp[0]), __builtin_fmaf(xv[2 * k + 1], one_, -(float)hp[1]));
         hw[2 * HALF + k] = __builtin_bit_cast(uint32_t, hp);
         lw[2 * HALF + k] = __builtin_bit_cast(uint32_t, lp);
         // (round 4, measured and dropped: the low piece as v_fma_mixlo_f16 / v_fma_mixhi_f16 through inline asm -- 2.5 instead of 3 VALU per value,
         // rgb 4.7e-8 instead of 5.5e-8 from the fp32 kernel's -- ran +0.6 % / +1.6 % (forward / with ReLU bits): the solver does not place asm
         // statements under the MFMAs, and the high half is a read-modify-write of the low half's register)
-#endif
     }
-#else
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float a = acc[e];           // bias already inside
-        const float y = __builtin_bit_cast(float, max(__builtin_bit_cast(int, a), c.floor));
-        if (MASKS) mbits = __builtin_amdgcn_alignbit(mbits, __builtin_bit_cast(uint32_t, y) - 1u, 31);      // inactive = (y == 0), see the fp16 branch
-        const float xv = ZADD ? y + z[e] : y;
-        split_store_f(xv, o, 4 * HALF + e);
-        if (DUMP) dv[e] = xv;
-    }
-#endif
     if (DUMP) { if (c.dump[cblk]) *reinterpret_cast<f32x4*>(c.dump[cblk] + 16 * T) = dv; }
     if (HALF == 1) pin(o);
     if (MASKS) asm volatile("" : "+v"(mbits));
@@ -348,7 +294,7 @@ __device__ __forceinline__ void epi16(const f32x4& acc, FOp& o, const Epi16& c, 
 // accumulator tile of the previous layer (12 - 25 single-instruction statements) spread over the others, the two DMA pieces behind MFMAs 16
 // and 19 -- each gap closed by sched_barrier(0), so the compiler keeps the order as written (its own scheduling inside a gap is one or two
 // instructions).  Budget per gap (MI355X_MICROARCH.md): the MFMA holds the vector issue 8 of its 16 cycles, a VALU / LDS instruction costs
-// 4: one extra instruction per gap leaves the pipe fed.  -DSNR_NO_PLACED: the sched_group_barrier request of round 3 instead (A/B).
+// 4: one extra instruction per gap leaves the pipe fed.
 struct E16State {
     float y[4], l[4];
     f32x4 z;
@@ -378,6 +324,9 @@ __device__ __forceinline__ void e16_op(E16State& s, const f32x4& acc, FOp& o, co
         else { constexpr int q = k2 - 6; const h2 lp = __builtin_amdgcn_cvt_pkrtz(s.l[2 * q], s.l[2 * q + 1]); lw[2 * HALF + q] = __builtin_bit_cast(uint32_t, lp); }
     }
 }
+// placement in a group: a fragment read every PL_FSTEP-th gap from gap PL_F0, the two DMA pieces behind MFMAs PL_DMA0 and PL_DMA1, a
+// conversion of at most twelve operations shifted by PL_SHIFT gaps
+constexpr int PL_FSTEP = 2, PL_F0 = 0, PL_DMA0 = 16, PL_DMA1 = 19, PL_SHIFT = 1;
 template <int I, int T0, bool TO_P, bool HAS_F, int PIECE0, bool HAS_E, int HALF, bool MASKS, bool ZADD>
 __device__ __forceinline__ void g16_step(f32x4 (&accC)[2][16], f32x4 (&accP)[2][16], const FOp (&x)[2], const Frag16& f, Frag16& fn, const char* wq,
                                          const Ring& ring, unsigned voff, E16State& s, const f32x4& eacc, FOp& eo, const Epi16& c, int T, int g, uint32_t& mbits) {
@@ -387,31 +336,16 @@ __device__ __forceinline__ void g16_step(f32x4 (&accC)[2][16], f32x4 (&accP)[2][
     else if constexpr (TO_P) accP[cb][T0 + t] = SNR_MFMA16(f.lo[t], x[cb].hi, accC[cb][T0 + t], 0, 0, 0);
     else accC[cb][T0 + t] = SNR_MFMA16(f.lo[t], x[cb].hi, accC[cb][T0 + t], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);        // (the gap's instruction BEHIND its MFMA: inside one region the compiler puts a load first)
-#ifndef SNR_PL_FSTEP
-#define SNR_PL_FSTEP 2          /* a fragment read every FSTEP-th gap, from gap SNR_PL_F0 */
-#endif
-#ifndef SNR_PL_F0
-#define SNR_PL_F0 0
-#endif
-#ifndef SNR_PL_DMA0
-#define SNR_PL_DMA0 16
-#endif
-#ifndef SNR_PL_DMA1
-#define SNR_PL_DMA1 19
-#endif
-#ifndef SNR_PL_SHIFT
-#define SNR_PL_SHIFT 1
-#endif
-    if constexpr (HAS_F && I >= SNR_PL_F0 && I < SNR_PL_F0 + 8 * SNR_PL_FSTEP && ((I - SNR_PL_F0) % SNR_PL_FSTEP) == 0) {
-        constexpr int fi = (I - SNR_PL_F0) / SNR_PL_FSTEP, ft = fi / 2, pl = fi % 2;
+    if constexpr (HAS_F && I >= PL_F0 && I < PL_F0 + 8 * PL_FSTEP && ((I - PL_F0) % PL_FSTEP) == 0) {
+        constexpr int fi = (I - PL_F0) / PL_FSTEP, ft = fi / 2, pl = fi % 2;
         if constexpr (pl == 0) fn.hi[ft] = *reinterpret_cast<const fwdx8*>(wq + (2 * ft) * 1024);
         else fn.lo[ft] = *reinterpret_cast<const fwdx8*>(wq + (2 * ft + 1) * 1024);
     }
-    if constexpr (PIECE0 >= 0 && I == SNR_PL_DMA0) ring_pieces<(PIECE0 >= 0 ? PIECE0 : 0), 1>(ring, voff);
-    if constexpr (PIECE0 >= 0 && I == SNR_PL_DMA1) ring_pieces<(PIECE0 >= 0 ? PIECE0 + 1 : 0), 1>(ring, voff);
+    if constexpr (PIECE0 >= 0 && I == PL_DMA0) ring_pieces<(PIECE0 >= 0 ? PIECE0 : 0), 1>(ring, voff);
+    if constexpr (PIECE0 >= 0 && I == PL_DMA1) ring_pieces<(PIECE0 >= 0 ? PIECE0 + 1 : 0), 1>(ring, voff);
     if constexpr (HAS_E) {
         constexpr int NE = (ZADD ? 1 : 0) + 4 * (1 + 2 * (MASKS ? 1 : 0) + (ZADD ? 1 : 0)) + 8;
-        constexpr int SHIFT = NE <= 12 ? SNR_PL_SHIFT : 0;          // twelve operations: the odd gaps (the fragment reads have the even ones)
+        constexpr int SHIFT = NE <= 12 ? PL_SHIFT : 0;          // twelve operations: the odd gaps (the fragment reads have the even ones)
         // operations k with gap(k) == I, gap(k) = k * 24 / NE + SHIFT  (NE <= 25: at most two per gap)
         constexpr int KA = ((I - SHIFT) * NE + 23) / 24;              // first k with k * 24 / NE >= I - SHIFT
         constexpr int KB = ((I - SHIFT + 1) * NE + 23) / 24;          // first k of the next gap
@@ -458,14 +392,7 @@ __device__ __forceinline__ void layer16(f32x4 (&accP)[2][16], Ring& ring, char* 
     const char* w = ring_acquire(ring, lds) + lane * 16;
     load16(fa, w);
     if constexpr (!TAIL || 2 < NCH) ring_pieces<0, 2>(ring, voff);
-#ifdef SNR_EXP_EPIIND     /* timing experiment: the MFMAs do not wait for the conversions (they multiply the layer's first operand step throughout) */
-    FOp x_first[2] = {xc[0], xc[1]};
-#define SNR_MMA16_CALL(T0_, LASTS_, FCUR) mma16<T0_, LASTS_>(accC, accP, x_first, FCUR); asm volatile("" :: "v"(xc[0].hi), "v"(xc[0].lo), "v"(xc[1].hi), "v"(xc[1].lo));
-#else
-#define SNR_MMA16_CALL(T0_, LASTS_, FCUR) mma16<T0_, LASTS_>(accC, accP, xc, FCUR);
-#endif
     // group G: step S = G / GPS, tiles 4 (G % GPS); position Q = G % 4 in its chunk W = G / 4
-#if !defined(SNR_NO_PLACED)
 #define SNR_GROUP16_PLACED(G, FCUR, FNXT)                                                                                  \
     {                                                                                                                      \
         constexpr int S_ = (G) / GPS, T0_ = 4 * ((G) % GPS), Q_ = (G) % 4, W_ = (G) / 4;                                   \
@@ -479,14 +406,13 @@ __device__ __forceinline__ void layer16(f32x4 (&accP)[2][16], Ring& ring, char* 
                                                                    mw[2 * cb_ + (T_ >> 3)], std::make_integer_sequence<int, 24>{}); \
         if constexpr (!LASTS_ && ((G) % GPS) == GPS - 1) { xc[0] = xn[0]; xc[1] = xn[1]; }                                 \
     }
-#endif
 #define SNR_GROUP16(G, FCUR, FNXT)                                                                                         \
     {                                                                                                                      \
         constexpr int S_ = (G) / GPS, T0_ = 4 * ((G) % GPS), Q_ = (G) % 4, W_ = (G) / 4;                                   \
         constexpr bool LASTS_ = S_ == 7;                                                                                   \
         if constexpr (Q_ != 3) load16(FNXT, w + (Q_ + 1) * 8192);                                                          \
         else if constexpr ((G) + 1 < NG) { w = ring_acquire<TAIL && W_ + 1 == NCH - 1>(ring, lds) + lane * 16; load16(FNXT, w); } \
-        SNR_MMA16_CALL(T0_, LASTS_, FCUR)                                                                                  \
+        mma16<T0_, LASTS_>(accC, accP, xc, FCUR);                                                                          \
         if constexpr (Q_ != 3) { if constexpr (!TAIL || W_ + 2 < NCH) ring_pieces<2 * Q_ + 2, 2>(ring, voff); }            \
         else if constexpr ((G) + 1 < NG) { if constexpr (!TAIL || W_ + 3 < NCH) ring_pieces<0, 2>(ring, voff); }           \
         if constexpr (!LASTS_) {                                                                                           \
@@ -503,7 +429,6 @@ __device__ __forceinline__ void layer16(f32x4 (&accP)[2][16], Ring& ring, char* 
         if constexpr (!LASTS_ && ((G) % GPS) == GPS - 1) { xc[0] = xn[0]; xc[1] = xn[1]; }                                 \
     }
 #define SNR_GROUP16_PAIR(G) SNR_GROUP16(G, fa, fb) SNR_GROUP16((G) + 1, fb, fa)
-#if !defined(SNR_NO_PLACED)
 #define SNR_GROUP16_PPAIR(G) SNR_GROUP16_PLACED(G, fa, fb) SNR_GROUP16_PLACED((G) + 1, fb, fa)
     if constexpr (NT16 == 16 && !DUMP) {
         E16State es;
@@ -515,7 +440,6 @@ __device__ __forceinline__ void layer16(f32x4 (&accP)[2][16], Ring& ring, char* 
         SNR_GROUP16_PPAIR(24) SNR_GROUP16_PPAIR(26) SNR_GROUP16_PPAIR(28) SNR_GROUP16_PPAIR(30)
     } else
 #undef SNR_GROUP16_PPAIR
-#endif
     {
     SNR_GROUP16_PAIR(0) SNR_GROUP16_PAIR(2) SNR_GROUP16_PAIR(4) SNR_GROUP16_PAIR(6)
     SNR_GROUP16_PAIR(8) SNR_GROUP16_PAIR(10) SNR_GROUP16_PAIR(12) SNR_GROUP16_PAIR(14)
@@ -526,7 +450,6 @@ __device__ __forceinline__ void layer16(f32x4 (&accP)[2][16], Ring& ring, char* 
     }
 #undef SNR_GROUP16_PAIR
 #undef SNR_GROUP16
-#undef SNR_MMA16_CALL
 }
 
 // x | x[lane ^ 32] (the two lanes hold disjoint bits): gfx950 v_permlane32_swap, no LDS round trip
@@ -1396,9 +1319,7 @@ __global__ void pack_bf16_kernel(const float* __restrict__ Wt, int n_out, int k_
         }
         const long long base = (((long long)s * n_tiles + tile) * 2) * 512;      // 16-bit elements; plane stride 512
         if (!transpose) {                                // the forward stream in the forward chain's element type
-#ifdef SNR_FWD_F16
             v = fminf(fmaxf(v, -65504.f), 65504.f);      // (a weight beyond the fp16 range saturates instead of becoming an infinity)
-#endif
             const fwd_t hi = (fwd_t)v;
             const fwd_t lo = (fwd_t)(v - (float)hi);
             reinterpret_cast<fwd_t*>(dst)[base + lane * 8 + j] = hi;
@@ -1489,12 +1410,10 @@ int snr_bf16_launch_fwd_(int mode, const DecoderIO& io, const Layout& L, const f
 
 int snr_bf16_launch_bwd_(int mode, const BwdIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, void* stream_) {
     const unsigned grid = (unsigned)((io.n_points + 127) / 128);
-#define SNR_BWD_KERNEL bf::bf16_bwd16_kernel
     if (io.gdump) {
         if (mode != 0) return SNR_E_ARG;
-        SNR_BWD_KERNEL<0, true><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
-    } else if (mode == 0) SNR_BWD_KERNEL<0><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
-    else SNR_BWD_KERNEL<1><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
-#undef SNR_BWD_KERNEL
+        bf::bf16_bwd16_kernel<0, true><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
+    } else if (mode == 0) bf::bf16_bwd16_kernel<0><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
+    else bf::bf16_bwd16_kernel<1><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
     return snr_check_launch_();
 }

@@ -4,4 +4,5 @@
 namespace snr { struct RayGeom; }
 // validate snr_render_args and decode it into the by-value kernel argument
 int snr_fill_geom_(const snr_render_args* a, snr::RayGeom* g, int need_model);
-extern "C" int snr_check_launch_(void);
+// SNR_OK, or SNR_E_LAUNCH with the HIP error kept for snr_last_hip_error
+int snr_check_launch_(void);

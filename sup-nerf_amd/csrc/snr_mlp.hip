@@ -1,5 +1,5 @@
-// Fused decoder kernels for gfx950 (MI355X): positional encoding -> code-conditioned MLP on the
-// fp32 MFMA pipe -> (optionally) wavefront alpha composite, in one launch.
+// The exact-fp32 training forward of the decoder for gfx950 (MI355X): positional encoding -> code-conditioned MLP on the
+// fp32 MFMA pipe, saving the ReLU bits and every layer's input for the backward, in one launch.
 //
 // Design:
 //   * One workgroup = 4 wavefronts = 128 consecutive sample points; one wave per SIMD so each wave
@@ -13,7 +13,7 @@
 //   * Weights stream from L2 through a double-buffered LDS ring in 32-deep k-chunks (ROWS x 32 fp32,
 //     XOR-swizzled 16-byte slots -> conflict-free ds_read_b128) filled by LDS-DMA, shared by the 4 waves.
 //   * Bias / latent adds, ReLU, softplus, the 256->1 density head and the 128->3 colour head run on
-//     the VALU in the accumulator layout; the composite is a 64-lane product scan.
+//     the VALU in the accumulator layout.
 #include "snr_mlp_core.hpp"
 #include "snr_host.hpp"
 
@@ -31,9 +31,9 @@ namespace snr {
 // lane's point p = lane & 31 (both half-waves hold the same point).  Outputs sigma, r, g, b valid in
 // every lane.  All four waves of the workgroup must call it together (block-wide barriers inside).
 // -------------------------------------------------------------------------------------------
-template <bool STAGED, bool MASKS>      // MASKS: the launch saves the ReLU bits (io.masks).  STAGED (the points decoder, which is what trains): activation dumps through LDS, whole cache lines per store
-__device__ __forceinline__ void decoder_forward_tile(const DecoderIO& io, const Layout& L, float* lds, long long gp /*clamped point id*/, bool live,
-                                                     long long tile32, float x, float y, float z, float dx, float dy, float dz,
+// The ReLU bits go to io.masks; the activation dumps are staged through LDS, whole cache lines per store.
+__device__ __forceinline__ void decoder_forward_tile(const DecoderIO& io, const Layout& L, float* lds, long long gp /*clamped point id*/, long long tile32,
+                                                     float x, float y, float z, float dx, float dy, float dz,
                                                      float& o_sigma, float& o_r, float& o_g, float& o_b) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -42,7 +42,7 @@ __device__ __forceinline__ void decoder_forward_tile(const DecoderIO& io, const 
     const int n_relu = n_relu_layers(sb, tb);
     // a workgroup covers 4 wave tiles; the last one of a launch may own tiles past the end (buffers are sized for ceil(P/32) tiles)
     const bool tile_live = tile32 * 32 < io.n_points;
-    const int dump_rows = STAGED ? (int)((io.n_points - tile32 * 32) < 32 ? (io.n_points - tile32 * 32) : 32) : 0;       // rows of this wave's tile that exist
+    const int dump_rows = (int)((io.n_points - tile32 * 32) < 32 ? (io.n_points - tile32 * 32) : 32);       // rows of this wave's tile that exist
     float* const dump_scr = lds + LDS_SCRATCH + wave * PE_WAVE;      // the wave's positional-encoding scratch, idle after the prologue
     const float* bias = lds + LDS_BIAS;            // staged in the prologue
     const float* heads = bias + L.n_mfma_layers * 256;   // sigma_w (256) | sigma_b | rgb2_w (384) | rgb2_b, as in the packed stream
@@ -118,11 +118,10 @@ __device__ __forceinline__ void decoder_forward_tile(const DecoderIO& io, const 
     step<8, 8>(acc, in[1], pipe, lds, 256, tid);
     {
         const int la = latent_after(0, sb, tb);
-        if (lat_in_lds && la >= 0) epilogue<8, 8, MASKS>(acc, in, true, lds + LDS_LAT + la * 256, h, mask);
-        else epilogue<8, 8, MASKS>(acc, in, true, la >= 0 ? lat + la * 256 : nullptr, h, mask);
-        if (MASKS && tile_live) io.masks[(tile32 * n_relu + 0) * 64 + lane] = make_uint4(mask[0], mask[1], mask[2], mask[3]);
-        if constexpr (STAGED) { if (io.act && tile_live) dump_operand_staged<8>(in, io.act + ((long long)0 * io.n_points + tile32 * 32) * 256, dump_rows, dump_scr, lane); }
-        else if (io.act && live) dump_operand<8>(in, io.act + ((long long)0 * io.n_points + gp) * 256, h);
+        if (lat_in_lds && la >= 0) epilogue<8, 8, true>(acc, in, true, lds + LDS_LAT + la * 256, h, mask);
+        else epilogue<8, 8, true>(acc, in, true, la >= 0 ? lat + la * 256 : nullptr, h, mask);
+        if (tile_live) io.masks[(tile32 * n_relu + 0) * 64 + lane] = make_uint4(mask[0], mask[1], mask[2], mask[3]);
+        if (io.act && tile_live) dump_operand_staged<8>(in, io.act + ((long long)0 * io.n_points + tile32 * 32) * 256, dump_rows, dump_scr, lane);
     }
 
     SNR32_STAMP(1);      // enc_xyz + its epilogue
@@ -145,12 +144,11 @@ __device__ __forceinline__ void decoder_forward_tile(const DecoderIO& io, const 
         if (is_view) step<8, 8>(acc, in[8], pipe, lds, rows_after, tid);
         const bool relu = (li != li_encshape);
         const int la = latent_after(li, sb, tb);
-        if (lat_in_lds && la >= 0) epilogue<8, 8, MASKS>(acc, in, relu, lds + LDS_LAT + la * 256, h, mask);
-        else epilogue<8, 8, MASKS>(acc, in, relu, la >= 0 ? lat + la * 256 : nullptr, h, mask);
-        if (MASKS && relu && tile_live)
+        if (lat_in_lds && la >= 0) epilogue<8, 8, true>(acc, in, relu, lds + LDS_LAT + la * 256, h, mask);
+        else epilogue<8, 8, true>(acc, in, relu, la >= 0 ? lat + la * 256 : nullptr, h, mask);
+        if (relu && tile_live)
             io.masks[(tile32 * n_relu + relu_slot(li, sb)) * 64 + lane] = make_uint4(mask[0], mask[1], mask[2], mask[3]);
-        if constexpr (STAGED) { if (io.act && tile_live) dump_operand_staged<8>(in, io.act + ((long long)li * io.n_points + tile32 * 32) * 256, dump_rows, dump_scr, lane); }
-        else if (io.act && live) dump_operand<8>(in, io.act + ((long long)li * io.n_points + gp) * 256, h);
+        if (io.act && tile_live) dump_operand_staged<8>(in, io.act + ((long long)li * io.n_points + tile32 * 32) * 256, dump_rows, dump_scr, lane);
         if (li <= 6) SNR32_STAMP(1 + li);      // layer li + its epilogue (+ bias init of the next)
         if (li == li_encshape) {
             // density head: softplus(w_sigma . y + b)   (src/model_supnerf.py:257)
@@ -181,10 +179,9 @@ __device__ __forceinline__ void decoder_forward_tile(const DecoderIO& io, const 
     step<4, 8>(acc, in[6], pipe, lds, 128, tid);
     step<4, 8>(acc, in[7], pipe, lds, 0, tid);
     SNR32_STAMP(9);      // rgb.0's chunks
-    epilogue<4, 8, MASKS>(acc, in, true, nullptr, h, mask);
-    if (MASKS && tile_live) io.masks[(tile32 * n_relu + (n_relu - 1)) * 64 + lane] = make_uint4(mask[0], mask[1], 0u, 0u);
-    if constexpr (STAGED) { if (io.act && tile_live) dump_operand_staged<4>(in, io.act + ((long long)(li_last + 1) * io.n_points + tile32 * 32) * 256, dump_rows, dump_scr, lane); }
-    else if (io.act && live) dump_operand<4>(in, io.act + ((long long)(li_last + 1) * io.n_points + gp) * 256, h);
+    epilogue<4, 8, true>(acc, in, true, nullptr, h, mask);
+    if (tile_live) io.masks[(tile32 * n_relu + (n_relu - 1)) * 64 + lane] = make_uint4(mask[0], mask[1], 0u, 0u);
+    if (io.act && tile_live) dump_operand_staged<4>(in, io.act + ((long long)(li_last + 1) * io.n_points + tile32 * 32) * 256, dump_rows, dump_scr, lane);
     {
         const float* w2 = heads + (L.rgb2_w - L.sigma_w);
         float pr = 0.f, pg = 0.f, pb = 0.f;
@@ -212,32 +209,23 @@ __device__ __forceinline__ void decoder_forward_tile(const DecoderIO& io, const 
 // ===========================================================================================
 // kernels
 // ===========================================================================================
-// MODE 0: explicit points (SUPNeRF.forward drop-in).  MODE 1: fused render (sampling + composite).
-template <int MODE, bool MASKS>
+// The exact-fp32 TRAINING forward: explicit points, ReLU bits and activation dumps.
 __global__ void __launch_bounds__(256, 1)
-decoder_fwd_kernel(DecoderIO io, Layout L, const float* __restrict__ xyz, const float* __restrict__ viewdir, RayGeom g,
-                   float* __restrict__ out_rgb, float* __restrict__ out_depth, float* __restrict__ out_acc) {
+decoder_train_fwd_kernel(DecoderIO io, Layout L, const float* __restrict__ xyz, const float* __restrict__ viewdir) {
     __shared__ __attribute__((aligned(16))) float lds[LDS_TOTAL];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31;
     const long long tile128 = blockIdx.x;
     const long long gp_raw = tile128 * 128 + wave * 32 + p;
     const bool live = gp_raw < io.n_points;
     const long long gp = live ? gp_raw : io.n_points - 1;
-    float x, y, z, dx, dy, dz, zc = 0.f;
-    if (MODE == 0) {
-        x = xyz[gp * 3]; y = xyz[gp * 3 + 1]; z = xyz[gp * 3 + 2];
-        dx = viewdir[gp * 3]; dy = viewdir[gp * 3 + 1]; dz = viewdir[gp * 3 + 2];
-    } else {
-        const long long ray = gp / g.S;
-        const SamplePoint sp = make_sample(g, ray, (int)(gp - ray * g.S));
-        x = sp.x; y = sp.y; z = sp.z; dx = sp.dx; dy = sp.dy; dz = sp.dz; zc = sp.zc;
-    }
+    const float x = xyz[gp * 3], y = xyz[gp * 3 + 1], z = xyz[gp * 3 + 2];
+    const float dx = viewdir[gp * 3], dy = viewdir[gp * 3 + 1], dz = viewdir[gp * 3 + 2];
     float sg, cr, cg, cb;
 #ifdef SNR_STAMPS   /* diagnostic build (tools/build_diag.sh): the sigma buffer receives {s_memtime, s_memrealtime} at both ends of the workgroup */
     unsigned long long st_c0 = 0, st_r0 = 0;
     if (tid == 0) asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_c0), "=s"(st_r0) :: "memory");
 #endif
-    decoder_forward_tile<MODE == 0, MASKS>(io, L, lds, gp, live, tile128 * 4 + wave, x, y, z, dx, dy, dz, sg, cr, cg, cb);
+    decoder_forward_tile(io, L, lds, gp, tile128 * 4 + wave, x, y, z, dx, dy, dz, sg, cr, cg, cb);
 #ifdef SNR_STAMPS
     if (tid == 0 && io.sigmas) {
         unsigned long long c1, r1;
@@ -251,31 +239,6 @@ decoder_fwd_kernel(DecoderIO io, Layout L, const float* __restrict__ xyz, const 
         if (io.rgbs) { io.rgbs[gp * 3] = cr; io.rgbs[gp * 3 + 1] = cg; io.rgbs[gp * 3 + 2] = cb; }
     }
 #endif
-    if (MODE == 1) {
-        float* comp = lds + LDS_COMP;
-        if (lane < 32) {
-            float* c = comp + (wave * 32 + p) * COMP_STRIDE;
-            c[0] = sg; c[1] = cr; c[2] = cg; c[3] = cb; c[4] = zc;
-        }
-        __syncthreads();
-        const int S = g.S;
-        const int rays_here = 128 / S;           // host guarantees 128 % S == 0
-        const bool white = g.flags & SNR_WHITE_BKGD;
-        for (int r = wave; r < rays_here; r += 4) {
-            const long long ray = tile128 * rays_here + r;
-            if (ray >= g.n_rays) break;
-            const float* c0 = comp + r * S * COMP_STRIDE;
-            RayOut o = composite_ray_fwd(S, lane, white, [&](int k, float& s_, float& r_, float& g_, float& b_, float& z_, float& zn_) {
-                const float* c = c0 + k * COMP_STRIDE;
-                s_ = c[0]; r_ = c[1]; g_ = c[2]; b_ = c[3]; z_ = c[4];
-                zn_ = (k < S - 1) ? c[COMP_STRIDE + 4] : 0.f;
-            });
-            if (lane == 0) {
-                out_rgb[ray * 3] = o.r; out_rgb[ray * 3 + 1] = o.g; out_rgb[ray * 3 + 2] = o.b;
-                out_depth[ray] = o.depth; out_acc[ray] = o.acc;
-            }
-        }
-    }
 }
 
 }  // namespace snr
@@ -286,8 +249,8 @@ int snr_bf16_supported_(int sb, int tb, long long points_per_obj);
 int snr_bf16_launch_fwd_(int mode, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
                          float* depth, float* acc, void* stream_);
 // The exact-fp32 forward runs on the two-waves-per-SIMD kernel of snr_mlp16.hip (v_mfma_f32_16x16x4_f32, 16 points per wave: round 4).  This
-// file's one-wave-per-SIMD kernel (v_mfma_f32_32x32x2_f32, rounds 1-3) still serves the TRAINING forward of the exact-fp32 step (activation
-// dumps staged through LDS) and, with -DSNR_FWD32, every fp32 forward for A/B timing (tools/build_variant.sh).
+// file's one-wave-per-SIMD kernel (v_mfma_f32_32x32x2_f32, rounds 1-3) serves only the TRAINING forward of the exact-fp32 step (activation
+// dumps staged through LDS).
 int snr_fp32_fwd16_launch_(int mode, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
                            float* depth, float* acc, void* stream_);
 
@@ -316,13 +279,10 @@ int snr_decoder_fwd(const float* xyz, const float* viewdir, const float* latent,
         return snr_bf16_launch_fwd_(0, io, L, xyz, viewdir, g, nullptr, nullptr, nullptr, stream_);
     }
     if (precision != SNR_FP32) return SNR_E_ARG;
-#ifndef SNR_FWD32
     // (training dumps stay on this file's kernel: its LDS-staged dump stores write whole cache lines, 13.9 against 14.2 ms per fp32 step)
     if (!activations) return snr_fp32_fwd16_launch_(0, io, L, xyz, viewdir, g, nullptr, nullptr, nullptr, stream_);
-#endif
     const unsigned grid = (unsigned)((n_points + 127) / 128);
-    if (relu_masks) decoder_fwd_kernel<0, true><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g, nullptr, nullptr, nullptr);
-    else decoder_fwd_kernel<0, false><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g, nullptr, nullptr, nullptr);
+    decoder_train_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir);
     return snr_check_launch_();
 }
 
@@ -344,13 +304,7 @@ int snr_render_fwd(const snr_render_args* a, float* rgb, float* depth, float* ac
         return snr_bf16_launch_fwd_(1, io, L, nullptr, nullptr, g, rgb, depth, acc_trans, stream_);
     }
     if (a->precision != SNR_FP32) return SNR_E_ARG;
-#ifndef SNR_FWD32
     return snr_fp32_fwd16_launch_(1, io, L, nullptr, nullptr, g, rgb, depth, acc_trans, stream_);
-#endif
-    const unsigned grid = (unsigned)((P + 127) / 128);
-    if (relu_masks) decoder_fwd_kernel<1, true><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, nullptr, nullptr, g, rgb, depth, acc_trans);
-    else decoder_fwd_kernel<1, false><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, nullptr, nullptr, g, rgb, depth, acc_trans);
-    return snr_check_launch_();
 }
 
 }  // extern "C"

@@ -166,12 +166,6 @@ __device__ __forceinline__ void store_masks16x4(uint4* __restrict__ dst /* tile'
 #define SNR16_STAMP_HWID(i) do {} while (0)
 #endif
 
-#ifdef SNR16_NO_PRIO
-#define SNR16_PRIO(p) do {} while (0)
-#else
-#define SNR16_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#endif
-
 template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
 __global__ void __launch_bounds__(WAVES * 64, 2)
 decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__ xyz, const float* __restrict__ viewdir, RayGeom gm,
@@ -192,7 +186,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     // and at equal priority its ready MFMA wins the ALUs nearly every time: the prologue then takes 69 000 cycles instead of 9 000 and the matrix
     // pipe is fed by one wave (0.87 of its rate) for that long.  With priority the prologue is over in a fraction of that and two waves share
     // the pipe again (tools/_diag/stamps16.py).
-    SNR16_PRIO(3);
+    __builtin_amdgcn_s_setprio(3);
     float px, py, pz, dx, dy, dz, zc = 0.f;
     if (MODE == 0) {
         px = xyz[gp * 3]; py = xyz[gp * 3 + 1]; pz = xyz[gp * 3 + 2];
@@ -276,7 +270,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
         if (WAVES == 4) __syncthreads();      // the scratch lies over ring buffer 1: every wave has read its operands before any wave requests chunk 1
     }
 
-    SNR16_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     SNR16_STAMP(1);
     // ---- enc_xyz: 64 -> 256 from explicit operand tiles (two chunks)
     f32x4 accP[16];
@@ -351,7 +345,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     }
 
     SNR16_STAMP(5);
-    SNR16_PRIO(3);
+    __builtin_amdgcn_s_setprio(3);
     // ---- rgb.0's output (accP tiles 0..7): ReLU + bits, then rgb.2 (128 -> 3) on the VALU
     float o_r, o_g, o_b;
     {
@@ -431,14 +425,6 @@ using namespace snr;
 //     L2 -> LDS weight traffic per point (8 B/clk/CU).  Taken whenever it fits: the ray (render mode) inside 64 points, LDS <= 80 KiB.
 //   WAVES = 8 -- 128 points per 512-thread workgroup, one per CU; both waves of a SIMD run the same program between the same barriers.
 // The workgroup's latent rows are staged in LDS when its points belong to ONE object and the table has at most LDS_LAT_ROWS rows.
-static int fwd16_waves_override() {
-#ifdef SNR16_FORCE_WAVES
-    return SNR16_FORCE_WAVES;
-#else
-    static const int v = [] { const char* e = getenv("SNR_FP32_WAVES"); return e ? atoi(e) : 0; }();      // diagnostic: 4 or 8
-    return v;
-#endif
-}
 
 template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
 static int launch16(const DecoderIO& io, const Layout& L, const Lds16& lo, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
@@ -476,9 +462,6 @@ int snr_fp32_fwd16_launch_(int mode, const DecoderIO& io, const Layout& L, const
     if (io.act) return SNR_E_UNSUPPORTED;          // (training dumps: snr_mlp.hip's kernel, whose dump stores are staged through LDS)
     const bool lat4 = (io.points_per_obj % 64) == 0 && L.n_lat <= LDS_LAT_ROWS;
     const Lds16 lo4 = make_lds16(4, L.n_mfma_layers, lat4 ? L.n_lat : LDS_LAT_ROWS + 1);
-    bool four = lo4.total * 4 <= 80 * 1024 && (mode == 0 || (g.S <= 64 && 64 % g.S == 0));
-    if (fwd16_waves_override() == 8) four = false;
-    if (fwd16_waves_override() == 4 && !(mode == 0 || (g.S <= 64 && 64 % g.S == 0))) four = false;
-    else if (fwd16_waves_override() == 4) four = true;
+    const bool four = lo4.total * 4 <= 80 * 1024 && (mode == 0 || (g.S <= 64 && 64 % g.S == 0));
     return four ? launch16_w<4>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st) : launch16_w<8>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st);
 }

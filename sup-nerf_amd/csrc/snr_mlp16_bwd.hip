@@ -265,12 +265,6 @@ __device__ __forceinline__ void ray_grad_tail16(const RayGeom& g, float* __restr
 #define SNR16_BSTAMP(i) do {} while (0)
 #endif
 
-#ifdef SNR16_NO_PRIO
-#define SNR16_PRIO(p) do {} while (0)
-#else
-#define SNR16_PRIO(p) __builtin_amdgcn_s_setprio(p)       /* prologue and tail at high priority: see snr_mlp16.hip */
-#endif
-
 // MODE 0: explicit points (backward of SUPNeRF.forward).  MODE 1: fused render.
 template <int MODE>
 __global__ void __launch_bounds__(256, 2)
@@ -290,7 +284,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     const long long tile32m = (tile32 * 32 < io.n_points) ? tile32 : 0;       // (wave tiles past the end read tile 0's bits: results discarded)
 
     SNR16_BSTAMP(0);
-    SNR16_PRIO(3);
+    __builtin_amdgcn_s_setprio(3);       // prologue and tail at high priority: see snr_mlp16.hip
     Dma16 dm;
     dm.voff = lane * 16u + 4096u;
     dm.lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)lds);
@@ -399,7 +393,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();             // chunk 0 and sigma_w have landed; every wave is done with the composite scratch (ring buffer 1)
 
-    SNR16_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     SNR16_BSTAMP(2);
     // ---- rgb.0^T : 128 -> 256
     f32x4 accP[18];
@@ -408,9 +402,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     load_bits(relu_slot(li_last, sb), mw_next);          // the first boundary's bits (layer li_last's), requested before its chunks
     layer_b<16, 4, false>(accP, xh, ring, lds, ones, dm, stream, layer_base(li_last), rows_of(li_last));
 
-#ifndef SNR16_TAILSTAMPS
     SNR16_BSTAMP(3);
-#endif
     // ---- 256-wide layers in reverse: texture .., enc_viewdir, enc_shape, shape ..
     f32x4 gdir[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     int la_pending = -1;               // latent layer whose four wave rows wait in LDS for the next rendezvous
@@ -441,11 +433,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
         // accP = gradient wrt the INPUT of layer li = previous output + latent term
         const int la = latent_after(li - 1, sb, tb);
         if (la >= 0 && io.partial) { reduce16_store(accP, lds + LB_RED + wave * 256, lane, tile_live); la_pending = la; }
-        if (li == li_view) { gdir[0] = accP[16]; gdir[1] = accP[17];
-#ifndef SNR16_TAILSTAMPS
-            SNR16_BSTAMP(4);
-#endif
-        }
+        if (li == li_view) { gdir[0] = accP[16]; gdir[1] = accP[17]; SNR16_BSTAMP(4); }
     }
     SNR16_BSTAMP(5);
 
@@ -453,7 +441,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     layer_xyz_b(accP, ring, lds, mw_next, dm, layer_base(0), flush);
 
     SNR16_BSTAMP(6);
-    SNR16_PRIO(3);
+    __builtin_amdgcn_s_setprio(3);
     // ---- positional-encoding backward through the per-wave scratch rows (over ring buffer 0: the stream is done, every wave passed its last barrier)
     float* sc = lds + wave * PE_WAVE16 + n * PE_ROW;
 #pragma unroll
@@ -465,9 +453,6 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
 #pragma unroll
         for (int r = 0; r < 4; ++r) sc[64 + 16 * T + 4 * g + r] = gdir[T][r];
     __syncthreads();
-#ifdef SNR16_TAILSTAMPS
-    SNR16_BSTAMP(3);
-#endif
     float gx = 0.f, gy = 0.f, gz = 0.f, hx = 0.f, hy = 0.f, hz = 0.f;
     auto pe_grad = [&](const float* row, int q, int n_freq, float sn, float cs, float& ax, float& ay, float& az) {
         const int a = q % 3, f = q / 3;
@@ -501,9 +486,6 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     hx += __shfl_xor(hx, 16, 64); hx += __shfl_xor(hx, 32, 64);
     hy += __shfl_xor(hy, 16, 64); hy += __shfl_xor(hy, 32, 64);
     hz += __shfl_xor(hz, 16, 64); hz += __shfl_xor(hz, 32, 64);
-#ifdef SNR16_TAILSTAMPS
-    SNR16_BSTAMP(4);
-#endif
 
     if (MODE == 0) {
         if (live && g == 0) {

@@ -1,7 +1,6 @@
 // Shared pieces of the two-waves-per-SIMD fp32 kernels (forward: snr_mlp16.hip, backward: snr_mlp16_bwd.hip): the LDS map, the scalar-base
 // LDS-DMA of the weight ring, and the v_mfma_f32_16x16x4_f32 tile product with its fragment pipeline.
 #pragma once
-#include <stdlib.h>
 #include "snr_mlp_core.hpp"
 
 namespace snr {

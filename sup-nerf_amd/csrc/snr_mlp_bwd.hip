@@ -364,12 +364,10 @@ static size_t bwd_ws_bytes(int64_t n_points, int64_t points_per_obj, int sb, int
     return (size_t)((tiles * (int64_t)(sb + tb) * 256 + tree) * sizeof(float) + 256);
 }
 
-// the exact-fp32 backward: the two-waves-per-SIMD kernel where it applies (no training dumps, a ray inside 64 points), else the
-// one-wave 32x32x2 kernel of rounds 1-3 (-DSNR_BWD32: always, for A/B timing).  *tile = points per partial row.
+// the exact-fp32 backward: the two-waves-per-SIMD kernel where it applies (no training dumps, a ray inside 64 points, latent gradients
+// only for objects of a multiple of 64 points), else the one-wave 32x32x2 kernel of rounds 1-3.  *tile = points per partial row.
 static int launch_fp32_bwd(int mode, const BwdIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, void* stream_, int* tile) {
-#ifndef SNR_BWD32
     if (snr_fp32_bwd16_supported_(mode, io, g)) { *tile = 64; return snr_fp32_bwd16_launch_(mode, io, L, xyz, viewdir, g, stream_); }
-#endif
     *tile = 32;
     const unsigned grid = (unsigned)((io.n_points + 127) / 128);
     if (mode == 0) decoder_bwd_kernel<0><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);

@@ -29,6 +29,10 @@ def test_library_exports_every_declared_symbol(amd):
     declared = set(re.findall(r"\b(snr_[a-z_0-9]+)\s*\(", hdr))
     assert declared == set(amd._lib.exported_symbols()), declared ^ set(amd._lib.exported_symbols())
     lib = amd._lib.lib()                      # loads without a GPU; no compute call is made here
+    # ... and nothing else: no kernel handle, C++ launcher or internal helper in the dynamic symbol table
+    nm = subprocess.run(["nm", "-D", "--defined-only", amd._lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    dynamic = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    assert dynamic == declared, (sorted(dynamic - declared)[:20], sorted(declared - dynamic))
     for s in declared:
         assert hasattr(lib, s)
     assert lib.snr_abi_version() == amd._lib.header_abi_version() == int(re.search(r"SNR_ABI_VERSION (\d+)", hdr).group(1))

@@ -93,11 +93,6 @@ for _ in range(3):
                                  d_lat.data_ptr(), d_o.data_ptr(), d_d.data_ptr(), dbg2.data_ptr(), ws.data_ptr(), wsb, stream()) == 0
 torch.cuda.synchronize()
 rawb = dbg2.cpu().numpy().view(np.uint64).reshape(-1, 8)[: N * S // 16].astype(np.int64)
-if os.environ.get("SNR_STAMP_TAIL"):      # library built with -DSNR16_TAILSTAMPS: slots 3, 4 lie inside the tail
-    for a_, b_, nm in ((6, 3, "enc_xyz^T done -> scratch written + barrier"), (3, 4, "-> encoding gradient done"), (4, 7, "-> end (ray tail)")):
-        dd = rawb[:, b_] - rawb[:, a_]
-        print(f"  tail: {nm:46s} median {np.median(dd):8.0f}  p10 {np.percentile(dd, 10):8.0f}  p90 {np.percentile(dd, 90):8.0f}")
-    rawb[:, 3] = rawb[:, 2]; rawb[:, 4] = rawb[:, 2]
 report("backward", rawb,
        ["start", "composite backward done", "colour head done", "rgb.0^T done", "texture^T + enc_viewdir^T", "enc_shape^T + shape^T", "enc_xyz^T done", "end (encoding, ray tail)"])
 print("per wave: 7040 MFMAs x 32 cycles = 225280 cycles of matrix work; two waves share a SIMD's pipe")
