@@ -166,7 +166,7 @@ class given_relu_masks:
 def decoder_forward(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor,
                     shape_code: Tensor, texture_code: Tensor,
                     num_xyz_freq: int = 10, num_dir_freq: int = 4,
-                    relu_masks: Optional[Sequence[Tensor]] = None) -> Tuple[Tensor, Tensor]:
+                    relu_masks: Optional[Sequence[Tensor]] = None, latent: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """sigma (N,S,1), rgb (N,S,3) for xyz/viewdir (N,S,3) and codes (B,latent).
 
     Restates ``SUPNeRF.forward`` (src/model_supnerf.py:241-269) ==
@@ -179,6 +179,9 @@ def decoder_forward(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor,
     pre-activation sits within rounding of zero lands on either side of the ReLU depending on the summation order, which moves
     that point's gradient by percents in ANY two correct implementations; with the masks an implementation saved, the oracle
     differentiates the same piecewise-linear function as that implementation, and the comparison can be tight.
+
+    ``latent`` (tests only): the (B, shape_blocks+texture_blocks, W) latent terms ``latent_terms`` would compute; given, the codes are
+    not used (pass None) and autograd reaches the latent terms themselves, the quantity the backward kernels return.
     """
     relu_i = [0]
     if relu_masks is None:
@@ -193,25 +196,29 @@ def decoder_forward(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor,
 
     sb, tb = _count_blocks(params)
     n_ray = xyz.shape[0]
-    n_obj = shape_code.shape[0]
+    n_obj = (latent if latent is not None else shape_code).shape[0]
     per_obj = int(n_ray / n_obj)
-    # (B, L) -> (B*per_obj, 1, L): every ray of object b sees code b
-    shape_rows = shape_code.repeat_interleave(per_obj, dim=0).unsqueeze(1)
-    tex_rows = texture_code.repeat_interleave(per_obj, dim=0).unsqueeze(1)
+    if latent is not None:
+        # (B, NLAT, W) -> (B*per_obj, 1, W) per latent slot
+        lat_rows = [latent[:, j].repeat_interleave(per_obj, dim=0).unsqueeze(1) for j in range(sb + tb)]
+    else:
+        # (B, L) -> (B*per_obj, 1, L): every ray of object b sees code b
+        shape_rows = shape_code.repeat_interleave(per_obj, dim=0).unsqueeze(1)
+        tex_rows = texture_code.repeat_interleave(per_obj, dim=0).unsqueeze(1)
 
     def lin(name, t):
         return F.linear(t, params[name + ".weight"], params[name + ".bias"])
 
     h = relu(lin("encoding_xyz.0", positional_encoding(xyz, num_xyz_freq)))
     for j in range(1, sb + 1):
-        z = F.relu(lin(f"shape_latent_layer_{j}.0", shape_rows))
+        z = lat_rows[j - 1] if latent is not None else F.relu(lin(f"shape_latent_layer_{j}.0", shape_rows))
         h = relu(lin(f"shape_layer_{j}.0", h + z))
     h = lin("encoding_shape", h)                       # no activation
     sigma = F.softplus(lin("sigma.0", h))              # beta=1, threshold=20
     h = relu(lin("encoding_viewdir.0",
                  torch.cat([h, positional_encoding(viewdir, num_dir_freq)], dim=-1)))
     for j in range(1, tb + 1):
-        z = F.relu(lin(f"texture_latent_layer_{j}.0", tex_rows))
+        z = lat_rows[sb + j - 1] if latent is not None else F.relu(lin(f"texture_latent_layer_{j}.0", tex_rows))
         h = relu(lin(f"texture_layer_{j}.0", h + z))
     rgb = lin("rgb.2", relu(lin("rgb.0", h)))          # raw linear output, no sigmoid
     return sigma, rgb
