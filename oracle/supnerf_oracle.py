@@ -166,7 +166,8 @@ class given_relu_masks:
 def decoder_forward(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor,
                     shape_code: Tensor, texture_code: Tensor,
                     num_xyz_freq: int = 10, num_dir_freq: int = 4,
-                    relu_masks: Optional[Sequence[Tensor]] = None, latent: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                    relu_masks: Optional[Sequence[Tensor]] = None, latent: Optional[Tensor] = None,
+                    taps: Optional[list] = None) -> Tuple[Tensor, Tensor]:
     """sigma (N,S,1), rgb (N,S,3) for xyz/viewdir (N,S,3) and codes (B,latent).
 
     Restates ``SUPNeRF.forward`` (src/model_supnerf.py:241-269) ==
@@ -182,6 +183,8 @@ def decoder_forward(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor,
 
     ``latent`` (tests only): the (B, shape_blocks+texture_blocks, W) latent terms ``latent_terms`` would compute; given, the codes are
     not used (pass None) and autograd reaches the latent terms themselves, the quantity the backward kernels return.
+
+    ``taps`` (tests only): a list that receives (name, input, output) of every linear layer in call order (``decoder_taps``).
     """
     relu_i = [0]
     if relu_masks is None:
@@ -207,7 +210,10 @@ def decoder_forward(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor,
         tex_rows = texture_code.repeat_interleave(per_obj, dim=0).unsqueeze(1)
 
     def lin(name, t):
-        return F.linear(t, params[name + ".weight"], params[name + ".bias"])
+        out = F.linear(t, params[name + ".weight"], params[name + ".bias"])
+        if taps is not None:
+            taps.append((name, t, out))
+        return out
 
     h = relu(lin("encoding_xyz.0", positional_encoding(xyz, num_xyz_freq)))
     for j in range(1, sb + 1):
@@ -222,6 +228,37 @@ def decoder_forward(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor,
         h = relu(lin(f"texture_layer_{j}.0", h + z))
     rgb = lin("rgb.2", relu(lin("rgb.0", h)))          # raw linear output, no sigmoid
     return sigma, rgb
+
+
+_HEADS = ("sigma.0", "rgb.2")
+
+
+def decoder_taps(params: Dict[str, Tensor], xyz: Tensor, viewdir: Tensor, latent: Tensor, d_sig: Tensor, d_rgb: Tensor,
+                 relu_masks: Optional[Sequence[Tensor]] = None, dtype: torch.dtype = torch.float64):
+    """What the training kernels write to HBM for the points ``xyz``, ``viewdir`` (P,3) of B objects (object-major, P / B each), latent terms
+    ``latent`` (B, NLAT, 256) and upstream gradients ``d_sig`` (P,) / ``d_rgb`` (P,3), computed in ``dtype`` (tests only).
+
+    The MFMA layers are numbered in forward order: 0 encoding_xyz, 1..sb shape layers, sb+1 encoding_shape, sb+2 encoding_viewdir,
+    sb+3..sb+tb+2 texture layers, sb+tb+3 rgb.0 -- n = sb+tb+4 slots.  Returns (X, G, g_sigma):
+    * X[l] (P, 256): the output of layer l after its activation and after the latent term is added, i.e. the input of layer l+1 (for the
+      view layer its first 256 columns); X[n-1] = ReLU(rgb.0), the input of rgb.2, 128 columns (``activations`` of snr_decoder_fwd).
+    * G[l] (P, 256): the gradient wrt layer l's pre-activation; encoding_shape's includes the density head's term, rgb.0's has 128 columns
+      (``layer_grads`` of snr_decoder_bwd).
+    * g_sigma (P, 1): the gradient wrt the density head's pre-activation.
+    So dW_l = G[l]^T X[l-1] (layer 0: the positional encoding of xyz; the view layer: X[sb+1] | PE(viewdir)) and db_l = sum_p G[l]."""
+    p = {k: v.detach().to(dtype).requires_grad_() for k, v in params.items()}
+    xyz, viewdir = xyz.detach().to(dtype).reshape(-1, 1, 3), viewdir.detach().to(dtype).reshape(-1, 1, 3)
+    rec = []
+    with torch.enable_grad():
+        sigma, rgb = decoder_forward(p, xyz, viewdir, None, None, relu_masks=relu_masks, latent=latent.detach().to(dtype), taps=rec)
+        mfma = [(i, o) for n, i, o in rec if n not in _HEADS]
+        heads = {n: (i, o) for n, i, o in rec if n in _HEADS}
+        grads = torch.autograd.grad([sigma, rgb], [o for _, o in mfma] + [heads["sigma.0"][1]],
+                                    [d_sig.detach().to(dtype).reshape(sigma.shape), d_rgb.detach().to(dtype).reshape(rgb.shape)])
+    P = xyz.shape[0]
+    X = [i[..., :256].detach().reshape(P, -1) for i, _ in mfma[1:]] + [heads["rgb.2"][0].detach().reshape(P, -1)]
+    G = [g.reshape(P, -1) for g in grads[:-1]]
+    return X, G, grads[-1].reshape(P, 1)
 
 
 # --------------------------------------------------------------------------

@@ -282,7 +282,8 @@ class _DecoderBase(nn.Module):
             #   "bf16x3" = the split kernels, insisting (raises where unsupported);
             #   a tuple (forward chain, backward chain[, products]) picks each piece.
             x3, d3 = xyz.reshape(-1, 3), viewdir.reshape(-1, 3)
-            ppo, probe_pts = self._points_shape(x3, d3, lat, pad=lat.shape[1] > 0)
+            # (padded like DecoderPointsTrain pads: only when there are latent terms -- ``lat`` has a dummy row when there are none)
+            ppo, probe_pts = self._points_shape(x3, d3, lat, pad=self.shape_blocks + self.texture_blocks > 0)
             prec = self.precision
             if prec in (None, "auto"):
                 packed = ops._packed_for(ops.per_point_tensor_names(self.shape_blocks, self.texture_blocks), w, self.shape_blocks,
