@@ -11,7 +11,19 @@ src/optimizer_kitti.py:13-16, src/optimizer_waymo.py:13-16), ``from utils import
   * in ``model_supnerf`` / ``model_codenerf`` / ``model_autorf``: ``SUPNeRF`` / ``CodeNeRF`` / ``AutoRFMix`` -> the reference's OWN class
     with this package's HIP ``forward`` grafted on (``model.hip_decoder_class``): its constructor builds the stock ``ImgEncoder`` as
     src/model_supnerf.py:168-175 does, the state-dict is the reference's key for key (strict ``load_state_dict`` of
-    src/optimizer_nuscenes.py:1796 passes), ``encode_img`` / ``pose_update`` stay stock PyTorch.
+    src/optimizer_nuscenes.py:1796 passes), ``encode_img`` / ``pose_update`` stay stock PyTorch;
+  * in ``trainer_unified_nuscenes`` / ``trainer_nerf_nuscenes`` (train_nuscenes.py:9-10; recognised as the modules that define an
+    ``nn.Module`` named ``ParallelModel``): ``ParallelModel`` -> a subclass of the reference's own class (``training_wrapper_class``) whose
+    constructor runs the original and then sets ``train_decoder_weights = True`` on the decoder it wraps
+    (src/trainer_unified_nuscenes.py:227-229), so that the trainers' ``loss_total.mean().backward()`` reaches the 28 decoder tensors their
+    AdamW steps (:414-421).  ``nn.DataParallel`` replicas copy the flag with their shallow ``__dict__`` copy.
+
+The reference's optimisers (src/optimizer_nuscenes.py:1762-1769) keep the decoder a constant: its weights still ``requires_grad``, but their
+AdamW holds codes and pose only.  A trainer that is NOT recognised would step a decoder that never receives a gradient, silently; while
+installed, one global ``torch.optim`` step pre-hook raises ``SnrError`` instead, before the step changes anything, when the stepping optimizer
+holds a decoder weight that a constant-decoder forward (``train_decoder_weights`` False, grad mode) saw requiring a gradient and whose
+``grad`` is None (or, seen through an ``nn.DataParallel`` replica, only the zeros ``Broadcast.backward`` fills in).  The message names the
+parameter; the fix is ``model.train_decoder_weights = True``.
 
 Modules that are already imported are patched in place, and every module that did ``from utils import render_rays_v2`` BEFORE the
 install is re-pointed too (its global is the original function object: found by identity).  Modules that are imported LATER are patched
@@ -25,9 +37,13 @@ import sys
 import threading
 import types
 
+import torch.nn as nn
+from torch.optim.optimizer import register_optimizer_step_pre_hook
+
 from . import model as M
 from . import renderer as R
 from . import utils as U
+from ._lib import SnrError
 
 # what is rebound, by the KIND of reference module (recognised by content, under whichever name the caller imported it)
 UTILS_NAMES = ("render_rays", "render_rays_v2", "render_rays_specified", "render_full_img", "render_virtual_imgs", "prepare_pixel_samples",
@@ -35,12 +51,14 @@ UTILS_NAMES = ("render_rays", "render_rays_v2", "render_rays_specified", "render
                "sample_from_rays", "sample_from_rays_v2", "ray_box_intersection", "ray_box_intersection_tensor")
 RENDERER_NAMES = ("NeRFRenderer", "render_rays_v3", "volume_rendering3")
 DECODER_CLASSES = ("SUPNeRF", "CodeNeRF", "AutoRFMix")
-# module names the reference's scripts use for the four files (top-level after sys.path.insert(0, 'src'), or through the src package)
-TARGET_MODULES = tuple(p + n for n in ("utils", "renderer", "model_supnerf", "model_codenerf", "model_autorf") for p in ("", "src."))
+TRAINER_CLASS = "ParallelModel"
+# module names the reference's scripts use for its files (top-level after sys.path.insert(0, 'src'), or through the src package)
+TARGET_MODULES = tuple(p + n for n in ("utils", "renderer", "model_supnerf", "model_codenerf", "model_autorf", "trainer_unified_nuscenes",
+                                       "trainer_nerf_nuscenes") for p in ("", "src."))
 
 _ORIG = "__supnerf_amd_originals__"
 _LOCK = threading.RLock()
-_state = {"hook": None, "patched": [], "rebound": []}
+_state = {"hook": None, "step_hook": None, "patched": [], "rebound": []}
 
 
 def _kind(mod):
@@ -54,17 +72,71 @@ def _kind(mod):
     return None
 
 
+def _trainer_class(mod):
+    """The reference's own ``ParallelModel`` if ``mod`` defines one (src/trainer_unified_nuscenes.py:19, src/trainer_nerf_nuscenes.py:18),
+    else None.  Independent of ``_kind``: trainer_unified_nuscenes also holds ``SUPNeRF`` and is a "model" importer as well."""
+    c = getattr(mod, "__dict__", {}).get(TRAINER_CLASS)
+    if isinstance(c, type) and issubclass(c, nn.Module) and c.__module__ == getattr(mod, "__name__", None):
+        return c.__dict__.get("__supnerf_amd_original__", c)
+    return None
+
+
+_WRAPPERS = {}
+
+
+def training_wrapper_class(ref_cls):
+    """A subclass of the reference's ``ParallelModel`` whose constructor runs the original one and then, if the ``model`` it received (the
+    reference's first parameter, src/trainer_unified_nuscenes.py:20) is one of this package's decoders, sets ``train_decoder_weights = True``
+    on it: the reference's trainers differentiate the decoder weights and step them.  Any other model (a stock ``nn.Module``, ``None``) is
+    left alone.  Built from the caller's class object at run time, like ``model.hip_decoder_class``; nothing of the reference is stored."""
+    hit = _WRAPPERS.get(ref_cls)
+    if hit is not None:
+        return hit
+
+    def __init__(self, *args, **kwargs):
+        ref_cls.__init__(self, *args, **kwargs)
+        model = kwargs["model"] if "model" in kwargs else (args[0] if args else None)
+        if isinstance(model, M._DecoderBase):
+            model.train_decoder_weights = True
+
+    cls = type(ref_cls.__name__, (ref_cls,), {
+        "__init__": __init__, "__module__": ref_cls.__module__, "__qualname__": ref_cls.__qualname__,
+        "__doc__": f"{ref_cls.__module__}.{ref_cls.__name__} that trains a supnerf_amd decoder (supnerf_amd.binding.training_wrapper_class).",
+        "__supnerf_amd_original__": ref_cls})
+    _WRAPPERS[ref_cls] = cls
+    return cls
+
+
+def _step_pre_hook(optimizer, args, kwargs):
+    """Global ``torch.optim`` step pre-hook while installed (module docstring): raise before a step over a decoder weight that a constant-
+    decoder forward left without a gradient.  Per step: one membership test per parameter of the optimizer."""
+    runs = M._CONSTANT_RUNS
+    if not runs:
+        return None
+    held = [p for group in optimizer.param_groups for p in group["params"] if id(p) in runs]
+    for p in held:
+        ref, name, via_replica = runs.get(id(p), (None, None, False))
+        if ref is not None and ref() is p and (p.grad is None or via_replica):
+            raise SnrError(f"supnerf_amd: {type(optimizer).__name__}.step() would update the decoder parameter '{name}' "
+                           f"{tuple(p.shape)}, which has no gradient: the decoder ran as a constant (model.train_decoder_weights is "
+                           "False), so it would never train.  Set model.train_decoder_weights = True before the forward to train the "
+                           "decoder, or leave the decoder's weights out of the optimizer to optimise codes / poses only.")
+    for p in held:                  # seen by a step: "since the last step" starts again for these
+        runs.pop(id(p), None)
+    return None
+
+
 def _is_ours(mod):
     return getattr(mod, "__name__", "").split(".")[0] == "supnerf_amd"
 
 
 def patch_module(mod):
     """Rebind the hot-path names of ONE reference module (see the module docstring).  Returns {name: (original, replacement)}; a module
-    that is not one of the reference's four files (or is this package's own) is left alone."""
+    that is not one of the reference's files named above (or is this package's own) is left alone."""
     if mod is None or _is_ours(mod):
         return {}
-    kind = _kind(mod)
-    if kind is None:
+    kind, trainer = _kind(mod), _trainer_class(mod)
+    if kind is None and trainer is None:
         return {}
     with _LOCK:
         saved = mod.__dict__.setdefault(_ORIG, {})
@@ -86,12 +158,14 @@ def patch_module(mod):
             for n in RENDERER_NAMES:
                 if n in mod.__dict__:
                     rebind(n, getattr(R, n))
-        else:
+        elif kind == "model":
             for n in DECODER_CLASSES:
                 c = mod.__dict__.get(n)
                 # only a class this module DEFINES: optimizer_*.py also hold ``SUPNeRF`` as an imported name (re-pointed by identity below)
                 if isinstance(c, type) and c.__module__ == mod.__name__ and not issubclass(c, M._DecoderBase):
                     rebind(n, M.hip_decoder_class(c))
+        if trainer is not None:
+            rebind(TRAINER_CLASS, training_wrapper_class(trainer))
         if done and mod not in _state["patched"]:
             _state["patched"].append(mod)
         return done
@@ -183,15 +257,22 @@ def install(model_module=None, utils_module=None, renderer_module=None, *, extra
         if hook and _state["hook"] is None:
             _state["hook"] = _PatchFinder()
             sys.meta_path.insert(0, _state["hook"])
+        if _state["step_hook"] is None:
+            M._CONSTANT_RUNS = {}
+            _state["step_hook"] = register_optimizer_step_pre_hook(_step_pre_hook)
         return {"patched": report, "rebound": n, "hook": _state["hook"] is not None}
 
 
 def uninstall():
-    """Undo ``install``: restore every rebound name and remove the import hook."""
+    """Undo ``install``: restore every rebound name and remove the import hook and the optimizer step hook."""
     with _LOCK:
         if _state["hook"] is not None and _state["hook"] in sys.meta_path:
             sys.meta_path.remove(_state["hook"])
         _state["hook"] = None
+        if _state["step_hook"] is not None:
+            _state["step_hook"].remove()
+            _state["step_hook"] = None
+        M._CONSTANT_RUNS = None
         for mod, name, old in reversed(_state["rebound"]):
             mod.__dict__[name] = old
         _state["rebound"].clear()

@@ -24,6 +24,8 @@
 // The fma chain of an output differs from the 32x32x2 kernel's in the ORDER of the k terms (a 16x16x4 MFMA sums k = 16 T + {r, 4 + r,
 // 8 + r, 12 + r}, the 32x32x2 form k = 32 c + 8 j + {e, 4 + e}): both are exact fp32 fma chains over the same products, results agree
 // to fp32 round-off, not bit for bit.
+#include <atomic>
+
 #include "snr_mlp16_core.hpp"
 #include "snr_host.hpp"
 
@@ -430,10 +432,15 @@ template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
 static int launch16(const DecoderIO& io, const Layout& L, const Lds16& lo, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
                     float* depth, float* acc, hipStream_t st) {
     auto kern = decoder_fwd16_kernel<MODE, WAVES, LATLDS, MASKS, DUMP>;
-    static bool attr_set = false;          // (dynamic LDS beyond the default cap must be granted once per kernel)
-    if (!attr_set) {
+    // Dynamic LDS beyond the default cap must be granted per kernel, and (if HIP scopes the attribute per device) per device: one bit per
+    // device that has it.  nn.DataParallel enters here from one host thread per device.  Two threads may both grant it; that is harmless.
+    static std::atomic<uint64_t> granted{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return SNR_E_LAUNCH;
+    const uint64_t bit = dev < 64 ? (uint64_t)1 << dev : 0;          // (devices past 64: granted on every launch)
+    if (!(granted.load(std::memory_order_acquire) & bit)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SNR_E_LAUNCH;
-        attr_set = true;
+        granted.fetch_or(bit, std::memory_order_release);
     }
     const unsigned grid = (unsigned)((io.n_points + WAVES * 16 - 1) / (WAVES * 16));
     kern<<<grid, WAVES * 64, (size_t)lo.total * 4, st>>>(io, L, lo, xyz, viewdir, g, rgb, depth, acc);

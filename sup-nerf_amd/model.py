@@ -15,6 +15,7 @@ What runs where:
 import importlib
 import sys
 import threading
+import weakref
 from typing import Optional
 
 import torch
@@ -35,6 +36,42 @@ def _leaf(module, name):
         if p is None:
             p = getattr(module, name)
     return p
+
+
+def _grad_leaf(t):
+    """The tensor whose ``.grad`` a backward through the weight ``t`` fills: ``t`` itself, or -- in a replica made by
+    ``torch.nn.parallel.replicate`` -- the source parameter: the replica's weights are outputs of ONE ``Broadcast`` over all the source
+    parameters, output k <- input k mod (number of inputs), and ``Broadcast.backward`` sums into that input.  None when neither applies."""
+    if t.is_leaf:
+        return t
+    fn = t.grad_fn
+    if type(fn).__name__ != "BroadcastBackward":
+        return None
+    nxt = fn.next_functions
+    src = getattr(nxt[t.output_nr % len(nxt)][0], "variable", None) if nxt else None
+    return src if src is not None and src.shape == t.shape else None
+
+
+# supnerf_amd.install()'s safety net (binding.py): while it is active, a forward that treats the decoder as a CONSTANT under grad mode
+# (``train_decoder_weights`` False) notes here the weights that require a gradient they will not get,
+# {id(leaf): (weakref, state-dict name, through a replica)}; an optimizer step over one of them without a gradient then raises.  A weight
+# seen through a replica counts as without one whatever its ``grad``: ``Broadcast.backward`` hands every source parameter zeros as soon as
+# any replica weight (the encoder's, the pose head's) is differentiated.  None (not installed): nothing is noted.
+_CONSTANT_RUNS = None
+
+
+_WEIGHT_PATHS = {}
+
+
+def _decoder_weight_paths(shape_blocks, texture_blocks):
+    """(state-dict name, submodule path, parameter name) of every decoder weight: the per-point layers and the latent layers."""
+    hit = _WEIGHT_PATHS.get((shape_blocks, texture_blocks))
+    if hit is None:
+        names = list(ops.per_point_tensor_names(shape_blocks, texture_blocks))
+        names += [f"{k}_latent_layer_{j + 1}.0.{q}" for k, n in (("shape", shape_blocks), ("texture", texture_blocks))
+                  for j in range(n) for q in ("weight", "bias")]
+        hit = _WEIGHT_PATHS[(shape_blocks, texture_blocks)] = tuple((n, tuple(n.split(".")[:-1]), n.split(".")[-1]) for n in names)
+    return hit
 
 
 # One lock for the two per-module weight caches (packed stream, stacked latent layers): the decoder is entered from one thread per GPU under
@@ -106,6 +143,29 @@ class _DecoderBase(nn.Module):
 
     def _per_point_params(self):
         return {n: self._param(n) for n in ops.per_point_tensor_names(self.shape_blocks, self.texture_blocks)}
+
+    def _note_decoder_run(self, constant):
+        """Under ``install()`` and grad mode, tell the optimizer step hook (see ``_CONSTANT_RUNS``) which decoder weights (per-point and latent
+        layers) requiring a gradient this forward left without one (``constant``: a constant-decoder forward with ``train_decoder_weights``
+        False), or differentiated after all (a training-mode forward: their earlier notes are dropped)."""
+        runs = _CONSTANT_RUNS
+        if runs is None or not torch.is_grad_enabled() or (constant and self.train_decoder_weights) or (not constant and not runs):
+            return
+        for name, path, leaf_name in _decoder_weight_paths(self.shape_blocks, self.texture_blocks):
+            m = self
+            for part in path:
+                m = m._modules[part]
+            t = _leaf(m, leaf_name)
+            leaf = _grad_leaf(t) if t.requires_grad else None
+            if leaf is None:
+                continue
+            if not constant:
+                runs.pop(id(leaf), None)
+                continue
+            via_replica = leaf is not t
+            old = runs.get(id(leaf))
+            if old is None or old[0]() is not leaf or old[2] != via_replica:
+                runs[id(leaf)] = (weakref.ref(leaf), name, via_replica)
 
     def packed_weights(self) -> torch.Tensor:
         pp = self._per_point_params()
@@ -266,6 +326,7 @@ class _DecoderBase(nn.Module):
         lat = self.latent_terms(shape_latent, texture_latent)
         if self.train_decoder_weights and torch.is_grad_enabled():
             # training mode (src/trainer_unified_nuscenes.py:120-129,334): gradients also reach the per-point decoder weights
+            self._note_decoder_run(constant=False)
             w = [p for p in self._per_point_params().values()]
             # ``precision`` decides the arithmetic of the step.  Evidence (60 AdamW steps against the same steps on the CPU oracle in float64,
             # tests/test_driver_gpu.py::test_training_outcome_fp32_and_bf16x3_track_the_oracle; all the combinations:
@@ -295,6 +356,7 @@ class _DecoderBase(nn.Module):
                 self._auto_precision(prec, ppo, None)
             sig, rgb = ops.DecoderPointsTrain.apply(x3, d3, lat, self.shape_blocks, self.texture_blocks, prec, *w)
             return sig.view(*lead, 1), rgb.view(*lead, 3)
+        self._note_decoder_run(constant=True)
         x3, d3 = xyz.reshape(-1, 3), viewdir.reshape(-1, 3)
         packed = self.packed_weights()
         need_lat = torch.is_grad_enabled() and lat.requires_grad and self.shape_blocks + self.texture_blocks > 0
@@ -318,6 +380,7 @@ class _DecoderBase(nn.Module):
 
     def fused_render(self, rays_o, rays_d, t_vals, xyz_div, z_scale, shape_latent, texture_latent, cfg: "ops.RenderCfg"):
         """rays -> (rgb (N,3), depth (N,), acc_trans (N,)) in one launch (see ops.FusedRender)."""
+        self._note_decoder_run(constant=True)
         lat = self.latent_terms(shape_latent, texture_latent)
         packed = self.packed_weights()
         cfg.latent_bias = self.latent_biases(lat)

@@ -3,7 +3,9 @@
 MI355X path.
 
 What it does, in this order: (1) ``supnerf_amd.install()`` -- the import hook that re-points ``utils.render_rays_v2`` ...,
-``model_supnerf.SUPNeRF`` ..., ``renderer.NeRFRenderer`` ... as the script's own ``import`` statements load them (binding.py); (2) makes
+``model_supnerf.SUPNeRF`` ..., ``renderer.NeRFRenderer`` ... as the script's own ``import`` statements load them, and the trainers'
+``ParallelModel`` so that ``train_nuscenes.py`` trains the decoder (binding.py; an unrecognised trainer that would step a decoder without
+gradients gets an ``SnrError`` from ``optimizer.step()``); (2) makes
 ``sys.argv`` and ``sys.path[0]`` what ``python <script.py> ...`` would have made them (the scripts compute ``src/`` from the working
 directory themselves, optimize_nuscenes.py:1-3); (3) ``runpy.run_path(script, run_name='__main__')`` in THIS interpreter.  No GPU call is
 made before the script starts and no process is replaced (no ``exec``), so the launcher is safe on pools that forbid re-exec after HIP
