@@ -115,19 +115,23 @@ def _count_blocks(params: Dict[str, Tensor]) -> Tuple[int, int]:
     return sb, tb
 
 
-def latent_terms(params: Dict[str, Tensor], shape_code: Tensor, texture_code: Tensor) -> Tensor:
+def latent_terms(params: Dict[str, Tensor], shape_code: Tensor, texture_code: Tensor,
+                 relu_mask: Optional[Tensor] = None) -> Tensor:
     """Per-object latent vectors z_j = ReLU(Lin_j(code)) that the decoder adds to
     the hidden state before every shape / texture block
-    (src/model_supnerf.py:253,261).  Returns (B, shape_blocks+texture_blocks, W)."""
+    (src/model_supnerf.py:253,261).  Returns (B, shape_blocks+texture_blocks, W).
+
+    ``relu_mask`` (tests only): a 0/1 tensor shaped like the output whose entries are the ReLU's derivative (as
+    ``decoder_forward``'s ``relu_masks``): a pre-activation within rounding of zero does not flip between two implementations."""
     sb, tb = _count_blocks(params)
-    outs = []
+    pre = []
     for j in range(1, sb + 1):
-        outs.append(F.relu(F.linear(shape_code, params[f"shape_latent_layer_{j}.0.weight"],
-                                    params[f"shape_latent_layer_{j}.0.bias"])))
+        pre.append(F.linear(shape_code, params[f"shape_latent_layer_{j}.0.weight"], params[f"shape_latent_layer_{j}.0.bias"]))
     for j in range(1, tb + 1):
-        outs.append(F.relu(F.linear(texture_code, params[f"texture_latent_layer_{j}.0.weight"],
-                                    params[f"texture_latent_layer_{j}.0.bias"])))
-    return torch.stack(outs, dim=1)
+        pre.append(F.linear(texture_code, params[f"texture_latent_layer_{j}.0.weight"], params[f"texture_latent_layer_{j}.0.bias"]))
+    if relu_mask is not None:
+        return _ReluWithGivenMask.apply(torch.stack(pre, dim=1), relu_mask)
+    return torch.stack([F.relu(t) for t in pre], dim=1)
 
 
 class _ReluWithGivenMask(torch.autograd.Function):
@@ -448,6 +452,37 @@ def volume_rendering_batch(sigmas, rgbs, z_vals):
 def volume_rendering3(sigmas, rgbs, z_vals, white_bkgd=False):
     """src/renderer.py:355-379 -- z (N,S) per ray."""
     return composite(sigmas, rgbs, z_vals, white_bkgd=white_bkgd)
+
+
+def fused_render(params: Dict[str, Tensor], rays_o: Tensor, rays_d: Tensor, t_vals: Tensor, z_mode: str, n_samples: int,
+                 rays_per_obj: int, z_scale: Tensor, box_half: Optional[Tensor] = None, shape_code: Optional[Tensor] = None,
+                 texture_code: Optional[Tensor] = None, latent: Optional[Tensor] = None,
+                 relu_masks: Optional[Sequence[Tensor]] = None, white_bkgd: bool = False, metric_z: bool = False):
+    """What one ``snr_render_fwd`` launch computes (include/supnerf_hip.h) with xyz_div = xyz_mul = 1 and the identity frame: rays_o,
+    rays_d (N,3), ray r of object r // rays_per_obj, z_scale (B,).  Returns rgb (N,3), depth (N), acc_trans (N), differentiable in
+    every tensor argument (tests only).
+
+    ``z_mode`` lays out the depths t: "shared" t_vals (S,), "per_object" (B,S), "per_ray" (N,S); "box": t_vals is the (N,S) jitter
+    table, and the depths are family B's stratified samples between the bounds of the slab test of o_n = rays_o / z_scale against
+    +-box_half (B,3), near = far = -1 where the ray misses; the points then lie on o_n + t d.  ``metric_z`` (SNR_METRIC_Z): the
+    composite's depth is |t d| z_scale instead of t.  The decoder sees the codes, or given ``latent`` terms (``decoder_forward``)."""
+    N, S = rays_o.shape[0], n_samples
+    obj = torch.arange(N, device=rays_o.device) // rays_per_obj
+    zs = z_scale[obj]
+    if z_mode == "box":
+        o = rays_o / zs[:, None]
+        h = box_half[obj]
+        t_near, t_far, hit = slab_intersect(o, rays_d, -h, h)
+        minus1 = torch.full_like(t_near, -1.0)
+        t = unit_interval_samples(torch.where(hit, t_near, minus1)[:, None], torch.where(hit, t_far, minus1)[:, None], S, t_vals)
+    else:
+        o = rays_o
+        t = {"shared": lambda: t_vals[None, :].expand(N, S), "per_object": lambda: t_vals[obj], "per_ray": lambda: t_vals}[z_mode]()
+    xyz = o[:, None, :] + rays_d[:, None, :] * t[:, :, None]
+    z = torch.norm(xyz - o[:, None, :], dim=-1) * zs[:, None] if metric_z else t
+    sig, rgb = decoder_forward(params, xyz, rays_d[:, None, :].expand(N, S, 3), shape_code, texture_code, relu_masks=relu_masks,
+                               latent=latent)
+    return composite(sig, rgb, z, white_bkgd=white_bkgd)
 
 
 # --------------------------------------------------------------------------

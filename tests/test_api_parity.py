@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, dev, md  # noqa: F401  (amd, dev: fixtures)
 from relu_bits import relu_bits_of
 
 pytestmark = pytest.mark.gpu
@@ -14,18 +15,6 @@ pytestmark = pytest.mark.gpu
 TOL_RGB, TOL_ACC = 2e-5, 2e-5
 TOL_DEPTH_MEAN, TOL_DEPTH_MAX = 1e-5, 1e-4       # metres; north_star bound on the mean is 1e-4
 TOL_PSNR_DB = 0.01                               # north_star: PSNR delta <= 0.01 dB
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
 
 
 @pytest.fixture(scope="module", params=["fp32", "auto", ("fp32", "auto")], ids=["fp32", "auto", "fp32fwd_bf16x3bwd"])
@@ -44,10 +33,6 @@ def jitter(amd):
         amd.utils.JITTER_OVERRIDE = t
     yield set_
     amd.utils.JITTER_OVERRIDE = None
-
-
-def md(a, b):
-    return float((a.detach().double().cpu() - torch.as_tensor(b).double().cpu()).abs().max())
 
 
 def close_grad(a, b, rel=2e-4):

@@ -14,38 +14,11 @@ import pytest
 import torch
 
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, check_per_ray, dev, make_model, md, per_ray_errors, rel  # noqa: F401  (amd, dev: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 TOL_RGB, TOL_ACC, TOL_DEPTH_MEAN, TOL_DEPTH_MAX, TOL_PSNR = 2e-5, 2e-5, 1e-5, 1e-4, 0.01
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
-
-
-def make_model(amd, dev, params, precision):
-    m = amd.CodeNeRF(shape_blocks=3, texture_blocks=1)
-    m.load_state_dict(params, strict=True)
-    m.precision = precision
-    return m.to(dev)
-
-
-def md(a, b):
-    return float((a.detach().double().cpu() - torch.as_tensor(b).detach().double().cpu()).abs().max())
-
-
-def rel(a, b):
-    b = torch.as_tensor(b).detach().double().cpu()
-    return md(a, b) / (float(b.abs().max()) + 1e-30)
 
 
 def scene(index, im_sz, S, seed):
@@ -268,15 +241,12 @@ def test_family_b_per_ray_gradients_mask_matched(amd, dev, oracle_params, precis
     go64, gd64, _, _, gsc64, gtc64 = oracle(torch.float64)
     assert bool(hit.any()) and bool((~hit).any())
     assert md(fw[0], out32[0]) < TOL_RGB and md(fw[1], out32[1]) < TOL_DEPTH_MAX and md(fw[2], out32[2]) < TOL_ACC
+    bad = []
     for name, got, ref32, true in (("d_rays_o", d_o, go32, go64), ("d_rays_d", d_d, gd32, gd64)):
-        scale = true.abs().amax(dim=1).clamp_min(1e-12)                                     # per ray
-        err = (got.detach().cpu().double() - true).abs().amax(dim=1) / scale
-        floor = (ref32.double() - true).abs().amax(dim=1) / scale
-        bad = (err > 1e-3) & (err > 8 * floor)
-        print(f"[per-ray {name}, {precision}] median rel err {float(err.median()):.1e} (fp32 oracle {float(floor.median()):.1e}), "
-              f"99th pct {float(err.quantile(0.99)):.1e} ({float(floor.quantile(0.99)):.1e}), worst {float(err.max()):.1e}, rays outside the band: {int(bad.sum())}")
-        assert float(err.median()) < 2e-5 + 4 * float(floor.median())
-        assert int(bad.sum()) == 0, (name, torch.nonzero(bad).flatten()[:10], err[bad][:10], floor[bad][:10])
+        bad += check_per_ray(f"{name}, {precision}", got, ref32, true)
+        err, floor = per_ray_errors(got, ref32, true)
+        assert float(err.median()) < 2e-5 + 4 * float(floor.median()), (name, float(err.median()), float(floor.median()))
+    assert not bad, bad
     # the codes' gradients through the latent terms (the kernel's d_latent chained through the latent layers by torch): tight once the masks agree
     sc, tc = sc0.to(dev).requires_grad_(), tc0.to(dev).requires_grad_()
     model.latent_terms(sc, tc).backward(d_lat)

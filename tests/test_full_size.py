@@ -19,6 +19,7 @@ import torch
 
 from loop_oracle import oracle_loop
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, dev, make_model, md, rel  # noqa: F401  (amd, dev: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,34 +27,6 @@ N_RAYS, S, IM = 4096, 64, 64
 TOL_RGB, TOL_ACC, TOL_DEPTH_MEAN, TOL_DEPTH_MAX, TOL_PSNR = 2e-5, 2e-5, 1e-5, 1e-4, 0.01
 GRAD_REL = {"fp32": 2e-4, "auto": 2e-4}         # relative to the gradient's largest entry, aggregated over 4096 x 64 points: the same bound for
                                                  # both arithmetics (measured: fp32 7e-6 / 7e-5, bf16x3 4e-5 / 8e-5 for codes / pose)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
-
-
-def make_model(amd, dev, params, precision):
-    m = amd.CodeNeRF(shape_blocks=3, texture_blocks=1)
-    m.load_state_dict(params, strict=True)
-    m.precision = precision
-    return m.to(dev)
-
-
-def md(a, b):
-    return float((a.detach().double().cpu() - torch.as_tensor(b).detach().double().cpu()).abs().max())
-
-
-def rel(a, b):
-    b = torch.as_tensor(b).detach().double().cpu()
-    return md(a, b) / (float(b.abs().max()) + 1e-30)
 
 
 def psnr_fg(rgb, tgt, occ):

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, dev, md  # noqa: F401  (amd, dev: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -17,25 +18,9 @@ TOL_ACC = 2e-5
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
-
-
-@pytest.fixture(scope="module")
 def packed(amd, dev, oracle_params):
     p = {k: v.to(dev) for k, v in oracle_params.items()}
     return amd.ops.pack_weights(p, 3, 1), p
-
-
-def maxdiff(a, b):
-    return float((a.detach().double().cpu() - torch.as_tensor(b).double().cpu()).abs().max())
 
 
 # ------------------------------------------------------------------ composite
@@ -45,17 +30,17 @@ def test_composite_variants(amd, dev, golden):
     sig, rgbs = g["sigmas"].to(dev), g["rgbs"].to(dev)
     out = ops.composite_fwd(sig.squeeze(-1), rgbs, g["z_shared"].to(dev), ops.Z_SHARED, False)
     for a, k in zip(out, ("vr2_rgb", "vr2_depth", "vr2_acc")):
-        assert maxdiff(a, g[k]) < 2e-5, k
+        assert md(a, g[k]) < 2e-5, k
     out = ops.composite_fwd(sig.squeeze(-1), rgbs, g["z_ray"].to(dev), ops.Z_PER_RAY, True)
     for a, k in zip(out, ("white_rgb", "white_depth", "white_acc")):
-        assert maxdiff(a, g[k]) < 2e-5, k
+        assert md(a, g[k]) < 2e-5, k
     out = ops.composite_fwd(sig.squeeze(-1), rgbs, g["z_ray"].to(dev), ops.Z_PER_RAY, False)
     for a, k in zip(out, ("vr3_rgb", "vr3_depth", "vr3_acc")):
-        assert maxdiff(a, g[k]) < 2e-5, k
+        assert md(a, g[k]) < 2e-5, k
     B, S = g["z_obj"].shape
     out = ops.composite_fwd(sig.squeeze(-1), rgbs, g["z_obj"].to(dev), ops.Z_PER_OBJECT, False, rays_per_obj=sig.shape[0] // B)
     for a, k in zip(out, ("batch_rgb", "batch_depth", "batch_acc")):
-        assert maxdiff(a.view(g[k].shape), g[k]) < 2e-5, k
+        assert md(a.view(g[k].shape), g[k]) < 2e-5, k
 
 
 def test_composite_backward(amd, dev, golden):
@@ -65,11 +50,11 @@ def test_composite_backward(amd, dev, golden):
     rgbs = g["rgbs"].to(dev).requires_grad_()
     z = g["z"].to(dev).requires_grad_()
     r = ops.Composite.apply(sig, rgbs, z, ops.Z_PER_RAY, True, 0)
-    assert maxdiff(r[0], g["rgb"]) < 2e-5 and maxdiff(r[1], g["depth"]) < 2e-5 and maxdiff(r[2], g["acc"]) < 2e-5
+    assert md(r[0], g["rgb"]) < 2e-5 and md(r[1], g["depth"]) < 2e-5 and md(r[2], g["acc"]) < 2e-5
     ((r[0] * g["w_rgb"].to(dev)).sum() + (r[1] * g["w_depth"].to(dev)).sum() + (r[2] * g["w_acc"].to(dev)).sum()).backward()
-    assert maxdiff(sig.grad, g["d_sigmas"].squeeze(-1)) < 1e-4
-    assert maxdiff(rgbs.grad, g["d_rgbs"]) < 2e-5
-    assert maxdiff(z.grad, g["d_z"]) < 2e-4
+    assert md(sig.grad, g["d_sigmas"].squeeze(-1)) < 1e-4
+    assert md(rgbs.grad, g["d_rgbs"]) < 2e-5
+    assert md(z.grad, g["d_z"]) < 2e-4
 
 
 @pytest.mark.parametrize("S", [2, 7, 64, 65, 130, 256])   # S=1 is invalid in the reference too (empty delta)
@@ -87,10 +72,10 @@ def test_composite_ragged_sample_counts(amd, dev, S):
     out = ops.Composite.apply(sg, rg, zg, ops.Z_PER_RAY, True, 0)
     sum(((a * b.to(dev)).sum() for a, b in zip(out, w))).backward()
     for a, b in zip(out, ref):
-        assert maxdiff(a, b) < 3e-5
-    assert maxdiff(sg.grad, sig.grad) < 2e-4
-    assert maxdiff(rg.grad, rgbs.grad) < 3e-5
-    assert maxdiff(zg.grad, z.grad) < 5e-4
+        assert md(a, b) < 3e-5
+    assert md(sg.grad, sig.grad) < 2e-4
+    assert md(rg.grad, rgbs.grad) < 3e-5
+    assert md(zg.grad, z.grad) < 5e-4
 
 
 def test_composite_empty(amd, dev):
@@ -128,7 +113,7 @@ def test_partial_workgroups_stay_inside_their_buffers(amd, dev, packed, oracle_p
     assert lib.snr_decoder_fwd(ptr(x_d), ptr(v_d), ptr(lat_d), ptr(pk), P, P, 3, 1, ptr(sig), ptr(rgb), ptr(masks), None, prec, st) == 0
     torch.cuda.synchronize()
     assert bool((masks[mbytes:] == 0xAB).all()), "ReLU bits were stored past the end of the mask buffer"
-    assert maxdiff(sig, sig_o.view(P)) < 2e-5 and maxdiff(rgb, rgb_o.view(P, 3)) < 2e-5
+    assert md(sig, sig_o.view(P)) < 2e-5 and md(rgb, rgb_o.view(P, 3)) < 2e-5
     wsb = lib.snr_decoder_bwd_ws_bytes(P, P, 3, 1)
     ws = torch.full((wsb + 65536,), 0xCD, dtype=torch.uint8, device=dev)
     d_lat, d_x, d_v = torch.empty_like(lat_d), torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev)
@@ -145,8 +130,8 @@ def test_partial_workgroups_stay_inside_their_buffers(amd, dev, packed, oracle_p
     sc_m, tc_m = sc.clone().requires_grad_(), tc.clone().requires_grad_()
     sig_m, rgb_m = O.decoder_forward(oracle_params, xyz, vd, sc_m, tc_m, relu_masks=decode_relu_bits(masks[:mbytes], P, 3, 1))
     ((sig_m.view(P) * w_s).sum() + (rgb_m.view(P, 3) * w_c).sum()).backward()
-    assert maxdiff(sc_g.grad, sc_m.grad) <= 1e-4 * float(sc_m.grad.abs().max()) + 1e-7
-    assert maxdiff(tc_g.grad, tc_m.grad) <= 1e-4 * float(tc_m.grad.abs().max()) + 1e-7
+    assert md(sc_g.grad, sc_m.grad) <= 1e-4 * float(sc_m.grad.abs().max()) + 1e-7
+    assert md(tc_g.grad, tc_m.grad) <= 1e-4 * float(tc_m.grad.abs().max()) + 1e-7
 
 
 def test_scene_composite_golden(amd, dev, golden):
@@ -156,8 +141,8 @@ def test_scene_composite_golden(amd, dev, golden):
     S = g["b0_z"].shape[1] // n_obj
     for run in (0, S):          # rank sort, and the merge of the per-object sorted lists (what scene.py asks for)
         rgb, depth, acc = amd.ops.scene_composite(g["b0_sigmas"].to(dev), g["b0_rgbs"].to(dev), g["b0_z"].to(dev), run_length=run)
-        assert maxdiff(rgb, g["b0_rgb"]) < TOL_RGB and maxdiff(acc, g["b0_acc"]) < TOL_ACC
-        assert float((depth.cpu() - g["b0_depth"]).abs().mean()) < TOL_DEPTH_MEAN and maxdiff(depth, g["b0_depth"]) < TOL_DEPTH_MAX
+        assert md(rgb, g["b0_rgb"]) < TOL_RGB and md(acc, g["b0_acc"]) < TOL_ACC
+        assert float((depth.cpu() - g["b0_depth"]).abs().mean()) < TOL_DEPTH_MEAN and md(depth, g["b0_depth"]) < TOL_DEPTH_MAX
 
 
 @pytest.mark.parametrize("Nb,S,P", [(1, 64, 37), (3, 64, 501), (4, 64, 257), (2, 128, 40), (4, 32, 77), (8, 32, 33), (5, 64, 130), (8, 64, 64), (7, 33, 50),
@@ -178,26 +163,26 @@ def test_scene_composite_shapes(amd, dev, Nb, S, P):
     generic = amd.ops.scene_composite(sig.to(dev), rgb.to(dev), z.to(dev))
     for run in (0, S):
         got = amd.ops.scene_composite(sig.to(dev), rgb.to(dev), z.to(dev), run_length=run)
-        assert maxdiff(got[0], want[0]) < TOL_RGB and maxdiff(got[2], want[2]) < TOL_ACC
-        assert maxdiff(got[1], want[1]) < TOL_DEPTH_MAX
+        assert md(got[0], want[0]) < TOL_RGB and md(got[2], want[2]) < TOL_ACC
+        assert md(got[1], want[1]) < TOL_DEPTH_MAX
         assert all(torch.equal(a, b) for a, b in zip(got, generic))             # the merge path places every sample where the rank sort does
     if Nb > 1:      # two objects sharing every depth exactly: the reference keeps the later sample of each pair and drops the other
         z2 = z.clone().view(P, Nb, S); z2[:, 1] = z2[:, 0]; z2 = z2.view(P, Nb * S)
         want2 = O.scene_composite(sig, rgb, z2)
         for run in (0, S):
             got2 = amd.ops.scene_composite(sig.to(dev), rgb.to(dev), z2.to(dev), run_length=run)
-            assert maxdiff(got2[0], want2[0]) < TOL_RGB and maxdiff(got2[1], want2[1]) < TOL_DEPTH_MAX and maxdiff(got2[2], want2[2]) < TOL_ACC
+            assert md(got2[0], want2[0]) < TOL_RGB and md(got2[1], want2[1]) < TOL_DEPTH_MAX and md(got2[2], want2[2]) < TOL_ACC
     # repeated depths INSIDE a list (ties within one object and across objects), and a wrong hint: lists that are not ascending must give the
     # rank sort's answer (the kernel checks the order per pixel)
     z3 = (z.view(P, Nb, S) * 4).round() / 4
     z3 = z3.view(P, Nb * S)
     want3 = O.scene_composite(sig, rgb, z3)
     got3 = amd.ops.scene_composite(sig.to(dev), rgb.to(dev), z3.to(dev), run_length=S)
-    assert maxdiff(got3[0], want3[0]) < TOL_RGB and maxdiff(got3[1], want3[1]) < TOL_DEPTH_MAX and maxdiff(got3[2], want3[2]) < TOL_ACC
+    assert md(got3[0], want3[0]) < TOL_RGB and md(got3[1], want3[1]) < TOL_DEPTH_MAX and md(got3[2], want3[2]) < TOL_ACC
     zr = z.view(P, Nb, S).flip(-1).reshape(P, Nb * S).contiguous()
     want4 = O.scene_composite(sig, rgb, zr)
     got4 = amd.ops.scene_composite(sig.to(dev), rgb.to(dev), zr.to(dev), run_length=S)
-    assert maxdiff(got4[0], want4[0]) < TOL_RGB and maxdiff(got4[1], want4[1]) < TOL_DEPTH_MAX and maxdiff(got4[2], want4[2]) < TOL_ACC
+    assert md(got4[0], want4[0]) < TOL_RGB and md(got4[1], want4[1]) < TOL_DEPTH_MAX and md(got4[2], want4[2]) < TOL_ACC
 
 
 def test_scene_composite_limits(amd, dev):
@@ -242,11 +227,11 @@ def test_encode_family_a(amd, dev, golden, tag):
     xo, vo = O.points_on_rays(ro.cpu(), vd.cpu(), z.cpu())
     xo = xo / np.float32(g["obj_diag"])
     xo, vo = O.object_frame_transforms(xo, vo, False, bool(g["kitti2nusc"]), bool(g["shapenet_obj_cood"]))
-    assert maxdiff(xyz, xo) == 0.0
-    assert maxdiff(vdir, vo) == 0.0
-    assert maxdiff(zz, z.cpu()[None].expand(ro.shape[0], S)) == 0.0
-    assert maxdiff(pe, O.positional_encoding(xo, 10)) < 2e-6
-    assert maxdiff(ped, O.positional_encoding(vo[:, 0], 4)) < 2e-6
+    assert md(xyz, xo) == 0.0
+    assert md(vdir, vo) == 0.0
+    assert md(zz, z.cpu()[None].expand(ro.shape[0], S)) == 0.0
+    assert md(pe, O.positional_encoding(xo, 10)) < 2e-6
+    assert md(ped, O.positional_encoding(vo[:, 0], 4)) < 2e-6
 
 
 def test_encode_family_b_metric_depth(amd, dev, golden):
@@ -266,9 +251,9 @@ def test_encode_family_b_metric_depth(amd, dev, golden):
     cfg = ops.RenderCfg(S, ops.Z_PER_RAY, ro.shape[0], 3, 1, metric_z=True)
     one = torch.ones(1, device=dev)
     xyz, vdir, zz = ops.encode(o_n.to(dev), vd.to(dev), t.to(dev), one, torch.tensor([float(diag / 2)], device=dev), cfg)
-    assert maxdiff(xyz, xyz_o) < 1e-6
-    assert maxdiff(zz, zv_o) < 2e-6
-    assert maxdiff(zz, g["z_vals"]) < 2e-6
+    assert md(xyz, xyz_o) < 1e-6
+    assert md(zz, zv_o) < 2e-6
+    assert md(zz, g["z_vals"]) < 2e-6
 
 
 # ------------------------------------------------------------------ decoder
@@ -285,8 +270,8 @@ def test_decoder_forward_golden(amd, dev, golden, packed, tag, precision):
         return
     sig, rgb, _ = amd.ops.decoder_fwd(g["xyz"].reshape(-1, 3).to(dev), g["viewdir"].reshape(-1, 3).to(dev), lat, pk, 3, 1,
                                       precision=precision)
-    assert maxdiff(sig.view(N, S, 1), g["sigmas"]) < 2e-5
-    assert maxdiff(rgb.view(N, S, 3), g["rgbs"]) < 2e-5
+    assert md(sig.view(N, S, 1), g["sigmas"]) < 2e-5
+    assert md(rgb.view(N, S, 3), g["rgbs"]) < 2e-5
 
 
 def test_decoder_forward_other_block_counts(amd, dev):
@@ -305,8 +290,8 @@ def test_decoder_forward_other_block_counts(amd, dev):
         pk = amd.ops.pack_weights({k: v.to(dev) for k, v in params.items()}, sb, tb)
         lat_d = lat.to(dev) if sb + tb else torch.zeros(B, 1, 256, device=dev)
         sig, rgb, _ = amd.ops.decoder_fwd(xyz.reshape(-1, 3).to(dev), vd.reshape(-1, 3).to(dev), lat_d, pk, sb, tb, precision=prec)
-        assert maxdiff(sig.view(N, S, 1), sig_o) < 2e-5, (sb, tb, prec)
-        assert maxdiff(rgb.view(N, S, 3), rgb_o) < 2e-5, (sb, tb, prec)
+        assert md(sig.view(N, S, 1), sig_o) < 2e-5, (sb, tb, prec)
+        assert md(rgb.view(N, S, 3), rgb_o) < 2e-5, (sb, tb, prec)
 
 
 def test_latent_terms_folded_into_biases(amd, dev, golden, packed, oracle_params):
@@ -329,11 +314,11 @@ def test_latent_terms_folded_into_biases(amd, dev, golden, packed, oracle_params
         cfg.latent_bias = bias
         outs.append(ops.render_fwd(ro, vd, z, div, None, lat, pk, cfg, save_for_bwd=True))
     for a, b, tol in zip(outs[0][:5], outs[1][:5], (2e-6, 2e-5, 2e-6, 2e-5, 2e-5)):
-        assert maxdiff(a, b) < tol
+        assert md(a, b) < tol
     # ReLU bits: identical up to pre-activations within rounding of zero
     diff_bits = int((outs[0][5] != outs[1][5]).sum())
     assert diff_bits <= outs[0][5].numel() // 100000 + 8, diff_bits
-    assert maxdiff(outs[1][0], g["rgb"]) < 2e-5
+    assert md(outs[1][0], g["rgb"]) < 2e-5
     with pytest.raises(amd.SnrError):
         cfg.latent_bias = lb[:, :2]
         ops.render_fwd(ro, vd, z, div, None, lat, pk, cfg)
@@ -353,9 +338,9 @@ def test_render_family_a_golden(amd, dev, golden, packed, oracle_params, tag, pr
                         precision=precision)
     div = torch.tensor([float(g["obj_diag"])], device=dev)
     rgb, depth, acc, *_ = ops.render_fwd(ro, vd, z, div, None, lat, pk, cfg)
-    assert maxdiff(rgb, g["rgb"]) < TOL_RGB
-    assert float((depth.cpu() - g["depth"]).abs().mean()) < TOL_DEPTH_MEAN and maxdiff(depth, g["depth"]) < TOL_DEPTH_MAX
-    assert maxdiff(acc, g["acc"]) < TOL_ACC
+    assert md(rgb, g["rgb"]) < TOL_RGB
+    assert float((depth.cpu() - g["depth"]).abs().mean()) < TOL_DEPTH_MEAN and md(depth, g["depth"]) < TOL_DEPTH_MAX
+    assert md(acc, g["acc"]) < TOL_ACC
 
 
 @pytest.mark.parametrize("P", [1, 127, 128, 1000, 70000])

@@ -14,14 +14,9 @@ import torch
 
 from cpu_arith import golden_equal
 from oracle import supnerf_oracle as O
+from oracle_bands import amd  # noqa: F401  (a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
 
 
 def test_library_exports_every_declared_symbol(amd):

@@ -5,29 +5,9 @@ import pytest
 import torch
 
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, dev, md, rel  # noqa: F401  (amd, dev: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
-
-
-def md(a, b):
-    return float((a.detach().double().cpu() - torch.as_tensor(b).detach().double().cpu()).abs().max())
-
-
-def rel(a, b):
-    b = torch.as_tensor(b).detach().double().cpu()
-    return md(a, b) / (float(b.abs().max()) + 1e-30)
 
 
 # ------------------------------------------------------------------ loss tail (src/optimizer_nuscenes.py:729-744)

@@ -25,74 +25,13 @@ import torch.nn.functional as F
 
 import planted_decoder as PD
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, band_of, check_per_object, check_per_ray, dev, make_model  # noqa: F401  (amd, dev: fixtures)
 from relu_bits import decode_relu_bits, relu_bits_of
 
 pytestmark = pytest.mark.gpu
 
-# the bands of tests/test_opaque_regime.py, with their derivation:
-# fp32 kernels: another sample of the same rounding noise as the fp32 oracle, so a few times its distance
-C_FP32, FLOOR_FP32 = 4.0, 2e-5
-# split kernels: the backward chain multiplies bf16 pieces, 2^-17 per product where fp32 rounds at 2^-24, i.e. 2^7 times an fp32 rounding;
-# the fp32 oracle's distance already sums ~2^4 roundings over a 256-wide layer, leaving 2^3 -- times the fp32 factor 4; floor 2^-14, eight
-# 2^-17 roundings
-C_BF16X3, FLOOR_BF16X3 = 32.0, 2.0 ** -14
-BANDS = {"fp32": (C_FP32, FLOOR_FP32), "bf16x3": (C_BF16X3, FLOOR_BF16X3)}
-
 PRECISIONS = ["fp32", "bf16x3", ("fp32", "bf16x3")]
 PREC_ID = lambda p: "-".join(p) if isinstance(p, tuple) else p
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
-
-
-def band_of(precision):
-    """The band of the arithmetic the BACKWARD ran in."""
-    b = precision[1] if isinstance(precision, tuple) else precision
-    return "fp32" if b == "fp32" else "bf16x3"
-
-
-def in_band(got, o32, o64, band, name=""):
-    """|got - f64| <= C |o32 - f64| + floor, relative to max |f64|; returns (ok, worst ratio, message)."""
-    c, floor = BANDS[band]
-    got, o32, o64 = [torch.as_tensor(t).detach().double().cpu() for t in (got, o32, o64)]
-    top = float(o64.abs().max()) + 1e-30
-    e_got, e32 = float((got - o64).abs().max()) / top, float((o32 - o64).abs().max()) / top
-    lim = c * e32 + floor
-    ok = bool(torch.isfinite(got).all()) and e_got <= lim
-    return ok, (e_got / lim if ok else float("inf")), f"{name} [{band}]: {e_got:.2e} of max {top:.3e}, fp32 oracle {e32:.2e}, band {lim:.2e}"
-
-
-def check_per_object(pairs, band, objects=None):
-    """``pairs``: (name, got, o32, o64) with the object as dim 0; every object against its own float64 row."""
-    bad, worst = [], {}
-    for name, got, o32, o64 in pairs:
-        got = torch.as_tensor(got).detach().cpu()
-        assert got.shape == o64.shape, (name, tuple(got.shape), tuple(o64.shape))
-        for b in range(o64.shape[0]):
-            ok, r, msg = in_band(got[b], o32[b], o64[b], band, f"{name}[obj {b if objects is None else objects[b]}]")
-            if not ok:
-                bad.append(msg)
-            if name not in worst or r > worst[name][0]:
-                worst[name] = (r, msg)
-    for r, msg in worst.values():
-        print("worst", msg)
-    assert not bad, bad[:8]
-
-
-def make_model(amd, dev, params, precision, blocks=(3, 1)):
-    m = amd.CodeNeRF(shape_blocks=blocks[0], texture_blocks=blocks[1])
-    m.load_state_dict(params, strict=True)
-    m.precision = precision
-    return m.to(dev)
 
 
 def capture_latent(m):
@@ -108,14 +47,6 @@ def capture_latent(m):
     return got
 
 
-def latent_masked(p, sc, tc, sb, tb, on):
-    """O.latent_terms whose ReLU derivative is ``on`` (the GPU's z > 0): a latent pre-activation within rounding of zero must not flip
-    between the two sides of the comparison either."""
-    pre = [F.linear(sc, p[f"shape_latent_layer_{j}.0.weight"], p[f"shape_latent_layer_{j}.0.bias"]) for j in range(1, sb + 1)]
-    pre += [F.linear(tc, p[f"texture_latent_layer_{j}.0.weight"], p[f"texture_latent_layer_{j}.0.bias"]) for j in range(1, tb + 1)]
-    return O._ReluWithGivenMask.apply(torch.stack(pre, dim=1), on.to(pre[0].dtype))
-
-
 def codes(B, seed):
     g = torch.Generator().manual_seed(seed)
     return [torch.randn(B, 256, generator=g) * 0.3 for _ in range(2)]
@@ -129,15 +60,30 @@ def obj_scale(B, per_obj, seed):
 
 
 # ------------------------------------------------------------------ a. points decoder (snr_decoder_bwd, mode 0)
-def oracle_points(params, xyz, vd, sc, tc, sb, tb, lat_on, masks, ws, wr, dt):
-    """Gradients wrt the latent terms and the codes of sum(sig ws) + sum(rgb wr); xyz (P,3) object-major."""
-    p = {k: v.to(dt) for k, v in params.items()}
-    sc, tc = sc.to(dt).clone().requires_grad_(), tc.to(dt).clone().requires_grad_()
-    lat = latent_masked(p, sc, tc, sb, tb, lat_on)
+def oracle_latent(p, dt, lat, codes, lat_on):
+    """The oracle's latent terms in dtype ``dt``, their gradient kept: ``lat`` as given, or those of ``codes`` (sc, tc) whose ReLU
+    derivative is ``lat_on`` (the GPU's z > 0: a pre-activation within rounding of zero must not flip between the two sides of the
+    comparison either).  Returns (latent, sc, tc), the codes None when ``lat`` is given."""
+    if codes is None:
+        return lat.to(dt).clone().requires_grad_(), None, None
+    sc, tc = [c.to(dt).clone().requires_grad_() for c in codes]
+    lat = O.latent_terms(p, sc, tc, relu_mask=lat_on)
     lat.retain_grad()
+    return lat, sc, tc
+
+
+def grad_of(x):
+    return None if x is None else x.grad
+
+
+def oracle_points(params, xyz, vd, masks, ws, wr, dt, lat=None, codes=None, lat_on=None):
+    """Gradients of sum(sig ws) + sum(rgb wr), xyz (P,3) object-major, latent terms as ``oracle_latent`` makes them: (d_latent,
+    d_shapecode, d_texturecode)."""
+    p = {k: v.to(dt) for k, v in params.items()}
+    lat, sc, tc = oracle_latent(p, dt, lat, codes, lat_on)
     s, r = O.decoder_forward(p, xyz.to(dt)[:, None], vd.to(dt)[:, None], None, None, relu_masks=masks, latent=lat)
     ((s.reshape(-1) * ws.to(dt)).sum() + (r.reshape(-1, 3) * wr.to(dt)).sum()).backward()
-    return lat.grad, sc.grad if sb else None, tc.grad if tb else None
+    return lat.grad, grad_of(sc), grad_of(tc)
 
 
 def run_points(amd, dev, B, n, precision, blocks=(3, 1), seed=0):
@@ -160,7 +106,7 @@ def run_points(amd, dev, B, n, precision, blocks=(3, 1), seed=0):
     ((sig.reshape(-1) * ws.to(dev)).sum() + (rgb.reshape(-1, 3) * wr.to(dev)).sum()).backward()
     lat = lats[0]
     on = (lat.detach() > 0).cpu()
-    ref = {dt: oracle_points(params, xyz, vd, sc, tc, sb, tb, on, masks, ws, wr, dt) for dt in (torch.float32, torch.float64)}
+    ref = {dt: oracle_points(params, xyz, vd, masks, ws, wr, dt, codes=(sc, tc), lat_on=on) for dt in (torch.float32, torch.float64)}
     pairs = [("d_latent", lat.grad, ref[torch.float32][0], ref[torch.float64][0])]
     if sb:
         pairs.append(("d_shapecode", sc_d.grad, ref[torch.float32][1], ref[torch.float64][1]))
@@ -199,46 +145,18 @@ def test_points_other_latent_layouts(amd, dev, blocks, precision):
 
 
 # ------------------------------------------------------------------ b. fused render backward (snr_render_bwd, mode 1)
-def oracle_render(params, ro, rd, t, mode, S, n, zs, half, sc, tc, lat_on, masks, wts, dt):
+def oracle_render(params, ro, rd, t, mode, S, n, zs, half, masks, wts, dt, lat=None, codes=None, lat_on=None):
+    """Gradients of the fused render (white background; depths metric except per object) on the oracle in dtype ``dt``, latent terms as
+    ``oracle_latent`` makes them: dict of d_rays_o, d_rays_d, d_t (per ray only), d_latent, d_shapecode, d_texturecode."""
     p = {k: v.to(dt) for k, v in params.items()}
-    ro, rd, sc, tc = [x.to(dt).clone().requires_grad_() for x in (ro, rd, sc, tc)]
+    ro, rd = ro.to(dt).clone().requires_grad_(), rd.to(dt).clone().requires_grad_()
     t = t.to(dt).clone().requires_grad_() if mode == "per_ray" else t.to(dt)
-    N = ro.shape[0]
-    obj = torch.arange(N) // n
-    zs = zs.to(dt)[obj]
-    if mode == "box":
-        o_n = ro / zs[:, None]
-        h = half.to(dt)[obj]
-        t_near, t_far, hit = O.slab_intersect(o_n, rd, -h, h)
-        near = torch.where(hit, t_near, torch.full_like(t_near, -1.0))[:, None]
-        far = torch.where(hit, t_far, torch.full_like(t_far, -1.0))[:, None]
-        tt = O.unit_interval_samples(near, far, S, t)
-        xyz = o_n[:, None, :] + tt[:, :, None] * rd[:, None, :]
-        zc = torch.norm(xyz - o_n[:, None, :], dim=-1) * zs[:, None]
-    else:
-        tt = t[obj] if mode == "per_object" else t
-        xyz = ro[:, None, :] + rd[:, None, :] * tt[:, :, None]
-        zc = torch.norm(xyz - ro[:, None, :], dim=-1) * zs[:, None] if mode == "per_ray" else tt
-    lat = latent_masked(p, sc, tc, 3, 1, lat_on)
-    lat.retain_grad()
-    sig, rgb = O.decoder_forward(p, xyz, rd[:, None, :].expand(N, S, 3), None, None, relu_masks=masks, latent=lat)
-    out = O.composite(sig, rgb, zc, white_bkgd=True)
+    lat, sc, tc = oracle_latent(p, dt, lat, codes, lat_on)
+    out = O.fused_render(p, ro, rd, t, mode, S, n, zs.to(dt), half.to(dt) if mode == "box" else None, latent=lat, relu_masks=masks,
+                         white_bkgd=True, metric_z=mode != "per_object")
     sum((a * w.to(dt)).sum() for a, w in zip(out, wts)).backward()
-    return dict(d_rays_o=ro.grad, d_rays_d=rd.grad, d_t=t.grad if mode == "per_ray" else None, d_latent=lat.grad, d_shapecode=sc.grad,
-                d_texturecode=tc.grad)
-
-
-def check_per_ray(name, got, ref32, true):
-    """tests/test_family_b_fused.py::test_family_b_per_ray_gradients_mask_matched's rule: every ray within 1e-3 of ITS OWN float64 gradient,
-    or within 8x what the fp32 oracle manages on that ray (grazing rays are ill-conditioned in fp32 whoever computes them)."""
-    got, ref32, true = [torch.as_tensor(x).detach().cpu().double().reshape(x.shape[0], -1) for x in (got, ref32, true)]
-    scale = true.abs().amax(dim=1).clamp_min(1e-12)
-    err = (got - true).abs().amax(dim=1) / scale
-    floor = (ref32 - true).abs().amax(dim=1) / scale
-    bad = ~torch.isfinite(err) | ((err > 1e-3) & (err > 8 * floor))
-    print(f"[per-ray {name}] median rel err {float(err.median()):.1e} (fp32 oracle {float(floor.median()):.1e}), worst {float(err.max()):.1e}"
-          f" (fp32 oracle {float(floor.max()):.1e}), rays outside: {int(bad.sum())}")
-    return [] if not bool(bad.any()) else [(name, torch.nonzero(bad).flatten()[:10].tolist(), err[bad][:10].tolist(), floor[bad][:10].tolist())]
+    return dict(d_rays_o=ro.grad, d_rays_d=rd.grad, d_t=t.grad if mode == "per_ray" else None, d_latent=lat.grad, d_shapecode=grad_of(sc),
+                d_texturecode=grad_of(tc))
 
 
 # (z mode, S, rays per object, objects): rays x S per object, and the fp32 kernel (bf16x3: the split kernel, 32-point tiles, throughout)
@@ -296,15 +214,15 @@ def test_render_latent_gradient_per_object(amd, dev, oracle_params, case, precis
     masks = relu_bits_of(out[0], 3, 1, n_samples=S)
     sum((a * w.to(dev)).sum() for a, w in zip(out, wts)).backward()
     on = (lats[0].detach() > 0).cpu()
-    r32, r64 = [oracle_render(oracle_params, o, d, t, mode, S, n, zs, half, sc, tc, on, masks, wts, dt) for dt in (torch.float32, torch.float64)]
-    band = "fp32" if precision == "fp32" else "bf16x3"
+    r32, r64 = [oracle_render(oracle_params, o, d, t, mode, S, n, zs, half, masks, wts, dt, codes=(sc, tc), lat_on=on)
+                for dt in (torch.float32, torch.float64)]
     bad = []
     for name, got in (("d_rays_o", leaves[0].grad), ("d_rays_d", leaves[1].grad), ("d_t", leaves[2].grad if mode == "per_ray" else None)):
         if got is not None:
             bad += check_per_ray(name, got, r32[name], r64[name])
     assert not bad, bad
     got = dict(d_latent=lats[0].grad, d_shapecode=leaves[3].grad, d_texturecode=leaves[4].grad)
-    check_per_object([(k, v, r32[k], r64[k]) for k, v in got.items()], band)
+    check_per_object([(k, v, r32[k], r64[k]) for k, v in got.items()], band_of(precision))
 
 
 # ------------------------------------------------------------------ c. family B, split backward, small S
@@ -414,14 +332,6 @@ def latent_input(B, nlat, seed):
     return torch.relu(torch.randn(B, nlat, 256, generator=g) * 0.3)
 
 
-def oracle_latent_grad(params, xyz, vd, lat, masks, ws, wr, dt):
-    p = {k: v.to(dt) for k, v in params.items()}
-    lat = lat.to(dt).clone().requires_grad_()
-    s, r = O.decoder_forward(p, xyz.to(dt)[:, None], vd.to(dt)[:, None], None, None, relu_masks=masks, latent=lat)
-    ((s.reshape(-1) * ws.to(dt)).sum() + (r.reshape(-1, 3) * wr.to(dt)).sum()).backward()
-    return lat.grad
-
-
 @pytest.mark.parametrize("n,B,precision", [
     (32 * 1025, 1, "bf16x3"),        # three-level tree, 32-point tiles
     (32 * 1025, 1, "fp32"),          # three-level tree, round-2 fp32 (32*1025 % 64 != 0)
@@ -441,7 +351,7 @@ def test_abi_decoder_workspace_and_output(amd, dev, oracle_params, n, B, precisi
     sig, _, masks = ops.decoder_fwd(xd, vdd, ld, packed, 3, 1, save_masks=True, precision=precision)
     d_lat = abi_bwd(amd, dev, 0, (xd, vdd, ld, packed, masks, sig, ws.to(dev), wr.to(dev), 3, 1), precision)
     mk = decode_relu_bits(masks, P, 3, 1)
-    r32, r64 = [oracle_latent_grad(oracle_params, xyz, vd, lat, mk, ws, wr, dt) for dt in (torch.float32, torch.float64)]
+    r32, r64 = [oracle_points(oracle_params, xyz, vd, mk, ws, wr, dt, lat=lat)[0] for dt in (torch.float32, torch.float64)]
     check_per_object([("d_latent", d_lat, r32, r64)], band_of(precision))
 
 
@@ -461,34 +371,9 @@ def test_abi_render_workspace_and_output(amd, dev, oracle_params, case, precisio
     fw = ops.render_fwd(*operands, save_for_bwd=True)
     d_lat = abi_bwd(amd, dev, 1, (operands, (fw[3], fw[4], fw[5], *[w.to(dev) for w in wts])), precision)
     mk = decode_relu_bits(fw[5], B * n * S, 3, 1)
-    r32, r64 = [oracle_render_latent(oracle_params, o, d, t, mode, S, n, zs, half, lat, mk, wts, dt) for dt in (torch.float32, torch.float64)]
+    r32, r64 = [oracle_render(oracle_params, o, d, t, mode, S, n, zs, half, mk, wts, dt, lat=lat)["d_latent"]
+                for dt in (torch.float32, torch.float64)]
     check_per_object([("d_latent", d_lat, r32, r64)], band_of(precision))
-
-
-def oracle_render_latent(params, ro, rd, t, mode, S, n, zs, half, lat, masks, wts, dt):
-    """d_latent of the render at given latent terms (no codes)."""
-    p = {k: v.to(dt) for k, v in params.items()}
-    N = ro.shape[0]
-    ro, rd, t = ro.to(dt), rd.to(dt), t.to(dt)
-    obj = torch.arange(N) // n
-    zsr = zs.to(dt)[obj]
-    if mode == "box":
-        o_n = ro / zsr[:, None]
-        h = half.to(dt)[obj]
-        t_near, t_far, hit = O.slab_intersect(o_n, rd, -h, h)
-        near = torch.where(hit, t_near, torch.full_like(t_near, -1.0))[:, None]
-        far = torch.where(hit, t_far, torch.full_like(t_far, -1.0))[:, None]
-        tt = O.unit_interval_samples(near, far, S, t)
-        xyz = o_n[:, None, :] + tt[:, :, None] * rd[:, None, :]
-        zc = torch.norm(xyz - o_n[:, None, :], dim=-1) * zsr[:, None]
-    else:
-        xyz = ro[:, None, :] + rd[:, None, :] * t[:, :, None]
-        zc = torch.norm(xyz - ro[:, None, :], dim=-1) * zsr[:, None]
-    lat = lat.to(dt).clone().requires_grad_()
-    sig, rgb = O.decoder_forward(p, xyz, rd[:, None, :].expand(N, S, 3), None, None, relu_masks=masks, latent=lat)
-    out = O.composite(sig, rgb, zc, white_bkgd=True)
-    sum((a * w.to(dt)).sum() for a, w in zip(out, wts)).backward()
-    return lat.grad
 
 
 # ------------------------------------------------------------------ e. many objects
@@ -534,6 +419,6 @@ def test_more_objects_than_a_grid_row_holds(amd, dev, oracle_params, precision):
     idx = torch.cat([torch.arange(b * n, (b + 1) * n) for b in objs]).to(dev)
     mk = torch.cat([masks[b * per_tile:(b + 1) * per_tile] for b in objs])
     mk = decode_relu_bits(mk, len(objs) * n, 3, 1)
-    args = [x[idx].cpu() for x in (xyz, vd)] + [lat[objs].cpu(), mk] + [x[idx].cpu() for x in (ws, wr)]
-    r32, r64 = [oracle_latent_grad(oracle_params, *args, dt) for dt in (torch.float32, torch.float64)]
+    args = [x[idx].cpu() for x in (xyz, vd)] + [mk] + [x[idx].cpu() for x in (ws, wr)]
+    r32, r64 = [oracle_points(oracle_params, *args, dt, lat=lat[objs].cpu())[0] for dt in (torch.float32, torch.float64)]
     check_per_object([("d_latent", d_lat[objs], r32, r64)], band_of(precision), objects=objs)

@@ -10,54 +10,10 @@ import torch
 
 import planted_decoder as PD
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, band_of, check_all, dev, make_model  # noqa: F401  (amd, dev: fixtures)
 from relu_bits import relu_bits_of
 
 pytestmark = pytest.mark.gpu
-
-# fp32 kernels: another sample of the same rounding noise as the fp32 oracle, so a few times its distance
-C_FP32, FLOOR_FP32 = 4.0, 2e-5
-# split kernels: the backward chain multiplies bf16 pieces, 2^-17 per product where fp32 rounds at 2^-24, i.e. 2^7 times an fp32 rounding;
-# the fp32 oracle's distance already sums ~2^4 roundings over a 256-wide layer, leaving 2^3 -- times the fp32 factor 4; floor 2^-14, eight
-# 2^-17 roundings
-C_BF16X3, FLOOR_BF16X3 = 32.0, 2.0 ** -14
-BANDS = {"fp32": (C_FP32, FLOOR_FP32), "bf16x3": (C_BF16X3, FLOOR_BF16X3), "auto": (C_BF16X3, FLOOR_BF16X3)}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
-
-
-def make_model(amd, dev, params, precision, blocks=(3, 1)):
-    m = amd.CodeNeRF(shape_blocks=blocks[0], texture_blocks=blocks[1])
-    m.load_state_dict(params, strict=True)
-    m.precision = precision
-    return m.to(dev)
-
-
-def in_band(got, o32, o64, precision, name=""):
-    """|got - f64| <= C |o32 - f64| + floor, relative to max |f64|; returns the message for the assert."""
-    c, floor = BANDS[precision]
-    got, o32, o64 = [torch.as_tensor(t).detach().double().cpu() for t in (got, o32, o64)]
-    top = float(o64.abs().max()) + 1e-30
-    e_got, e32 = float((got - o64).abs().max()) / top, float((o32 - o64).abs().max()) / top
-    ok = bool(torch.isfinite(got).all()) and e_got <= c * e32 + floor
-    return ok, f"{name} [{precision}]: {e_got:.2e} of max {top:.3e}, fp32 oracle {e32:.2e}, band {c * e32 + floor:.2e}"
-
-
-def check_all(pairs, precision):
-    msgs = [in_band(g, a, b, precision, n) for n, g, a, b in pairs]
-    for ok, m in msgs:
-        print(m)
-    bad = [m for ok, m in msgs if not ok]
-    assert not bad, bad
 
 
 # ------------------------------------------------------------------ a. points decoder
@@ -93,31 +49,16 @@ def test_points_decoder_opaque(amd, dev, precision):
 
 
 # ------------------------------------------------------------------ b. fused render
-def oracle_render(params, ro, rd, t, mode, S, n, white, zs, half, sc, tc, masks, dt, wts):
-    """The fused render's computation in the oracle's terms, in dtype ``dt``; returns outputs and gradients wrt (ro, rd, t, sc, tc)."""
-    p = {k: v.to(dt) for k, v in params.items()}
-    ro, rd, sc, tc = [x.to(dt).clone().requires_grad_() for x in (ro, rd, sc, tc)]
-    t = t.to(dt).clone().requires_grad_() if mode == "per_ray" else t.to(dt)
-    N = ro.shape[0]
-    obj = torch.arange(N) // n
-    zs = zs.to(dt)[obj]
-    if mode == "box":
-        o_n = ro / zs[:, None]
-        h = half.to(dt)[obj]
-        t_near, t_far, hit = O.slab_intersect(o_n, rd, -h, h)
-        near = torch.where(hit, t_near, torch.full_like(t_near, -1.0))[:, None]
-        far = torch.where(hit, t_far, torch.full_like(t_far, -1.0))[:, None]
-        tt = O.unit_interval_samples(near, far, S, t)
-        xyz = o_n[:, None, :] + tt[:, :, None] * rd[:, None, :]
-        zc = torch.norm(xyz - o_n[:, None, :], dim=-1) * zs[:, None]
-    else:
-        tt = {"shared": lambda: t[None, :].expand(N, S), "per_object": lambda: t[obj], "per_ray": lambda: t}[mode]()
-        xyz = ro[:, None, :] + rd[:, None, :] * tt[:, :, None]
-        zc = torch.norm(xyz - ro[:, None, :], dim=-1) * zs[:, None] if mode == "per_ray" else tt
-    sig, rgb = O.decoder_forward(p, xyz, rd[:, None, :].expand(N, S, 3), sc, tc, relu_masks=masks)
-    out = O.composite(sig, rgb, zc, white_bkgd=white)
-    sum((a * w.to(dt)).sum() for a, w in zip(out, wts)).backward()
-    return [x.detach() for x in out], [ro.grad, rd.grad, t.grad if mode == "per_ray" else None, sc.grad, tc.grad]
+def oracle_render(params, o, d, t, mode, S, n, white, zs, half, sc, tc, masks, wts, dt):
+    """The fused render on the oracle in dtype ``dt``; returns outputs and gradients wrt (rays_o, rays_d, t (per ray only), sc, tc)."""
+    c = lambda x: x.to(dt)
+    leaves = [c(x).clone().requires_grad_() for x in (o, d, t, sc, tc)]
+    if mode != "per_ray":
+        leaves[2] = c(t)
+    out = O.fused_render({k: c(v) for k, v in params.items()}, *leaves[:3], mode, S, n, c(zs), c(half) if mode == "box" else None,
+                         shape_code=leaves[3], texture_code=leaves[4], relu_masks=masks, white_bkgd=white, metric_z=mode in ("per_ray", "box"))
+    sum((a * c(w)).sum() for a, w in zip(out, wts)).backward()
+    return [x.detach() for x in out], [x.grad if x.requires_grad else None for x in leaves]
 
 
 RENDER_CASES = [  # (z mode, S, objects, rays per object, white background)
@@ -158,15 +99,15 @@ def test_fused_render_opaque(amd, dev, case, precision):
         assert m.last_precision["forward"] == "bf16x3", m.last_precision
     masks = relu_bits_of(out[0], 3, 1, n_samples=S)
     sum((a * w.to(dev)).sum() for a, w in zip(out, wts)).backward()
-    r32, g32 = oracle_render(params, o, d, t, mode, S, n, white, zs, half, sc, tc, masks, torch.float32, wts)
-    r64, g64 = oracle_render(params, o, d, t, mode, S, n, white, zs, half, sc, tc, masks, torch.float64, wts)
+    (r32, g32), (r64, g64) = [oracle_render(params, o, d, t, mode, S, n, white, zs, half, sc, tc, masks, wts, dt)
+                              for dt in (torch.float32, torch.float64)]
     assert float((r64[2] < 1e-6).double().mean()) > 0.3                     # opaque rays are there
     pairs = [(nm, a, b, c) for nm, a, b, c in zip(("rgb", "depth", "acc"), out, r32, r64)]
     grads = [leaves[0].grad, leaves[1].grad, leaves[2].grad if mode == "per_ray" else None, leaves[3].grad, leaves[4].grad]
     for nm, a, b, c in zip(("d_rays_o", "d_rays_d", "d_t", "d_shapecode", "d_texturecode"), grads, g32, g64):
         if c is not None:
             pairs.append((nm, a, b, c))
-    check_all(pairs, "fp32" if precision == "fp32" else "bf16x3")
+    check_all(pairs, band_of(precision))
 
 
 @pytest.mark.parametrize("precision", ["fp32", "auto"])
@@ -190,7 +131,7 @@ def test_fused_render_opaque_forward_ragged_objects(amd, dev, n, S, precision):
         xyz, vd = O.points_on_rays(o.to(dt), d.to(dt), z.to(dt))
         sig, rgb = O.decoder_forward(p, xyz, vd, sc.to(dt), tc.to(dt))
         refs.append(O.composite(sig, rgb, torch.norm(xyz - o.to(dt)[:, None], dim=-1), white_bkgd=True))
-    check_all([(nm, a, b, c) for nm, a, b, c in zip(("rgb", "depth", "acc"), out, refs[0], refs[1])], "fp32" if precision == "fp32" else "bf16x3")
+    check_all([(nm, a, b, c) for nm, a, b, c in zip(("rgb", "depth", "acc"), out, refs[0], refs[1])], band_of(precision))
 
 
 # ------------------------------------------------------------------ c. the far field
@@ -226,7 +167,7 @@ def test_far_field_gradients_family_a(amd, dev, golden, precision):
     assert float((acc64 > 0.99).double().mean()) > 0.5 and float((acc64 < 1e-6).double().mean()) > 0.05     # mostly background
     got = list(out[:3]) + [sc.grad, tc.grad, pose.grad]
     names = ("rgb", "depth", "acc", "d_shapecode", "d_texturecode", "d_cam_pose")
-    check_all([(nm, a, b, c) for nm, a, b, c in zip(names, got, ref[torch.float32], ref[torch.float64])], "fp32" if precision == "fp32" else "bf16x3")
+    check_all([(nm, a, b, c) for nm, a, b, c in zip(names, got, ref[torch.float32], ref[torch.float64])], band_of(precision))
 
 
 # ------------------------------------------------------------------ d. standalone composites with saturating inputs
@@ -316,8 +257,7 @@ def test_training_sigma_head_gradients(amd, dev):
     g = torch.Generator().manual_seed(13)
     sc, tc = [torch.randn(B, 256, generator=g) * 0.3 for _ in range(2)]
     wts = [torch.randn(B * n, 3, generator=g), torch.randn(B * n, generator=g), torch.randn(B * n, generator=g)]
-    m = make_model(amd, dev, params, "fp32")
-    m.train_decoder_weights = True
+    m = make_model(amd, dev, params, "fp32", train=True)
     sig, rgb = m(xyz.to(dev), vd.to(dev), sc.to(dev), tc.to(dev))
     masks = relu_bits_of(sig, 3, 1)
     out = O.composite(sig, rgb, z.to(dev), white_bkgd=False)
@@ -353,8 +293,8 @@ def test_fused_render_other_block_counts(amd, dev, blocks, precision):
     out = m.fused_render(leaves[0], leaves[1], leaves[2], torch.ones(B, device=dev), torch.ones(B, device=dev), leaves[3], leaves[4], cfg)
     masks = relu_bits_of(out[0], sb, tb, n_samples=S)
     sum((a * w.to(dev)).sum() for a, w in zip(out, wts)).backward()
-    r32, g32 = oracle_render(params, o, d, z, "per_ray", S, n, True, torch.ones(B), None, sc, tc, masks, torch.float32, wts)
-    r64, g64 = oracle_render(params, o, d, z, "per_ray", S, n, True, torch.ones(B), None, sc, tc, masks, torch.float64, wts)
+    (r32, g32), (r64, g64) = [oracle_render(params, o, d, z, "per_ray", S, n, True, torch.ones(B), None, sc, tc, masks, wts, dt)
+                              for dt in (torch.float32, torch.float64)]
     pairs = [(nm, a, b, c) for nm, a, b, c in zip(("rgb", "depth", "acc"), out, r32, r64)]
     for nm, a, b, c in zip(("d_rays_o", "d_rays_d", "d_t", "d_shapecode", "d_texturecode"), [x.grad for x in leaves], g32, g64):
         if (nm == "d_shapecode" and sb == 0) or (nm == "d_texturecode" and tb == 0):

@@ -7,20 +7,9 @@ import pytest
 import torch
 
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, dev  # noqa: F401  (amd, dev: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
 
 
 def strided(t):

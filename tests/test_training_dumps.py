@@ -9,7 +9,7 @@ In training mode (``model.train_decoder_weights``, ``ops.DecoderPointsTrain``) t
   tiles per object.
 The oracle's ``decoder_taps`` gives the same slots (tests/test_oracle_taps.py checks that they rebuild autograd's weight gradients).
 
-Bands as in tests/test_opaque_regime.py: |got - f64| <= C |fp32 oracle - f64| + floor, relative to the tensor's largest float64 entry, with
+Bands of tests/oracle_bands.py: |got - f64| <= C |fp32 oracle - f64| + floor, relative to the tensor's largest float64 entry, with
 C = 4 for the fp32 kernels and 32 for the split ones.  Dumps live at the front of NaN-filled buffers with a guard behind them: every live row
 must be written and finite, and nothing may be written past the end."""
 import pytest
@@ -17,48 +17,12 @@ import torch
 import torch.nn.functional as F
 
 from oracle import supnerf_oracle as O
+from oracle_bands import amd, band_of, check_all, dev, make_model  # noqa: F401  (amd, dev: fixtures)
 from relu_bits import decode_relu_bits, relu_bits_of
 
 pytestmark = pytest.mark.gpu
 
-C_FP32, FLOOR_FP32 = 4.0, 2e-5
-C_BF16X3, FLOOR_BF16X3 = 32.0, 2.0 ** -14
-BANDS = {"fp32": (C_FP32, FLOOR_FP32), "bf16x3": (C_BF16X3, FLOOR_BF16X3)}
 GUARD = 16384            # floats (64 KiB) of NaN behind every dump
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def amd():
-    import supnerf_amd
-    return supnerf_amd
-
-
-def in_band(got, o32, o64, band, name=""):
-    """(ok, message): |got - f64| <= C |o32 - f64| + floor relative to max |f64|; the message names the worst row."""
-    c, floor = BANDS[band]
-    got, o32, o64 = [torch.as_tensor(t).detach().cpu().double() for t in (got, o32, o64)]
-    assert got.shape == o64.shape, (name, tuple(got.shape), tuple(o64.shape))
-    top = float(o64.abs().max()) + 1e-30
-    err = torch.nan_to_num((got - o64).abs(), nan=float("inf"))
-    e_got, e32 = float(err.max()) / top, float((o32 - o64).abs().max()) / top
-    lim = c * e32 + floor
-    row = int(err.reshape(err.shape[0], -1).amax(1).argmax()) if err.dim() else 0
-    ok = bool(torch.isfinite(got).all()) and e_got <= lim
-    return ok, f"{name} [{band}]: {e_got:.2e} of max {top:.3e} (worst row {row}), fp32 oracle {e32:.2e}, band {lim:.2e}"
-
-
-def check_all(pairs, band):
-    msgs = [in_band(g, a, b, band, n) for n, g, a, b in pairs]
-    worst = max(msgs, key=lambda m: float(m[1].split(": ")[1].split(" ")[0]))
-    print("worst", worst[1])
-    bad = [m for ok, m in msgs if not ok]
-    assert not bad, bad[:8]
 
 
 def arith(precision):
@@ -139,8 +103,8 @@ def compare_dumps(X, G, ref, precision, rows=None, tag=""):
         gx, gg = (X[s, :, :w], G[s, :, :w]) if rows is None else (X[s, rows, :w], G[s, rows, :w])
         pairs_x.append((f"{tag}X[{s}]", gx.cpu(), ref[torch.float32][0][s], ref[torch.float64][0][s]))
         pairs_g.append((f"{tag}G[{s}]", gg.cpu(), ref[torch.float32][1][s], ref[torch.float64][1][s]))
-    check_all(pairs_x, "fp32" if fwd == "fp32" else "bf16x3")
-    check_all(pairs_g, "fp32" if bwd == "fp32" else "bf16x3")
+    check_all(pairs_x, band_of(fwd))
+    check_all(pairs_g, band_of(bwd))
 
 
 # ------------------------------------------------------------------ a. the dumps themselves
@@ -211,15 +175,6 @@ def e2e_cases():
     return out
 
 
-def make_model(amd, dev, params, precision, sb, tb):
-    m = amd.CodeNeRF(shape_blocks=sb, texture_blocks=tb)
-    m.load_state_dict(params, strict=True)
-    m.precision = precision
-    m = m.to(dev)
-    m.train_decoder_weights = True
-    return m
-
-
 def expected_run(sb, tb, precision, per_obj):
     """(forward, backward) arithmetic the training step must report in model.last_precision."""
     split = split_takes(sb, tb, trained_per_obj(sb, tb, per_obj))
@@ -242,7 +197,7 @@ def test_training_step_every_gradient(amd, dev, sb, tb, batch, precision):
     scale = (1.0 + torch.arange(B, dtype=torch.float32)).repeat_interleave(R)[:, None, None]
     ws, wr = torch.randn(B * R, S, 1, generator=g) * scale, torch.randn(B * R, S, 3, generator=g) * scale
 
-    m = make_model(amd, dev, params, precision, sb, tb)
+    m = make_model(amd, dev, params, precision, (sb, tb), train=True)
     sc, tc = sc0.to(dev).requires_grad_(), tc0.to(dev).requires_grad_()
     sig, rgb = m(xyz.to(dev), vd.to(dev), sc, tc)
     fwd, bwd = expected_run(sb, tb, precision, per_obj)
@@ -275,7 +230,7 @@ def test_training_step_every_gradient(amd, dev, sb, tb, batch, precision):
 def test_training_losses_and_bucket(amd, dev, sb, tb, precision):
     """trainer.nerf_losses into a GradBucket, as tests/test_driver_gpu.py::test_training_step_matches_oracle does at 3/1 blocks."""
     T = amd.trainer
-    m = make_model(amd, dev, O.init_decoder_params(sb, tb, seed=80 + sb), precision, sb, tb)
+    m = make_model(amd, dev, O.init_decoder_params(sb, tb, seed=80 + sb), precision, (sb, tb), train=True)
     codes = T.CodeTables(5, 256, seed=4).to(dev)
     g = torch.Generator().manual_seed(22)
     B, n, S = 2, 32, 64
