@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 8
+#define SNR_ABI_VERSION 9
 
 enum {
     SNR_OK = 0,
@@ -314,6 +314,49 @@ int snr_adamw_table_step(const void* table, int n_tensors, int64_t max_numel, co
 size_t snr_weight_grad_ws_bytes(int64_t n_points, int n_out, int n_in);
 int snr_weight_grad(const float* G, int64_t ldg, int n_out, const float* X, int64_t ldx, int n_in, int64_t n_points,
                     float* dW, int64_t ld_dw, float* db, int precision, void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Geometry: the density of a shape code on a lattice, and the iso-surface of such a grid.
+ *
+ * A lattice (HOST struct, like snr_render_args) is n[0] x n[1] x n[2] points, 1 <= n[a] <= 512, point (i0, i1, i2) at
+ * lo[a] + h[a] * i_a per axis, evaluated as one fp32 multiply and one fp32 add (no fma).  A grid of B objects is (B, n0, n1, n2) floats,
+ * object-major, then axis 0 (x) major, axis 2 (z) fastest: linear index v = (i0 n1 + i1) n2 + i2.
+ * ---------------------------------------------------------------------------------- */
+typedef struct snr_lattice {
+    float lo[3];
+    float h[3];
+    int32_t n[3];
+} snr_lattice;
+
+/* Density-only decoder, exact fp32: the chain of snr_decoder_fwd with SNR_FP32 up to the density head and nothing after it (no view
+ * direction, no encoding_viewdir, texture or rgb layers).  sigmas is bit-identical to the sigmas snr_decoder_fwd returns for the same
+ * points, packed weights (texture rows present, unread) and latent terms (B,NLAT,256).
+ * snr_density_fwd: xyz (P,3), points_per_obj = P / B, sigmas (P).
+ * snr_density_grid: the points of `lattice` for each of n_objects objects, generated in the kernel; sigmas (B, n0, n1, n2). */
+int snr_density_fwd(const float* xyz, const float* latent, const float* packed, int64_t n_points, int64_t points_per_obj,
+                    int shape_blocks, int texture_blocks, float* sigmas, void* stream);
+int snr_density_grid(const snr_lattice* lattice, int64_t n_objects, const float* latent, const float* packed, int shape_blocks,
+                     int texture_blocks, float* sigmas, void* stream);
+
+/* Iso-surface of n_grids grids on `lattice` (2 <= n[a] <= 512) by marching tetrahedra on the Kuhn split.  A sample is inside iff
+ * value > level.  Cell (i0, i1, i2) (index c = (i0 (n1-1) + i1) (n2-1) + i2) has corners v000 + bits (bit a = +1 on axis a) and splits
+ * into 6 tetrahedra v000 -> v000+e_a -> v000+e_a+e_b -> v111, one per permutation (a,b,c) in the order 012, 021, 102, 120, 201, 210.
+ * Every tetrahedron edge is a grid edge from its lower endpoint u in one of 7 directions d (0..6 = x, y, z, xy, xz, yz, xyz), edge id
+ * 7 u + d.  One vertex per crossing edge, in edge-id order: t = (level - f(u)) / (f(u+d) - f(u)), coordinate lo + h (i + t d) per axis,
+ * every step rounded to fp32.  Faces (int32 vertex indices, local to the object) in the order cell, tetrahedron, triangle: one triangle
+ * for 1 or 3 corners inside, two for 2 (the quad split along the diagonal through its vertex of smallest edge id), counter-clockwise
+ * seen from the outside (the low side); tests/iso_restatement.py states the whole rule set step by step.
+ *
+ * Pass 1, snr_iso_count: tri_count (B, cells) uint8 triangles per cell, edge_mask (B, n0 n1 n2) uint8 crossing edges per grid vertex
+ * (bit d), edge_count (B, n0 n1 n2) uint8 = popcount(edge_mask).
+ * The caller then scans per object: tri_scan, edge_scan = the INCLUSIVE int32 prefix sums of tri_count and edge_count along each
+ * object's row, and vert_offset, tri_offset (B) int64 = where each object's vertices / triangles start in the output.
+ * Pass 2, snr_iso_emit: verts (sum V, 3) fp32, faces (sum F, 3) int32. */
+int snr_iso_count(const float* grid, int64_t n_grids, const snr_lattice* lattice, float level, uint8_t* tri_count, uint8_t* edge_mask,
+                  uint8_t* edge_count, void* stream);
+int snr_iso_emit(const float* grid, int64_t n_grids, const snr_lattice* lattice, float level, const uint8_t* edge_mask,
+                 const int32_t* edge_scan, const int32_t* tri_scan, const int64_t* vert_offset, const int64_t* tri_offset, float* verts,
+                 int32_t* faces, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,10 @@ class RenderArgs(C.Structure):
                 ("rng_threads", C.c_uint64)]
 
 
+class Lattice(C.Structure):
+    _fields_ = [("lo", C.c_float * 3), ("h", C.c_float * 3), ("n", C.c_int32 * 3)]
+
+
 _lib = None
 
 
@@ -75,6 +79,10 @@ _SIGS = {
     "snr_latent_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
     "snr_latent_bwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
     "snr_adamw_table_step": (C.c_int, [_P, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "snr_density_fwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    "snr_density_grid": (C.c_int, [C.POINTER(Lattice), C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "snr_iso_count": (C.c_int, [_P, C.c_int64, C.POINTER(Lattice), C.c_float, _P, _P, _P, _P]),
+    "snr_iso_emit": (C.c_int, [_P, C.c_int64, C.POINTER(Lattice), C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 

@@ -168,12 +168,20 @@ __device__ __forceinline__ void store_masks16x4(uint4* __restrict__ dst /* tile'
 #define SNR16_STAMP_HWID(i) do {} while (0)
 #endif
 
+// Where a launch's points come from: modes 0 and 2 read xyz, mode 1 makes them on rays (RayGeom), mode 3 on a lattice.
+template <int MODE> struct PointSrc { using T = RayGeom; };
+template <> struct PointSrc<3> { using T = snr_lattice; };
+
+// MODE 0: explicit points; 1: fused render; 2 and 3: density only (explicit points; points of a lattice, object-major, x-major / z fastest):
+// the same chain up to the density head -- same instructions, so the same sigma bit for bit -- and nothing after it: no view direction, no
+// enc_viewdir / texture / rgb layers.  The stream's last request is then enc_shape's last chunk.
 template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
 __global__ void __launch_bounds__(WAVES * 64, 2)
-decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__ xyz, const float* __restrict__ viewdir, RayGeom gm,
+decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__ xyz, const float* __restrict__ viewdir, typename PointSrc<MODE>::T gm,
                      float* __restrict__ out_rgb, float* __restrict__ out_depth, float* __restrict__ out_acc) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int WGP = WAVES * 16;                      // points per workgroup
+    constexpr bool DENS = MODE >= 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, g = lane >> 4;
     const long long tile_wg = blockIdx.x;
     const long long gp_raw = tile_wg * WGP + wave * 16 + n;
@@ -190,13 +198,23 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     // the pipe again (tools/_diag/stamps16.py).
     __builtin_amdgcn_s_setprio(3);
     float px, py, pz, dx, dy, dz, zc = 0.f;
-    if (MODE == 0) {
+    if constexpr (MODE == 0) {
         px = xyz[gp * 3]; py = xyz[gp * 3 + 1]; pz = xyz[gp * 3 + 2];
         dx = viewdir[gp * 3]; dy = viewdir[gp * 3 + 1]; dz = viewdir[gp * 3 + 2];
-    } else {
+    } else if constexpr (MODE == 1) {
         const PointId id = point_id(gm, tile_wg, WGP, wave * 16 + n, live);
         const SamplePoint sp = make_sample(gm, id.ray, id.s, id.obj);
         px = sp.x; py = sp.y; pz = sp.z; dx = sp.dx; dy = sp.dy; dz = sp.dz; zc = sp.zc;
+    } else if constexpr (MODE == 2) {
+        px = xyz[gp * 3]; py = xyz[gp * 3 + 1]; pz = xyz[gp * 3 + 2];
+        dx = dy = dz = 0.f;
+    } else {
+        // lattice point (i, j, k) of the lane's object: lo + h * i per axis, one multiply and one add (the library builds with -ffp-contract=off)
+        const long long obj = gp / io.points_per_obj;
+        const unsigned v = (unsigned)(gp - obj * io.points_per_obj), nyz = (unsigned)(gm.n[1] * gm.n[2]);
+        const unsigned i = v / nyz, jk = v - i * nyz, j = jk / (unsigned)gm.n[2], k = jk - j * (unsigned)gm.n[2];
+        px = gm.lo[0] + gm.h[0] * (float)i; py = gm.lo[1] + gm.h[1] * (float)j; pz = gm.lo[2] + gm.h[2] * (float)k;
+        dx = dy = dz = 0.f;
     }
     const float* bias = lds + lo.bias;
     const float* heads = bias + L.n_mfma_layers * 256;       // sigma_w (256) | sigma_b | rgb2_w (384) | rgb2_b, as in the packed stream
@@ -242,7 +260,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
                 sc[4 + q] = sn[1]; sc[4 + 3 * XYZ_FREQ + q] = cs[1];
             }
         }
-        {
+        if constexpr (!DENS) {
             const int q = 3 * g;
             f32x2 sn, cs;
             pe_sincos2(f32x2{ldexpf(pick3(dx, dy, dz, q % 3), q / 3), ldexpf(pick3(dx, dy, dz, (q + 1) % 3), (q + 1) / 3)}, &sn, &cs);
@@ -254,9 +272,11 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
         }
         if (g == 0) {
             sc[0] = px; sc[1] = py; sc[2] = pz; sc[63] = 0.f;
-            sc[64] = dx; sc[65] = dy; sc[66] = dz;
+            if constexpr (!DENS) {
+                sc[64] = dx; sc[65] = dy; sc[66] = dz;
 #pragma unroll
-            for (int f = D_DIR; f < 32; ++f) sc[64 + f] = 0.f;
+                for (int f = D_DIR; f < 32; ++f) sc[64 + f] = 0.f;
+            }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -268,7 +288,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
 #pragma unroll
         for (int T = 0; T < 2; ++T)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) xd[T][r] = sc[64 + 16 * T + 4 * g + r];
+            for (int r = 0; r < 4; ++r) xd[T][r] = DENS ? 0.f : sc[64 + 16 * T + 4 * g + r];
         if (WAVES == 4) __syncthreads();      // the scratch lies over ring buffer 1: every wave has read its operands before any wave requests chunk 1
     }
 
@@ -314,11 +334,12 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     auto after_layer_input = [&](int lp) {      // ReLU bits of layer lp, collected while it was consumed
         if (MASKS && lp != li_encshape && tile_live) store_masks16x4(io.masks + (tile32 * n_relu + relu_slot(lp, sb)) * 64, mw, wave, lane);
     };
+    const int li_stop = DENS ? li_encshape : li_last;       // density only: the stream ends with enc_shape
 #pragma unroll 1
-    for (int li = 1; li <= li_last; ++li) {
+    for (int li = 1; li <= li_stop; ++li) {
         const int lp = li - 1;
         const Epi c = epi_of(lp);
-        if (li == li_view) {
+        if (!DENS && li == li_view) {
             SNR16_STAMP(3);
             // density head on enc_shape's finished sums (accP, no activation, no latent): softplus(w_sigma . y + b), src/model_supnerf.py:257.
             // One pass of 64 fma here instead of an fma + a head-weight fetch in EVERY layer's per-value epilogue: on this chip a VALU
@@ -335,9 +356,27 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
             const float pre = s + heads[L.sigma_b - L.sigma_w];
             o_sigma = pre > 20.f ? pre : log1pf(expf(pre));
         }
-        layer_from_acc<16, WAVES, LATLDS, MASKS, DUMP>(accP, ring, lds, bias + li * 256, c, g, dm, layer_base(li), li == li_view, xd, layer_first(li + 1),
-                                                       (li == li_last) ? 128 : 256, mw);
+        const bool end = DENS && li == li_stop;
+        layer_from_acc<16, WAVES, LATLDS, MASKS, DUMP>(accP, ring, lds, bias + li * 256, c, g, dm, layer_base(li), !DENS && li == li_view, xd,
+                                                       end ? nullptr : layer_first(li + 1), end ? 0 : (li == li_last) ? 128 : 256, mw);
         after_layer_input(lp);
+    }
+    if constexpr (DENS) {
+        // the density head above, the same instructions on the same sums.  (Kept as a copy: one helper for both places changes the register
+        // allocation of the modes 0 / 1 instantiations, whose code this variant leaves as it was.)
+        float s = 0.f;
+#pragma unroll
+        for (int T = 0; T < 16; ++T) {
+            const f32x4 ws = *reinterpret_cast<const f32x4*>(heads + 16 * T + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s = fmaf(ws[r], accP[T][r], s);
+        }
+        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 32, 64);
+        const float pre = s + heads[L.sigma_b - L.sigma_w];
+        o_sigma = pre > 20.f ? pre : log1pf(expf(pre));
+        if (live && g == 0) io.sigmas[gp] = o_sigma;
+        return;
     }
     SNR16_STAMP(4);
     {   // rgb.0: 256 -> 128
@@ -388,7 +427,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     if (live && g == 0) {
         if (io.rgbs) { io.rgbs[gp * 3] = o_r; io.rgbs[gp * 3 + 1] = o_g; io.rgbs[gp * 3 + 2] = o_b; }
     }
-    if (MODE == 1) {
+    if constexpr (MODE == 1) {
         float* comp = lds + lo.comp;             // (WAVES = 4: over ring buffer 0 -- every wave is past the last chunk's barrier)
         if (g == 0) {
             float* c = comp + (wave * 16 + n) * COMP_STRIDE;
@@ -429,8 +468,8 @@ using namespace snr;
 // The workgroup's latent rows are staged in LDS when its points belong to ONE object and the table has at most LDS_LAT_ROWS rows.
 
 template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
-static int launch16(const DecoderIO& io, const Layout& L, const Lds16& lo, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
-                    float* depth, float* acc, hipStream_t st) {
+static int launch16(const DecoderIO& io, const Layout& L, const Lds16& lo, const float* xyz, const float* viewdir, const typename PointSrc<MODE>::T& g,
+                    float* rgb, float* depth, float* acc, hipStream_t st) {
     auto kern = decoder_fwd16_kernel<MODE, WAVES, LATLDS, MASKS, DUMP>;
     // Dynamic LDS beyond the default cap must be granted per kernel, and (if HIP scopes the attribute per device) per device: one bit per
     // device that has it.  nn.DataParallel enters here from one host thread per device.  Two threads may both grant it; that is harmless.
@@ -472,3 +511,49 @@ int snr_fp32_fwd16_launch_(int mode, const DecoderIO& io, const Layout& L, const
     const bool four = lo4.total * 4 <= 80 * 1024 && (mode == 0 || (g.S <= 64 && 64 % g.S == 0));
     return four ? launch16_w<4>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st) : launch16_w<8>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st);
 }
+
+// density only (modes 2 and 3): the shapes and the latent staging of mode 0, no ReLU bits, no dumps
+template <int MODE, int WAVES>
+static int launch16_dens(const DecoderIO& io, const Layout& L, const float* xyz, const typename PointSrc<MODE>::T& src, hipStream_t st) {
+    const bool latlds = (io.points_per_obj % (WAVES * 16)) == 0 && L.n_lat <= LDS_LAT_ROWS;
+    const Lds16 lo = make_lds16(WAVES, L.n_mfma_layers, latlds ? L.n_lat : LDS_LAT_ROWS + 1);
+    if (latlds) return launch16<MODE, WAVES, true, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+    return launch16<MODE, WAVES, false, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+}
+
+template <int MODE>
+static int density_launch(const DecoderIO& io, const float* xyz, const typename PointSrc<MODE>::T& src, void* stream_) {
+    const Layout L = make_layout(io.sb, io.tb);
+    const bool lat4 = (io.points_per_obj % 64) == 0 && L.n_lat <= LDS_LAT_ROWS;
+    const bool four = make_lds16(4, L.n_mfma_layers, lat4 ? L.n_lat : LDS_LAT_ROWS + 1).total * 4 <= 80 * 1024;      // as snr_fp32_fwd16_launch_, mode 0
+    hipStream_t st = (hipStream_t)stream_;
+    return four ? launch16_dens<MODE, 4>(io, L, xyz, src, st) : launch16_dens<MODE, 8>(io, L, xyz, src, st);
+}
+
+extern "C" {
+
+int snr_density_fwd(const float* xyz, const float* latent, const float* packed, int64_t n_points, int64_t points_per_obj, int sb, int tb,
+                    float* sigmas, void* stream_) {
+    if (!xyz || !latent || !packed || !sigmas) return SNR_E_ARG;
+    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
+    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
+    if (n_points == 0) return SNR_OK;
+    DecoderIO io{packed, latent, sb, tb, (long long)n_points, (long long)points_per_obj, sigmas, nullptr, nullptr, nullptr, false};
+    io.latent_bias = nullptr;
+    return density_launch<2>(io, xyz, RayGeom{}, stream_);
+}
+
+int snr_density_grid(const snr_lattice* lattice, int64_t n_objects, const float* latent, const float* packed, int sb, int tb, float* sigmas,
+                     void* stream_) {
+    if (!lattice || !latent || !packed || !sigmas) return SNR_E_ARG;
+    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_objects < 0) return SNR_E_ARG;
+    for (int a = 0; a < 3; ++a)
+        if (lattice->n[a] < 1 || lattice->n[a] > 512) return SNR_E_ARG;
+    const long long ppo = (long long)lattice->n[0] * lattice->n[1] * lattice->n[2];
+    if (n_objects == 0) return SNR_OK;
+    DecoderIO io{packed, latent, sb, tb, (long long)n_objects * ppo, ppo, sigmas, nullptr, nullptr, nullptr, false};
+    io.latent_bias = nullptr;
+    return density_launch<3>(io, nullptr, *lattice, stream_);
+}
+
+}  // extern "C"

@@ -1,0 +1,202 @@
+"""``supnerf_amd.geometry`` -- the surface a shape code stands for.
+
+After an optimisation or a training run a caller holds one 256-float shape code per object; this module turns codes into geometry:
+
+  * ``query_density(model, xyz, shapecode)``: sigma at arbitrary decoder-frame points, B codes, object-major (``snr_density_fwd``);
+  * ``density_grid(model, shapecode, resolution, bound)``: sigma on a lattice generated in the kernel, (B, nx, ny, nz)
+    (``snr_density_grid``);
+  * ``extract_mesh(model_or_grid, shapecode, level=...)``: the iso-surface sigma = level by marching tetrahedra on the GPU
+    (``snr_iso_count`` -> two ``torch.cumsum`` -> ``snr_iso_emit``), one (verts (V,3) fp32, faces (F,3) int32) pair per object;
+  * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame;
+  * ``write_ply(path, verts, faces)``: binary little-endian PLY (host code).
+
+The density kernels run the exact fp32 chain of the decoder forward up to its density head and stop there (no view direction, no colour
+branch): sigma is bit-identical to ``ops.decoder_fwd(..., precision="fp32")``.  Latent terms come from ``model.latent_terms`` with a zero
+texture code (the texture rows feed nothing the density reads).  The mesh rules (vertex order, quad split, winding) are those of
+include/supnerf_hip.h, restated in tests/iso_restatement.py.  There is no CPU path: CPU tensors raise ``SnrError``."""
+import numpy as np
+import torch
+
+from . import _lib
+from . import model as M
+from . import ops
+from . import utils as U
+from ._lib import Lattice, SnrError, check
+
+MAX_RESOLUTION = 512
+
+
+def _decoder(model):
+    if not isinstance(model, M._DecoderBase):
+        raise SnrError(f"supnerf_amd.geometry needs a supnerf_amd decoder (CodeNeRF / SUPNeRF, or a reference class under install()), "
+                       f"got {type(model).__name__}")
+    return model
+
+
+def _gpu(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise SnrError(f"supnerf_amd.geometry: {what} must be a tensor on the GPU (no CPU fallback)")
+    return t
+
+
+def _codes(shapecode):
+    sc = _gpu(shapecode, "shapecode").detach()
+    if sc.dim() == 1:
+        sc = sc.unsqueeze(0)
+    if sc.dim() != 2 or sc.shape[1] != 256:
+        raise SnrError(f"shapecode must be (256,) or (B, 256), got {tuple(shapecode.shape)}")
+    return sc.float().contiguous()
+
+
+def _latent(model, sc):
+    """(B, NLAT, 256) latent terms of the shape codes (texture code zero: the density never reads the texture terms)."""
+    with torch.no_grad():
+        return model.latent_terms(sc, torch.zeros_like(sc)).detach().float().contiguous()
+
+
+def lattice(resolution, bound=(-0.5, 0.5)):
+    """The ``Lattice`` (lo, h, n per axis) of ``resolution`` (int or triple) points over ``bound``: a scalar pair (lo, hi) or a per-axis
+    pair (lo[3], hi[3]).  h = (hi - lo) / (n - 1) in fp32 (0 where n = 1); the kernels place point i at lo + h i (fp32 multiply, add)."""
+    n = np.broadcast_to(np.asarray(resolution, dtype=np.int64), (3,))
+    if (n < 1).any() or (n > MAX_RESOLUTION).any():
+        raise SnrError(f"resolution must be 1..{MAX_RESOLUTION} points per axis, got {tuple(int(x) for x in n)}")
+    lo, hi = bound
+    lo = np.broadcast_to(np.asarray(lo, dtype=np.float32), (3,)).astype(np.float32)
+    hi = np.broadcast_to(np.asarray(hi, dtype=np.float32), (3,)).astype(np.float32)
+    h = np.where(n > 1, (hi - lo) / np.maximum(n - 1, 1).astype(np.float32), np.float32(0)).astype(np.float32)
+    lat = Lattice()
+    for a in range(3):
+        lat.lo[a], lat.h[a], lat.n[a] = float(lo[a]), float(h[a]), int(n[a])
+    return lat
+
+
+def lattice_points(lat, device=None):
+    """(nx*ny*nz, 3) fp32 points of a ``Lattice`` in the kernels' order (x-major, z fastest), computed on the host by the same formula."""
+    axes = [torch.tensor(lat.lo[a], dtype=torch.float32) + torch.tensor(lat.h[a], dtype=torch.float32) *
+            torch.arange(lat.n[a], dtype=torch.float32) for a in range(3)]
+    X, Y, Z = torch.meshgrid(*axes, indexing="ij")
+    return torch.stack([X, Y, Z], dim=-1).reshape(-1, 3).to(device)
+
+
+def query_density(model, xyz, shapecode):
+    """sigma (P,) at decoder-frame points ``xyz`` (P, 3), object-major over the B codes of ``shapecode`` (B, 256): P / B points each."""
+    model = _decoder(model)
+    sc = _codes(shapecode)
+    xyz = ops._f32c(_gpu(xyz, "xyz").detach())
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise SnrError(f"xyz must be (P, 3), got {tuple(xyz.shape)}")
+    B, P = sc.shape[0], xyz.shape[0]
+    if P % B:
+        raise SnrError(f"{P} points do not split evenly over {B} objects")
+    dev = xyz.device
+    sig = torch.empty(P, device=dev)
+    if P == 0:
+        return sig
+    lat, packed = _latent(model, sc), model.packed_weights()
+    ops._need_gpu(lat, packed)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_density_fwd(ops._p(xyz), ops._p(lat), ops._p(packed), P, P // B, model.shape_blocks, model.texture_blocks,
+                                         ops._p(sig), ops._stream(dev)), "snr_density_fwd")
+    return sig
+
+
+def density_grid(model, shapecode, resolution, bound=(-0.5, 0.5)):
+    """sigma (B, nx, ny, nz) of each code on the lattice ``lattice(resolution, bound)``, generated in the kernel (no point array)."""
+    model = _decoder(model)
+    sc = _codes(shapecode)
+    lat = lattice(resolution, bound)
+    dev = sc.device
+    B = sc.shape[0]
+    out = torch.empty(B, lat.n[0], lat.n[1], lat.n[2], device=dev)
+    latent, packed = _latent(model, sc), model.packed_weights()
+    ops._need_gpu(latent, packed)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_density_grid(lat, B, ops._p(latent), ops._p(packed), model.shape_blocks, model.texture_blocks, ops._p(out),
+                                          ops._stream(dev)), "snr_density_grid")
+    return out
+
+
+def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=(-0.5, 0.5)):
+    """Iso-surface {sigma = level} per object: a list of (verts (V, 3) fp32, faces (F, 3) int32) on the GPU, faces counter-clockwise
+    seen from the low side (outward normals around a dense object), vertices in ``bound``'s decoder coordinates (``to_object_frame``
+    maps them to the object's frame).  ``model_or_grid``: a decoder (then ``shapecode`` (B, 256) and ``resolution`` make the grid with
+    ``density_grid``) or a grid tensor (B, nx, ny, nz) / (nx, ny, nz) over ``bound`` (the decoder is skipped).  A non-finite grid value
+    raises ``SnrError``.  One host synchronisation: the sizes of the output."""
+    if torch.is_tensor(model_or_grid):
+        grid = _gpu(model_or_grid, "the grid").detach()
+        if grid.dim() == 3:
+            grid = grid.unsqueeze(0)
+        if grid.dim() != 4:
+            raise SnrError(f"a grid is (B, nx, ny, nz) or (nx, ny, nz), got {tuple(model_or_grid.shape)}")
+        grid = ops._f32c(grid)
+        lat = lattice(tuple(grid.shape[1:]), bound)
+    else:
+        if shapecode is None:
+            raise SnrError("extract_mesh(model, shapecode, ...): the shape codes are missing")
+        grid = density_grid(model_or_grid, shapecode, resolution, bound)
+        lat = lattice(resolution, bound)
+    if min(lat.n) < 2:
+        raise SnrError(f"extract_mesh needs at least 2 points per axis, got {tuple(lat.n)}")
+    dev = grid.device
+    B = grid.shape[0]
+    nv = lat.n[0] * lat.n[1] * lat.n[2]
+    nc = (lat.n[0] - 1) * (lat.n[1] - 1) * (lat.n[2] - 1)
+    if B == 0:
+        return []
+    level = float(np.float32(level))
+    lib, st = _lib.lib(), ops._stream(dev)
+    tri_count = torch.empty(B, nc, dtype=torch.uint8, device=dev)
+    edge_mask = torch.empty(B, nv, dtype=torch.uint8, device=dev)
+    edge_count = torch.empty(B, nv, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.snr_iso_count(ops._p(grid), B, lat, level, ops._ptr(tri_count, torch.uint8), ops._ptr(edge_mask, torch.uint8),
+                                ops._ptr(edge_count, torch.uint8), st), "snr_iso_count")
+        # per object: <= 7 * 512^3 vertices and <= 12 * 511^3 triangles, both below 2^31
+        edge_scan = torch.cumsum(edge_count, dim=1, dtype=torch.int32)
+        tri_scan = torch.cumsum(tri_count, dim=1, dtype=torch.int32)
+        n_vert, n_tri = edge_scan[:, -1].long(), tri_scan[:, -1].long()
+        vert_off, tri_off = torch.cumsum(n_vert, 0) - n_vert, torch.cumsum(n_tri, 0) - n_tri
+        bad = (~torch.isfinite(grid)).any().long().view(1)
+        host = torch.cat([bad, n_vert, n_tri]).cpu().tolist()
+        if host[0]:
+            raise SnrError("extract_mesh: the grid holds a non-finite value")
+        nvs, nts = host[1:1 + B], host[1 + B:]
+        verts = torch.empty(sum(nvs), 3, device=dev)
+        faces = torch.empty(sum(nts), 3, dtype=torch.int32, device=dev)
+        check(lib.snr_iso_emit(ops._p(grid), B, lat, level, ops._ptr(edge_mask, torch.uint8), ops._ptr(edge_scan, torch.int32),
+                               ops._ptr(tri_scan, torch.int32), ops._ptr(vert_off, torch.int64), ops._ptr(tri_off, torch.int64),
+                               ops._ptr(verts), ops._ptr(faces, torch.int32), st), "snr_iso_emit")
+    out, v0, f0 = [], 0, 0
+    for b in range(B):
+        out.append((verts[v0:v0 + nvs[b]], faces[f0:f0 + nts[b]]))
+        v0 += nvs[b]
+        f0 += nts[b]
+    return out
+
+
+def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False):
+    """Decoder-frame points (..., 3) -> the object's metric frame, inverting the package's point mappings:
+    family "a" (``utils`` render paths, ``_render_shared_z``): x = F (p / obj_diag);
+    family "b" (``renderer.NeRFRenderer``): x = F (p / (obj_diag / 2)), obj_diag = |(l, w, h)|;
+    F = ``utils._frame(False, kitti2nusc, shapenet_obj_cood)``, the frame both paths hand the kernels (a signed permutation: F^-1 = F^T)."""
+    if family not in ("a", "b"):
+        raise SnrError(f"family is 'a' (utils render paths) or 'b' (NeRFRenderer), got {family!r}")
+    v = torch.as_tensor(verts)
+    m = torch.tensor(U._frame(False, kitti2nusc, shapenet_obj_cood), dtype=v.dtype, device=v.device).view(3, 3)
+    scale = float(obj_diag) if family == "a" else float(obj_diag) / 2
+    return (v @ m) * scale
+
+
+def write_ply(path, verts, faces):
+    """Binary little-endian PLY: float x, y, z per vertex, a uchar-counted int list per triangle."""
+    v = np.ascontiguousarray(torch.as_tensor(verts).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), dtype="<i4").reshape(-1, 3)
+    rec = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    rec["n"], rec["i"] = 3, f
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(rec.tobytes())
