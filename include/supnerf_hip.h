@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 9
+#define SNR_ABI_VERSION 10
 
 enum {
     SNR_OK = 0,
@@ -337,6 +337,17 @@ int snr_density_fwd(const float* xyz, const float* latent, const float* packed, 
                     int shape_blocks, int texture_blocks, float* sigmas, void* stream);
 int snr_density_grid(const snr_lattice* lattice, int64_t n_objects, const float* latent, const float* packed, int shape_blocks,
                      int texture_blocks, float* sigmas, void* stream);
+/* snr_density_fwd plus the ReLU bits of encoding_xyz and the shape layers, in snr_decoder_fwd's relu_masks layout
+ * (snr_mask_bytes(P, sb, tb) bytes; texture-branch slots are not written). sigmas bit-identical to snr_density_fwd. */
+int snr_density_fwd_masks(const float* xyz, const float* latent, const float* packed, int64_t n_points, int64_t points_per_obj,
+                          int shape_blocks, int texture_blocks, float* sigmas, void* relu_masks, void* stream);
+/* Backward of snr_density_fwd: d_xyz (P,3) and d_latent (B,NLAT,256; texture rows zero), each nullable, given d_sigmas (P).
+ * d_latent needs points_per_obj % 64 == 0 (else SNR_E_UNSUPPORTED); workspace: snr_decoder_bwd_ws_bytes().
+ * relu_masks, sigmas: from snr_density_fwd_masks (or snr_decoder_fwd) on the same points.  d_xyz and the shape rows of d_latent are
+ * bit for bit those of snr_decoder_bwd with SNR_FP32 and d_rgbs = 0 (zeros of either sign compare equal). */
+int snr_density_bwd(const float* xyz, const float* latent, const float* packed, const void* relu_masks, const float* sigmas,
+                    const float* d_sigmas, int64_t n_points, int64_t points_per_obj, int shape_blocks, int texture_blocks,
+                    float* d_latent, float* d_xyz, void* workspace, size_t ws_bytes, void* stream);
 
 /* Iso-surface of n_grids grids on `lattice` (2 <= n[a] <= 512) by marching tetrahedra on the Kuhn split.  A sample is inside iff
  * value > level.  Cell (i0, i1, i2) (index c = (i0 (n1-1) + i1) (n2-1) + i2) has corners v000 + bits (bit a = +1 on axis a) and splits

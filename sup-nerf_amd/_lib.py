@@ -81,6 +81,8 @@ _SIGS = {
     "snr_adamw_table_step": (C.c_int, [_P, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "snr_density_fwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P]),
     "snr_density_grid": (C.c_int, [C.POINTER(Lattice), C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "snr_density_fwd_masks": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
+    "snr_density_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "snr_iso_count": (C.c_int, [_P, C.c_int64, C.POINTER(Lattice), C.c_float, _P, _P, _P, _P]),
     "snr_iso_emit": (C.c_int, [_P, C.c_int64, C.POINTER(Lattice), C.c_float, _P, _P, _P, _P, _P, _P, _P, _P]),
 }

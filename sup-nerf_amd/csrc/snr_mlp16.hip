@@ -174,7 +174,8 @@ template <> struct PointSrc<3> { using T = snr_lattice; };
 
 // MODE 0: explicit points; 1: fused render; 2 and 3: density only (explicit points; points of a lattice, object-major, x-major / z fastest):
 // the same chain up to the density head -- same instructions, so the same sigma bit for bit -- and nothing after it: no view direction, no
-// enc_viewdir / texture / rgb layers.  The stream's last request is then enc_shape's last chunk.
+// enc_viewdir / texture / rgb layers.  The stream's last request is then enc_shape's last chunk.  With MASKS (mode 2 only: snr_density_fwd_masks)
+// the ReLU bits of enc_xyz and the shape layers go to their slots of the full forward's layout; the texture-branch slots are not written.
 template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
 __global__ void __launch_bounds__(WAVES * 64, 2)
 decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__ xyz, const float* __restrict__ viewdir, typename PointSrc<MODE>::T gm,
@@ -512,11 +513,18 @@ int snr_fp32_fwd16_launch_(int mode, const DecoderIO& io, const Layout& L, const
     return four ? launch16_w<4>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st) : launch16_w<8>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st);
 }
 
-// density only (modes 2 and 3): the shapes and the latent staging of mode 0, no ReLU bits, no dumps
+// density only (modes 2 and 3): the shapes and the latent staging of mode 0, no dumps.  Mode 2 saves the ReLU bits of enc_xyz and the shape
+// layers when io.masks is set (the slots snr_decoder_fwd writes for them; the texture-branch slots are left as they are)
 template <int MODE, int WAVES>
 static int launch16_dens(const DecoderIO& io, const Layout& L, const float* xyz, const typename PointSrc<MODE>::T& src, hipStream_t st) {
     const bool latlds = (io.points_per_obj % (WAVES * 16)) == 0 && L.n_lat <= LDS_LAT_ROWS;
     const Lds16 lo = make_lds16(WAVES, L.n_mfma_layers, latlds ? L.n_lat : LDS_LAT_ROWS + 1);
+    if constexpr (MODE == 2) {
+        if (io.masks) {
+            if (latlds) return launch16<MODE, WAVES, true, true, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+            return launch16<MODE, WAVES, false, true, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+        }
+    }
     if (latlds) return launch16<MODE, WAVES, true, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
     return launch16<MODE, WAVES, false, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
 }
@@ -539,6 +547,17 @@ int snr_density_fwd(const float* xyz, const float* latent, const float* packed, 
     if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
     if (n_points == 0) return SNR_OK;
     DecoderIO io{packed, latent, sb, tb, (long long)n_points, (long long)points_per_obj, sigmas, nullptr, nullptr, nullptr, false};
+    io.latent_bias = nullptr;
+    return density_launch<2>(io, xyz, RayGeom{}, stream_);
+}
+
+int snr_density_fwd_masks(const float* xyz, const float* latent, const float* packed, int64_t n_points, int64_t points_per_obj, int sb, int tb,
+                          float* sigmas, void* relu_masks, void* stream_) {
+    if (!xyz || !latent || !packed || !sigmas || !relu_masks) return SNR_E_ARG;
+    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
+    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
+    if (n_points == 0) return SNR_OK;
+    DecoderIO io{packed, latent, sb, tb, (long long)n_points, (long long)points_per_obj, sigmas, nullptr, (uint4*)relu_masks, nullptr, false};
     io.latent_bias = nullptr;
     return density_launch<2>(io, xyz, RayGeom{}, stream_);
 }

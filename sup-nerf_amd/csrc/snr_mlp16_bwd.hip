@@ -265,11 +265,15 @@ __device__ __forceinline__ void ray_grad_tail16(const RayGeom& g, float* __restr
 #define SNR16_BSTAMP(i) do {} while (0)
 #endif
 
-// MODE 0: explicit points (backward of SUPNeRF.forward).  MODE 1: fused render.
+// MODE 0: explicit points (backward of SUPNeRF.forward).  MODE 1: fused render.  MODE 2: explicit points, density only (backward of
+// snr_density_fwd): no view direction, no colour head, rgb.0^T, texture layers or enc_viewdir^T.  The stream starts at enc_shape^T; the density
+// head's seed lands on zeroed accumulators, which is what enc_viewdir^T hands the full kernel when d_rgbs = 0 (a sum of signed zeros), so
+// d_xyz and the shape rows of the latent gradient are the full kernel's at d_rgbs = 0.  The texture rows of the partials are written as zeros.
 template <int MODE>
 __global__ void __launch_bounds__(256, 2)
 decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float* __restrict__ viewdir, RayGeom gm) {
     __shared__ __attribute__((aligned(16))) float lds[LB_TOTAL];
+    constexpr bool DENS = MODE == 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, g = lane >> 4;
     const long long tile64 = blockIdx.x;
     const long long tile16 = tile64 * 4 + wave;
@@ -307,16 +311,19 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     };
     auto rows_of = [&](int li) { return li == li_view ? K_VIEW_PAD : (li == 0 ? 4 * K_XYZ_PAD /* four chunks at a time: layer_xyz_b */ : 256); };
 
-    // ---- start the stream; the density head's weights -> LDS (one row)
-    chunk_b(dm, stream, lds, lds, 256);
+    // ---- start the stream (density only: at enc_shape^T); the density head's weights -> LDS (one row)
+    chunk_b(dm, DENS ? layer_base(li_encshape) : stream, lds, lds, 256);
     if (wave == 0) row_dma16(dm, io.packed + L.sigma_w, lds + LB_SIGW, lds);
 
     // ---- this lane's point and its upstream gradient
     float x, y, z, dx, dy, dz, tval = 0.f, zc = 0.f, uval = 0.f;
     long long ray = 0, obj = 0;
-    if (MODE == 0) {
+    if constexpr (MODE == 0) {
         x = xyz[gp * 3]; y = xyz[gp * 3 + 1]; z = xyz[gp * 3 + 2];
         dx = viewdir[gp * 3]; dy = viewdir[gp * 3 + 1]; dz = viewdir[gp * 3 + 2];
+    } else if constexpr (DENS) {
+        x = xyz[gp * 3]; y = xyz[gp * 3 + 1]; z = xyz[gp * 3 + 2];
+        dx = dy = dz = 0.f;
     } else {
         const PointId id = point_id(gm, tile64, 64, wave * 16 + n, live);
         ray = id.ray; obj = id.obj;
@@ -324,11 +331,15 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
         x = sp.x; y = sp.y; z = sp.z; dx = sp.dx; dy = sp.dy; dz = sp.dz; zc = sp.zc; tval = sp.t; uval = sp.u;
     }
     float gs = 0.f, gr = 0.f, ggr = 0.f, gb = 0.f, gzc = 0.f;
-    if (MODE == 0) {
+    if constexpr (MODE == 0) {
         if (live) {
             gs = io.d_sigmas ? io.d_sigmas[gp] : 0.f;
             if (io.d_rgbs) { gr = io.d_rgbs[gp * 3]; ggr = io.d_rgbs[gp * 3 + 1]; gb = io.d_rgbs[gp * 3 + 2]; }
         }
+    } else if constexpr (DENS) {
+        if (live) gs = io.d_sigmas[gp];
+        if (io.partial)           // texture rows of this workgroup's partials: nothing reaches them
+            for (int t = 0; t < tb; ++t) io.partial[(tile64 * L.n_lat + sb + t) * 256 + tid] = 0.f;
     } else {
         float* comp = lds + LB_RING1;            // (over ring buffer 1: chunk 1 is requested behind the barriers below)
         if (g == 0) comp[(wave * 16 + n) * COMP_STRIDE + 5] = zc;
@@ -377,7 +388,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     SNR16_BSTAMP(1);
     // ---- colour head backward: g_h = W2^T d_rgb, masked by rgb.0's ReLU bits -> the eight operand tiles of rgb.0^T
     f32x4 xh[8];
-    {
+    if constexpr (!DENS) {
         uint32_t mw[4];
         load_bits(n_relu - 1, mw);
         const float* w2 = io.packed + L.rgb2_w;
@@ -399,8 +410,15 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     f32x4 accP[18];
     uint32_t mw[4], mw_next[4];
     const uint32_t ones[4] = {~0u, ~0u, ~0u, ~0u};
-    load_bits(relu_slot(li_last, sb), mw_next);          // the first boundary's bits (layer li_last's), requested before its chunks
-    layer_b<16, 4, false>(accP, xh, ring, lds, ones, dm, stream, layer_base(li_last), rows_of(li_last));
+    if constexpr (DENS) {         // (enc_shape, the first layer here, has no activation: mw_next is not applied there)
+#pragma unroll
+        for (int T = 0; T < 16; ++T) accP[T] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mw_next[i] = ~0u;
+    } else {
+        load_bits(relu_slot(li_last, sb), mw_next);          // the first boundary's bits (layer li_last's), requested before its chunks
+        layer_b<16, 4, false>(accP, xh, ring, lds, ones, dm, stream, layer_base(li_last), rows_of(li_last));
+    }
 
     SNR16_BSTAMP(3);
     // ---- 256-wide layers in reverse: texture .., enc_viewdir, enc_shape, shape ..
@@ -410,8 +428,9 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
         if (la_pending >= 0) flush_latent_rows(lds + LB_RED, io.partial + (tile64 * L.n_lat + la_pending) * 256, tid);
         la_pending = -1;
     };
+    const int li_first = DENS ? li_encshape : li_last;
 #pragma unroll 1
-    for (int li = li_last; li >= 1; --li) {
+    for (int li = li_first; li >= 1; --li) {
         const bool relu = (li != li_encshape);
 #pragma unroll
         for (int i = 0; i < 4; ++i) mw[i] = relu ? mw_next[i] : ~0u;
@@ -428,12 +447,12 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
         load_bits(li - 1 >= 1 ? relu_slot(li - 1, sb) : 0, mw_next);
         const float* base = layer_base(li);
         const float* nxt = (li - 1 >= 1) ? layer_base(li - 1) : layer_base(0);
-        if (li == li_view) layer_b<18, 8, true>(accP, nullptr, ring, lds, mw, dm, base, nxt, rows_of(li - 1), flush);
+        if (!DENS && li == li_view) layer_b<18, 8, true>(accP, nullptr, ring, lds, mw, dm, base, nxt, rows_of(li - 1), flush);
         else layer_b<16, 8, true>(accP, nullptr, ring, lds, mw, dm, base, nxt, rows_of(li - 1), flush);
         // accP = gradient wrt the INPUT of layer li = previous output + latent term
         const int la = latent_after(li - 1, sb, tb);
         if (la >= 0 && io.partial) { reduce16_store(accP, lds + LB_RED + wave * 256, lane, tile_live); la_pending = la; }
-        if (li == li_view) { gdir[0] = accP[16]; gdir[1] = accP[17]; SNR16_BSTAMP(4); }
+        if (!DENS && li == li_view) { gdir[0] = accP[16]; gdir[1] = accP[17]; SNR16_BSTAMP(4); }
     }
     SNR16_BSTAMP(5);
 
@@ -448,10 +467,12 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     for (int T = 0; T < 4; ++T)
 #pragma unroll
         for (int r = 0; r < 4; ++r) sc[16 * T + 4 * g + r] = accP[T][r];
+    if constexpr (!DENS) {
 #pragma unroll
-    for (int T = 0; T < 2; ++T)
+        for (int T = 0; T < 2; ++T)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sc[64 + 16 * T + 4 * g + r] = gdir[T][r];
+            for (int r = 0; r < 4; ++r) sc[64 + 16 * T + 4 * g + r] = gdir[T][r];
+    }
     __syncthreads();
     float gx = 0.f, gy = 0.f, gz = 0.f, hx = 0.f, hy = 0.f, hz = 0.f;
     auto pe_grad = [&](const float* row, int q, int n_freq, float sn, float cs, float& ax, float& ay, float& az) {
@@ -469,7 +490,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
             pe_grad(sc, q + 1, XYZ_FREQ, sn[1], cs[1], gx, gy, gz);
         }
     }
-    {
+    if constexpr (!DENS) {
         const int q = 3 * g;
         f32x2 sn, cs;
         pe_sincos2(f32x2{ldexpf(pick3(dx, dy, dz, q % 3), q / 3), ldexpf(pick3(dx, dy, dz, (q + 1) % 3), (q + 1) / 3)}, &sn, &cs);
@@ -479,6 +500,14 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
         pe_sincos(ldexpf(pick3(dx, dy, dz, (q + 2) % 3), (q + 2) / 3), &s1, &c1);
         pe_grad(sc + 64, q + 2, DIR_FREQ, s1, c1, hx, hy, hz);
     }
+    if constexpr (DENS) {
+        if (g == 0) { gx += sc[0]; gy += sc[1]; gz += sc[2]; }
+        gx += __shfl_xor(gx, 16, 64); gx += __shfl_xor(gx, 32, 64);
+        gy += __shfl_xor(gy, 16, 64); gy += __shfl_xor(gy, 32, 64);
+        gz += __shfl_xor(gz, 16, 64); gz += __shfl_xor(gz, 32, 64);
+        if (live && g == 0 && io.d_xyz) { io.d_xyz[gp * 3] = gx; io.d_xyz[gp * 3 + 1] = gy; io.d_xyz[gp * 3 + 2] = gz; }
+        return;
+    }
     if (g == 0) { gx += sc[0]; gy += sc[1]; gz += sc[2]; hx += sc[64]; hy += sc[65]; hz += sc[66]; }
     gx += __shfl_xor(gx, 16, 64); gx += __shfl_xor(gx, 32, 64);
     gy += __shfl_xor(gy, 16, 64); gy += __shfl_xor(gy, 32, 64);
@@ -487,7 +516,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     hy += __shfl_xor(hy, 16, 64); hy += __shfl_xor(hy, 32, 64);
     hz += __shfl_xor(hz, 16, 64); hz += __shfl_xor(hz, 32, 64);
 
-    if (MODE == 0) {
+    if constexpr (MODE == 0) {
         if (live && g == 0) {
             if (io.d_xyz) { io.d_xyz[gp * 3] = gx; io.d_xyz[gp * 3 + 1] = gy; io.d_xyz[gp * 3 + 2] = gz; }
             if (io.d_dir) { io.d_dir[gp * 3] = hx; io.d_dir[gp * 3 + 1] = hy; io.d_dir[gp * 3 + 2] = hz; }
@@ -516,6 +545,7 @@ int snr_fp32_bwd16_supported_(int mode, const BwdIO& io, const RayGeom& g) {
 int snr_fp32_bwd16_launch_(int mode, const BwdIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, void* stream_) {
     const unsigned grid = (unsigned)((io.n_points + 63) / 64);
     if (mode == 0) decoder_bwd16_kernel<0><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
+    else if (mode == 2) decoder_bwd16_kernel<2><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, nullptr, g);
     else decoder_bwd16_kernel<1><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, nullptr, nullptr, g);
     return snr_check_launch_();
 }

@@ -414,6 +414,33 @@ int snr_decoder_bwd(const float* xyz, const float* viewdir, const float* latent,
     return SNR_OK;
 }
 
+// backward of snr_density_fwd: always the two-waves kernel (snr_mlp16_bwd.hip, mode 2), so the latent gradient needs whole 64-point workgroups
+int snr_density_bwd(const float* xyz, const float* latent, const float* packed, const void* relu_masks, const float* sigmas,
+                    const float* d_sigmas, int64_t n_points, int64_t points_per_obj, int sb, int tb, float* d_latent, float* d_xyz,
+                    void* workspace, size_t ws_bytes, void* stream_) {
+    if (!xyz || !latent || !packed || !relu_masks || !sigmas || !d_sigmas) return SNR_E_ARG;
+    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
+    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
+    if (n_points == 0) return SNR_OK;
+    const bool want_lat = d_latent && (sb + tb) > 0;
+    if (want_lat) {
+        if (points_per_obj % 64) return SNR_E_UNSUPPORTED;
+        if (!workspace || ws_bytes < bwd_ws_bytes(n_points, points_per_obj, sb, tb)) return SNR_E_WORKSPACE;
+    }
+    BwdIO io{};
+    io.packed = packed; io.latent = latent; io.sb = sb; io.tb = tb; io.n_points = n_points; io.points_per_obj = points_per_obj;
+    io.masks = (const uint4*)relu_masks; io.sigmas = sigmas; io.d_sigmas = d_sigmas;
+    io.partial = want_lat ? (float*)workspace : nullptr;
+    io.d_xyz = d_xyz;
+    const Layout L = make_layout(sb, tb);
+    const int rc = snr_fp32_bwd16_launch_(2, io, L, xyz, nullptr, RayGeom{}, stream_);
+    if (rc != SNR_OK) return rc;
+    if (want_lat)
+        return snr_launch_reduce_latent_(io.partial, io.partial + ((n_points + 63) / 64) * (int64_t)(sb + tb) * 256, points_per_obj / 64, sb + tb,
+                                         n_points / points_per_obj, d_latent, stream_);
+    return SNR_OK;
+}
+
 size_t snr_render_bwd_ws_bytes(const snr_render_args* a) {
     if (!a) return 0;
     return bwd_ws_bytes(a->n_rays * (int64_t)a->n_samples, a->rays_per_obj * (int64_t)a->n_samples, a->shape_blocks, a->texture_blocks);

@@ -7,13 +7,20 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     (``snr_density_grid``);
   * ``extract_mesh(model_or_grid, shapecode, level=...)``: the iso-surface sigma = level by marching tetrahedra on the GPU
     (``snr_iso_count`` -> two ``torch.cumsum`` -> ``snr_iso_emit``), one (verts (V,3) fp32, faces (F,3) int32) pair per object;
-  * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame;
-  * ``write_ply(path, verts, faces)``: binary little-endian PLY (host code).
+  * ``density(model, xyz, shapecode)``: sigma (P,) like ``query_density``, differentiable wrt ``xyz`` and ``shapecode``
+    (``ops.DensityPoints``: ``snr_density_fwd_masks`` forward, ``snr_density_bwd`` backward), for losses that read the density only;
+  * ``density_gradient(model, xyz, shapecode)``: sigma and d sigma / d xyz in two launches, no autograd;
+  * ``vertex_normals(model, meshes, shapecode)``: unit outward normals -grad sigma / |grad sigma| at the vertices of ``extract_mesh``;
+  * ``vertex_colors(model, meshes, normals, shapecode, texturecode)``: the decoder's raw rgb at every vertex, seen head-on;
+  * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
+  * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
 
 The density kernels run the exact fp32 chain of the decoder forward up to its density head and stop there (no view direction, no colour
 branch): sigma is bit-identical to ``ops.decoder_fwd(..., precision="fp32")``.  Latent terms come from ``model.latent_terms`` with a zero
 texture code (the texture rows feed nothing the density reads).  The mesh rules (vertex order, quad split, winding) are those of
-include/supnerf_hip.h, restated in tests/iso_restatement.py.  There is no CPU path: CPU tensors raise ``SnrError``."""
+include/supnerf_hip.h, restated in tests/iso_restatement.py.  The density backward runs the fp32 backward kernel from d sigma alone (no colour
+branch): d xyz and the shape-code gradient are bit for bit those of the full backward with a zero colour gradient.  There is no CPU path:
+CPU tensors raise ``SnrError``."""
 import numpy as np
 import torch
 
@@ -100,6 +107,140 @@ def query_density(model, xyz, shapecode):
     return sig
 
 
+def _points(xyz, B):
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise SnrError(f"xyz must be (P, 3), got {tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
+    _gpu(xyz, "xyz")
+    if xyz.shape[0] % B:
+        raise SnrError(f"{xyz.shape[0]} points do not split evenly over {B} objects")
+    return xyz
+
+
+def density(model, xyz, shapecode):
+    """sigma (P,) at decoder-frame points ``xyz`` (P, 3), object-major over the B codes of ``shapecode`` (B, 256) -- the values of
+    ``query_density`` -- with autograd to ``xyz`` and ``shapecode`` (through ``model.latent_terms(shapecode, 0)``).  The decoder's
+    weights are constants here: with grad mode on and ``model.train_decoder_weights`` set this raises rather than leave them without
+    a gradient."""
+    model = _decoder(model)
+    if torch.is_grad_enabled() and model.train_decoder_weights:
+        raise SnrError("geometry.density does not differentiate the decoder weights: with train_decoder_weights set, run it under "
+                       "torch.no_grad() or use the model's forward")
+    sc = _gpu(shapecode, "shapecode")
+    if sc.dim() == 1:
+        sc = sc.unsqueeze(0)
+    if sc.dim() != 2 or sc.shape[1] != 256 or sc.shape[0] < 1:
+        raise SnrError(f"shapecode must be (256,) or (B, 256), got {tuple(shapecode.shape)}")
+    xyz = _points(xyz, sc.shape[0])
+    sc = sc.float()
+    model._note_decoder_run(constant=True)
+    lat = model.latent_terms(sc, torch.zeros_like(sc))
+    packed = model.packed_weights()
+    ops._need_gpu(lat, packed)
+    return ops.DensityPoints.apply(xyz, lat, packed, model.shape_blocks, model.texture_blocks)
+
+
+def density_gradient(model, xyz, shapecode):
+    """(sigma (P,), d sigma / d xyz (P, 3)) at decoder-frame points ``xyz``, object-major over ``shapecode`` (B, 256); no autograd.  Two
+    launches: the density forward saving its ReLU bits, then its backward with d sigma = 1."""
+    model = _decoder(model)
+    sc = _codes(shapecode)
+    xyz = ops._f32c(_points(xyz, sc.shape[0]).detach())
+    if xyz.shape[0] == 0:
+        return torch.empty(0, device=xyz.device), torch.empty(0, 3, device=xyz.device)
+    lat, packed = _latent(model, sc), model.packed_weights()
+    ops._need_gpu(lat, packed)
+    sb, tb = model.shape_blocks, model.texture_blocks
+    sig, masks = ops.density_fwd(xyz, lat, packed, sb, tb, save_masks=True)
+    _, grad = ops.density_bwd(xyz, lat, packed, masks, sig, torch.ones_like(sig), sb, tb, need_latent=False)
+    return sig, grad
+
+
+def _meshes(meshes):
+    if isinstance(meshes, tuple) and len(meshes) == 2 and torch.is_tensor(meshes[0]):
+        raise SnrError("meshes is the list extract_mesh returns, one (verts, faces) pair per object")
+    out = []
+    for m in meshes:
+        if not isinstance(m, (tuple, list)) or len(m) != 2:
+            raise SnrError("meshes is the list extract_mesh returns, one (verts, faces) pair per object")
+        v, f = m
+        _gpu(v, "verts")
+        _gpu(f, "faces")
+        if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+            raise SnrError(f"a mesh is verts (V, 3) and faces (F, 3), got {tuple(v.shape)} and {tuple(f.shape)}")
+        out.append((v, f))
+    return out
+
+
+def _per_object(codes, n, what):
+    c = _codes(codes)
+    if c.shape[0] != n:
+        raise SnrError(f"{n} meshes but {c.shape[0]} {what}s")
+    return c
+
+
+def face_normal_sums(verts, faces):
+    """(V, 3): per vertex the sum of the cross products (v1 - v0) x (v2 - v0) of its faces, i.e. the area-weighted mean face normal up to
+    a positive factor; outward for the winding of ``extract_mesh``."""
+    v = verts.detach().float()
+    f = faces.long()
+    out = torch.zeros_like(v)
+    if f.shape[0]:
+        a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+        fn = torch.cross(b - a, c - a, dim=1)
+        for k in range(3):
+            out.index_add_(0, f[:, k], fn)
+    return out
+
+
+def vertex_normals(model, meshes, shapecode):
+    """One (V, 3) tensor of unit normals per mesh of ``meshes`` (the list ``extract_mesh`` returns for ``shapecode`` (B, 256)):
+    n = -grad sigma / |grad sigma|, the outward normal of the decoder's surface, from ``density_gradient`` (one launch pair per object).
+    Where |grad sigma| is zero or not finite, the area-weighted mean of the adjacent face normals stands in."""
+    model = _decoder(model)
+    meshes = _meshes(meshes)
+    sc = _per_object(shapecode, len(meshes), "shape code")
+    out = []
+    for b, (v, f) in enumerate(meshes):
+        if v.shape[0] == 0:
+            out.append(torch.empty(0, 3, device=v.device))
+            continue
+        _, g = density_gradient(model, v, sc[b:b + 1])
+        norm = g.norm(dim=1, keepdim=True)
+        good = torch.isfinite(norm) & (norm > 0)
+        n = torch.where(good, -g / torch.where(good, norm, torch.ones_like(norm)), torch.zeros_like(g))
+        if not bool(good.all()):
+            fn = face_normal_sums(v, f)
+            fn = fn / fn.norm(dim=1, keepdim=True).clamp_min(1e-30)
+            n = torch.where(good, n, fn)
+        out.append(n)
+    return out
+
+
+def vertex_colors(model, meshes, normals, shapecode, texturecode):
+    """One (V, 3) tensor per mesh: the decoder's raw rgb (no sigmoid, as the decoder returns it) at each vertex, seen head-on (view direction
+    -normal), through the exact fp32 decoder forward with ``model.latent_terms(shapecode, texturecode)`` of that object."""
+    model = _decoder(model)
+    meshes = _meshes(meshes)
+    if len(normals) != len(meshes):
+        raise SnrError(f"{len(meshes)} meshes but {len(normals)} normal tensors")
+    sc = _per_object(shapecode, len(meshes), "shape code")
+    tc = _per_object(texturecode, len(meshes), "texture code")
+    with torch.no_grad():
+        lat = model.latent_terms(sc, tc).detach().float().contiguous()
+    packed = model.packed_weights()
+    out = []
+    for b, ((v, _), n) in enumerate(zip(meshes, normals)):
+        n = _gpu(n, "normals")
+        if tuple(n.shape) != tuple(v.shape):
+            raise SnrError(f"normals of mesh {b} must be {tuple(v.shape)}, got {tuple(n.shape)}")
+        if v.shape[0] == 0:
+            out.append(torch.empty(0, 3, device=v.device))
+            continue
+        _, rgb, _ = ops.decoder_fwd(v.detach(), -n.detach(), lat[b:b + 1], packed, model.shape_blocks, model.texture_blocks, precision="fp32")
+        out.append(rgb)
+    return out
+
+
 def density_grid(model, shapecode, resolution, bound=(-0.5, 0.5)):
     """sigma (B, nx, ny, nz) of each code on the lattice ``lattice(resolution, bound)``, generated in the kernel (no point array)."""
     model = _decoder(model)
@@ -174,27 +315,59 @@ def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=
     return out
 
 
-def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False):
+def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False, direction=False):
     """Decoder-frame points (..., 3) -> the object's metric frame, inverting the package's point mappings:
     family "a" (``utils`` render paths, ``_render_shared_z``): x = F (p / obj_diag);
     family "b" (``renderer.NeRFRenderer``): x = F (p / (obj_diag / 2)), obj_diag = |(l, w, h)|;
-    F = ``utils._frame(False, kitti2nusc, shapenet_obj_cood)``, the frame both paths hand the kernels (a signed permutation: F^-1 = F^T)."""
+    F = ``utils._frame(False, kitti2nusc, shapenet_obj_cood)``, the frame both paths hand the kernels (a signed permutation: F^-1 = F^T).
+    ``direction=True``: directions such as normals, F applied without the scale (unit vectors stay unit)."""
     if family not in ("a", "b"):
         raise SnrError(f"family is 'a' (utils render paths) or 'b' (NeRFRenderer), got {family!r}")
     v = torch.as_tensor(verts)
     m = torch.tensor(U._frame(False, kitti2nusc, shapenet_obj_cood), dtype=v.dtype, device=v.device).view(3, 3)
+    if direction:
+        return v @ m
     scale = float(obj_diag) if family == "a" else float(obj_diag) / 2
     return (v @ m) * scale
 
 
-def write_ply(path, verts, faces):
-    """Binary little-endian PLY: float x, y, z per vertex, a uchar-counted int list per triangle."""
+def quantize_colors(colors):
+    """(V, 3) colours -> uint8 as ``write_ply`` stores them: round(clamp(c, 0, 1) * 255), half to even; NaN counts as 0."""
+    c = np.nan_to_num(np.asarray(torch.as_tensor(colors).detach().cpu().numpy(), dtype=np.float64), nan=0.0)
+    return np.rint(np.clip(c, 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def write_ply(path, verts, faces, normals=None, colors=None):
+    """Binary little-endian PLY: float x, y, z per vertex (then float nx, ny, nz with ``normals``, uchar red, green, blue with ``colors``:
+    ``quantize_colors``), a uchar-counted int list per triangle."""
     v = np.ascontiguousarray(torch.as_tensor(verts).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
     f = np.ascontiguousarray(torch.as_tensor(faces).detach().cpu().numpy(), dtype="<i4").reshape(-1, 3)
     rec = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
     rec["n"], rec["i"] = 3, f
+    props = "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None or colors is not None:
+        fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+        cols = [("x", v[:, 0]), ("y", v[:, 1]), ("z", v[:, 2])]
+        if normals is not None:
+            n = np.asarray(torch.as_tensor(normals).detach().cpu().numpy(), dtype="<f4")
+            if n.shape != v.shape:
+                raise SnrError(f"normals must be {v.shape}, got {n.shape}")
+            fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+            cols += [("nx", n[:, 0]), ("ny", n[:, 1]), ("nz", n[:, 2])]
+            props += "property float nx\nproperty float ny\nproperty float nz\n"
+        if colors is not None:
+            c = quantize_colors(colors)
+            if c.shape != v.shape:
+                raise SnrError(f"colors must be {v.shape}, got {c.shape}")
+            fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+            cols += [("red", c[:, 0]), ("green", c[:, 1]), ("blue", c[:, 2])]
+            props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        vrec = np.empty(v.shape[0], dtype=np.dtype(fields))
+        for name, col in cols:
+            vrec[name] = col
+        v = vrec
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {v.shape[0]}\n{props}"
               f"element face {f.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))

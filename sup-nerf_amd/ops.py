@@ -681,6 +681,108 @@ class DecoderPoints(torch.autograd.Function):
         return d_xyz, d_dir, d_lat, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------ density-only decoder on points
+def _density_shapes(xyz, latent, shape_blocks, texture_blocks):
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise SnrError(f"xyz must be (P, 3), got {tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
+    n_lat = max(shape_blocks + texture_blocks, 1)
+    if not torch.is_tensor(latent) or latent.dim() != 3 or latent.shape[0] < 1 or tuple(latent.shape[1:]) != (n_lat, 256):
+        raise SnrError(f"latent must be (B, {n_lat}, 256), got {tuple(latent.shape) if torch.is_tensor(latent) else type(latent).__name__}")
+    P, B = xyz.shape[0], latent.shape[0]
+    if P % B:
+        raise SnrError(f"{P} points do not split evenly over {B} objects")
+    return P, B
+
+
+def density_fwd(xyz, latent, packed, shape_blocks, texture_blocks, save_masks=False):
+    """Density-only exact-fp32 decoder: xyz (P,3); latent (B,NLAT,256) -> sigmas (P,)[, relu masks].  sigma is bit-identical to
+    ``decoder_fwd(..., precision="fp32")``'s; the masks (``save_masks``) hold encoding_xyz's and the shape layers' ReLU bits in
+    ``decoder_fwd``'s layout, the texture-branch slots unwritten (``snr_density_fwd_masks``)."""
+    P, B = _density_shapes(xyz, latent, shape_blocks, texture_blocks)
+    _need_gpu(xyz, latent, packed)
+    xyz, latent = _f32c(xyz), _f32c(latent)
+    dev = xyz.device
+    sig = torch.empty(P, device=dev)
+    masks = None
+    if save_masks:
+        masks = torch.empty(_lib.lib().snr_mask_bytes(P, shape_blocks, texture_blocks), dtype=torch.uint8, device=dev)
+    if P == 0:
+        return sig, masks
+    with torch.cuda.device(dev):
+        if save_masks:
+            check(_lib.lib().snr_density_fwd_masks(_p(xyz), _p(latent), _p(packed), P, P // B, shape_blocks, texture_blocks, _p(sig), _p(masks),
+                                                   _stream(dev)), "snr_density_fwd_masks")
+        else:
+            check(_lib.lib().snr_density_fwd(_p(xyz), _p(latent), _p(packed), P, P // B, shape_blocks, texture_blocks, _p(sig), _stream(dev)),
+                  "snr_density_fwd")
+    return sig, masks
+
+
+def density_bwd(xyz, latent, packed, masks, sigmas, d_sig, shape_blocks, texture_blocks, need_latent=True, need_xyz=True):
+    """Backward of ``density_fwd`` (``snr_density_bwd``): (d_latent (B,NLAT,256) or None, d_xyz (P,3) or None) given d_sig (P,).  The
+    texture rows of d_latent are zero; the latent gradient needs a multiple of 64 points per object.  Equal, bit for bit, to
+    ``decoder_bwd(..., d_rgb=0, precision="fp32")``'s d_xyz and shape rows."""
+    P, B = _density_shapes(xyz, latent, shape_blocks, texture_blocks)
+    if masks is None or sigmas is None or d_sig is None:
+        raise SnrError("density_bwd needs the ReLU bits and densities saved by density_fwd(..., save_masks=True) and d_sig")
+    if tuple(sigmas.shape) != (P,) or tuple(d_sig.shape) != (P,):
+        raise SnrError(f"sigmas and d_sig must be ({P},), got {tuple(sigmas.shape)} and {tuple(d_sig.shape)}")
+    _need_gpu(xyz, latent, packed, masks, sigmas, d_sig)
+    xyz, latent, sigmas, d_sig, masks = _f32c(xyz), _f32c(latent), _f32c(sigmas), _f32c(d_sig), masks.contiguous()
+    if masks.dtype != torch.uint8 or masks.numel() < _lib.lib().snr_mask_bytes(P, shape_blocks, texture_blocks):
+        raise SnrError("density_bwd: masks must be the uint8 buffer density_fwd(..., save_masks=True) returned for these points")
+    lat_rows = shape_blocks + texture_blocks > 0
+    if need_latent and lat_rows and (P // B) % 64:
+        raise SnrError(f"the latent gradient of the density path needs a multiple of 64 points per object, got {P // B} "
+                       "(DensityPoints pads them)")
+    dev = xyz.device
+    d_latent = (torch.empty_like(latent) if lat_rows else torch.zeros_like(latent)) if need_latent else None
+    d_xyz = torch.empty_like(xyz) if need_xyz else None
+    if P == 0:
+        return (torch.zeros_like(latent) if need_latent else None), d_xyz
+    ws_bytes = _lib.lib().snr_decoder_bwd_ws_bytes(P, P // B, shape_blocks, texture_blocks) if need_latent and lat_rows else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_density_bwd(_p(xyz), _p(latent), _p(packed), _p(masks), _p(sigmas), _p(d_sig), P, P // B, shape_blocks,
+                                         texture_blocks, _p(d_latent), _p(d_xyz), _p(ws), ws_bytes, _stream(dev)), "snr_density_bwd")
+    return d_latent, d_xyz
+
+
+class DensityPoints(torch.autograd.Function):
+    """sigma of the decoder on explicit points, density head only.  Differentiable wrt xyz and the latent terms (the decoder weights are
+    constants on this path).  With a latent gradient to form, every object's points are padded to a multiple of 64 with dummy points
+    whose upstream gradient is zero."""
+
+    @staticmethod
+    def forward(ctx, xyz, latent, packed, shape_blocks, texture_blocks):
+        P, B = _density_shapes(xyz, latent, shape_blocks, texture_blocks)
+        xyz, latent = _f32c(xyz), _f32c(latent)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        n = P // B
+        n_pad = -(-n // 64) * 64 if (ctx.needs_input_grad[1] and shape_blocks + texture_blocks > 0 and n % 64) else 0
+        ctx.pad = (B, n, n_pad)
+        if n_pad:
+            xyz = _pad_rows(xyz, B, n, n_pad)
+        sig, masks = density_fwd(xyz, latent, packed, shape_blocks, texture_blocks, save_masks=need)
+        if need:
+            ctx.save_for_backward(xyz, latent, packed, masks, sig)
+            ctx.cfg = (shape_blocks, texture_blocks)
+        return _unpad_rows(sig, B, n, n_pad) if n_pad else sig
+
+    @staticmethod
+    def backward(ctx, d_sig):
+        xyz, latent, packed, masks, sig = ctx.saved_tensors
+        sb, tb = ctx.cfg
+        B, n, n_pad = ctx.pad
+        d_sig = _f32c(d_sig)
+        if n_pad:
+            d_sig = _pad_rows(d_sig, B, n, n_pad)
+        d_lat, d_xyz = density_bwd(xyz, latent, packed, masks, sig, d_sig, sb, tb, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        if n_pad and d_xyz is not None:
+            d_xyz = _unpad_rows(d_xyz, B, n, n_pad)
+        return d_xyz, d_lat, None, None, None
+
+
 def weight_grad(G, n_out, X, n_in, want_bias=True, out=None, ws=None, precision="fp32"):
     """dW (n_out, n_in) = G[:, :n_out]^T X[:, :n_in] and db (n_out,) = column sums of G, one split-K MFMA launch + one reduction
     (include/supnerf_hip.h: snr_weight_grad).  G, X: 2-D fp32 row-major views (a column slice of a wider buffer is fine).  ``out``:
