@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 11
+#define SNR_ABI_VERSION 12
 
 enum {
     SNR_OK = 0,
@@ -399,6 +399,32 @@ int snr_band_compact(const int32_t* state, const int32_t* scan, int64_t n_grids,
 int snr_band_fill(float* grid, int64_t n_grids, const snr_lattice* lattice, const int32_t* state, const float* fill, void* stream);
 int snr_band_seam(const float* grid, int64_t n_grids, const snr_lattice* lattice, float level, int32_t stamp, int32_t* state, int32_t* bricks,
                   int32_t* n_new, void* stream);
+
+/* Iso-surface backward: vertex gradients of snr_iso_emit's output to the grid values, and the grid points the surface touches.
+ * The derivative is the one of the piecewise function whose topology (edge_mask) is the forward's: topology changes carry no gradient,
+ * and the level gets none.  A vertex on crossing edge (u, d) has va = f(u), vb = f(u + d) (one of them > level, the other not), so
+ * t = (level - va) / (vb - va) and c_a = lo_a + h_a (i_a + t d_a).  For its upstream gradient g (3 floats):
+ *   s = sum over the axes a with d_a = 1 of g_a h_a, in axis order, fp32 (s = 0 + g_a h_a + ...);
+ *   w = s / ((vb - va) * (vb - va));
+ *   d f(u) += w * (level - vb),  d f(u + d) += w * (va - level).
+ * vb - va is never zero on a crossing edge but can be tiny: the gradient is then large.  That is inherent to an iso-surface at fixed
+ * topology; nothing is clamped.
+ *
+ * snr_iso_grad: d_verts (sum V, 3) fp32, laid out as snr_iso_emit wrote verts (vert_offset, edge_mask, edge_scan of the same forward) ->
+ * d_grid (B, n0, n1, n2) fp32, dense.  Each grid point GATHERS its terms, accumulating acc = 0 + term + ... in fp32 in a fixed order:
+ * first its outgoing crossing edges d = 0..6 (bit d of its own edge_mask; vertex edge_scan - popc(m) + popc(m & (2^d - 1))), then its
+ * incoming ones d = 0..6 (bit d of the point u - dir(d), where that point exists).  No atomics: the result is deterministic.  A point
+ * on no crossing edge gets +0.  on_surface (B, n0, n1, n2) uint8 (nullable) = 1 iff the point is an end of at least one crossing edge.
+ * snr_iso_surface_points: the flagged points of each object, in grid order, into a list of points_per_obj slots per object (object b at
+ * rows b points_per_obj ...): xyz (B points_per_obj, 3) the lattice coordinate lo + h i (one fp32 multiply, one add: snr_density_fwd
+ * there returns the value snr_density_grid stored, bit for bit), d_sigmas (B points_per_obj) the point's d_grid.  Slot = scan - 1 with
+ * scan the INCLUSIVE int32 prefix sum of on_surface along each object's row; slots from the object's count to points_per_obj are
+ * padding: xyz = lo, d_sigmas = 0.  A point whose slot is >= points_per_obj is not written. */
+int snr_iso_grad(const float* grid, int64_t n_grids, const snr_lattice* lattice, float level, const uint8_t* edge_mask,
+                 const int32_t* edge_scan, const int64_t* vert_offset, const float* d_verts, float* d_grid, uint8_t* on_surface,
+                 void* stream);
+int snr_iso_surface_points(const uint8_t* on_surface, const int32_t* surface_scan, const float* d_grid, int64_t n_grids,
+                           const snr_lattice* lattice, int64_t points_per_obj, float* xyz, float* d_sigmas, void* stream);
 
 #ifdef __cplusplus
 }

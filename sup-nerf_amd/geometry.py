@@ -9,7 +9,7 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     that the surface crosses (a coarse pass, ``snr_band_*``, ``snr_density_bricks``); exact wherever the mesh reads it;
   * ``extract_mesh(model_or_grid, shapecode, level=...)``: the iso-surface sigma = level by marching tetrahedra on the GPU
     (``snr_iso_count`` -> two ``torch.cumsum`` -> ``snr_iso_emit``), one (verts (V,3) fp32, faces (F,3) int32) pair per object
-    (``narrow_band=True``: on the narrow-band grid);
+    (``narrow_band=True``: on the narrow-band grid; ``differentiable=True``: vertices with autograd to the grid or the shape codes);
   * ``density(model, xyz, shapecode)``: sigma (P,) like ``query_density``, differentiable wrt ``xyz`` and ``shapecode``
     (``ops.DensityPoints``: ``snr_density_fwd_masks`` forward, ``snr_density_bwd`` backward), for losses that read the density only;
   * ``density_gradient(model, xyz, shapecode)``: sigma and d sigma / d xyz in two launches, no autograd;
@@ -366,17 +366,28 @@ def narrow_band_grid(model, shapecode, resolution, *, level, band=0.0, bound=(-0
     return NarrowBand(grid, state != 0, rounds, points)
 
 
-def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=(-0.5, 0.5), narrow_band=False, band=0.0):
+def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=(-0.5, 0.5), narrow_band=False, band=0.0,
+                 differentiable=False):
     """Iso-surface {sigma = level} per object: a list of (verts (V, 3) fp32, faces (F, 3) int32) on the GPU, faces counter-clockwise
     seen from the low side (outward normals around a dense object), vertices in ``bound``'s decoder coordinates (``to_object_frame``
     maps them to the object's frame).  ``model_or_grid``: a decoder (then ``shapecode`` (B, 256) and ``resolution`` make the grid with
     ``density_grid``) or a grid tensor (B, nx, ny, nz) / (nx, ny, nz) over ``bound`` (the decoder is skipped).  A non-finite grid value
     raises ``SnrError``.  One host synchronisation: the sizes of the output.  ``narrow_band=True`` (decoder only): the grid comes from
-    ``narrow_band_grid(..., band=band)`` -- the same mesh wherever its coarse pass finds the surface, for a fraction of the decoder work."""
+    ``narrow_band_grid(..., band=band)`` -- the same mesh wherever its coarse pass finds the surface, for a fraction of the decoder work.
+
+    ``differentiable=True`` (under grad mode): the vertices carry a ``grad_fn`` -- to the grid tensor (``ops.IsoVertices``), or to
+    ``shapecode`` through ``model.latent_terms(shapecode, 0)`` (``ops.IsoVerticesLatent``: the backward runs the density decoder at the
+    grid points the surface touches only).  The derivative is that of the vertex formula at the forward's topology: topology changes
+    carry no gradient, nor does ``level``; an edge whose two values nearly agree gives a large one.  Vertices and faces are the same as
+    without it.  On a narrow-band grid the gradient is exact wherever its mesh equals the dense mesh (see ``narrow_band_grid``).  The
+    decoder's weights are constants: with ``model.train_decoder_weights`` set and grad mode on this raises, as ``density`` does."""
     if narrow_band and torch.is_tensor(model_or_grid):
         raise SnrError("extract_mesh(narrow_band=True) builds its grid with the decoder: pass the model and the shape codes")
+    grad = bool(differentiable) and torch.is_grad_enabled()
     if torch.is_tensor(model_or_grid):
-        grid = _gpu(model_or_grid, "the grid").detach()
+        grid = _gpu(model_or_grid, "the grid")
+        if not grad:
+            grid = grid.detach()
         if grid.dim() == 3:
             grid = grid.unsqueeze(0)
         if grid.dim() != 4:
@@ -386,6 +397,11 @@ def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=
     else:
         if shapecode is None:
             raise SnrError("extract_mesh(model, shapecode, ...): the shape codes are missing")
+        if grad:
+            model = _decoder(model_or_grid)
+            if model.train_decoder_weights:
+                raise SnrError("extract_mesh(differentiable=True) does not differentiate the decoder weights: with train_decoder_weights "
+                               "set, run it under torch.no_grad() or use the model's forward")
         if narrow_band:
             grid = narrow_band_grid(model_or_grid, shapecode, resolution, level=level, band=band, bound=bound).grid
         else:
@@ -393,35 +409,25 @@ def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=
         lat = lattice(resolution, bound)
     if min(lat.n) < 2:
         raise SnrError(f"extract_mesh needs at least 2 points per axis, got {tuple(lat.n)}")
-    dev = grid.device
     B = grid.shape[0]
-    nv = lat.n[0] * lat.n[1] * lat.n[2]
-    nc = (lat.n[0] - 1) * (lat.n[1] - 1) * (lat.n[2] - 1)
     if B == 0:
         return []
     level = float(np.float32(level))
-    lib, st = _lib.lib(), ops._stream(dev)
-    tri_count = torch.empty(B, nc, dtype=torch.uint8, device=dev)
-    edge_mask = torch.empty(B, nv, dtype=torch.uint8, device=dev)
-    edge_count = torch.empty(B, nv, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.snr_iso_count(ops._p(grid), B, lat, level, ops._ptr(tri_count, torch.uint8), ops._ptr(edge_mask, torch.uint8),
-                                ops._ptr(edge_count, torch.uint8), st), "snr_iso_count")
-        # per object: <= 7 * 512^3 vertices and <= 12 * 511^3 triangles, both below 2^31
-        edge_scan = torch.cumsum(edge_count, dim=1, dtype=torch.int32)
-        tri_scan = torch.cumsum(tri_count, dim=1, dtype=torch.int32)
-        n_vert, n_tri = edge_scan[:, -1].long(), tri_scan[:, -1].long()
-        vert_off, tri_off = torch.cumsum(n_vert, 0) - n_vert, torch.cumsum(n_tri, 0) - n_tri
-        bad = (~torch.isfinite(grid)).any().long().view(1)
-        host = torch.cat([bad, n_vert, n_tri]).cpu().tolist()
-        if host[0]:
-            raise SnrError("extract_mesh: the grid holds a non-finite value")
-        nvs, nts = host[1:1 + B], host[1 + B:]
-        verts = torch.empty(sum(nvs), 3, device=dev)
-        faces = torch.empty(sum(nts), 3, dtype=torch.int32, device=dev)
-        check(lib.snr_iso_emit(ops._p(grid), B, lat, level, ops._ptr(edge_mask, torch.uint8), ops._ptr(edge_scan, torch.int32),
-                               ops._ptr(tri_scan, torch.int32), ops._ptr(vert_off, torch.int64), ops._ptr(tri_off, torch.int64),
-                               ops._ptr(verts), ops._ptr(faces, torch.int32), st), "snr_iso_emit")
+    if not grad:
+        m = ops.iso_extract(grid, lat, level)
+        verts, faces, nvs, nts = m.verts, m.faces, m.n_verts, m.n_faces
+    elif torch.is_tensor(model_or_grid):
+        verts, faces, sizes = ops.IsoVertices.apply(grid, lat, level)
+        nvs, nts = sizes.tolist()
+    else:
+        sc = shapecode.unsqueeze(0) if shapecode.dim() == 1 else shapecode
+        sc = sc.float()
+        model._note_decoder_run(constant=True)
+        latent = model.latent_terms(sc, torch.zeros_like(sc))
+        packed = model.packed_weights()
+        ops._need_gpu(latent, packed)
+        verts, faces, sizes = ops.IsoVerticesLatent.apply(latent, packed, grid, lat, level, model.shape_blocks, model.texture_blocks)
+        nvs, nts = sizes.tolist()
     out, v0, f0 = [], 0, 0
     for b in range(B):
         out.append((verts[v0:v0 + nvs[b]], faces[f0:f0 + nts[b]]))

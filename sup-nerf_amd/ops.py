@@ -8,7 +8,7 @@ import math
 import threading
 import warnings
 import weakref
-from typing import Dict, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -782,6 +782,135 @@ class DensityPoints(torch.autograd.Function):
             d_xyz = _unpad_rows(d_xyz, B, n, n_pad)
         return d_xyz, d_lat, None, None, None
 
+
+
+# ------------------------------------------------------------------------------------ iso-surface and its backward
+class IsoMesh(NamedTuple):
+    verts: torch.Tensor        # (sum V, 3) fp32, object after object
+    faces: torch.Tensor        # (sum F, 3) int32, indices local to each object
+    n_verts: list              # V per object
+    n_faces: list              # F per object
+    edge_mask: torch.Tensor    # (B, nv) uint8: the crossing edges of each grid point (the forward's topology)
+    edge_scan: torch.Tensor    # (B, nv) int32: inclusive scan of their counts per object
+    vert_offset: torch.Tensor  # (B,) int64: where each object's vertices start
+
+
+def iso_extract(grid, lat, level):
+    """Marching tetrahedra of the fp32 grids (B, n0, n1, n2) on ``lat`` (a ``Lattice``): ``snr_iso_count``, two ``torch.cumsum`` per object,
+    ``snr_iso_emit``; one host read (the output sizes).  A non-finite grid value raises.  Returns an ``IsoMesh``."""
+    B = grid.shape[0]
+    nv = lat.n[0] * lat.n[1] * lat.n[2]
+    nc = (lat.n[0] - 1) * (lat.n[1] - 1) * (lat.n[2] - 1)
+    dev = grid.device
+    lib, st = _lib.lib(), _stream(dev)
+    tri_count = torch.empty(B, nc, dtype=torch.uint8, device=dev)
+    edge_mask = torch.empty(B, nv, dtype=torch.uint8, device=dev)
+    edge_count = torch.empty(B, nv, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.snr_iso_count(_p(grid), B, lat, level, _ptr(tri_count, torch.uint8), _ptr(edge_mask, torch.uint8),
+                                _ptr(edge_count, torch.uint8), st), "snr_iso_count")
+        # per object: <= 7 * 512^3 vertices and <= 12 * 511^3 triangles, both below 2^31
+        edge_scan = torch.cumsum(edge_count, dim=1, dtype=torch.int32)
+        tri_scan = torch.cumsum(tri_count, dim=1, dtype=torch.int32)
+        n_vert, n_tri = edge_scan[:, -1].long(), tri_scan[:, -1].long()
+        vert_off, tri_off = torch.cumsum(n_vert, 0) - n_vert, torch.cumsum(n_tri, 0) - n_tri
+        bad = (~torch.isfinite(grid)).any().long().view(1)
+        host = torch.cat([bad, n_vert, n_tri]).cpu().tolist()
+        if host[0]:
+            raise SnrError("extract_mesh: the grid holds a non-finite value")
+        nvs, nts = host[1:1 + B], host[1 + B:]
+        verts = torch.empty(sum(nvs), 3, device=dev)
+        faces = torch.empty(sum(nts), 3, dtype=torch.int32, device=dev)
+        check(lib.snr_iso_emit(_p(grid), B, lat, level, _ptr(edge_mask, torch.uint8), _ptr(edge_scan, torch.int32),
+                               _ptr(tri_scan, torch.int32), _ptr(vert_off, torch.int64), _ptr(tri_off, torch.int64),
+                               _ptr(verts), _ptr(faces, torch.int32), st), "snr_iso_emit")
+    return IsoMesh(verts, faces, nvs, nts, edge_mask, edge_scan, vert_off)
+
+
+def iso_grad(grid, lat, level, edge_mask, edge_scan, vert_offset, d_verts, want_surface=False):
+    """Backward of ``iso_extract``'s vertices (``snr_iso_grad``): d_grid (B, n0, n1, n2) fp32 from d_verts (sum V, 3), gathered per grid
+    point in a fixed order (deterministic); with ``want_surface`` also on_surface (B, nv) uint8, 1 at the ends of crossing edges."""
+    B = grid.shape[0]
+    dev = grid.device
+    d_verts = _f32c(d_verts)
+    d_grid = torch.empty(grid.shape, device=dev)
+    on = torch.empty(edge_mask.shape, dtype=torch.uint8, device=dev) if want_surface else None
+    if B:
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_iso_grad(_p(grid), B, lat, level, _ptr(edge_mask, torch.uint8), _ptr(edge_scan, torch.int32),
+                                          _ptr(vert_offset, torch.int64), _p(d_verts) if d_verts.numel() else C.c_void_p(0), _p(d_grid),
+                                          _p(on), _stream(dev)), "snr_iso_grad")
+    return d_grid, on
+
+
+def iso_surface_points(on_surface, d_grid, lat):
+    """The grid points flagged by ``iso_grad`` as a point list for the density backward (``snr_iso_surface_points``): (xyz (B n, 3) lattice
+    coordinates, d_sig (B n), n, counts (B,) int64 on the device) with n the largest count rounded up to a multiple of 64 (the padding
+    points: xyz = lo, d_sig = 0).  One host read (n)."""
+    B = on_surface.shape[0]
+    dev = on_surface.device
+    scan = torch.cumsum(on_surface, dim=1, dtype=torch.int32)
+    counts = scan[:, -1].long() if B else torch.zeros(0, dtype=torch.int64, device=dev)
+    n = -(-int(counts.max()) // 64) * 64 if B else 0
+    xyz = torch.empty(B * n, 3, device=dev)
+    d_sig = torch.empty(B * n, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_iso_surface_points(_ptr(on_surface, torch.uint8), _ptr(scan, torch.int32), _p(d_grid), B, lat, n, _p(xyz),
+                                                    _p(d_sig), _stream(dev)), "snr_iso_surface_points")
+    return xyz, d_sig, n, counts
+
+
+class IsoVertices(torch.autograd.Function):
+    """Iso-surface vertices of grids (B, n0, n1, n2), differentiable wrt the grid values at the forward's topology.  Forward: ``iso_extract``
+    (output unchanged).  Saves the grid, edge_mask and edge_scan (4 + 1 + 4 = 9 bytes per grid point) rather than rerun the count pass.
+    Backward: ``snr_iso_grad``.  Returns (verts, faces, sizes): sizes (2, B) int64 on the host, V and F per object."""
+
+    @staticmethod
+    def forward(ctx, grid, lat, level):
+        m = iso_extract(grid, lat, level)
+        ctx.save_for_backward(grid, m.edge_mask, m.edge_scan, m.vert_offset)
+        ctx.cfg = (lat, level)
+        sizes = torch.tensor([m.n_verts, m.n_faces], dtype=torch.int64)
+        ctx.mark_non_differentiable(m.faces, sizes)
+        return m.verts, m.faces, sizes
+
+    @staticmethod
+    def backward(ctx, d_verts, d_faces, d_sizes):
+        grid, edge_mask, edge_scan, vert_off = ctx.saved_tensors
+        lat, level = ctx.cfg
+        d_grid, _ = iso_grad(grid, lat, level, edge_mask, edge_scan, vert_off, d_verts)
+        return d_grid, None, None
+
+
+class IsoVerticesLatent(torch.autograd.Function):
+    """Iso-surface vertices of the density grids of B objects, differentiable wrt their latent terms (B, NLAT, 256).  ``grid`` must hold
+    the density forward's value at both ends of every crossing edge (a dense grid, or a narrow-band grid at its fixpoint); its other
+    values only decide the topology.  Forward: ``iso_extract`` of the grid.  Backward: ``snr_iso_grad`` -> ``snr_iso_surface_points`` ->
+    ``density_fwd(save_masks=True)`` and ``density_bwd(need_latent=True)`` on the surface points of all B objects in one launch each: the
+    decoder runs at those points only.  Returns (verts, faces, sizes) like ``IsoVertices``."""
+
+    @staticmethod
+    def forward(ctx, latent, packed, grid, lat, level, shape_blocks, texture_blocks):
+        m = iso_extract(grid, lat, level)
+        ctx.save_for_backward(latent, packed, grid, m.edge_mask, m.edge_scan, m.vert_offset)
+        ctx.cfg = (lat, level, shape_blocks, texture_blocks)
+        sizes = torch.tensor([m.n_verts, m.n_faces], dtype=torch.int64)
+        ctx.mark_non_differentiable(m.faces, sizes)
+        return m.verts, m.faces, sizes
+
+    @staticmethod
+    def backward(ctx, d_verts, d_faces, d_sizes):
+        latent, packed, grid, edge_mask, edge_scan, vert_off = ctx.saved_tensors
+        lat, level, sb, tb = ctx.cfg
+        d_grid, on = iso_grad(grid, lat, level, edge_mask, edge_scan, vert_off, d_verts, want_surface=True)
+        xyz, d_sig, n, _ = iso_surface_points(on, d_grid, lat)
+        if n == 0:
+            return torch.zeros_like(latent), None, None, None, None, None, None
+        latent = _f32c(latent)
+        sig, masks = density_fwd(xyz, latent, packed, sb, tb, save_masks=True)
+        d_lat, _ = density_bwd(xyz, latent, packed, masks, sig, d_sig, sb, tb, need_latent=True, need_xyz=False)
+        return d_lat, None, None, None, None, None, None
 
 def weight_grad(G, n_out, X, n_in, want_bias=True, out=None, ws=None, precision="fp32"):
     """dW (n_out, n_in) = G[:, :n_out]^T X[:, :n_in] and db (n_out,) = column sums of G, one split-K MFMA launch + one reduction
