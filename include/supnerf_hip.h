@@ -52,7 +52,13 @@ enum {
  *   p = o_n + t d (xyz_div is NOT applied), composite depth |p - o_n| z_scale with SNR_METRIC_Z (:114)
  * `t_vals` then is the (N,S) jitter in [0,1) (the reference's rand_like draw), or NULL: the kernel draws it itself with
  * Philox4x32-10 (see rng_* below).  The backward kernel returns the gradient THROUGH the bounds to rays_o / rays_d like the
- * reference's autograd (maximum / minimum split ties evenly, as torch does) unless SNR_BOX_DETACH is set. */
+ * reference's autograd (maximum / minimum split ties evenly, as torch does) unless SNR_BOX_DETACH is set.
+ * Rules of the slab test and of its gradient (tests/test_special_rays_gpu.py):
+ *   1. a NaN in the slab test (0 * inf: rays_d[a] == +-0 with o_n[a] exactly on that face) makes the ray a miss and reaches no output;
+ *   2. ties in maximum / minimum split the gradient evenly: 1/2-1/2 through a box edge, 1/4-1/4-1/2 through a corner (two nested maximum);
+ *   3. an axis with rays_d[a] == +-0 adds exactly nothing to the gradient of the bounds (0 gradient * infinite 1/d is 0; torch: NaN);
+ *   4. the comparisons are strict: t_far > t_near (touching an edge is a miss) and t_far > 0 (a box behind the origin is a miss); an
+ *      origin inside the box is a hit with near < 0. */
 enum { SNR_Z_SHARED = 0 /* (S,) */, SNR_Z_PER_OBJECT = 1 /* (B,S) */, SNR_Z_PER_RAY = 2 /* (N,S) */, SNR_Z_BOX = 3 /* none: box bounds */ };
 
 /* arithmetic of the decoder GEMMs.  SNR_FP32: v_mfma_f32_32x32x2_f32, bit-for-bit an fp32 fmaf chain.

@@ -362,21 +362,52 @@ def slab_intersect(o: Tensor, d: Tensor, bmin: Tensor, bmax: Tensor):
     return t_near, t_far, hit
 
 
+def guarded_slab_axes(o: Tensor, d: Tensor, bmin: Tensor, bmax: Tensor):
+    """Per-axis entry / exit depths (lo, hi) of ``guarded_slab_intersect``, which reduces them across the axes like ``slab_intersect``:
+    ``slab_intersect`` with the same VALUES (t_near, t_far, hit bit for bit) and a gradient that stays finite where a direction
+    component is exactly 0 -- the rule of the HIP kernels (include/supnerf_hip.h, SNR_Z_BOX), which torch's autograd of the plain formula
+    cannot state: there it multiplies a zero gradient by the infinite 1/d and returns NaN, on hits and misses alike.  A component with
+    d == 0 divides by a substituted 1, so no infinity enters the graph, and takes the plain formula's values detached: -inf / +inf where
+    the origin is strictly inside that slab (the axis constrains nothing), the plain +-inf or NaN otherwise (the ray misses).  That axis
+    then contributes exactly nothing to the gradient of the bounds; every other axis, ties included, is the plain function's."""
+    zero = d == 0
+    free = zero & (o > bmin) & (o < bmax)
+    inv = torch.reciprocal(torch.where(zero, torch.ones_like(d), d))
+    ta, tb = (bmin - o) * inv, (bmax - o) * inv
+    inv0 = torch.reciprocal(d.detach())
+    pa, pb = ((bmin - o) * inv0).detach(), ((bmax - o) * inv0).detach()         # the plain values where d == 0
+    ninf, pinf = torch.full_like(ta, -float("inf")), torch.full_like(ta, float("inf"))
+    lo = torch.where(free, ninf, torch.where(zero, torch.minimum(pa, pb), torch.minimum(ta, tb)))
+    hi = torch.where(free, pinf, torch.where(zero, torch.maximum(pa, pb), torch.maximum(ta, tb)))
+    return lo, hi
+
+
+def guarded_slab_intersect(o: Tensor, d: Tensor, bmin: Tensor, bmax: Tensor):
+    """``slab_intersect`` on ``guarded_slab_axes``: the same (t_near, t_far, hit) bit for bit, a finite gradient on every ray."""
+    lo, hi = guarded_slab_axes(o, d, bmin, bmax)
+    t_near = torch.maximum(torch.maximum(lo[..., 0], lo[..., 1]), lo[..., 2])
+    t_far = torch.minimum(torch.minimum(hi[..., 0], hi[..., 1]), hi[..., 2])
+    hit = t_far > t_near
+    hit = torch.logical_and(hit, (t_far * hit) > 0)
+    return t_near, t_far, hit
+
+
 def aabb_sampled_rays(rays_o: Tensor, viewdir: Tensor, obj_sz, n_samples: int,
-                      jitter: Optional[Tensor] = None, detach_bounds: bool = False):
+                      jitter: Optional[Tensor] = None, detach_bounds: bool = False, slab=slab_intersect):
     """Family B sample preparation.  Restates ``NeRFRenderer.prepare_sampled_rays``
     (src/renderer.py:91-115).  obj_sz = (w, l, h); box half extents are
     (l, w, h)/diag in the frame where origins are divided by diag/2; rays that
     miss get near=far=-1; z_vals is the metric distance |xyz-o|*diag/2.
     ``detach_bounds`` reproduces ``render_rays_v3`` where the slab test runs in
-    numpy float64-free detached form (src/renderer.py:425-432)."""
+    numpy float64-free detached form (src/renderer.py:425-432).  ``slab``: the slab test, ``slab_intersect`` or a function of its
+    signature (``guarded_slab_intersect``)."""
     obj_sz = np.asarray(obj_sz)
     diag = np.linalg.norm(obj_sz).astype(np.float32)
     w, l, h = [float(v) for v in obj_sz]
     half = torch.tensor([l / diag, w / diag, h / diag], dtype=torch.float32, device=rays_o.device)
     o_n = rays_o / (diag / 2)
     src_o, src_d = (o_n.detach(), viewdir.detach()) if detach_bounds else (o_n, viewdir)
-    t_near, t_far, hit = slab_intersect(src_o, src_d, -half.expand_as(src_o), half.expand_as(src_o))
+    t_near, t_far, hit = slab(src_o, src_d, -half.expand_as(src_o), half.expand_as(src_o))
     minus1 = torch.full_like(t_near, -1.0)
     near = torch.where(hit, t_near, minus1)[:, None]
     far = torch.where(hit, t_far, minus1)[:, None]
@@ -457,7 +488,8 @@ def volume_rendering3(sigmas, rgbs, z_vals, white_bkgd=False):
 def fused_render(params: Dict[str, Tensor], rays_o: Tensor, rays_d: Tensor, t_vals: Tensor, z_mode: str, n_samples: int,
                  rays_per_obj: int, z_scale: Tensor, box_half: Optional[Tensor] = None, shape_code: Optional[Tensor] = None,
                  texture_code: Optional[Tensor] = None, latent: Optional[Tensor] = None,
-                 relu_masks: Optional[Sequence[Tensor]] = None, white_bkgd: bool = False, metric_z: bool = False):
+                 relu_masks: Optional[Sequence[Tensor]] = None, white_bkgd: bool = False, metric_z: bool = False, slab=slab_intersect,
+                 box_detach: bool = False):
     """What one ``snr_render_fwd`` launch computes (include/supnerf_hip.h) with xyz_div = xyz_mul = 1 and the identity frame: rays_o,
     rays_d (N,3), ray r of object r // rays_per_obj, z_scale (B,).  Returns rgb (N,3), depth (N), acc_trans (N), differentiable in
     every tensor argument (tests only).
@@ -465,14 +497,16 @@ def fused_render(params: Dict[str, Tensor], rays_o: Tensor, rays_d: Tensor, t_va
     ``z_mode`` lays out the depths t: "shared" t_vals (S,), "per_object" (B,S), "per_ray" (N,S); "box": t_vals is the (N,S) jitter
     table, and the depths are family B's stratified samples between the bounds of the slab test of o_n = rays_o / z_scale against
     +-box_half (B,3), near = far = -1 where the ray misses; the points then lie on o_n + t d.  ``metric_z`` (SNR_METRIC_Z): the
-    composite's depth is |t d| z_scale instead of t.  The decoder sees the codes, or given ``latent`` terms (``decoder_forward``)."""
+    composite's depth is |t d| z_scale instead of t.  The decoder sees the codes, or given ``latent`` terms (``decoder_forward``).
+    ``slab``: the slab test of "box", ``slab_intersect`` or a function of its signature (``guarded_slab_intersect``); ``box_detach``
+    (SNR_BOX_DETACH): the bounds are constants of the backward."""
     N, S = rays_o.shape[0], n_samples
     obj = torch.arange(N, device=rays_o.device) // rays_per_obj
     zs = z_scale[obj]
     if z_mode == "box":
         o = rays_o / zs[:, None]
         h = box_half[obj]
-        t_near, t_far, hit = slab_intersect(o, rays_d, -h, h)
+        t_near, t_far, hit = slab(o.detach(), rays_d.detach(), -h, h) if box_detach else slab(o, rays_d, -h, h)
         minus1 = torch.full_like(t_near, -1.0)
         t = unit_interval_samples(torch.where(hit, t_near, minus1)[:, None], torch.where(hit, t_far, minus1)[:, None], S, t_vals)
     else:

@@ -54,10 +54,11 @@ def _pow2(n):
 
 def _box_bounds(rays_o_n, viewdir, obj_sz, diag):
     """near/far (N,1) of the box with half extents (l,w,h)/diag; rays that miss get -1/-1
-    (src/renderer.py:95-107)."""
+    (src/renderer.py:95-107).  The values are the reference's; the gradient follows the one-launch path's rule for a direction component
+    that is exactly 0 (``utils._slab_guarded``), so both paths agree on a finite pose gradient for axis-parallel rays."""
     w, l, h = [float(v) for v in obj_sz]
     half = torch.tensor([l / diag, w / diag, h / diag], dtype=torch.float32, device=rays_o_n.device)
-    t_near, t_far, hit = U._slab(rays_o_n, viewdir, -half.expand_as(rays_o_n), half.expand_as(rays_o_n))
+    t_near, t_far, hit = U._slab_guarded(rays_o_n, viewdir, -half.expand_as(rays_o_n), half.expand_as(rays_o_n))
     minus1 = torch.full_like(t_near, -1.0)
     return torch.where(hit, t_near, minus1)[:, None], torch.where(hit, t_far, minus1)[:, None], hit
 

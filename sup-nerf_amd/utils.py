@@ -521,6 +521,28 @@ def _slab(ray_o, ray_d, aabb_min, aabb_max):
     return t_near, t_far, hit
 
 
+def _slab_guarded(ray_o, ray_d, aabb_min, aabb_max):
+    """``_slab`` with the same values bit for bit and the gradient rule of the SNR_Z_BOX kernels (include/supnerf_hip.h): an axis whose
+    direction component is exactly 0 adds nothing to the gradient of the bounds, where autograd through ``reciprocal(0)`` multiplies a
+    zero gradient by infinity and returns NaN (on hits and on misses).  Such a component divides by a substituted 1 and takes the plain
+    values detached: -inf / +inf with the origin strictly inside the slab, the plain +-inf or NaN (a miss) otherwise."""
+    zero = ray_d == 0
+    free = zero & (ray_o > aabb_min) & (ray_o < aabb_max)
+    inv = torch.reciprocal(torch.where(zero, torch.ones_like(ray_d), ray_d))
+    ta, tb = (aabb_min - ray_o) * inv, (aabb_max - ray_o) * inv
+    with torch.no_grad():
+        inv0 = torch.reciprocal(ray_d)
+        pa, pb = (aabb_min - ray_o) * inv0, (aabb_max - ray_o) * inv0
+        ninf, pinf = torch.full_like(pa, -float("inf")), torch.full_like(pa, float("inf"))
+    lo = torch.where(free, ninf, torch.where(zero, torch.minimum(pa, pb), torch.minimum(ta, tb)))
+    hi = torch.where(free, pinf, torch.where(zero, torch.maximum(pa, pb), torch.maximum(ta, tb)))
+    t_near = torch.maximum(torch.maximum(lo[..., 0], lo[..., 1]), lo[..., 2])
+    t_far = torch.minimum(torch.minimum(hi[..., 0], hi[..., 1]), hi[..., 2])
+    hit = t_far > t_near
+    hit = torch.logical_and(hit, (t_far * hit) > 0)
+    return t_near, t_far, hit
+
+
 def ray_box_intersection(ray_o, ray_d, aabb_min=None, aabb_max=None):
     """src/utils.py:236-280: numpy twin of the slab test."""
     if aabb_min is None:

@@ -41,6 +41,19 @@ def make_model(amd, dev, params, precision, blocks=(3, 1), train=False):
     return m
 
 
+def capture_latent(m):
+    """Make ``m.latent_terms`` keep its output's gradient: the raw d_latent the backward kernel + reduction returned."""
+    orig, got = m.latent_terms, []
+
+    def latent_terms(sc, tc):
+        z = orig(sc, tc)
+        z.retain_grad()
+        got.append(z)
+        return z
+    m.latent_terms = latent_terms
+    return got
+
+
 def md(a, b):
     return float((a.detach().double().cpu() - torch.as_tensor(b).detach().double().cpu()).abs().max())
 

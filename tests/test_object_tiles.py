@@ -25,26 +25,13 @@ import torch.nn.functional as F
 
 import planted_decoder as PD
 from oracle import supnerf_oracle as O
-from oracle_bands import amd, band_of, check_per_object, check_per_ray, dev, make_model  # noqa: F401  (amd, dev: fixtures)
+from oracle_bands import amd, band_of, capture_latent, check_per_object, check_per_ray, dev, make_model  # noqa: F401  (amd, dev: fixtures)
 from relu_bits import decode_relu_bits, relu_bits_of
 
 pytestmark = pytest.mark.gpu
 
 PRECISIONS = ["fp32", "bf16x3", ("fp32", "bf16x3")]
 PREC_ID = lambda p: "-".join(p) if isinstance(p, tuple) else p
-
-
-def capture_latent(m):
-    """Make ``m.latent_terms`` keep its output's gradient: the raw d_latent the backward kernel + reduction returned."""
-    orig, got = m.latent_terms, []
-
-    def latent_terms(sc, tc):
-        z = orig(sc, tc)
-        z.retain_grad()
-        got.append(z)
-        return z
-    m.latent_terms = latent_terms
-    return got
 
 
 def codes(B, seed):
