@@ -27,6 +27,7 @@
 #include <atomic>
 
 #include "snr_mlp16_core.hpp"
+#include "snr_grid.hpp"
 #include "snr_host.hpp"
 
 namespace snr {
@@ -595,10 +596,9 @@ int snr_density_fwd_masks(const float* xyz, const float* latent, const float* pa
 
 int snr_density_bricks(const snr_lattice* lattice, int64_t n_objects, const int32_t* bricks, int64_t n_bricks, const float* latent,
                        const float* packed, int sb, int tb, float* sigmas, void* stream_) {
-    if (!lattice || !bricks || !latent || !packed || !sigmas) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_objects < 0 || n_bricks < 0) return SNR_E_ARG;
-    for (int a = 0; a < 3; ++a)
-        if (lattice->n[a] < 1 || lattice->n[a] > 512) return SNR_E_ARG;
+    GridDims G;
+    if (grid_check(lattice, n_objects, 1, G) != SNR_OK || !bricks || !latent || !packed || !sigmas) return SNR_E_ARG;
+    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_bricks < 0) return SNR_E_ARG;
     if (n_objects == 0 || n_bricks == 0) return SNR_OK;
     // points_per_obj = one brick: the latent staging of a single-object workgroup applies (512 is a whole number of workgroups).  A launch is
     // 4 threads per point and HIP caps a launch below 2^32 threads: at most 2^20 bricks (2^29 points) per launch, the list taken in pieces.
@@ -615,13 +615,11 @@ int snr_density_bricks(const snr_lattice* lattice, int64_t n_objects, const int3
 
 int snr_density_grid(const snr_lattice* lattice, int64_t n_objects, const float* latent, const float* packed, int sb, int tb, float* sigmas,
                      void* stream_) {
-    if (!lattice || !latent || !packed || !sigmas) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_objects < 0) return SNR_E_ARG;
-    for (int a = 0; a < 3; ++a)
-        if (lattice->n[a] < 1 || lattice->n[a] > 512) return SNR_E_ARG;
-    const long long ppo = (long long)lattice->n[0] * lattice->n[1] * lattice->n[2];
+    GridDims G;
+    if (grid_check(lattice, n_objects, 1, G) != SNR_OK || !latent || !packed || !sigmas) return SNR_E_ARG;
+    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS) return SNR_E_ARG;
     if (n_objects == 0) return SNR_OK;
-    DecoderIO io{packed, latent, sb, tb, (long long)n_objects * ppo, ppo, sigmas, nullptr, nullptr, nullptr, false};
+    DecoderIO io{packed, latent, sb, tb, (long long)n_objects * G.nv, G.nv, sigmas, nullptr, nullptr, nullptr, false};
     io.latent_bias = nullptr;
     return density_launch<3>(io, nullptr, *lattice, stream_);
 }

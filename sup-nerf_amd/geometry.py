@@ -29,11 +29,10 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
 from . import model as M
 from . import ops
 from . import utils as U
-from ._lib import Lattice, SnrError, check
+from ._lib import Lattice, SnrError
 
 MAX_RESOLUTION = 512
 BRICK = 8                # narrow band: bricks of 8^3 lattice points (512, a whole number of the density kernel's workgroups)
@@ -52,19 +51,38 @@ def _gpu(t, what):
     return t
 
 
-def _codes(shapecode):
-    sc = _gpu(shapecode, "shapecode").detach()
+def _codes(shapecode, keep_graph=False):
+    sc = _gpu(shapecode, "shapecode")
     if sc.dim() == 1:
         sc = sc.unsqueeze(0)
     if sc.dim() != 2 or sc.shape[1] != 256:
         raise SnrError(f"shapecode must be (256,) or (B, 256), got {tuple(shapecode.shape)}")
-    return sc.float().contiguous()
+    return sc.float() if keep_graph else sc.detach().float().contiguous()
 
 
 def _latent(model, sc):
     """(B, NLAT, 256) latent terms of the shape codes (texture code zero: the density never reads the texture terms)."""
     with torch.no_grad():
         return model.latent_terms(sc, torch.zeros_like(sc)).detach().float().contiguous()
+
+
+def _decoder_inputs(model, shapecode, differentiable=None):
+    """What every density launch takes from (model, shapecode): (codes (B, 256), latent terms (B, NLAT, 256), packed weights).  The latent
+    terms are ``_latent``'s.  ``differentiable``: the caller's name, for the variant that keeps the autograd graph from ``shapecode`` to the
+    latent terms; the decoder's weights are constants on it, so under grad mode it notes the run as such and refuses
+    ``train_decoder_weights``."""
+    model = _decoder(model)
+    if differentiable:
+        if torch.is_grad_enabled() and model.train_decoder_weights:
+            raise SnrError(f"{differentiable} does not differentiate the decoder weights: with train_decoder_weights set, run it under "
+                           "torch.no_grad() or use the model's forward")
+        sc = _codes(shapecode, keep_graph=True)
+        model._note_decoder_run(constant=True)
+        latent = model.latent_terms(sc, torch.zeros_like(sc))
+    else:
+        sc = _codes(shapecode)
+        latent = _latent(model, sc)
+    return sc, _gpu(latent, "the model's latent terms"), _gpu(model.packed_weights(), "the model's weights")
 
 
 def lattice(resolution, bound=(-0.5, 0.5)):
@@ -93,33 +111,8 @@ def lattice_points(lat, device=None):
 
 def query_density(model, xyz, shapecode):
     """sigma (P,) at decoder-frame points ``xyz`` (P, 3), object-major over the B codes of ``shapecode`` (B, 256): P / B points each."""
-    model = _decoder(model)
-    sc = _codes(shapecode)
-    xyz = ops._f32c(_gpu(xyz, "xyz").detach())
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise SnrError(f"xyz must be (P, 3), got {tuple(xyz.shape)}")
-    B, P = sc.shape[0], xyz.shape[0]
-    if P % B:
-        raise SnrError(f"{P} points do not split evenly over {B} objects")
-    dev = xyz.device
-    sig = torch.empty(P, device=dev)
-    if P == 0:
-        return sig
-    lat, packed = _latent(model, sc), model.packed_weights()
-    ops._need_gpu(lat, packed)
-    with torch.cuda.device(dev):
-        check(_lib.lib().snr_density_fwd(ops._p(xyz), ops._p(lat), ops._p(packed), P, P // B, model.shape_blocks, model.texture_blocks,
-                                         ops._p(sig), ops._stream(dev)), "snr_density_fwd")
-    return sig
-
-
-def _points(xyz, B):
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise SnrError(f"xyz must be (P, 3), got {tuple(xyz.shape) if torch.is_tensor(xyz) else type(xyz).__name__}")
-    _gpu(xyz, "xyz")
-    if xyz.shape[0] % B:
-        raise SnrError(f"{xyz.shape[0]} points do not split evenly over {B} objects")
-    return xyz
+    _, latent, packed = _decoder_inputs(model, shapecode)
+    return ops.density_fwd(_gpu(xyz, "xyz").detach(), latent, packed, model.shape_blocks, model.texture_blocks)[0]
 
 
 def density(model, xyz, shapecode):
@@ -127,37 +120,18 @@ def density(model, xyz, shapecode):
     ``query_density`` -- with autograd to ``xyz`` and ``shapecode`` (through ``model.latent_terms(shapecode, 0)``).  The decoder's
     weights are constants here: with grad mode on and ``model.train_decoder_weights`` set this raises rather than leave them without
     a gradient."""
-    model = _decoder(model)
-    if torch.is_grad_enabled() and model.train_decoder_weights:
-        raise SnrError("geometry.density does not differentiate the decoder weights: with train_decoder_weights set, run it under "
-                       "torch.no_grad() or use the model's forward")
-    sc = _gpu(shapecode, "shapecode")
-    if sc.dim() == 1:
-        sc = sc.unsqueeze(0)
-    if sc.dim() != 2 or sc.shape[1] != 256 or sc.shape[0] < 1:
-        raise SnrError(f"shapecode must be (256,) or (B, 256), got {tuple(shapecode.shape)}")
-    xyz = _points(xyz, sc.shape[0])
-    sc = sc.float()
-    model._note_decoder_run(constant=True)
-    lat = model.latent_terms(sc, torch.zeros_like(sc))
-    packed = model.packed_weights()
-    ops._need_gpu(lat, packed)
-    return ops.DensityPoints.apply(xyz, lat, packed, model.shape_blocks, model.texture_blocks)
+    _, latent, packed = _decoder_inputs(model, shapecode, differentiable="geometry.density")
+    return ops.DensityPoints.apply(_gpu(xyz, "xyz"), latent, packed, model.shape_blocks, model.texture_blocks)
 
 
 def density_gradient(model, xyz, shapecode):
     """(sigma (P,), d sigma / d xyz (P, 3)) at decoder-frame points ``xyz``, object-major over ``shapecode`` (B, 256); no autograd.  Two
     launches: the density forward saving its ReLU bits, then its backward with d sigma = 1."""
-    model = _decoder(model)
-    sc = _codes(shapecode)
-    xyz = ops._f32c(_points(xyz, sc.shape[0]).detach())
-    if xyz.shape[0] == 0:
-        return torch.empty(0, device=xyz.device), torch.empty(0, 3, device=xyz.device)
-    lat, packed = _latent(model, sc), model.packed_weights()
-    ops._need_gpu(lat, packed)
+    _, latent, packed = _decoder_inputs(model, shapecode)
+    xyz = _gpu(xyz, "xyz").detach().float().contiguous()
     sb, tb = model.shape_blocks, model.texture_blocks
-    sig, masks = ops.density_fwd(xyz, lat, packed, sb, tb, save_masks=True)
-    _, grad = ops.density_bwd(xyz, lat, packed, masks, sig, torch.ones_like(sig), sb, tb, need_latent=False)
+    sig, masks = ops.density_fwd(xyz, latent, packed, sb, tb, save_masks=True)
+    _, grad = ops.density_bwd(xyz, latent, packed, masks, sig, torch.ones_like(sig), sb, tb, need_latent=False)
     return sig, grad
 
 
@@ -249,18 +223,8 @@ def vertex_colors(model, meshes, normals, shapecode, texturecode):
 
 def density_grid(model, shapecode, resolution, bound=(-0.5, 0.5)):
     """sigma (B, nx, ny, nz) of each code on the lattice ``lattice(resolution, bound)``, generated in the kernel (no point array)."""
-    model = _decoder(model)
-    sc = _codes(shapecode)
-    lat = lattice(resolution, bound)
-    dev = sc.device
-    B = sc.shape[0]
-    out = torch.empty(B, lat.n[0], lat.n[1], lat.n[2], device=dev)
-    latent, packed = _latent(model, sc), model.packed_weights()
-    ops._need_gpu(latent, packed)
-    with torch.cuda.device(dev):
-        check(_lib.lib().snr_density_grid(lat, B, ops._p(latent), ops._p(packed), model.shape_blocks, model.texture_blocks, ops._p(out),
-                                          ops._stream(dev)), "snr_density_grid")
-    return out
+    _, latent, packed = _decoder_inputs(model, shapecode)
+    return ops.density_grid(lattice(resolution, bound), latent, packed, model.shape_blocks, model.texture_blocks)
 
 
 def coarse_lattice(lat):
@@ -325,40 +289,29 @@ def narrow_band_grid(model, shapecode, resolution, *, level, band=0.0, bound=(-0
         ib = ib.to(dev) != 0
     if B == 0:
         return NarrowBand(grid, state != 0, 0, 0)
-    latent, packed = _latent(model, sc), model.packed_weights()
-    ops._need_gpu(latent, packed)
-    lib, st = _lib.lib(), ops._stream(dev)
+    _, latent, packed = _decoder_inputs(model, sc)
     sb, tb = model.shape_blocks, model.texture_blocks
-    n_bricks = B * nb[0] * nb[1] * nb[2]
-    coarse = torch.empty(B, clat.n[0], clat.n[1], clat.n[2], device=dev)
     fill = torch.empty(B, *nb, device=dev)
-    bricks = torch.empty(n_bricks, 4, dtype=torch.int32, device=dev)
+    bricks = torch.empty(B * nb[0] * nb[1] * nb[2], 4, dtype=torch.int32, device=dev)
     n_new = torch.zeros(1, dtype=torch.int32, device=dev)
-    i32 = torch.int32
     with torch.cuda.device(dev):
-        check(lib.snr_density_grid(clat, B, ops._p(latent), ops._p(packed), sb, tb, ops._p(coarse), st), "snr_density_grid")
-        check(lib.snr_band_classify(ops._p(coarse), B, lat, level, band, ops._ptr(state, i32), ops._ptr(fill), st), "snr_band_classify")
+        coarse = ops.density_grid(clat, latent, packed, sb, tb)
+        ops.band_classify(coarse, lat, level, band, state, fill)
         if initial_bricks is not None:
-            state.copy_(ib.to(i32))
-        scan = torch.cumsum((state == 1).view(-1), 0, dtype=i32)
-        check(lib.snr_band_compact(ops._ptr(state, i32), ops._ptr(scan, i32), B, lat, ops._ptr(bricks, i32), st), "snr_band_compact")
-        check(lib.snr_band_fill(ops._p(grid), B, lat, ops._ptr(state, i32), ops._ptr(fill), st), "snr_band_fill")
-
-        def evaluate(k):
-            check(lib.snr_density_bricks(lat, B, ops._ptr(bricks, i32), k, ops._p(latent), ops._p(packed), sb, tb, ops._p(grid), st),
-                  "snr_density_bricks")
-
+            state.copy_(ib.to(torch.int32))
+        scan = torch.cumsum((state == 1).view(-1), 0, dtype=torch.int32)
+        ops.band_compact(state, scan, lat, bricks)
+        ops.band_fill(grid, lat, state, fill)
         evaluated = int(scan[-1])                      # host read: the size of the first brick list
         if evaluated:
-            evaluate(evaluated)
+            ops.density_bricks(lat, bricks, evaluated, latent, packed, sb, tb, grid)
         rounds, stamp = 0, 2
         while True:
-            check(lib.snr_band_seam(ops._p(grid), B, lat, level, stamp, ops._ptr(state, i32), ops._ptr(bricks, i32), ops._ptr(n_new, i32), st),
-                  "snr_band_seam")
+            ops.band_seam(grid, lat, level, stamp, state, bricks, n_new)
             k = int(n_new.item())                      # host read: the bricks this round added
             if k == 0:
                 break
-            evaluate(k)
+            ops.density_bricks(lat, bricks, k, latent, packed, sb, tb, grid)
             evaluated += k
             rounds += 1
             stamp += 1
@@ -392,20 +345,18 @@ def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=
             grid = grid.unsqueeze(0)
         if grid.dim() != 4:
             raise SnrError(f"a grid is (B, nx, ny, nz) or (nx, ny, nz), got {tuple(model_or_grid.shape)}")
-        grid = ops._f32c(grid)
+        grid = grid.float().contiguous()
         lat = lattice(tuple(grid.shape[1:]), bound)
     else:
         if shapecode is None:
             raise SnrError("extract_mesh(model, shapecode, ...): the shape codes are missing")
+        model = model_or_grid
         if grad:
-            model = _decoder(model_or_grid)
-            if model.train_decoder_weights:
-                raise SnrError("extract_mesh(differentiable=True) does not differentiate the decoder weights: with train_decoder_weights "
-                               "set, run it under torch.no_grad() or use the model's forward")
+            _, latent, packed = _decoder_inputs(model, shapecode, differentiable="extract_mesh(differentiable=True)")
         if narrow_band:
-            grid = narrow_band_grid(model_or_grid, shapecode, resolution, level=level, band=band, bound=bound).grid
+            grid = narrow_band_grid(model, shapecode, resolution, level=level, band=band, bound=bound).grid
         else:
-            grid = density_grid(model_or_grid, shapecode, resolution, bound)
+            grid = density_grid(model, shapecode, resolution, bound)
         lat = lattice(resolution, bound)
     if min(lat.n) < 2:
         raise SnrError(f"extract_mesh needs at least 2 points per axis, got {tuple(lat.n)}")
@@ -416,17 +367,11 @@ def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=
     if not grad:
         m = ops.iso_extract(grid, lat, level)
         verts, faces, nvs, nts = m.verts, m.faces, m.n_verts, m.n_faces
-    elif torch.is_tensor(model_or_grid):
-        verts, faces, sizes = ops.IsoVertices.apply(grid, lat, level)
-        nvs, nts = sizes.tolist()
     else:
-        sc = shapecode.unsqueeze(0) if shapecode.dim() == 1 else shapecode
-        sc = sc.float()
-        model._note_decoder_run(constant=True)
-        latent = model.latent_terms(sc, torch.zeros_like(sc))
-        packed = model.packed_weights()
-        ops._need_gpu(latent, packed)
-        verts, faces, sizes = ops.IsoVerticesLatent.apply(latent, packed, grid, lat, level, model.shape_blocks, model.texture_blocks)
+        if torch.is_tensor(model_or_grid):
+            verts, faces, sizes = ops.IsoVertices.apply(grid, lat, level)
+        else:
+            verts, faces, sizes = ops.IsoVerticesLatent.apply(latent, packed, grid, lat, level, model.shape_blocks, model.texture_blocks)
         nvs, nts = sizes.tolist()
     out, v0, f0 = [], 0, 0
     for b in range(B):

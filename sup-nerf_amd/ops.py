@@ -783,6 +783,57 @@ class DensityPoints(torch.autograd.Function):
         return d_xyz, d_lat, None, None, None
 
 
+# ------------------------------------------------------------------------------------ density on lattices, and the narrow band's passes
+def density_grid(lat, latent, packed, shape_blocks, texture_blocks):
+    """sigma (B, n0, n1, n2) of the B objects of ``latent`` on the ``Lattice`` ``lat``, its points made in the kernel (``snr_density_grid``)."""
+    B, dev = latent.shape[0], latent.device
+    out = torch.empty(B, *lat.n, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_density_grid(lat, B, _p(latent), _p(packed), shape_blocks, texture_blocks, _p(out), _stream(dev)), "snr_density_grid")
+    return out
+
+
+def density_bricks(lat, bricks, n, latent, packed, shape_blocks, texture_blocks, out):
+    """sigma at the points of the first ``n`` bricks (object, I, J, K) of the int32 list ``bricks`` on ``lat``, written into the grids
+    ``out`` (B, n0, n1, n2) (``snr_density_bricks``); entries out of range are skipped, the other points of ``out`` are left alone."""
+    dev = out.device
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_density_bricks(lat, out.shape[0], _ptr(bricks, torch.int32), n, _p(latent), _p(packed), shape_blocks,
+                                            texture_blocks, _p(out), _stream(dev)), "snr_density_bricks")
+    return out
+
+
+def band_classify(coarse, lat, level, band, state, fill):
+    """Per brick of ``lat`` from the coarse grids: state 1 / 0 (active or not) and the fill value (``snr_band_classify``)."""
+    dev = coarse.device
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_band_classify(_p(coarse), coarse.shape[0], lat, level, band, _ptr(state, torch.int32), _ptr(fill), _stream(dev)),
+              "snr_band_classify")
+
+
+def band_compact(state, scan, lat, bricks):
+    """The bricks of state 1 as a list (object, I, J, K) in ``bricks``, at the slots their inclusive ``scan`` gives (``snr_band_compact``)."""
+    dev = state.device
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_band_compact(_ptr(state, torch.int32), _ptr(scan, torch.int32), state.shape[0], lat, _ptr(bricks, torch.int32),
+                                          _stream(dev)), "snr_band_compact")
+
+
+def band_fill(grid, lat, state, fill):
+    """The points of the bricks of state 0 set to their brick's fill value (``snr_band_fill``)."""
+    dev = grid.device
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_band_fill(_p(grid), grid.shape[0], lat, _ptr(state, torch.int32), _ptr(fill), _stream(dev)), "snr_band_fill")
+
+
+def band_seam(grid, lat, level, stamp, state, bricks, n_new):
+    """One growth round (``snr_band_seam``): the unevaluated bricks at the ends of crossing edges get state ``stamp`` and are listed in
+    ``bricks``; their number goes to ``n_new`` (1,) int32 on the device."""
+    dev = grid.device
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_band_seam(_p(grid), grid.shape[0], lat, level, stamp, _ptr(state, torch.int32), _ptr(bricks, torch.int32),
+                                       _ptr(n_new, torch.int32), _stream(dev)), "snr_band_seam")
+
 
 # ------------------------------------------------------------------------------------ iso-surface and its backward
 class IsoMesh(NamedTuple):
@@ -861,6 +912,15 @@ def iso_surface_points(on_surface, d_grid, lat):
     return xyz, d_sig, n, counts
 
 
+def _iso_forward(ctx, grid, lat, level, *saved):
+    """The forward of both iso Functions: ``iso_extract``, its topology saved after ``saved`` for the backward."""
+    m = iso_extract(grid, lat, level)
+    ctx.save_for_backward(*saved, grid, m.edge_mask, m.edge_scan, m.vert_offset)
+    sizes = torch.tensor([m.n_verts, m.n_faces], dtype=torch.int64)
+    ctx.mark_non_differentiable(m.faces, sizes)
+    return m.verts, m.faces, sizes
+
+
 class IsoVertices(torch.autograd.Function):
     """Iso-surface vertices of grids (B, n0, n1, n2), differentiable wrt the grid values at the forward's topology.  Forward: ``iso_extract``
     (output unchanged).  Saves the grid, edge_mask and edge_scan (4 + 1 + 4 = 9 bytes per grid point) rather than rerun the count pass.
@@ -868,12 +928,8 @@ class IsoVertices(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, grid, lat, level):
-        m = iso_extract(grid, lat, level)
-        ctx.save_for_backward(grid, m.edge_mask, m.edge_scan, m.vert_offset)
         ctx.cfg = (lat, level)
-        sizes = torch.tensor([m.n_verts, m.n_faces], dtype=torch.int64)
-        ctx.mark_non_differentiable(m.faces, sizes)
-        return m.verts, m.faces, sizes
+        return _iso_forward(ctx, grid, lat, level)
 
     @staticmethod
     def backward(ctx, d_verts, d_faces, d_sizes):
@@ -892,12 +948,8 @@ class IsoVerticesLatent(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, latent, packed, grid, lat, level, shape_blocks, texture_blocks):
-        m = iso_extract(grid, lat, level)
-        ctx.save_for_backward(latent, packed, grid, m.edge_mask, m.edge_scan, m.vert_offset)
         ctx.cfg = (lat, level, shape_blocks, texture_blocks)
-        sizes = torch.tensor([m.n_verts, m.n_faces], dtype=torch.int64)
-        ctx.mark_non_differentiable(m.faces, sizes)
-        return m.verts, m.faces, sizes
+        return _iso_forward(ctx, grid, lat, level, latent, packed)
 
     @staticmethod
     def backward(ctx, d_verts, d_faces, d_sizes):
@@ -911,6 +963,7 @@ class IsoVerticesLatent(torch.autograd.Function):
         sig, masks = density_fwd(xyz, latent, packed, sb, tb, save_masks=True)
         d_lat, _ = density_bwd(xyz, latent, packed, masks, sig, d_sig, sb, tb, need_latent=True, need_xyz=False)
         return d_lat, None, None, None, None, None, None
+
 
 def weight_grad(G, n_out, X, n_in, want_bias=True, out=None, ws=None, precision="fp32"):
     """dW (n_out, n_in) = G[:, :n_out]^T X[:, :n_in] and db (n_out,) = column sums of G, one split-K MFMA launch + one reduction

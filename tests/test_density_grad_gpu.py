@@ -2,36 +2,18 @@
 full fp32 backward at a zero colour gradient (bit for bit), ``geometry.density``'s gradients against float64 autograd of the oracle, normals of
 the planted box against their closed form, vertex colours against the decoder forward, and the guard against silently missing weight
 gradients."""
-import numpy as np
 import pytest
 import torch
 
+from geometry_cases import BOUND_BOX, LEVEL_BOX, box, codes as _codes, model as _model, points as _points
 from oracle import supnerf_oracle as O
 from oracle_bands import amd, dev, in_band  # noqa: F401  (fixtures)
-from planted_decoder import HALF, planted_params
+from planted_decoder import HALF
 from relu_bits import decode_relu_bits
 
 pytestmark = pytest.mark.gpu
 
 BLOCKS = [(0, 0), (0, 3), (3, 1), (5, 5), (8, 8)]
-
-
-def _model(amd, dev, sb, tb, params=None, seed=0):  # noqa: F811
-    m = amd.CodeNeRF(shape_blocks=sb, texture_blocks=tb)
-    m.load_state_dict(params if params is not None else O.init_decoder_params(sb, tb, seed=seed, sigma_bias=-2.0), strict=True)
-    return m.to(dev)
-
-
-def _codes(B, seed, dev):  # noqa: F811
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(B, 256, generator=g) * 0.5).to(dev)
-
-
-def _points(P, seed, dev):  # noqa: F811
-    g = torch.Generator().manual_seed(seed)
-    xyz = (torch.rand(P, 3, generator=g) - 0.5).to(dev)
-    vd = torch.nn.functional.normalize(torch.randn(P, 3, generator=g), dim=1).to(dev)
-    return xyz, vd, g
 
 
 @pytest.mark.parametrize("blocks", BLOCKS)
@@ -159,10 +141,9 @@ def test_density_gradients_against_float64(amd, dev, blocks):  # noqa: F811
 
 def _box(amd, dev, sb):  # noqa: F811
     from supnerf_amd import geometry as G
-    model = _model(amd, dev, sb, 1, params=planted_params(sb, 1, seed=sb))
+    model = box(amd, dev, sb, 1, seed=sb)
     sc = _codes(2, 20 + sb, dev)
-    level = float(np.log1p(np.exp(np.float32(0.0))))                # softplus(0): the surface d1 = H
-    meshes = G.extract_mesh(model, sc, level=level, resolution=96, bound=(-0.7, 0.7))
+    meshes = G.extract_mesh(model, sc, level=LEVEL_BOX, resolution=96, bound=BOUND_BOX)
     return model, sc, meshes
 
 

@@ -6,22 +6,12 @@ import pytest
 import torch
 
 import iso_restatement as I
+from geometry_cases import BOUND_BOX, LEVEL_BOX, box, codes as _codes, model as _model
 from oracle import supnerf_oracle as O
 from oracle_bands import amd, dev, in_band  # noqa: F401  (fixtures)
-from planted_decoder import HALF, H, planted_params
+from planted_decoder import HALF, H
 
 pytestmark = pytest.mark.gpu
-
-
-def _model(amd, dev, sb, tb, params=None, seed=0):  # noqa: F811
-    m = amd.CodeNeRF(shape_blocks=sb, texture_blocks=tb)
-    m.load_state_dict(params if params is not None else O.init_decoder_params(sb, tb, seed=seed, sigma_bias=-2.0), strict=True)
-    return m.to(dev)
-
-
-def _codes(B, seed, dev):  # noqa: F811
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(B, 256, generator=g) * 0.5).to(dev)
 
 
 @pytest.mark.parametrize("blocks", [(0, 0), (0, 3), (3, 1), (5, 5), (8, 8)])
@@ -119,11 +109,10 @@ def test_iso_rejects_non_finite_grids(amd, dev):  # noqa: F811
 @pytest.mark.parametrize("sb", [1, 3, 5])
 def test_planted_box_mesh(amd, dev, sb):  # noqa: F811
     from supnerf_amd import geometry as G
-    model = _model(amd, dev, sb, 1, params=planted_params(sb, 1, seed=sb))
+    model = box(amd, dev, sb, 1, seed=sb)
     sc = _codes(2, 20 + sb, dev)
-    level = float(np.log1p(np.exp(np.float32(0.0))))                # softplus(0): the surface d1 = H
-    res, bound = 96, (-0.7, 0.7)
-    meshes = G.extract_mesh(model, sc, level=level, resolution=res, bound=bound)
+    res = 96
+    meshes = G.extract_mesh(model, sc, level=LEVEL_BOX, resolution=res, bound=BOUND_BOX)
     hstep = 1.4 / (res - 1)
     assert len(meshes) == 2
     for v, fa in meshes:

@@ -9,30 +9,16 @@ import torch
 
 import iso_grad_restatement as IG
 import iso_restatement as IR
+from geometry_cases import BOUND_BOX, LEVEL_BOX, box, codes as _codes, model as _model, same_meshes as _same_meshes
 from oracle import supnerf_oracle as O
 from oracle_bands import amd, dev, in_band  # noqa: F401  (fixtures)
-from planted_decoder import WOBBLE, planted_params
+from planted_decoder import WOBBLE
 from relu_bits import decode_relu_bits
 
 pytestmark = pytest.mark.gpu
 
-LEVEL_BOX = float(np.log1p(np.exp(np.float32(0.0))))        # softplus(0): the planted box's surface d1 = H
-BOUND_BOX = (-0.7, 0.7)
-
-
-def _model(amd, dev, sb, tb, params=None, seed=0):  # noqa: F811
-    m = amd.CodeNeRF(shape_blocks=sb, texture_blocks=tb)
-    m.load_state_dict(params if params is not None else O.init_decoder_params(sb, tb, seed=seed, sigma_bias=-2.0), strict=True)
-    return m.to(dev)
-
-
 def _box(amd, dev, sb=3, tb=1, seed=1):  # noqa: F811
-    return _model(amd, dev, sb, tb, params=planted_params(sb, tb, seed=seed, wobble=WOBBLE))
-
-
-def _codes(B, seed, dev):  # noqa: F811
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(B, 256, generator=g) * 0.5).to(dev)
+    return box(amd, dev, sb, tb, seed, wobble=WOBBLE)
 
 
 def _weights(meshes, seed):
@@ -42,10 +28,6 @@ def _weights(meshes, seed):
 
 def _loss(meshes, w):
     return sum((v * wb).sum() for (v, _), wb in zip(meshes, w))
-
-
-def _same_meshes(a, b):
-    return len(a) == len(b) and all(torch.equal(va, vb) and torch.equal(fa, fb) for (va, fa), (vb, fb) in zip(a, b))
 
 
 def test_differentiable_meshes_are_the_meshes(amd, dev):  # noqa: F811

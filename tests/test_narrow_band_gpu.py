@@ -6,49 +6,23 @@ import pytest
 import torch
 
 import band_restatement as NB
-from oracle import supnerf_oracle as O
+from geometry_cases import BOUND_BOX, LEVEL_BOX, box, codes as _codes, latent, model as _model, same_meshes as _same_meshes
 from oracle_bands import amd, dev  # noqa: F401  (fixtures)
 from planted_decoder import FAR_PRE, WOBBLE, planted_params
 
 pytestmark = pytest.mark.gpu
 
-LEVEL_BOX = float(np.log1p(np.exp(np.float32(0.0))))        # softplus(0): the planted box's surface d1 = H
-BOUND_BOX = (-0.7, 0.7)
-
-
-def _model(amd, dev, sb, tb, params=None, seed=0):  # noqa: F811
-    m = amd.CodeNeRF(shape_blocks=sb, texture_blocks=tb)
-    m.load_state_dict(params if params is not None else O.init_decoder_params(sb, tb, seed=seed, sigma_bias=-2.0), strict=True)
-    return m.to(dev)
-
-
-def _codes(B, seed, dev):  # noqa: F811
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(B, 256, generator=g) * 0.5).to(dev)
-
-
 def _on_lattice(amd, model, sc, lat):  # noqa: F811
     """snr_density_grid on an arbitrary Lattice."""
-    from supnerf_amd import geometry as G, ops
-    B = sc.shape[0]
-    out = torch.empty(B, *lat.n, device=sc.device)
-    lat_t = G._latent(model, sc)
-    amd._lib.check(amd._lib.lib().snr_density_grid(lat, B, ops._p(lat_t), ops._p(model.packed_weights()), model.shape_blocks,
-                                                   model.texture_blocks, ops._p(out), ops._stream(sc.device)), "snr_density_grid")
-    return out
+    return amd.ops.density_grid(lat, latent(model, sc), model.packed_weights(), model.shape_blocks, model.texture_blocks)
 
 
 def _bricks(amd, model, sc, lat, bricks):  # noqa: F811
     """snr_density_bricks of the (n, 4) int32 list into a NaN-filled grid."""
-    from supnerf_amd import geometry as G, ops
-    B = sc.shape[0]
-    out = torch.full((B, *lat.n), float("nan"), device=sc.device)
+    out = torch.full((sc.shape[0], *lat.n), float("nan"), device=sc.device)
     bl = torch.as_tensor(bricks, dtype=torch.int32).reshape(-1, 4).to(sc.device).contiguous()
-    lat_t = G._latent(model, sc)
-    amd._lib.check(amd._lib.lib().snr_density_bricks(lat, B, ops._ptr(bl, torch.int32), bl.shape[0], ops._p(lat_t),
-                                                     ops._p(model.packed_weights()), model.shape_blocks, model.texture_blocks,
-                                                     ops._p(out), ops._stream(sc.device)), "snr_density_bricks")
-    return out
+    return amd.ops.density_bricks(lat, bl, bl.shape[0], latent(model, sc), model.packed_weights(), model.shape_blocks, model.texture_blocks,
+                                  out)
 
 
 def _listed_points(shape, B, bricks):
@@ -113,16 +87,11 @@ def _restated(amd, model, sc, R, bound, level, band=0.0, initial=None):  # noqa:
     return (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]), max(o[2] for o in out), sum(o[3] for o in out))
 
 
-def _same_meshes(a, b):
-    return len(a) == len(b) and all(torch.equal(va, vb) and torch.equal(fa, fb) for (va, fa), (vb, fb) in zip(a, b))
-
-
 @pytest.mark.parametrize("sb", [1, 3, 5])
 @pytest.mark.parametrize("far", [False, True])
 def test_planted_box_narrow_band_mesh_is_the_dense_mesh(amd, dev, sb, far):  # noqa: F811
     from supnerf_amd import geometry as G
-    params = planted_params(sb, 1, seed=sb, far_pre=FAR_PRE if far else None, wobble=WOBBLE)
-    model = _model(amd, dev, sb, 1, params=params)
+    model = box(amd, dev, sb, 1, seed=sb, far_pre=FAR_PRE if far else None, wobble=WOBBLE)
     sc = _codes(3, 40 + sb, dev)
     for R in (64, 129, 200):
         nbg = G.narrow_band_grid(model, sc, R, level=LEVEL_BOX, bound=BOUND_BOX)
@@ -143,7 +112,7 @@ def test_planted_box_narrow_band_mesh_is_the_dense_mesh(amd, dev, sb, far):  # n
 def test_growth_from_one_brick_reaches_the_whole_box(amd, dev):  # noqa: F811
     from supnerf_amd import geometry as G
     sb = 3
-    model = _model(amd, dev, sb, 1, params=planted_params(sb, 1, seed=7, wobble=WOBBLE))
+    model = box(amd, dev, sb, 1, seed=7, wobble=WOBBLE)
     sc = _codes(2, 9, dev)
     R = 96
     full = G.narrow_band_grid(model, sc, R, level=LEVEL_BOX, bound=BOUND_BOX)

@@ -10,42 +10,15 @@ The dense route at R = 512 takes at most 7 objects per grid launch (fewer than 2
 Prints one JSON line.
 
 usage: python tools/mesh_grad_time.py [--reps N] [--res R ...] [--batch B ...] [--commit SHA]"""
-import argparse
 import json
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import supnerf_amd as A  # noqa: E402
-from supnerf_amd import geometry as G, ops  # noqa: E402
-from planted_decoder import WOBBLE, planted_params  # noqa: E402
-
-LEVEL = float(np.log1p(np.exp(np.float32(0.0))))
-BOUND = (-0.7, 0.7)
-
-
-def commit():
-    try:
-        return subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, timeout=10).stdout.strip() or None
-    except Exception:
-        return None
-
-
-def timed(fn):
-    """Milliseconds of one call between two device events (host reads inside the call included)."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
+import geometry_common as C
+from geometry_common import BOUND_BOX as BOUND, LEVEL_BOX as LEVEL, timed
+from supnerf_amd import geometry as G, ops
 
 
 def row(model, sc0, R, narrow, reps):
@@ -76,7 +49,7 @@ def row(model, sc0, R, narrow, reps):
     grid = G.narrow_band_grid(model, sc0, R, level=LEVEL, bound=BOUND).grid if narrow else G.density_grid(model, sc0, R, BOUND)
     m = ops.iso_extract(grid, lat, LEVEL)
     d_verts = torch.cat(state["w"])
-    latent, packed = G._latent(model, sc0), model.packed_weights()
+    latent, packed = C.latent(model, sc0), model.packed_weights()
     sb, tb = model.shape_blocks, model.texture_blocks
     part = {}
 
@@ -109,29 +82,21 @@ def row(model, sc0, R, narrow, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--res", type=int, nargs="+", default=[128, 256, 512])
-    ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
-    ap.add_argument("--commit", default=None, help="commit to report when the tree has no .git")
-    a = ap.parse_args()
+    a = C.arguments(C.RES, C.BATCH)
     dev = torch.device("cuda:0")
     sb, tb = 3, 1
-    model = A.CodeNeRF(shape_blocks=sb, texture_blocks=tb)
-    model.load_state_dict(planted_params(sb, tb, seed=1, wobble=WOBBLE))
-    model = model.to(dev)
+    model = C.box_decoder(sb, tb, dev)
     rows = []
     for R in a.res:
         for B in a.batch:
-            sc = (torch.randn(B, 256, generator=torch.Generator().manual_seed(B)) * 0.5).to(dev)
+            sc = C.codes(B, B, dev)
             for narrow in (False, True):
                 if not narrow and B * R ** 3 >= 2 ** 30:
                     continue
                 r = row(model, sc, R, narrow, a.reps)
                 rows.append(r)
                 print(json.dumps(r), file=sys.stderr, flush=True)
-    print(json.dumps({"tool": "mesh_grad_time", "commit": a.commit or commit(), "device": torch.cuda.get_device_name(0), "blocks": [sb, tb],
-                      "level": LEVEL, "bound": list(BOUND), "rows": rows}))
+    C.report("mesh_grad_time", a, (sb, tb), level=LEVEL, bound=list(BOUND), rows=rows)
 
 
 if __name__ == "__main__":

@@ -12,46 +12,13 @@ where not, the dense grid's crossing edges the narrow band left unevaluated (the
 Last, the brick-mode kernel's points/s against the lattice kernel's (mode 3) on every brick of an R = 256 grid.  Prints one JSON line.
 
 usage: python tools/narrow_band_time.py [--reps N] [--res R ...] [--batch B ...] [--commit SHA]"""
-import argparse
 import json
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import supnerf_amd as A  # noqa: E402
-from supnerf_amd import geometry as G, ops  # noqa: E402
-from oracle import supnerf_oracle as O  # noqa: E402
-from planted_decoder import WOBBLE, planted_params  # noqa: E402
-
-
-def commit():
-    try:
-        return subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, timeout=10).stdout.strip() or None
-    except Exception:
-        return None
-
-
-def timed(fn):
-    """Milliseconds of one call between two device events (host reads inside the call included)."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def model_of(params, sb, tb, dev):
-    m = A.CodeNeRF(shape_blocks=sb, texture_blocks=tb)
-    m.load_state_dict(params)
-    return m.to(dev)
+import geometry_common as C
+from supnerf_amd import geometry as G, ops
 
 
 def same_meshes(a, b):
@@ -87,14 +54,10 @@ def row(model, sc, R, bound, level, reps):
     missed = 0 if equal else missed_edges(gd, nb.active, level)
     n_verts, n_faces = sum(int(v.shape[0]) for v, _ in md), sum(int(f.shape[0]) for _, f in md)
     del md, mn
-    iso = float(np.median([timed(lambda: G.extract_mesh(nb.grid, level=level, bound=bound)) for _ in range(reps)]))
+    iso = C.median_ms(lambda: G.extract_mesh(nb.grid, level=level, bound=bound), reps)
     del gd
     torch.cuda.empty_cache()
-    t_d, t_n = [], []
-    for _ in range(reps):                                                                      # alternate the two
-        t_d.append(timed(dense))
-        t_n.append(timed(narrow))
-    d, n = float(np.median(t_d)), float(np.median(t_n))
+    d, n = C.alternate(dense, narrow, reps)
     B = sc.shape[0]
     dense_points = B * R ** 3
     out = {"R": R, "B": B, "dense_grid_ms": round(d, 3), "narrow_grid_ms": round(n, 3), "grid_speedup": round(d / n, 3),
@@ -110,49 +73,35 @@ def row(model, sc, R, bound, level, reps):
 def brick_rate(model, R, reps, dev):
     """points/s of snr_density_bricks on every brick of an R^3 grid against snr_density_grid on the same grid (R a multiple of 8: the same
     points, the same values)."""
-    sc = (torch.randn(1, 256, generator=torch.Generator().manual_seed(3)) * 0.5).to(dev)
+    sc = C.codes(1, 3, dev)
     lat = G.lattice(R)
     nb = (R + 7) // 8
     idx = torch.arange(nb ** 3, device=dev, dtype=torch.int32)
     bricks = torch.stack([torch.zeros_like(idx), idx // (nb * nb), (idx // nb) % nb, idx % nb], 1).contiguous()
-    latent, packed = G._latent(model, sc), model.packed_weights()
+    latent, packed = C.latent(model, sc), model.packed_weights()
     out = torch.empty(1, R, R, R, device=dev)
-    st = ops._stream(dev)
-
-    def run():
-        A._lib.check(A._lib.lib().snr_density_bricks(lat, 1, ops._ptr(bricks, torch.int32), bricks.shape[0], ops._p(latent), ops._p(packed),
-                                                     model.shape_blocks, model.texture_blocks, ops._p(out), st), "snr_density_bricks")
+    run = lambda: ops.density_bricks(lat, bricks, bricks.shape[0], latent, packed, model.shape_blocks, model.texture_blocks, out)  # noqa: E731
     grid = lambda: G.density_grid(model, sc, R)                                                # noqa: E731
     run()
     same = bool(torch.equal(out, grid()))
-    t_b, t_g = [], []
-    for _ in range(reps):
-        t_b.append(timed(run))
-        t_g.append(timed(grid))
-    b, g = float(np.median(t_b)), float(np.median(t_g))
+    b, g = C.alternate(run, grid, reps)
     P = 512 * bricks.shape[0]
     return {"R": R, "points": P, "bricks_ms": round(b, 3), "lattice_ms": round(g, 3), "bricks_Gpts_s": round(P / b / 1e6, 4),
             "lattice_Gpts_s": round(R ** 3 / g / 1e6, 4), "ratio": round((P / b) / (R ** 3 / g), 4), "sigma_bit_identical": same}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--res", type=int, nargs="+", default=[128, 256, 512])
-    ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
-    ap.add_argument("--commit", default=None, help="commit to report when the tree has no .git")
-    a = ap.parse_args()
+    a = C.arguments(C.RES, C.BATCH)
     dev = torch.device("cuda:0")
     sb, tb = 3, 1
-    cases = {"box": (model_of(planted_params(sb, tb, seed=1, wobble=WOBBLE), sb, tb, dev), (-0.7, 0.7)),
-             "fog": (model_of(O.init_decoder_params(sb, tb, seed=0, sigma_bias=-2.0), sb, tb, dev), (-0.5, 0.5))}
+    cases = {"box": (C.box_decoder(sb, tb, dev), C.BOUND_BOX), "fog": (C.fog_decoder(sb, tb, dev), (-0.5, 0.5))}
     rows = []
     for name, (model, bound) in cases.items():
         for R in a.res:
             for B in a.batch:
-                sc = (torch.randn(B, 256, generator=torch.Generator().manual_seed(B)) * 0.5).to(dev)
+                sc = C.codes(B, B, dev)
                 if name == "box":
-                    level = float(np.log1p(np.exp(np.float32(0.0))))
+                    level = C.LEVEL_BOX
                 else:
                     # one code B times: a level cuts one fog code through its median only (the fog's sigma differs a little per code)
                     sc = sc[:1].repeat(B, 1)
@@ -163,8 +112,7 @@ def main():
                 rows.append(r)
                 print(json.dumps(r), file=sys.stderr, flush=True)
     rate = brick_rate(cases["fog"][0], 256, a.reps, dev)
-    print(json.dumps({"tool": "narrow_band_time", "commit": a.commit or commit(), "device": torch.cuda.get_device_name(0), "blocks": [sb, tb],
-                      "rows": rows, "brick_mode": rate}))
+    C.report("narrow_band_time", a, (sb, tb), rows=rows, brick_mode=rate)
 
 
 if __name__ == "__main__":
