@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 12
+#define SNR_ABI_VERSION 13
 
 enum {
     SNR_OK = 0,
@@ -431,6 +431,43 @@ int snr_iso_grad(const float* grid, int64_t n_grids, const snr_lattice* lattice,
                  void* stream);
 int snr_iso_surface_points(const uint8_t* on_surface, const int32_t* surface_scan, const float* d_grid, int64_t n_grids,
                            const snr_lattice* lattice, int64_t points_per_obj, float* xyz, float* d_sigmas, void* stream);
+
+/* Ray-cast surfaces: along each ray, the first point where the density rises through `level`.  The decoder work is snr_density_fwd on
+ * the point lists made here (and snr_density_fwd_masks / snr_density_bwd at the hit points, for normals and gradients); these entry points
+ * are the per-ray passes around it.  R rays (object-major when several objects share a launch), all arithmetic fp32, one rounding per
+ * written operation (no fma); tests/ray_restatement.py restates every rule step by step.
+ *   1. March of an interval [ta, tb] with S >= 2 samples: step = (tb - ta) / (S - 1); t_k = ta + step * k for k < S - 1 and t_{S-1} = tb
+ *      exactly; point p_k = o + t_k * d per axis (one multiply, one add).
+ *   2. A sample is inside iff sigma_k >= level (a NaN is outside, +inf inside).
+ *   3. First crossing: the smallest k in [0, S - 2] with sigma_k outside and sigma_{k+1} inside; its bracket is
+ *      (ta', tb', va, vb) = (t_k, t_{k+1}, sigma_k, sigma_{k+1}).
+ *   4. State, decided by the first march only: 2 = sigma_0 inside (the ray starts inside), else 1 = a crossing exists, else 0 = miss.
+ *      A ray of state 0 / 2 leaves the first march with the dummy interval [ta, ta] and va = vb = 0.
+ *   5. Refinement: the bracket of every state-1 ray is marched again (any S) and replaced by the first crossing of that march.  Both ends
+ *      of the sub-march are the bracket's ends bit for bit (rule 1), so it starts outside and ends inside and always has a crossing; a
+ *      state-1 ray whose march shows none (sigma not the decoder's) keeps its bracket.  Rays of state 0 / 2 are not touched.
+ *   6. Depth: t = ta + (level - va) / (vb - va) * (tb - ta) on state 1 (vb - va > 0), ta (= near) on state 2, 0 on state 0; width
+ *      = tb - ta on state 1, else 0: the depth and the true crossing both lie in the bracket.  Hit point x = o + t * d (every state).
+ *   7. Normal (state 1): snr_density_fwd_masks + snr_density_bwd with d_sigmas = 1 at x give g = grad sigma(x); slope = g . d summed in
+ *      axis order; normal = -g / |g| (the zero vector where |g| is 0 or not finite, and on states 0 / 2).  No gradient flows through it.
+ *   8. Gradient of the depth: the implicit function theorem on sigma(o + t d; code) = level at x -- not the derivative of rule 6's
+ *      interpolation, which is wrong by percents inside a bracket of a steep density.  With the upstream gradient d_t and
+ *      c = -d_t / slope on state 1, 0 elsewhere: d o = c g, d d = t c g, and the latent gradient is snr_density_bwd with d_sigmas = c on
+ *      the ReLU bits saved in rule 7 (objects padded to whole 64-point workgroups).  near, far, level and the topology get none; a
+ *      grazing ray (slope -> 0) gives a large one and nothing is clamped.  Rules 7 - 8 need no kernel of their own.
+ *
+ * snr_ray_march_points: rays_o, rays_d (R,3), ta, tb (R) -> xyz (R n_samples, 3), ray-major (rule 1).
+ * snr_ray_first_crossing: sigmas (R, n_samples) of the march of [ta, tb]; first = 1: writes state (R) uint8 and the bracket ta, tb, va, vb
+ *   (R) IN PLACE (rules 2 - 4); first = 0: reads state, replaces the bracket of state-1 rays (rule 5).
+ * snr_ray_hit_points: depth, width (R), xyz (R,3) (rule 6).
+ * n_samples < 2 or a null pointer: SNR_E_ARG; more than 2^31 threads (R n_samples points; 64 R from n_samples = 32 on in the crossing
+ * search, which then takes a wave per ray): SNR_E_UNSUPPORTED. */
+int snr_ray_march_points(const float* rays_o, const float* rays_d, const float* ta, const float* tb, int64_t n_rays, int n_samples,
+                         float* xyz, void* stream);
+int snr_ray_first_crossing(const float* sigmas, int64_t n_rays, int n_samples, float level, int first, float* ta, float* tb, float* va,
+                           float* vb, uint8_t* state, void* stream);
+int snr_ray_hit_points(const float* rays_o, const float* rays_d, const float* ta, const float* tb, const float* va, const float* vb,
+                       const uint8_t* state, int64_t n_rays, float level, float* depth, float* width, float* xyz, void* stream);
 
 #ifdef __cplusplus
 }

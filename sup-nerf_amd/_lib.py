@@ -92,6 +92,9 @@ _SIGS = {
     "snr_band_seam": (C.c_int, [_P, C.c_int64, C.POINTER(Lattice), C.c_float, C.c_int32, _P, _P, _P, _P]),
     "snr_iso_grad": (C.c_int, [_P, C.c_int64, C.POINTER(Lattice), C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "snr_iso_surface_points": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(Lattice), C.c_int64, _P, _P, _P]),
+    "snr_ray_march_points": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "snr_ray_first_crossing": (C.c_int, [_P, C.c_int64, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "snr_ray_hit_points": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
 }
 
 

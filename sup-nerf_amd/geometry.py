@@ -15,15 +15,22 @@ After an optimisation or a training run a caller holds one 256-float shape code 
   * ``density_gradient(model, xyz, shapecode)``: sigma and d sigma / d xyz in two launches, no autograd;
   * ``vertex_normals(model, meshes, shapecode)``: unit outward normals -grad sigma / |grad sigma| at the vertices of ``extract_mesh``;
   * ``vertex_colors(model, meshes, normals, shapecode, texturecode)``: the decoder's raw rgb at every vertex, seen head-on;
+  * ``ray_surface(model, rays_o, rays_d, near, far, shapecode, level=...)``: along each ray the first point where sigma rises through
+    ``level``: depth, state (miss / hit / starts inside), outward normal and the bracket width that bounds the depth's error, with autograd
+    from the depth to the ray origins, directions and shape codes (``ops.RaySurface``: ``snr_ray_*`` around the density launches);
+  * ``surface_depth(model, cam_pose, obj_diag, K, roi, shapecode, level=...)``: the same for a camera's pixel grid or listed pixels (lidar
+    returns), in metric units;
   * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
+    ``to_decoder_frame``: its inverse;
   * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
 
 The density kernels run the exact fp32 chain of the decoder forward up to its density head and stop there (no view direction, no colour
 branch): sigma is bit-identical to ``ops.decoder_fwd(..., precision="fp32")``.  Latent terms come from ``model.latent_terms`` with a zero
 texture code (the texture rows feed nothing the density reads).  The mesh rules (vertex order, quad split, winding) are those of
 include/supnerf_hip.h, restated in tests/iso_restatement.py.  The density backward runs the fp32 backward kernel from d sigma alone (no colour
-branch): d xyz and the shape-code gradient are bit for bit those of the full backward with a zero colour gradient.  There is no CPU path:
-CPU tensors raise ``SnrError``."""
+branch): d xyz and the shape-code gradient are bit for bit those of the full backward with a zero colour gradient.  The ray rules (march,
+first crossing, refinement, depth, implicit gradient) are the header's too, restated in tests/ray_restatement.py; a ray search reads nothing
+back to the host.  There is no CPU path: CPU tensors raise ``SnrError``."""
 from typing import NamedTuple
 
 import numpy as np
@@ -395,6 +402,113 @@ def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2
         return v @ m
     scale = float(obj_diag) if family == "a" else float(obj_diag) / 2
     return (v @ m) * scale
+
+
+def _frame_scale(obj_diag, family):
+    if family not in ("a", "b"):
+        raise SnrError(f"family is 'a' (utils render paths) or 'b' (NeRFRenderer), got {family!r}")
+    return float(obj_diag) if family == "a" else float(obj_diag) / 2
+
+
+def to_decoder_frame(points, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False, direction=False):
+    """The inverse of ``to_object_frame``: points (..., 3) of the object's metric frame -> the decoder frame, p = F^T (x / scale) with
+    the same frame matrix and scale (obj_diag for family "a", obj_diag / 2 for "b"); ``direction=True``: directions, without the scale.
+    Plain torch operations: differentiable wrt ``points``."""
+    scale = _frame_scale(obj_diag, family)
+    v = torch.as_tensor(points)
+    m = torch.tensor(U._frame(False, kitti2nusc, shapenet_obj_cood), dtype=v.dtype, device=v.device).view(3, 3)
+    if direction:
+        return v @ m.T
+    return (v / scale) @ m.T
+
+
+class RayHits(NamedTuple):
+    depth: torch.Tensor      # (B, N): t of the first crossing (units of |rays_d|); near where the ray starts inside; 0 on a miss
+    state: torch.Tensor      # (B, N) uint8: 0 miss, 1 hit, 2 the ray starts inside
+    normal: torch.Tensor     # (B, N, 3): unit outward normal -grad sigma / |grad sigma| at the hit point; zero where state != 1
+    width: torch.Tensor      # (B, N): width of the final bracket, which holds both the depth and the true crossing; 0 where state != 1
+
+
+DEFAULT_REFINE = (4, 5)          # the fastest of the four settings that shrink the bracket 256 times, as measured (DESIGN 4.7.3)
+
+
+def _ray_bound(v, what, shape, dev):
+    """near / far as a dense (B N,) fp32 device tensor: a python float, a 0-dim tensor or a tensor of the rays' leading shape."""
+    if torch.is_tensor(v):
+        if v.dim() == 0:
+            return v.detach().to(dev, torch.float32).expand(shape).reshape(-1).contiguous()
+        _gpu(v, what)
+        if tuple(v.shape) != tuple(shape):
+            raise SnrError(f"{what} must be a float, a 0-dim tensor or {tuple(shape)}, got {tuple(v.shape)}")
+        return v.detach().float().reshape(-1).contiguous()
+    return torch.full((int(np.prod(shape)),), float(v), device=dev)
+
+
+def ray_surface(model, rays_o, rays_d, near, far, shapecode, *, level, n_samples=64, refine=DEFAULT_REFINE):
+    """Along each ray rays_o + t rays_d, t in [near, far], the first point where the density of its object's shape code rises through
+    ``level``.  ``rays_o``, ``rays_d``: (B, N, 3) decoder-frame rays of the B codes of ``shapecode`` (B, 256), or (N, 3) with one code;
+    ``rays_d`` need not be unit (t is in units of |rays_d|).  ``near`` / ``far``: python floats, 0-dim tensors or (B, N).
+
+    The search: ``n_samples`` equidistant samples of [near, far]; a sample is inside iff sigma >= level; the first outside -> inside pair
+    is the ray's bracket.  ``refine = (levels, samples)``: ``levels`` times, the bracket is sampled again with ``samples`` points and
+    replaced by its first crossing -- (levels, 3) is bisection; the bracket shrinks by (samples - 1) ** levels.  The depth interpolates
+    linearly in the final bracket.  A surface thinner than a step of the first march between two samples is not seen.
+
+    Returns ``RayHits`` (depth, state, normal, width) shaped like the rays.  ``depth`` carries autograd to ``rays_o``, ``rays_d`` and
+    ``shapecode``: the derivative of the root of sigma(o + t d; code) = level at the point found (implicit function theorem), whatever
+    the bracket -- not that of the interpolation formula.  ``near``, ``far`` and ``level`` get no gradient, nor do changes of topology
+    (hit <-> miss, which crossing is first); a grazing ray (grad sigma . d -> 0) gets a large one, unclamped.  Misses and rays that start
+    inside get exactly zero.  The normals carry no gradient.  The decoder's weights are constants: with ``train_decoder_weights`` set and
+    grad mode on this raises, as ``density`` does.  Asynchronous on the current stream; nothing is read back to the host."""
+    o, d = _gpu(rays_o, "rays_o"), _gpu(rays_d, "rays_d")
+    if o.dim() not in (2, 3) or o.shape[-1] != 3 or tuple(d.shape) != tuple(o.shape):
+        raise SnrError(f"rays_o and rays_d must both be (B, N, 3) or (N, 3), got {tuple(o.shape)} and {tuple(d.shape)}")
+    n_samples = int(n_samples)
+    if n_samples < 2:
+        raise SnrError(f"n_samples must be at least 2, got {n_samples}")
+    levels, samples = (0, 2) if refine is None else refine
+    levels = int(levels)
+    samples = 2 if (levels == 0 and samples is None) else int(samples)
+    if levels < 0 or samples < 2:
+        raise SnrError(f"refine is (levels >= 0, samples >= 2), got {refine!r}")
+    if not torch.is_tensor(near) and not torch.is_tensor(far) and float(far) < float(near):
+        raise SnrError(f"far {far} lies before near {near}")
+    sc, latent, packed = _decoder_inputs(model, shapecode, differentiable="geometry.ray_surface")
+    lead = tuple(o.shape[:-1])
+    B = sc.shape[0]
+    if (o.dim() == 2 and B != 1) or (o.dim() == 3 and o.shape[0] != B):
+        raise SnrError(f"rays {tuple(o.shape)} do not match {B} shape code(s): (B, N, 3) rays, or (N, 3) with one code")
+    dev = o.device
+    ta, tb = _ray_bound(near, "near", lead, dev), _ray_bound(far, "far", lead, dev)
+    t, state, normal, width = ops.RaySurface.apply(o.reshape(-1, 3), d.reshape(-1, 3), ta, tb, latent, packed, float(np.float32(level)),
+                                                   n_samples, levels, samples, model.shape_blocks, model.texture_blocks)
+    return RayHits(t.view(lead), state.view(lead), normal.view(*lead, 3), width.view(lead))
+
+
+def surface_depth(model, cam_pose, obj_diag, K, roi, shapecode, *, level, im_sz=None, pixels=None, n_samples=64, refine=DEFAULT_REFINE,
+                  family="a", shapenet_obj_cood=False, kitti2nusc=False):
+    """The surface {sigma = level} of one object as a camera sees it, in metric units: ``ray_surface`` on the rays of ``utils.get_rays``
+    (a grid over ``roi``, ``im_sz`` x ``im_sz`` steps or one per pixel) or of ``utils.get_rays_specified`` (``pixels = (x_vec, y_vec)`` in
+    image coordinates: lidar returns), between the bounds of ``utils._sphere_bounds``.  ``cam_pose``: the camera in the object's frame
+    (3, 4), on the GPU.  Returns ``RayHits``: depth and width in metres along the unit view direction, normals in the object's frame
+    (``to_object_frame(direction=True)``), shaped (H, W[, 3]) for a grid and (n[, 3]) for listed pixels.  Gradients reach ``cam_pose``
+    through the ray operators and ``shapecode`` through ``ray_surface``; the bounds are detached, as in the render paths."""
+    scale = _frame_scale(obj_diag, family)
+    _gpu(cam_pose, "cam_pose")
+    if pixels is not None:
+        rays_o, viewdir = U.get_rays_specified(K, cam_pose, pixels[0], pixels[1])
+        shape = (rays_o.shape[0],)
+    else:
+        steps = None if im_sz is None else [int(im_sz), int(im_sz)]
+        rays_o, viewdir = U.get_rays(K, cam_pose, roi, uv_steps=steps)
+        x0, y0, x1, y1 = [int(v) for v in roi]
+        shape = (int(im_sz), int(im_sz)) if im_sz is not None else (y1 - y0, x1 - x0)
+    near, far = U._sphere_bounds(cam_pose, obj_diag)
+    o = to_decoder_frame(rays_o, obj_diag, family, shapenet_obj_cood, kitti2nusc)
+    d = to_decoder_frame(viewdir, obj_diag, family, shapenet_obj_cood, kitti2nusc, direction=True)
+    hits = ray_surface(model, o, d, near / scale, far / scale, shapecode, level=level, n_samples=n_samples, refine=refine)
+    normal = to_object_frame(hits.normal, obj_diag, family, shapenet_obj_cood, kitti2nusc, direction=True)
+    return RayHits((hits.depth * scale).view(shape), hits.state.view(shape), normal.view(*shape, 3), (hits.width * scale).view(shape))
 
 
 def quantize_colors(colors):

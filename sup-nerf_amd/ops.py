@@ -965,6 +965,131 @@ class IsoVerticesLatent(torch.autograd.Function):
         return d_lat, None, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------ ray-cast surfaces
+def _ray_shapes(rays_o, rays_d, *per_ray):
+    """R of rays_o, rays_d (R, 3) and any number of per-ray (R,) tensors: the sizes the ray kernels index by."""
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or tuple(rays_d.shape) != tuple(rays_o.shape):
+        raise SnrError(f"rays_o and rays_d must both be (R, 3), got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
+    R = rays_o.shape[0]
+    for t in per_ray:
+        if tuple(t.shape) != (R,):
+            raise SnrError(f"a per-ray tensor of {R} rays must be ({R},), got {tuple(t.shape)}")
+    return R
+
+
+def ray_march_points(rays_o, rays_d, ta, tb, n_samples):
+    """The (R n_samples, 3) point list of the march of [ta, tb] (R,) along rays_o + t rays_d (R, 3), ray-major: t_k = ta + step k with
+    step = (tb - ta) / (n_samples - 1), the last sample tb itself (``snr_ray_march_points``)."""
+    R, dev = _ray_shapes(rays_o, rays_d, ta, tb), rays_o.device
+    if n_samples < 2:
+        raise SnrError(f"a march takes at least 2 samples, got {n_samples}")
+    xyz = torch.empty(R * n_samples, 3, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_ray_march_points(_ptr(rays_o), _ptr(rays_d), _ptr(ta), _ptr(tb), R, n_samples, _ptr(xyz), _stream(dev)),
+              "snr_ray_march_points")
+    return xyz
+
+
+def ray_first_crossing(sigmas, ta, tb, level, va=None, vb=None, state=None):
+    """The first crossing of ``level`` (outside -> inside, inside iff sigma >= level) in sigmas (R, S), the densities of the march of
+    [ta, tb]; ``ta`` and ``tb`` (R,) are replaced IN PLACE by the crossing's bracket (``snr_ray_first_crossing``).  Without ``state``
+    this is the first march: it decides state (R,) uint8 (2 starts inside, 1 crossing, 0 miss) and rays of state 0 / 2 get the dummy
+    interval [ta, ta], va = vb = 0.  With ``state`` (and ``va``, ``vb``) it is a refinement: only state-1 rays change.  Returns
+    (ta, tb, va, vb, state)."""
+    if sigmas.dim() != 2 or not sigmas.is_contiguous() or tuple(ta.shape) != (sigmas.shape[0],) or tuple(tb.shape) != tuple(ta.shape):
+        raise SnrError(f"ray_first_crossing takes dense sigmas (R, S) and ta, tb (R,), got {tuple(sigmas.shape)}, {tuple(ta.shape)}, "
+                       f"{tuple(tb.shape)}")
+    R, S = sigmas.shape
+    dev = sigmas.device
+    first = state is None
+    if first:
+        va, vb = torch.empty(R, device=dev), torch.empty(R, device=dev)
+        state = torch.empty(R, dtype=torch.uint8, device=dev)
+    elif va is None or vb is None or any(tuple(t.shape) != (R,) for t in (va, vb, state)):
+        raise SnrError("a refinement march takes the va, vb and state (R,) of the march before it")
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_ray_first_crossing(_ptr(sigmas), R, S, level, int(first), _ptr(ta), _ptr(tb), _ptr(va), _ptr(vb),
+                                                _ptr(state, torch.uint8), _stream(dev)), "snr_ray_first_crossing")
+    return ta, tb, va, vb, state
+
+
+def ray_hit_points(rays_o, rays_d, ta, tb, va, vb, state, level):
+    """(depth (R,), width (R,), x (R, 3)) of the final brackets (``snr_ray_hit_points``): depth = ta + (level - va) / (vb - va) (tb - ta)
+    and width = tb - ta on state 1; depth = ta (the near bound), width 0 on state 2; both 0 on state 0; x = rays_o + depth rays_d."""
+    R, dev = _ray_shapes(rays_o, rays_d, ta, tb, va, vb, state), rays_o.device
+    depth, width, xyz = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, 3, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_ray_hit_points(_ptr(rays_o), _ptr(rays_d), _ptr(ta), _ptr(tb), _ptr(va), _ptr(vb), _ptr(state, torch.uint8), R,
+                                            level, _ptr(depth), _ptr(width), _ptr(xyz), _stream(dev)), "snr_ray_hit_points")
+    return depth, width, xyz
+
+
+def ray_brackets(rays_o, rays_d, near, far, latent, packed, level, n_samples, levels, refine_samples, shape_blocks, texture_blocks):
+    """The search of ``RaySurface``: the first march of [near, far] with ``n_samples`` samples, then ``levels`` marches of the brackets
+    with ``refine_samples``; each march is ``ray_march_points`` -> ``density_fwd`` -> ``ray_first_crossing``.  Returns
+    (ta, tb, va, vb, state); nothing is read back to the host."""
+    ta, tb = near.clone(), far.clone()
+    va = vb = state = None
+    for S in (n_samples,) + (refine_samples,) * levels:
+        xyz = ray_march_points(rays_o, rays_d, ta, tb, S)
+        sig, _ = density_fwd(xyz, latent, packed, shape_blocks, texture_blocks)
+        ta, tb, va, vb, state = ray_first_crossing(sig.view(-1, S), ta, tb, level, va, vb, state)
+    return ta, tb, va, vb, state
+
+
+class RaySurface(torch.autograd.Function):
+    """Along each of R = B n rays (object-major over the B objects of ``latent``), the first point where the density rises through
+    ``level``: (depth (R,), state (R,) uint8, normal (R, 3), width (R,)).  Forward: ``ray_brackets``, ``ray_hit_points``, then the density
+    forward (saving its ReLU bits) and backward (d sigma = 1) at the hit points x: g = grad sigma(x), normal = -g / |g| on state 1.
+    Backward of the depth by the implicit function theorem on sigma(o + t d; code) = level at x: with slope = g . d and
+    c = -d_depth / slope on state 1, 0 elsewhere: d rays_o = c g, d rays_d = t c g, d latent = ``density_bwd(d_sig = c)`` on the saved bits.
+    With a latent gradient to form, the hit points of every object are padded to a multiple of 64 as ``DensityPoints`` pads.  ``near``,
+    ``far`` and ``level`` get no gradient, nor does the topology (which crossing is first, hit or miss); nothing is clamped on a grazing ray."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, near, far, latent, packed, level, n_samples, levels, refine_samples, shape_blocks, texture_blocks):
+        _need_gpu(rays_o, rays_d, near, far, latent, packed)
+        o, d, latent = _f32c(rays_o.detach()), _f32c(rays_d.detach()), _f32c(latent.detach())
+        R, B = o.shape[0], latent.shape[0]
+        if R % B:
+            raise SnrError(f"{R} rays do not split evenly over {B} objects")
+        sb, tb = shape_blocks, texture_blocks
+        br = ray_brackets(o, d, _f32c(near.detach()), _f32c(far.detach()), latent, packed, level, n_samples, levels, refine_samples, sb, tb)
+        state = br[4]
+        t, width, x = ray_hit_points(o, d, *br, level)
+        n = R // B
+        n_pad = -(-n // 64) * 64 if (ctx.needs_input_grad[4] and sb + tb > 0 and n % 64) else 0
+        if n_pad:
+            x = _pad_rows(x, B, n, n_pad)
+        sig, masks = density_fwd(x, latent, packed, sb, tb, save_masks=True)
+        _, g = density_bwd(x, latent, packed, masks, sig, torch.ones_like(sig), sb, tb, need_latent=False)
+        if n_pad:
+            g = _unpad_rows(g, B, n, n_pad)
+        hit = state == 1
+        norm = g.norm(dim=1, keepdim=True)
+        good = hit[:, None] & torch.isfinite(norm) & (norm > 0)
+        normal = torch.where(good, -g / torch.where(good, norm, torch.ones_like(norm)), torch.zeros_like(g))
+        if any(ctx.needs_input_grad[i] for i in (0, 1, 4)):
+            slope = g[:, 0] * d[:, 0] + g[:, 1] * d[:, 1] + g[:, 2] * d[:, 2]
+            ctx.save_for_backward(d, t, g, slope, hit, x, latent, packed, masks, sig)
+            ctx.cfg = (sb, tb, B, n, n_pad)
+        ctx.mark_non_differentiable(state, normal, width)
+        return t, state, normal, width
+
+    @staticmethod
+    def backward(ctx, d_t, _d_state, _d_normal, _d_width):
+        d, t, g, slope, hit, x, latent, packed, masks, sig = ctx.saved_tensors
+        sb, tb, B, n, n_pad = ctx.cfg
+        c = torch.where(hit, -_f32c(d_t) / slope, torch.zeros_like(t))
+        d_o = c[:, None] * g if ctx.needs_input_grad[0] else None
+        d_d = (t * c)[:, None] * g if ctx.needs_input_grad[1] else None
+        d_lat = None
+        if ctx.needs_input_grad[4]:
+            d_lat, _ = density_bwd(x, latent, packed, masks, sig, _pad_rows(c, B, n, n_pad) if n_pad else c, sb, tb,
+                                   need_latent=True, need_xyz=False)
+        return d_o, d_d, None, None, d_lat, None, None, None, None, None, None, None
+
+
 def weight_grad(G, n_out, X, n_in, want_bias=True, out=None, ws=None, precision="fp32"):
     """dW (n_out, n_in) = G[:, :n_out]^T X[:, :n_in] and db (n_out,) = column sums of G, one split-K MFMA launch + one reduction
     (include/supnerf_hip.h: snr_weight_grad).  G, X: 2-D fp32 row-major views (a column slice of a wider buffer is fine).  ``out``:
