@@ -570,8 +570,6 @@ __global__ void __launch_bounds__(256) reduce_tiles_kernel(const float* __restri
 using namespace snr;
 
 // ============================================================================ C ABI
-int snr_bf16_pack_(const float* const* W, int sb, int tb, float* packed, void* stream_);   // snr_bf16.hip
-
 static thread_local const char* g_last_err = "";
 int snr_check_launch_(void) {
     hipError_t e = hipGetLastError();
@@ -586,7 +584,7 @@ int snr_abi_version(void) { return SNR_ABI_VERSION; }
 const char* snr_last_hip_error(void) { return g_last_err; }
 
 size_t snr_packed_bytes(int sb, int tb) {
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS) return 0;
+    if (!blocks_ok(sb, tb)) return 0;
     return (size_t)make_layout(sb, tb).total * sizeof(float);
 }
 
@@ -598,7 +596,7 @@ static inline int grid_for(long long total, int block = 256, int cap = 4096) {
 }
 
 int snr_pack_weights(const float* const* t, int n_tensors, int sb, int tb, float* packed, void* stream_) {
-    if (!t || !packed || sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS) return SNR_E_ARG;
+    if (!t || !packed || !blocks_ok(sb, tb)) return SNR_E_ARG;
     if (n_tensors != 2 * (sb + tb + 6)) return SNR_E_SHAPE;
     for (int i = 0; i < n_tensors; ++i) if (!t[i]) return SNR_E_ARG;
     hipStream_t st = (hipStream_t)stream_;
@@ -615,7 +613,6 @@ int snr_pack_weights(const float* const* t, int n_tensors, int sb, int tb, float
     int i_tex[MAX_BLOCKS]; for (int j = 0; j < tb; ++j) i_tex[j] = ti++;
     const int i_rgb0 = ti++;
     const int i_rgb2 = ti++;
-    const long long c256 = 256 * KC;
 
     // ---- forward stream
     float* f = packed + L.fwd;
@@ -645,7 +642,6 @@ int snr_pack_weights(const float* const* t, int n_tensors, int sb, int tb, float
     for (int j = sb - 1; j >= 0; --j) bwd(Wp(i_shape[j]), 256, 256, 256);
     bwd(Wp(i_xyz), 256, D_XYZ, K_XYZ_PAD);
     if (b - (packed + L.bwd) != L.bwd_floats) return SNR_E_SHAPE;
-    (void)c256;
 
     // ---- vectors
     auto vec = [&](const float* src, int n, long long off, int n_pad) {
@@ -761,7 +757,7 @@ int snr_encode_fwd(const snr_render_args* a, float* xyz, float* viewdir, float* 
 
 }  // extern "C"
 
-// shared with snr_mlp.hip
+// ---- shared with the other translation units (snr_host.hpp)
 int snr_fill_geom_(const snr_render_args* a, snr::RayGeom* g, int need_model) {
     if (!a || !a->rays_o || !a->rays_d) return SNR_E_ARG;
     if (a->n_rays < 0 || a->n_samples < 1 || a->z_mode < 0 || a->z_mode > SNR_Z_BOX) return SNR_E_ARG;
@@ -771,11 +767,10 @@ int snr_fill_geom_(const snr_render_args* a, snr::RayGeom* g, int need_model) {
         if (a->n_samples & (a->n_samples - 1)) return SNR_E_UNSUPPORTED;
     } else if (!a->t_vals || !a->xyz_div) return SNR_E_ARG;
     if ((a->flags & SNR_METRIC_Z) && !a->z_scale) return SNR_E_ARG;
-    if (a->rays_per_obj < 1 || (a->n_rays % a->rays_per_obj) != 0) return SNR_E_SHAPE;
+    if (!objects_ok(a->n_rays, a->rays_per_obj)) return SNR_E_SHAPE;
     if (need_model) {
         if (!a->latent || !a->packed) return SNR_E_ARG;
-        if (a->shape_blocks < 0 || a->texture_blocks < 0 || a->shape_blocks > snr::MAX_BLOCKS || a->texture_blocks > snr::MAX_BLOCKS)
-            return SNR_E_ARG;
+        if (!blocks_ok(a->shape_blocks, a->texture_blocks)) return SNR_E_ARG;
     }
     g->rays_o = a->rays_o; g->rays_d = a->rays_d; g->t_vals = a->t_vals; g->xyz_div = a->xyz_div; g->z_scale = a->z_scale;
     for (int i = 0; i < 9; ++i) g->m[i] = a->frame[i];
@@ -785,7 +780,6 @@ int snr_fill_geom_(const snr_render_args* a, snr::RayGeom* g, int need_model) {
     return SNR_OK;
 }
 
-// scratch needed behind the [obj][tiles][cols] partials for the reduction tree (floats)
 long long snr_reduce_scratch_floats_(long long tiles_per_obj, int n_lat, long long n_obj) {
     const long long lvl1 = (tiles_per_obj + snr::RED_CHUNK - 1) / snr::RED_CHUNK;
     const long long lvl2 = (lvl1 + snr::RED_CHUNK - 1) / snr::RED_CHUNK;

@@ -1,5 +1,5 @@
 // The lattice and Kuhn-edge rules of the geometry kernels (snr_iso.hip, snr_iso_grad.hip, snr_band.hip; the density entry points of
-// snr_mlp16.hip use the host part), stated once.  The specification is include/supnerf_hip.h ("Geometry", "Narrow band", "Iso-surface
+// snr_decoder.hip use the host part), stated once.  The specification is include/supnerf_hip.h ("Geometry", "Narrow band", "Iso-surface
 // backward").  Functions only, no __constant__ object: a table here would be copied into every code object that includes the header.
 //
 //   * a grid of n0 x n1 x n2 points per object, x-major (z fastest): point (i, j, k) has the linear index v = (i n1 + j) n2 + k;

@@ -245,66 +245,8 @@ decoder_train_fwd_kernel(DecoderIO io, Layout L, const float* __restrict__ xyz, 
 
 using namespace snr;
 
-int snr_bf16_supported_(int sb, int tb, long long points_per_obj);
-int snr_bf16_launch_fwd_(int mode, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
-                         float* depth, float* acc, void* stream_);
-// The exact-fp32 forward runs on the two-waves-per-SIMD kernel of snr_mlp16.hip (v_mfma_f32_16x16x4_f32, 16 points per wave: round 4).  This
-// file's one-wave-per-SIMD kernel (v_mfma_f32_32x32x2_f32, rounds 1-3) serves only the TRAINING forward of the exact-fp32 step (activation
-// dumps staged through LDS).
-int snr_fp32_fwd16_launch_(int mode, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
-                           float* depth, float* acc, void* stream_);
-
-extern "C" {
-
-int snr_precision_supported(int precision, int sb, int tb, int64_t points_per_obj) {
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS) return 0;
-    if (precision == SNR_FP32) return 1;
-    if (precision == SNR_BF16X3) return snr_bf16_supported_(sb, tb, points_per_obj);
-    return 0;
-}
-
-int snr_decoder_fwd(const float* xyz, const float* viewdir, const float* latent, const float* packed, int64_t n_points,
-                    int64_t points_per_obj, int sb, int tb, float* sigmas, float* rgbs, void* relu_masks, float* activations, int precision,
-                    void* stream_) {
-    if (!xyz || !viewdir || !latent || !packed) return SNR_E_ARG;
-    if (activations && !relu_masks) return SNR_E_ARG;                         /* training dumps go with the ReLU bits */
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
-    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
-    if (n_points == 0) return SNR_OK;
-    DecoderIO io{packed, latent, sb, tb, (long long)n_points, (long long)points_per_obj, sigmas, rgbs, (uint4*)relu_masks, activations, false};
-    RayGeom g{};
-    const Layout L = make_layout(sb, tb);
-    if (precision == SNR_BF16X3) {
-        if (!snr_bf16_supported_(sb, tb, points_per_obj)) return SNR_E_UNSUPPORTED;
-        return snr_bf16_launch_fwd_(0, io, L, xyz, viewdir, g, nullptr, nullptr, nullptr, stream_);
-    }
-    if (precision != SNR_FP32) return SNR_E_ARG;
-    // (training dumps stay on this file's kernel: its LDS-staged dump stores write whole cache lines, 13.9 against 14.2 ms per fp32 step)
-    if (!activations) return snr_fp32_fwd16_launch_(0, io, L, xyz, viewdir, g, nullptr, nullptr, nullptr, stream_);
-    const unsigned grid = (unsigned)((n_points + 127) / 128);
+int snr_fp32_train_fwd_launch_(const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, void* stream_) {
+    const unsigned grid = (unsigned)((io.n_points + 127) / 128);
     decoder_train_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir);
     return snr_check_launch_();
 }
-
-int snr_render_fwd(const snr_render_args* a, float* rgb, float* depth, float* acc_trans, float* sigmas, float* rgbs,
-                   void* relu_masks, void* stream_) {
-    RayGeom g;
-    int rc = snr_fill_geom_(a, &g, 1);
-    if (rc != SNR_OK) return rc;
-    if (!rgb || !depth || !acc_trans) return SNR_E_ARG;
-    if (a->n_samples > 128 || (128 % a->n_samples) != 0) return SNR_E_UNSUPPORTED;
-    if (a->n_rays == 0) return SNR_OK;
-    const long long P = a->n_rays * a->n_samples;
-    DecoderIO io{a->packed, a->latent, a->shape_blocks, a->texture_blocks, P, a->rays_per_obj * a->n_samples, sigmas, rgbs,
-                 (uint4*)relu_masks, nullptr, false};
-    io.latent_bias = a->latent_bias;
-    const Layout L = make_layout(a->shape_blocks, a->texture_blocks);
-    if (a->precision == SNR_BF16X3) {
-        if (!snr_bf16_supported_(a->shape_blocks, a->texture_blocks, a->rays_per_obj * a->n_samples)) return SNR_E_UNSUPPORTED;
-        return snr_bf16_launch_fwd_(1, io, L, nullptr, nullptr, g, rgb, depth, acc_trans, stream_);
-    }
-    if (a->precision != SNR_FP32) return SNR_E_ARG;
-    return snr_fp32_fwd16_launch_(1, io, L, nullptr, nullptr, g, rgb, depth, acc_trans, stream_);
-}
-
-}  // extern "C"

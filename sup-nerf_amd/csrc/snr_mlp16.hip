@@ -17,7 +17,7 @@
 //     of the EXISTING packed image (row-major 128-byte rows, 16-byte slots XOR-swizzled by (row >> 1) & 7) and the 64 lanes' reads are
 //     bank-conflict free on it (checked for all four ds_read_b128 lane groups), so snr_pack_weights is unchanged.
 //   * Layers run k-outer over the previous layer's tiles: input tile T of layer l + 1 is made from accumulator tile T of layer l
-//     (ReLU, latent add, ReLU bits, optional activation dump) just before its 64 MFMAs; two accumulator sets (previous layer's
+//     (ReLU, latent add, ReLU bits) just before its 64 MFMAs; two accumulator sets (previous layer's
 //     values, current sums: 64 + 64 registers), the last k-step deposits the finished tiles in the dead previous set.
 //   * One 32 KiB weight chunk (32 k) = two input tiles = 128 MFMAs per wave; ring of two buffers, one barrier per chunk as before.
 //
@@ -27,7 +27,6 @@
 #include <atomic>
 
 #include "snr_mlp16_core.hpp"
-#include "snr_grid.hpp"
 #include "snr_host.hpp"
 
 namespace snr {
@@ -38,7 +37,6 @@ struct Epi {
     const float* zlds;        // LATLDS: LDS row of the latent term added after the activation (the zero row if none)
     const float* zglb;        // !LATLDS: this lane's global latent row, or null
     float hi;                 // +inf, opaque (made once per kernel): the upper bound of the ReLU's v_med3
-    float* dump;              // training: this lane's row of the activation dump ([point][256] + 4 g), or null
 };
 struct EpiRegs { f32x4 z; };          // what a tile's epilogue reads from LDS, requested a tile ahead
 
@@ -80,7 +78,7 @@ __device__ __forceinline__ void acc_from_bias(f32x4 (&acc)[16], const float* bia
 // extra chunk behind the eight, the merge of the two ends of the layer cost 48 spilled registers).  On entry the layer's first chunk
 // (the direction chunk if `pre`) is in the current buffer; at its last chunk the layer requests `next_first` (next_rows rows; 0 = the
 // stream ends).  On return accP holds this layer's sums (bias included, no activation yet).
-template <int NT, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
+template <int NT, int WAVES, bool LATLDS, bool MASKS>
 __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, float* lds, const float* bias, const Epi& c, int g, const Dma16& dm,
                                                const float* base, bool pre, const f32x4 (&xe)[2], const float* next_first, int next_rows,
                                                uint32_t (&mw)[4]) {
@@ -110,7 +108,6 @@ __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, 
     uint32_t m16 = 0u;
 #pragma unroll
     for (int r = 3; r >= 0; --r) epi_value<MASKS>(accP[0], xa, c, e, r, m16);
-    if (DUMP) *reinterpret_cast<f32x4*>(c.dump) = xa;
 #pragma unroll
     for (int ch = 0; ch < 8; ++ch) {
         const float* src = (ch < 7) ? base + (ch + 1) * chunk_floats : next_first;
@@ -125,7 +122,6 @@ __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, 
             if (gi % PSTEP == 0 && (gi / PSTEP) * 8 * WAVES < rows) chunk_piece16<WAVES>(dm, src, dst, lds, rows, gi / PSTEP);
 #pragma unroll
             for (int k = (gi * 4) / NG; k < ((gi + 1) * 4) / NG; ++k) epi_value<MASKS>(accP[2 * ch + 1], xb, c, e, 3 - k, m16);
-            if (DUMP && gi == NG - 1) *reinterpret_cast<f32x4*>(c.dump + 16 * (2 * ch + 1)) = xb;
         });
         if (ch & 1) { mw[ch >> 1] = m16; m16 = 0u; }
         // second tile (T = 2 ch + 1) on xb; between its groups: tile 2 ch + 2's operand (the next chunk's first tile)
@@ -136,7 +132,6 @@ __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, 
                 if (gi == 0) e = epi_load<LATLDS>(c, 2 * ch + 2, g);
 #pragma unroll
                 for (int k = (gi * 4) / NG; k < ((gi + 1) * 4) / NG; ++k) epi_value<MASKS>(accP[2 * ch + 2], xa, c, e, 3 - k, m16);
-                if (DUMP && gi == NG - 1) *reinterpret_cast<f32x4*>(c.dump + 16 * (2 * ch + 2)) = xa;
             });
         }
         ring_turn(ring);
@@ -169,16 +164,10 @@ __device__ __forceinline__ void store_masks16x4(uint4* __restrict__ dst /* tile'
 #define SNR16_STAMP_HWID(i) do {} while (0)
 #endif
 
-// Where a launch's points come from: modes 0 and 2 read xyz, mode 1 makes them on rays (RayGeom), mode 3 on a lattice, mode 4 in listed
-// bricks of a lattice.
+// the kernel argument that says where a launch's points come from (the modes: snr_host.hpp)
 template <int MODE> struct PointSrc { using T = RayGeom; };
-template <> struct PointSrc<3> { using T = snr_lattice; };
-struct BrickSrc {
-    snr_lattice lat;
-    const int* bricks;           // (n_bricks, 4) int32: object, I, J, K -- brick (I, J, K) owns the points [8I, 8I+8) x [8J, 8J+8) x [8K, 8K+8)
-    long long n_objects;
-};
-template <> struct PointSrc<4> { using T = BrickSrc; };
+template <> struct PointSrc<MODE_LATTICE> { using T = snr_lattice; };
+template <> struct PointSrc<MODE_BRICKS> { using T = BrickSrc; };
 
 // MODE 0: explicit points; 1: fused render; 2 and 3: density only (explicit points; points of a lattice, object-major, x-major / z fastest):
 // the same chain up to the density head -- same instructions, so the same sigma bit for bit -- and nothing after it: no view direction, no
@@ -186,7 +175,7 @@ template <> struct PointSrc<4> { using T = BrickSrc; };
 // the ReLU bits of enc_xyz and the shape layers go to their slots of the full forward's layout; the texture-branch slots are not written.
 // MODE 4: density only on listed bricks of a lattice (snr_density_bricks): 512 points per brick, so every workgroup (64 or 128 points) lies in
 // one brick and belongs to that brick's object; mode 3's coordinates, a scattered store into the (B, n0, n1, n2) grid.
-template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
+template <int MODE, int WAVES, bool LATLDS, bool MASKS>
 __global__ void __launch_bounds__(WAVES * 64, 2)
 decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__ xyz, const float* __restrict__ viewdir, typename PointSrc<MODE>::T gm,
                      float* __restrict__ out_rgb, float* __restrict__ out_depth, float* __restrict__ out_acc) {
@@ -347,9 +336,6 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     float o_sigma = 0.f;
     float pos_inf = __builtin_inff();
     asm volatile("" : "+v"(pos_inf));          // (opaque: a literal +inf in v_med3 would be rewritten as canonicalise + v_max, per value)
-    // training dumps: a lane past the end holds the LAST point (gp is clamped), i.e. the same values as that point's own lane: its stores
-    // repeat that lane's bytes at that lane's address, so no per-lane predicate (= no divergent branch per tile) is needed
-    float* const dump_lane = DUMP ? io.act + gp * 256 + 4 * g : nullptr;
     auto epi_of = [&](int lp) {          // the epilogue applied to the OUTPUT of layer lp on its way into layer lp + 1
         const int la = latent_after(lp, sb, tb);
         Epi c;
@@ -357,7 +343,6 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
         c.zlds = (la >= 0) ? lds + lo.lat + la * 256 : zero;
         c.zglb = (la >= 0) ? lat_lane + la * 256 : nullptr;
         c.hi = pos_inf;
-        c.dump = DUMP ? dump_lane + (long long)lp * io.n_points * 256 : nullptr;
         return c;
     };
     auto after_layer_input = [&](int lp) {      // ReLU bits of layer lp, collected while it was consumed
@@ -386,7 +371,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
             o_sigma = pre > 20.f ? pre : log1pf(expf(pre));
         }
         const bool end = DENS && li == li_stop;
-        layer_from_acc<16, WAVES, LATLDS, MASKS, DUMP>(accP, ring, lds, bias + li * 256, c, g, dm, layer_base(li), !DENS && li == li_view, xd,
+        layer_from_acc<16, WAVES, LATLDS, MASKS>(accP, ring, lds, bias + li * 256, c, g, dm, layer_base(li), !DENS && li == li_view, xd,
                                                        end ? nullptr : layer_first(li + 1), end ? 0 : (li == li_last) ? 128 : 256, mw);
         after_layer_input(lp);
     }
@@ -414,7 +399,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     SNR16_STAMP(4);
     {   // rgb.0: 256 -> 128
         const Epi c = epi_of(li_last);
-        layer_from_acc<8, WAVES, LATLDS, MASKS, DUMP>(accP, ring, lds, bias + (li_last + 1) * 256, c, g, dm, layer_base(li_last + 1), false, xd, nullptr, 0, mw);
+        layer_from_acc<8, WAVES, LATLDS, MASKS>(accP, ring, lds, bias + (li_last + 1) * 256, c, g, dm, layer_base(li_last + 1), false, xd, nullptr, 0, mw);
         after_layer_input(li_last);
     }
 
@@ -426,7 +411,6 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
         const float* w2 = heads + (L.rgb2_w - L.sigma_w);
         float pr = 0.f, pg = 0.f, pb = 0.f;
         uint32_t m16 = 0u, mr[4] = {0u, 0u, 0u, 0u};
-        float* const dmp = DUMP ? dump_lane + (long long)(li_last + 1) * io.n_points * 256 : nullptr;
 #pragma unroll
         for (int T = 0; T < 8; ++T) {
             const f32x4 wr = *reinterpret_cast<const f32x4*>(w2 + 16 * T + 4 * g);
@@ -442,7 +426,6 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) { pr = fmaf(wr[r], xv[r], pr); pg = fmaf(wg[r], xv[r], pg); pb = fmaf(wb[r], xv[r], pb); }
-            if (DUMP) *reinterpret_cast<f32x4*>(dmp + 16 * T) = xv;
             if ((T & 3) == 3) { mr[T >> 2] = m16; m16 = 0u; }
         }
         if (MASKS && tile_live) store_masks16x4(io.masks + (tile32 * n_relu + (n_relu - 1)) * 64, mr, wave, lane);
@@ -500,10 +483,10 @@ using namespace snr;
 //   WAVES = 8 -- 128 points per 512-thread workgroup, one per CU; both waves of a SIMD run the same program between the same barriers.
 // The workgroup's latent rows are staged in LDS when its points belong to ONE object and the table has at most LDS_LAT_ROWS rows.
 
-template <int MODE, int WAVES, bool LATLDS, bool MASKS, bool DUMP>
+template <int MODE, int WAVES, bool LATLDS, bool MASKS>
 static int launch16(const DecoderIO& io, const Layout& L, const Lds16& lo, const float* xyz, const float* viewdir, const typename PointSrc<MODE>::T& g,
                     float* rgb, float* depth, float* acc, hipStream_t st) {
-    auto kern = decoder_fwd16_kernel<MODE, WAVES, LATLDS, MASKS, DUMP>;
+    auto kern = decoder_fwd16_kernel<MODE, WAVES, LATLDS, MASKS>;
     // Dynamic LDS beyond the default cap must be granted per kernel, and (if HIP scopes the attribute per device) per device: one bit per
     // device that has it.  nn.DataParallel enters here from one host thread per device.  Two threads may both grant it; that is harmless.
     static std::atomic<uint64_t> granted{0};
@@ -525,23 +508,23 @@ static int launch16_w(int mode, const DecoderIO& io, const Layout& L, const floa
     const bool latlds = (io.points_per_obj % (WAVES * 16)) == 0 && L.n_lat <= LDS_LAT_ROWS;
     const bool masks = io.masks != nullptr;
     const Lds16 lo = make_lds16(WAVES, L.n_mfma_layers, latlds ? L.n_lat : LDS_LAT_ROWS + 1);
-#define SNR_L16(M, LL, MK, DP) launch16<M, WAVES, LL, MK, DP>(io, L, lo, xyz, viewdir, g, rgb, depth, acc, st)
-    if (mode == 0) {
-        if (latlds) return masks ? SNR_L16(0, true, true, false) : SNR_L16(0, true, false, false);
-        return masks ? SNR_L16(0, false, true, false) : SNR_L16(0, false, false, false);
+#define SNR_L16(M, LL, MK) launch16<M, WAVES, LL, MK>(io, L, lo, xyz, viewdir, g, rgb, depth, acc, st)
+    if (mode == MODE_POINTS) {
+        if (latlds) return masks ? SNR_L16(0, true, true) : SNR_L16(0, true, false);
+        return masks ? SNR_L16(0, false, true) : SNR_L16(0, false, false);
     }
-    if (latlds) return masks ? SNR_L16(1, true, true, false) : SNR_L16(1, true, false, false);
-    return masks ? SNR_L16(1, false, true, false) : SNR_L16(1, false, false, false);
+    if (latlds) return masks ? SNR_L16(1, true, true) : SNR_L16(1, true, false);
+    return masks ? SNR_L16(1, false, true) : SNR_L16(1, false, false);
 #undef SNR_L16
 }
 
 int snr_fp32_fwd16_launch_(int mode, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
                            float* depth, float* acc, void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
-    if (io.act) return SNR_E_UNSUPPORTED;          // (training dumps: snr_mlp.hip's kernel, whose dump stores are staged through LDS)
+    if (io.act) return SNR_E_UNSUPPORTED;          // (training dumps: snr_mlp.hip's kernel, whose dump stores are staged through LDS; this one has none)
     const bool lat4 = (io.points_per_obj % 64) == 0 && L.n_lat <= LDS_LAT_ROWS;
     const Lds16 lo4 = make_lds16(4, L.n_mfma_layers, lat4 ? L.n_lat : LDS_LAT_ROWS + 1);
-    const bool four = lo4.total * 4 <= 80 * 1024 && (mode == 0 || (g.S <= 64 && 64 % g.S == 0));
+    const bool four = lo4.total * 4 <= 80 * 1024 && (mode == MODE_POINTS || (g.S <= 64 && 64 % g.S == 0));
     return four ? launch16_w<4>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st) : launch16_w<8>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st);
 }
 
@@ -551,14 +534,14 @@ template <int MODE, int WAVES>
 static int launch16_dens(const DecoderIO& io, const Layout& L, const float* xyz, const typename PointSrc<MODE>::T& src, hipStream_t st) {
     const bool latlds = (io.points_per_obj % (WAVES * 16)) == 0 && L.n_lat <= LDS_LAT_ROWS;
     const Lds16 lo = make_lds16(WAVES, L.n_mfma_layers, latlds ? L.n_lat : LDS_LAT_ROWS + 1);
-    if constexpr (MODE == 2) {
+    if constexpr (MODE == MODE_DENSITY) {
         if (io.masks) {
-            if (latlds) return launch16<MODE, WAVES, true, true, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
-            return launch16<MODE, WAVES, false, true, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+            if (latlds) return launch16<MODE, WAVES, true, true>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+            return launch16<MODE, WAVES, false, true>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
         }
     }
-    if (latlds) return launch16<MODE, WAVES, true, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
-    return launch16<MODE, WAVES, false, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+    if (latlds) return launch16<MODE, WAVES, true, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
+    return launch16<MODE, WAVES, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
 }
 
 template <int MODE>
@@ -570,58 +553,20 @@ static int density_launch(const DecoderIO& io, const float* xyz, const typename 
     return four ? launch16_dens<MODE, 4>(io, L, xyz, src, st) : launch16_dens<MODE, 8>(io, L, xyz, src, st);
 }
 
-extern "C" {
+int snr_density_points_launch_(const DecoderIO& io, const float* xyz, void* stream_) { return density_launch<MODE_DENSITY>(io, xyz, RayGeom{}, stream_); }
 
-int snr_density_fwd(const float* xyz, const float* latent, const float* packed, int64_t n_points, int64_t points_per_obj, int sb, int tb,
-                    float* sigmas, void* stream_) {
-    if (!xyz || !latent || !packed || !sigmas) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
-    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
-    if (n_points == 0) return SNR_OK;
-    DecoderIO io{packed, latent, sb, tb, (long long)n_points, (long long)points_per_obj, sigmas, nullptr, nullptr, nullptr, false};
-    io.latent_bias = nullptr;
-    return density_launch<2>(io, xyz, RayGeom{}, stream_);
-}
-
-int snr_density_fwd_masks(const float* xyz, const float* latent, const float* packed, int64_t n_points, int64_t points_per_obj, int sb, int tb,
-                          float* sigmas, void* relu_masks, void* stream_) {
-    if (!xyz || !latent || !packed || !sigmas || !relu_masks) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
-    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
-    if (n_points == 0) return SNR_OK;
-    DecoderIO io{packed, latent, sb, tb, (long long)n_points, (long long)points_per_obj, sigmas, nullptr, (uint4*)relu_masks, nullptr, false};
-    io.latent_bias = nullptr;
-    return density_launch<2>(io, xyz, RayGeom{}, stream_);
-}
-
-int snr_density_bricks(const snr_lattice* lattice, int64_t n_objects, const int32_t* bricks, int64_t n_bricks, const float* latent,
-                       const float* packed, int sb, int tb, float* sigmas, void* stream_) {
-    GridDims G;
-    if (grid_check(lattice, n_objects, 1, G) != SNR_OK || !bricks || !latent || !packed || !sigmas) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_bricks < 0) return SNR_E_ARG;
-    if (n_objects == 0 || n_bricks == 0) return SNR_OK;
-    // points_per_obj = one brick: the latent staging of a single-object workgroup applies (512 is a whole number of workgroups).  A launch is
-    // 4 threads per point and HIP caps a launch below 2^32 threads: at most 2^20 bricks (2^29 points) per launch, the list taken in pieces.
-    constexpr int64_t CHUNK = 1 << 20;
-    for (int64_t off = 0; off < n_bricks; off += CHUNK) {
-        const int64_t n = n_bricks - off < CHUNK ? n_bricks - off : CHUNK;
-        DecoderIO io{packed, latent, sb, tb, (long long)n * 512, 512, sigmas, nullptr, nullptr, nullptr, false};
-        io.latent_bias = nullptr;
-        const int rc = density_launch<4>(io, nullptr, BrickSrc{*lattice, bricks + off * 4, (long long)n_objects}, stream_);
+// A launch is 4 threads per point and HIP caps a launch below 2^32 threads: at most 2^20 bricks (2^29 points) per launch, the list taken in pieces.
+int snr_density_bricks_launch_(const DecoderIO& io_, const BrickSrc& src, long long n_bricks, void* stream_) {
+    constexpr long long CHUNK = 1 << 20;
+    for (long long off = 0; off < n_bricks; off += CHUNK) {
+        const long long n = n_bricks - off < CHUNK ? n_bricks - off : CHUNK;
+        DecoderIO io = io_;
+        io.n_points = n * 512;
+        const int rc = density_launch<MODE_BRICKS>(io, nullptr, BrickSrc{src.lat, src.bricks + off * 4, src.n_objects}, stream_);
         if (rc != SNR_OK) return rc;
     }
     return SNR_OK;
 }
 
-int snr_density_grid(const snr_lattice* lattice, int64_t n_objects, const float* latent, const float* packed, int sb, int tb, float* sigmas,
-                     void* stream_) {
-    GridDims G;
-    if (grid_check(lattice, n_objects, 1, G) != SNR_OK || !latent || !packed || !sigmas) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS) return SNR_E_ARG;
-    if (n_objects == 0) return SNR_OK;
-    DecoderIO io{packed, latent, sb, tb, (long long)n_objects * G.nv, G.nv, sigmas, nullptr, nullptr, nullptr, false};
-    io.latent_bias = nullptr;
-    return density_launch<3>(io, nullptr, *lattice, stream_);
-}
-
-}  // extern "C"
+// (the launchers stay in this order: it is the order of the kernels in the code object)
+int snr_density_lattice_launch_(const DecoderIO& io, const snr_lattice& lattice, void* stream_) { return density_launch<MODE_LATTICE>(io, nullptr, lattice, stream_); }

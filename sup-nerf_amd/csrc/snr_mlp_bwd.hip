@@ -1,4 +1,5 @@
-// Backward of the fused decoder / render kernels for gfx950.
+// Backward of the fused decoder / render kernels for gfx950, one wave per SIMD: the exact-fp32 backward with training dumps, of rays longer
+// than 64 points and of objects of 32 but not 64 points (the choice is made in snr_decoder.hip).
 //
 // Same structure as the forward (snr_mlp.hip): one workgroup = 4 waves = 128 sample points, gradients
 // stay in registers in the MFMA accumulator layout, and every layer is one transposed product
@@ -345,146 +346,11 @@ decoder_bwd_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const floa
 
 using namespace snr;
 
-int snr_launch_reduce_latent_(const float* partial, float* scratch, long long tiles_per_obj, int n_lat, long long n_obj, float* d_latent,
-                              void* stream);
-long long snr_reduce_scratch_floats_(long long tiles_per_obj, int n_lat, long long n_obj);
-int snr_bf16_supported_(int sb, int tb, long long points_per_obj);
-int snr_bf16_launch_bwd_(int mode, const BwdIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, void* stream_);
-// snr_mlp16_bwd.hip: the exact-fp32 backward with two waves per SIMD (16-point wave tiles)
-int snr_fp32_bwd16_supported_(int mode, const BwdIO& io, const RayGeom& g);
-int snr_fp32_bwd16_launch_(int mode, const BwdIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, void* stream_);
-
-// workspace = partial latent gradients [tiles][n_lat][256] + the reduction tree's scratch; sized for the smallest tile any kernel
-// writes a row for (32 points: a wave tile of the 32x32 kernels; snr_mlp16_bwd.hip writes one row per 64-point workgroup)
-static size_t bwd_ws_bytes(int64_t n_points, int64_t points_per_obj, int sb, int tb) {
-    const int64_t tiles = (n_points + 31) / 32;
-    const int64_t ppo = points_per_obj > 0 ? points_per_obj : n_points;
-    const int64_t n_obj = ppo > 0 ? (n_points + ppo - 1) / ppo : 1;
-    const int64_t tree = snr_reduce_scratch_floats_((ppo + 31) / 32, sb + tb, n_obj);
-    return (size_t)((tiles * (int64_t)(sb + tb) * 256 + tree) * sizeof(float) + 256);
-}
-
-// the exact-fp32 backward: the two-waves-per-SIMD kernel where it applies (no training dumps, a ray inside 64 points, latent gradients
-// only for objects of a multiple of 64 points), else the one-wave 32x32x2 kernel of rounds 1-3.  *tile = points per partial row.
-static int launch_fp32_bwd(int mode, const BwdIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, void* stream_, int* tile) {
-    if (snr_fp32_bwd16_supported_(mode, io, g)) { *tile = 64; return snr_fp32_bwd16_launch_(mode, io, L, xyz, viewdir, g, stream_); }
-    *tile = 32;
+// one partial latent-gradient row per 32-point wave tile.  Chosen by snr_decoder.hip where the two-waves kernel (snr_mlp16_bwd.hip) does not apply.
+int snr_fp32_bwd32_launch_(int mode, const BwdIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, void* stream_) {
     const unsigned grid = (unsigned)((io.n_points + 127) / 128);
-    if (mode == 0) decoder_bwd_kernel<0><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
-    else decoder_bwd_kernel<1><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, nullptr, nullptr, g);
+    if (mode == MODE_POINTS) decoder_bwd_kernel<0><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, xyz, viewdir, g);
+    else if (mode == MODE_RENDER) decoder_bwd_kernel<1><<<grid, 256, 0, (hipStream_t)stream_>>>(io, L, nullptr, nullptr, g);
+    else return SNR_E_UNSUPPORTED;          // (density backward: snr_mlp16_bwd.hip only)
     return snr_check_launch_();
 }
-
-extern "C" {
-
-size_t snr_decoder_bwd_ws_bytes(int64_t n_points, int64_t points_per_obj, int sb, int tb) { return bwd_ws_bytes(n_points, points_per_obj, sb, tb); }
-
-int snr_decoder_bwd(const float* xyz, const float* viewdir, const float* latent, const float* packed, const void* relu_masks,
-                    const float* sigmas, const float* d_sigmas, const float* d_rgbs, int64_t n_points, int64_t points_per_obj, int sb,
-                    int tb, float* d_latent, float* d_xyz, float* d_viewdir, float* layer_grads, void* workspace, size_t ws_bytes, int precision,
-                    void* stream_) {
-    if (n_points == 0) return SNR_OK;
-    if (!xyz || !viewdir || !latent || !packed || !relu_masks || !sigmas) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
-    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
-    const bool want_lat = d_latent && (sb + tb) > 0;
-    if (want_lat) {
-        if (points_per_obj % 32) return SNR_E_UNSUPPORTED;   // a wave tile must not straddle two objects
-        if (!workspace || ws_bytes < bwd_ws_bytes(n_points, points_per_obj, sb, tb)) return SNR_E_WORKSPACE;
-    }
-    BwdIO io{};
-    io.packed = packed; io.latent = latent; io.sb = sb; io.tb = tb; io.n_points = n_points; io.points_per_obj = points_per_obj;
-    io.masks = (const uint4*)relu_masks; io.sigmas = sigmas; io.d_sigmas = d_sigmas; io.d_rgbs = d_rgbs;
-    io.partial = want_lat ? (float*)workspace : nullptr;
-    io.d_xyz = d_xyz; io.d_dir = d_viewdir;
-    io.gdump = layer_grads;
-    RayGeom g{};
-    const Layout L = make_layout(sb, tb);
-    int rc, tile = 32;
-    if (precision == SNR_BF16X3) {
-        if (!snr_bf16_supported_(sb, tb, points_per_obj)) return SNR_E_UNSUPPORTED;
-        rc = snr_bf16_launch_bwd_(0, io, L, xyz, viewdir, g, stream_);
-    } else if (precision == SNR_FP32) {
-        rc = launch_fp32_bwd(0, io, L, xyz, viewdir, g, stream_, &tile);
-    } else return SNR_E_ARG;
-    if (rc != SNR_OK) return rc;
-    if (want_lat)
-        return snr_launch_reduce_latent_(io.partial, io.partial + ((n_points + tile - 1) / tile) * (int64_t)(sb + tb) * 256, points_per_obj / tile, sb + tb,
-                                         n_points / points_per_obj, d_latent, stream_);
-    return SNR_OK;
-}
-
-// backward of snr_density_fwd: always the two-waves kernel (snr_mlp16_bwd.hip, mode 2), so the latent gradient needs whole 64-point workgroups
-int snr_density_bwd(const float* xyz, const float* latent, const float* packed, const void* relu_masks, const float* sigmas,
-                    const float* d_sigmas, int64_t n_points, int64_t points_per_obj, int sb, int tb, float* d_latent, float* d_xyz,
-                    void* workspace, size_t ws_bytes, void* stream_) {
-    if (!xyz || !latent || !packed || !relu_masks || !sigmas || !d_sigmas) return SNR_E_ARG;
-    if (sb < 0 || tb < 0 || sb > MAX_BLOCKS || tb > MAX_BLOCKS || n_points < 0) return SNR_E_ARG;
-    if (points_per_obj < 1 || (n_points % points_per_obj) != 0) return SNR_E_SHAPE;
-    if (n_points == 0) return SNR_OK;
-    const bool want_lat = d_latent && (sb + tb) > 0;
-    if (want_lat) {
-        if (points_per_obj % 64) return SNR_E_UNSUPPORTED;
-        if (!workspace || ws_bytes < bwd_ws_bytes(n_points, points_per_obj, sb, tb)) return SNR_E_WORKSPACE;
-    }
-    BwdIO io{};
-    io.packed = packed; io.latent = latent; io.sb = sb; io.tb = tb; io.n_points = n_points; io.points_per_obj = points_per_obj;
-    io.masks = (const uint4*)relu_masks; io.sigmas = sigmas; io.d_sigmas = d_sigmas;
-    io.partial = want_lat ? (float*)workspace : nullptr;
-    io.d_xyz = d_xyz;
-    const Layout L = make_layout(sb, tb);
-    const int rc = snr_fp32_bwd16_launch_(2, io, L, xyz, nullptr, RayGeom{}, stream_);
-    if (rc != SNR_OK) return rc;
-    if (want_lat)
-        return snr_launch_reduce_latent_(io.partial, io.partial + ((n_points + 63) / 64) * (int64_t)(sb + tb) * 256, points_per_obj / 64, sb + tb,
-                                         n_points / points_per_obj, d_latent, stream_);
-    return SNR_OK;
-}
-
-size_t snr_render_bwd_ws_bytes(const snr_render_args* a) {
-    if (!a) return 0;
-    return bwd_ws_bytes(a->n_rays * (int64_t)a->n_samples, a->rays_per_obj * (int64_t)a->n_samples, a->shape_blocks, a->texture_blocks);
-}
-
-int snr_render_bwd(const snr_render_args* a, const float* sigmas, const float* rgbs, const void* relu_masks, const float* d_rgb,
-                   const float* d_depth, const float* d_acc, float* d_latent, float* d_rays_o, float* d_rays_d, float* d_t,
-                   void* workspace, size_t ws_bytes, void* stream_) {
-    RayGeom g;
-    int rc = snr_fill_geom_(a, &g, 1);
-    if (rc != SNR_OK) return rc;
-    if (a->n_rays == 0) return SNR_OK;
-    if (!sigmas || !rgbs || !relu_masks) return SNR_E_ARG;
-    if (a->n_samples > 128 || (128 % a->n_samples) != 0) return SNR_E_UNSUPPORTED;
-#ifndef SNR_STAMPS      /* the diagnostic build borrows d_t as its stamp buffer */
-    if (d_t && a->z_mode != SNR_Z_PER_RAY) return SNR_E_UNSUPPORTED;
-#endif
-    const int sb = a->shape_blocks, tb = a->texture_blocks;
-    const long long P = a->n_rays * a->n_samples;
-    const long long ppo = a->rays_per_obj * a->n_samples;
-    const bool want_lat = d_latent && (sb + tb) > 0;
-    if (want_lat) {
-        if (ppo % 32) return SNR_E_UNSUPPORTED;
-        if (!workspace || ws_bytes < bwd_ws_bytes(P, ppo, sb, tb)) return SNR_E_WORKSPACE;
-    }
-    BwdIO io{};
-    io.packed = a->packed; io.latent = a->latent; io.sb = sb; io.tb = tb; io.n_points = P; io.points_per_obj = ppo;
-    io.masks = (const uint4*)relu_masks; io.sigmas = sigmas; io.rgbs = rgbs;
-    io.d_rgb = d_rgb; io.d_depth = d_depth; io.d_acc = d_acc;
-    io.partial = want_lat ? (float*)workspace : nullptr;
-    io.d_rays_o = d_rays_o; io.d_rays_d = d_rays_d; io.d_t = d_t;
-    const Layout L = make_layout(sb, tb);
-    int tile = 32;
-    if (a->precision == SNR_BF16X3) {
-        if (!snr_bf16_supported_(sb, tb, ppo)) return SNR_E_UNSUPPORTED;
-        rc = snr_bf16_launch_bwd_(1, io, L, nullptr, nullptr, g, stream_);
-    } else if (a->precision == SNR_FP32) {
-        rc = launch_fp32_bwd(1, io, L, nullptr, nullptr, g, stream_, &tile);
-    } else return SNR_E_ARG;
-    if (rc != SNR_OK) return rc;
-    if (want_lat)
-        return snr_launch_reduce_latent_(io.partial, io.partial + ((P + tile - 1) / tile) * (long long)(sb + tb) * 256, ppo / tile, sb + tb,
-                                         a->n_rays / a->rays_per_obj, d_latent, stream_);
-    return SNR_OK;
-}
-
-}  // extern "C"

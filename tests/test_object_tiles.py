@@ -2,7 +2,7 @@
 
 Every backward launch with code gradients (1) writes one row of latent-gradient partials per wave tile, (2) sums them per object in a
 deterministic tree (``snr_launch_reduce_latent_``, csrc/snr_aux.hip: chunks of RED_CHUNK = 32 tiles, one grid row per object, ping-pong
-scratch) and (3) does both in one workspace sized by ``bwd_ws_bytes`` (csrc/snr_mlp_bwd.hip) for 32-point tiles, whose tree scratch starts
+scratch) and (3) does both in one workspace sized by ``snr_decoder_bwd_ws_bytes`` (csrc/snr_decoder.hip) for 32-point tiles, whose tree scratch starts
 right behind the partials of the kernel that ran.  Every comparison here is per object: each object's (NLAT, 256) latent gradient and its
 code-gradient rows against that object's own float64 values, scaled by that object's own max, with distinct codes and distinct upstream
 weights per object -- so a row that went to a neighbour, or a tile counted twice, cannot hide behind a larger object.
@@ -10,7 +10,7 @@ weights per object -- so a row that went to a neighbour, or a tile counted twice
 Which kernel a parametrisation reaches (a change to these predicates moves the coverage below):
 * "bf16x3" (and the backward of the pair ("fp32", "bf16x3")): ``bf16_bwd16_kernel`` (csrc/snr_bf16.hip) whenever ``snr_bf16_supported_``
   holds: shape_blocks + texture_blocks <= 4 and points per object % 32 == 0.  Tile: 32 points.
-* "fp32": ``launch_fp32_bwd`` (csrc/snr_mlp_bwd.hip) takes the two-wave ``decoder_bwd16_kernel`` (csrc/snr_mlp16_bwd.hip, 64-point tiles)
+* "fp32": ``decoder_backward`` (csrc/snr_decoder.hip) takes the two-wave ``decoder_bwd16_kernel`` (csrc/snr_mlp16_bwd.hip, 64-point tiles)
   when ``snr_fp32_bwd16_supported_`` holds: no training dumps, points per object % 64 == 0 and, in render mode, S <= 64 with 64 % S == 0;
   otherwise the round-2 ``decoder_bwd_kernel`` (32-point tiles).  So in the points decoder 32, 96, 160, 32*31, 32*33, 32*1025 and the
   ragged 70 (padded to 96) are round-2 objects, and 64, 128, 32*32, 64*31..64*33, 32*1024 and the ragged 33 and 100 (padded to 64 and

@@ -15,7 +15,7 @@ the coverage):
   points per object % 32 == 0; both call ``make_sample``.  The ragged cases run without padding under no_grad ("auto" resolves to fp32).
 * backward "bf16x3" and ("fp32", "bf16x3"): ``bf16_bwd16_kernel`` -> ``ray_grad_tail`` (csrc/snr_device.hpp), always: in-wave finish for
   S in {4, 8, 16, 32}, LDS combine for S in {64, 128}.
-* backward "fp32": ``launch_fp32_bwd`` (csrc/snr_mlp_bwd.hip) takes the two-wave ``decoder_bwd16_kernel`` -> ``ray_grad_tail16``
+* backward "fp32": ``decoder_backward`` (csrc/snr_decoder.hip) takes the two-wave ``decoder_bwd16_kernel`` -> ``ray_grad_tail16``
   (csrc/snr_mlp16_bwd.hip) when points per object % 64 == 0 and S <= 64: (4, 32, 1), (4, 32, 3), (8, 32, 3), (16, 28, 1) finish in the wave
   (S <= 16), (32, 26, 3), (64, 26, 1), (64, 26, 3) combine through LDS; otherwise the round-2 ``decoder_bwd_kernel`` -> ``ray_grad_tail``:
   (4, 40, 3), (8, 28, 1), (16, 26, 3), (32, 27, 3) (points per object % 64 == 32) finish in the wave, (128, 26, 3) and (128, 9, 3) (S = 128)

@@ -2,7 +2,7 @@
 
 In training mode (``model.train_decoder_weights``, ``ops.DecoderPointsTrain``) the layer chains write every MFMA layer's input X_l (forward,
 ``activations``) and every layer's pre-activation gradient G_l (backward, ``layer_grads``); the weight gradients are G_l^T X_{l-1} from
-``ops.weight_grad``.  Four kernel instantiations serve only this path:
+``ops.weight_grad``.  Four kernel instantiations serve only this path (chosen by ``decoder_forward`` / ``decoder_backward``, csrc/snr_decoder.hip):
 * fp32: ``decoder_train_fwd_kernel`` (csrc/snr_mlp.hip; latent rows staged in LDS up to LDS_LAT_ROWS = 8, read from memory beyond) and
   ``decoder_bwd_kernel<0>`` with ``io.gdump`` (csrc/snr_mlp_bwd.hip; ``snr_fp32_bwd16_supported_`` refuses dumps);
 * split: ``bf16_fwd_kernel<0, true, false, true>`` and ``bf16_bwd16_kernel<0, true>`` (csrc/snr_bf16.hip), <= 4 blocks and whole 32-point
