@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 13
+#define SNR_ABI_VERSION 14
 
 enum {
     SNR_OK = 0,
@@ -468,6 +468,67 @@ int snr_ray_first_crossing(const float* sigmas, int64_t n_rays, int n_samples, f
                            float* vb, uint8_t* state, void* stream);
 int snr_ray_hit_points(const float* rays_o, const float* rays_d, const float* ta, const float* tb, const float* va, const float* vb,
                        const uint8_t* state, int64_t n_rays, float level, float* depth, float* width, float* xyz, void* stream);
+
+/* Mesh components: which vertices and faces of a triangle mesh hang together, and what each piece measures.  The mesh is the packed form
+ * snr_iso_emit writes, or any caller's of the same form: verts (sum V, 3) fp32 and faces (sum F, 3) int32 of n_objects objects, object
+ * after object, face indices local to their object; vert_offset, face_offset (n_objects + 1) int64 DEVICE arrays, ascending, from 0 to
+ * n_verts = sum V and n_faces = sum F: where each object's vertices / faces start (V <= 2^31 - 1 per object).
+ * tests/mesh_restatement.py restates every rule step by step.
+ *   1. Connectivity: two vertices are connected iff a chain of faces links them through shared vertex INDICES.  Equal positions do not
+ *      connect: the coincident vertices of a degenerate triangle stay distinct unless a face joins them.  A vertex no face names is a
+ *      component of its own with 0 faces.
+ *   2. Component ids are local to the object and fully determined by the mesh: component c is the one whose smallest vertex index is the
+ *      c-th smallest among the object's components (vertex 0 is always in component 0).  vert_label (sum V) int32; face_label (sum F)
+ *      int32 = the label of the face's first vertex.  The components of all objects are packed object after object too: comp_offset
+ *      (n_objects + 1) int64, component c of object b at comp_offset[b] + c.
+ *   3. Measures per component: n_verts and n_faces (int64, exact); bbox_lo, bbox_hi (C, 3) fp32, the exact min / max of its vertex
+ *      coordinates (finite coordinates; -0 and +0 count as equal); area and volume in float64: with a, b, c the face's vertices widened
+ *      to float64 and p0 the component's vertex of smallest index,
+ *          area term = |(b - a) x (c - a)| / 2,      volume term = (a - p0) . ((b - p0) x (c - p0)) / 6,
+ *      each summed over the component's faces.  The volume is signed: the iso rules wind faces counter-clockwise seen from the low side,
+ *      so a closed dense blob is positive and a closed cavity negative.  For a closed component the value does not depend on p0; for one
+ *      cut open (by the border of the grid) it is this rule's value and no more.  The sums run in a fixed order (below): two runs give
+ *      the same bits.  No floating-point atomics anywhere.
+ *   4. Selection: a subset of components gives a sub-mesh -- the kept vertices in their original order, the kept faces in their original
+ *      order, indices renumbered.  (Host policy over the labels; no kernel.)
+ *
+ * snr_mesh_hook: parent (sum V) int32 := the identity per object, then (a second launch) a lock-free union-find over the faces, one thread
+ *   per face, uniting (v0, v1) and (v0, v2): the larger root is hooked under the smaller by compare-and-swap, so at the end the root of a
+ *   component is its smallest vertex index.  Inside that launch every read of parent is an agent-scope atomic load and every update an
+ *   agent-scope compare-and-swap or atomic min (the L2s of the eight XCDs are not coherent with each other); no thread waits for another.
+ *   Every face's three indices are range-checked before use: a face with an index outside [0, V) is skipped and *bad (device int32, zeroed
+ *   by the caller) is set to 1.
+ * snr_mesh_flatten (a later launch: plain loads): root (sum V) int32 = the root above each vertex, is_root (sum V) uint8 = (root == vertex).
+ *   The caller then scans per object: root_scan = the INCLUSIVE int32 prefix sum of is_root along each object's vertices; its last entry
+ *   is the object's component count C.
+ * snr_mesh_label: vert_label[v] = root_scan[root[v]] - 1 (indices within the object), then face_label (rule 2; -1 on a bad first index).
+ * snr_mesh_boxes: comp_verts (sum C) int64, bbox_lo, bbox_hi (sum C, 3) of rule 3, by integer atomic add / min / max on order-preserving
+ *   keys of the coordinates (exact in any order).  A vertex whose label is not one of its object's components is not counted.
+ * snr_mesh_face_terms: the two float64 terms of rule 3 per face; slot i holds face order[i] (order: (sum F) int64, a permutation of the
+ *   packed face indices -- the faces sorted by component -- or NULL = as stored).  p0 = the vertex root[v0].  A face with a bad index
+ *   gives 0, 0.
+ * snr_mesh_segment_sum: area, volume (sum C) float64 from terms sorted by component: seg_start (sum C + 1) int64, component k's terms at
+ *   [seg_start[k], seg_start[k+1]).  A component's terms are cut into slabs of 4096; slab_offset (sum C + 1) int64 = the EXCLUSIVE prefix
+ *   sum of ceil(faces / 4096) per component.  Order of every sum: within a slab, thread t of 256 adds the terms t, t + 256, ... then a
+ *   binary tree over the threads (t += t + 128, t + 64, ...); per component, lane l of 64 adds its slab sums l, l + 64, ... then a
+ *   butterfly over the lanes.  partial: (n_slabs, 2) float64 scratch, n_slabs >= snr_mesh_slab_bound (= sum C + sum F / 4096), else
+ *   SNR_E_WORKSPACE.
+ * A null pointer or a negative size: SNR_E_ARG; more than 2^38 vertices, faces or components in a launch: SNR_E_UNSUPPORTED. */
+int snr_mesh_hook(const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, int64_t n_objects, int64_t n_verts,
+                  int64_t n_faces, int32_t* parent, int32_t* bad, void* stream);
+int snr_mesh_flatten(const int32_t* parent, const int64_t* vert_offset, int64_t n_objects, int64_t n_verts, int32_t* root, uint8_t* is_root,
+                     void* stream);
+int snr_mesh_label(const int32_t* root, const int32_t* root_scan, const int32_t* faces, const int64_t* vert_offset,
+                   const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, int32_t* vert_label, int32_t* face_label,
+                   void* stream);
+int snr_mesh_boxes(const float* verts, const int32_t* vert_label, const int64_t* vert_offset, const int64_t* comp_offset, int64_t n_objects,
+                   int64_t n_verts, int64_t n_comps, int64_t* comp_verts, float* bbox_lo, float* bbox_hi, void* stream);
+int snr_mesh_face_terms(const float* verts, const int32_t* faces, const int32_t* root, const int64_t* order, const int64_t* vert_offset,
+                        const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, double* area_terms,
+                        double* volume_terms, void* stream);
+int64_t snr_mesh_slab_bound(int64_t n_comps, int64_t n_faces);
+int snr_mesh_segment_sum(const double* area_terms, const double* volume_terms, const int64_t* seg_start, const int64_t* slab_offset,
+                         int64_t n_comps, int64_t n_faces, double* partial, int64_t n_slabs, double* area, double* volume, void* stream);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,13 @@ _SIGS = {
     "snr_ray_march_points": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "snr_ray_first_crossing": (C.c_int, [_P, C.c_int64, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P]),
     "snr_ray_hit_points": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
+    "snr_mesh_hook": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "snr_mesh_flatten": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "snr_mesh_label": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "snr_mesh_boxes": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "snr_mesh_face_terms": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "snr_mesh_slab_bound": (C.c_int64, [C.c_int64, C.c_int64]),
+    "snr_mesh_segment_sum": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
 }
 
 

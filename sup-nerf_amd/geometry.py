@@ -20,6 +20,11 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     from the depth to the ray origins, directions and shape codes (``ops.RaySurface``: ``snr_ray_*`` around the density launches);
   * ``surface_depth(model, cam_pose, obj_diag, K, roi, shapecode, level=...)``: the same for a camera's pixel grid or listed pixels (lidar
     returns), in metric units;
+  * ``mesh_components(meshes)``: the connected pieces of each mesh -- a component label per vertex and face and, per component, vertex and
+    face counts, bounding box, area and signed volume (``ops.mesh_components``: a lock-free union-find over the faces, ``snr_mesh_*``);
+    ``select_components(mesh, components, keep)``: the sub-mesh of some components, with the index maps back to the full mesh;
+    ``largest_component(meshes, by=..., drop_cavities=...)``: the object without its floaters (and, by default, without the closed pockets
+    inside it); ``extract_mesh(..., keep="largest")`` does it in one call;
   * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
     ``to_decoder_frame``: its inverse;
   * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
@@ -30,7 +35,9 @@ texture code (the texture rows feed nothing the density reads).  The mesh rules 
 include/supnerf_hip.h, restated in tests/iso_restatement.py.  The density backward runs the fp32 backward kernel from d sigma alone (no colour
 branch): d xyz and the shape-code gradient are bit for bit those of the full backward with a zero colour gradient.  The ray rules (march,
 first crossing, refinement, depth, implicit gradient) are the header's too, restated in tests/ray_restatement.py; a ray search reads nothing
-back to the host.  There is no CPU path: CPU tensors raise ``SnrError``."""
+back to the host.  The component rules (connectivity by vertex index, ids in the order of the smallest vertex index, float64 measures
+summed in a fixed order) are the header's as well, restated in tests/mesh_restatement.py.  There is no CPU path: CPU tensors raise
+``SnrError``."""
 from typing import NamedTuple
 
 import numpy as np
@@ -327,7 +334,7 @@ def narrow_band_grid(model, shapecode, resolution, *, level, band=0.0, bound=(-0
 
 
 def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=(-0.5, 0.5), narrow_band=False, band=0.0,
-                 differentiable=False):
+                 differentiable=False, keep=None):
     """Iso-surface {sigma = level} per object: a list of (verts (V, 3) fp32, faces (F, 3) int32) on the GPU, faces counter-clockwise
     seen from the low side (outward normals around a dense object), vertices in ``bound``'s decoder coordinates (``to_object_frame``
     maps them to the object's frame).  ``model_or_grid``: a decoder (then ``shapecode`` (B, 256) and ``resolution`` make the grid with
@@ -340,7 +347,13 @@ def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=
     grid points the surface touches only).  The derivative is that of the vertex formula at the forward's topology: topology changes
     carry no gradient, nor does ``level``; an edge whose two values nearly agree gives a large one.  Vertices and faces are the same as
     without it.  On a narrow-band grid the gradient is exact wherever its mesh equals the dense mesh (see ``narrow_band_grid``).  The
-    decoder's weights are constants: with ``model.train_decoder_weights`` set and grad mode on this raises, as ``density`` does."""
+    decoder's weights are constants: with ``model.train_decoder_weights`` set and grad mode on this raises, as ``density`` does.
+
+    ``keep="largest"``: each object's mesh is reduced to its largest connected component by area, closed pockets inside it dropped too:
+    the (verts, faces) of ``largest_component``; differentiable vertices keep their ``grad_fn``.  ``None`` (the default) returns the
+    whole iso-surface."""
+    if keep not in (None, "largest"):
+        raise SnrError(f"extract_mesh: keep is None or 'largest', got {keep!r}")
     if narrow_band and torch.is_tensor(model_or_grid):
         raise SnrError("extract_mesh(narrow_band=True) builds its grid with the decoder: pass the model and the shape codes")
     grad = bool(differentiable) and torch.is_grad_enabled()
@@ -385,7 +398,127 @@ def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=
         out.append((verts[v0:v0 + nvs[b]], faces[f0:f0 + nts[b]]))
         v0 += nvs[b]
         f0 += nts[b]
+    if keep == "largest":
+        return [(v, f) for v, f, _, _ in largest_component(out)]
     return out
+
+
+class Components(NamedTuple):
+    vert_label: torch.Tensor     # (V,) int32: the component of each vertex
+    face_label: torch.Tensor     # (F,) int32: the component of each face
+    n_verts: torch.Tensor        # (C,) int64
+    n_faces: torch.Tensor        # (C,) int64
+    area: torch.Tensor           # (C,) float64
+    volume: torch.Tensor         # (C,) float64, signed: positive for a closed dense piece, negative for a closed cavity
+    bbox_lo: torch.Tensor        # (C, 3) fp32
+    bbox_hi: torch.Tensor        # (C, 3) fp32
+
+
+def _one_or_many(meshes):
+    """(list of (verts, faces) pairs, whether the caller passed a single pair)."""
+    single = isinstance(meshes, (tuple, list)) and len(meshes) == 2 and torch.is_tensor(meshes[0])
+    return _meshes([tuple(meshes)] if single else meshes), single
+
+
+def mesh_components(meshes):
+    """The connected components of each mesh of ``meshes`` -- the list ``extract_mesh`` returns (vertices with a ``grad_fn`` are fine: the
+    analysis reads their values), or one (verts, faces) pair.  Returns one ``Components`` per object (a single one for a single pair).
+
+    Two vertices are connected iff a chain of faces links them through shared vertex indices (equal positions do not connect; a vertex no
+    face names is a component of its own with no faces).  Component ids are fully determined by the mesh: component c is the one whose
+    smallest vertex index is the c-th smallest.  ``volume`` is the signed sum of (a - p0) . ((b - p0) x (c - p0)) / 6 over the faces, p0 the
+    component's first vertex: ``extract_mesh`` winds faces counter-clockwise seen from the low side, so a closed dense blob is positive
+    and a closed cavity negative.  For a closed component the value does not depend on p0; a component the border of the grid cuts open
+    gets this formula's value and no more -- its ``bbox`` reaching ``bound`` is how to tell.  ``area`` and ``volume`` are float64 sums in a
+    fixed order (the same bits from run to run); counts and boxes are exact.
+
+    All objects go through the same launches; one host read (the component counts).  An empty mesh has C = 0.  A face index outside the
+    mesh raises ``SnrError``, as do CPU tensors."""
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    for v, f in ms:
+        if f.dtype != torch.int32:
+            raise SnrError(f"faces are int32, got {f.dtype}")
+    nvs, nfs = [v.shape[0] for v, _ in ms], [f.shape[0] for _, f in ms]
+    if len(ms) == 1:
+        verts, faces = ms[0][0].detach(), ms[0][1]
+    else:
+        verts, faces = torch.cat([v.detach().float() for v, _ in ms]), torch.cat([f for _, f in ms])
+    m = ops.mesh_components(verts, faces, nvs, nfs)
+    out, v0, f0 = [], 0, 0
+    for b in range(len(ms)):
+        c0, c1 = m.comp_offset[b], m.comp_offset[b + 1]
+        out.append(Components(m.vert_label[v0:v0 + nvs[b]], m.face_label[f0:f0 + nfs[b]], m.n_verts[c0:c1], m.n_faces[c0:c1], m.area[c0:c1],
+                              m.volume[c0:c1], m.bbox_lo[c0:c1], m.bbox_hi[c0:c1]))
+        v0 += nvs[b]
+        f0 += nfs[b]
+    return out[0] if single else out
+
+
+def _keep_mask(keep, C, dev):
+    if torch.is_tensor(keep) and keep.dtype == torch.bool:
+        if tuple(keep.shape) != (C,):
+            raise SnrError(f"a keep mask of {C} components must be ({C},), got {tuple(keep.shape)}")
+        return keep.to(dev)
+    ids = [int(i) for i in (keep.tolist() if torch.is_tensor(keep) else keep)]
+    if any(i < 0 or i >= C for i in ids):
+        raise SnrError(f"component ids must lie in [0, {C}), got {ids}")
+    mask = torch.zeros(C, dtype=torch.bool, device=dev)
+    if ids:
+        mask[torch.tensor(ids, dtype=torch.int64).to(dev)] = True
+    return mask
+
+
+def select_components(mesh, components, keep):
+    """The sub-mesh of the components ``keep`` (a bool mask (C,) or a list of ids) of ``mesh`` = (verts, faces) with its ``Components``:
+    (verts, faces, vert_index, face_index) -- the kept vertices and faces in their original order, face indices renumbered;
+    ``vert_index`` / ``face_index`` (int64) point into the original arrays, so per-vertex data of the full mesh (normals, colours) is
+    gathered with them.  ``verts`` is ``mesh[0][vert_index]``, a torch index: the ``grad_fn`` of a differentiable mesh carries through."""
+    v, f = _meshes([tuple(mesh)])[0]
+    c = components
+    if tuple(c.vert_label.shape) != (v.shape[0],) or tuple(c.face_label.shape) != (f.shape[0],):
+        raise SnrError(f"these components label {c.vert_label.shape[0]} vertices and {c.face_label.shape[0]} faces, the mesh has "
+                       f"{v.shape[0]} and {f.shape[0]}")
+    mask = _keep_mask(keep, c.n_verts.shape[0], v.device)
+    vkeep, fkeep = mask[c.vert_label.long()], mask[c.face_label.long()]
+    vert_index, face_index = torch.nonzero(vkeep).view(-1), torch.nonzero(fkeep).view(-1)
+    renumber = torch.cumsum(vkeep, 0, dtype=torch.int32) - 1
+    faces = renumber[f[face_index].long()].view(-1, 3)
+    return v[vert_index], faces, vert_index, face_index
+
+
+def largest_keep(components, by="area", drop_cavities=True):
+    """The (C,) bool mask ``largest_component`` keeps: the component with the most area (``by="area"``), the largest |volume|
+    (``"volume"``) or the most faces (``"faces"``), ties to the lowest id; with ``drop_cavities=False`` also every component of negative
+    volume whose bounding box lies inside the winner's."""
+    if by not in ("area", "volume", "faces"):
+        raise SnrError(f"by is 'area', 'volume' or 'faces', got {by!r}")
+    c = components
+    score = {"area": c.area, "volume": c.volume.abs(), "faces": c.n_faces}[by]
+    mask = torch.zeros(score.shape[0], dtype=torch.bool, device=score.device)
+    if score.shape[0] == 0:
+        return mask
+    w = torch.nonzero(score == score.max()).view(-1)[:1]                      # (the lowest id among equals)
+    mask[w] = True
+    if not drop_cavities:
+        inside = (c.bbox_lo >= c.bbox_lo[w]).all(1) & (c.bbox_hi <= c.bbox_hi[w]).all(1)
+        mask |= inside & (c.volume < 0)
+    return mask
+
+
+def largest_component(meshes, by="area", drop_cavities=True):
+    """Each object's mesh without its floaters: ``select_components`` of the component ``largest_keep`` picks, per object of ``meshes``
+    (the list ``extract_mesh`` returns, or one pair -> one tuple).  ``drop_cavities=True`` keeps that component alone, so closed pockets of
+    low density inside the body go too; ``False`` keeps them (negative volume, bounding box inside the winner's)."""
+    if by not in ("area", "volume", "faces"):
+        raise SnrError(f"by is 'area', 'volume' or 'faces', got {by!r}")
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    comps = mesh_components(ms)
+    out = [select_components(m, c, largest_keep(c, by, drop_cavities)) for m, c in zip(ms, comps)]
+    return out[0] if single else out
 
 
 def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False, direction=False):

@@ -965,6 +965,108 @@ class IsoVerticesLatent(torch.autograd.Function):
         return d_lat, None, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------ mesh components
+MESH_SLAB = 4096         # faces per slab of the fixed-order float64 sums (include/supnerf_hip.h: snr_mesh_segment_sum)
+
+
+class MeshComponents(NamedTuple):
+    vert_label: torch.Tensor   # (sum V,) int32: component of each vertex, local to its object
+    face_label: torch.Tensor   # (sum F,) int32: component of each face (its first vertex's)
+    n_comps: list              # C per object
+    comp_offset: list          # (B + 1): where each object's components start in the arrays below
+    n_verts: torch.Tensor      # (sum C,) int64
+    n_faces: torch.Tensor      # (sum C,) int64
+    area: torch.Tensor         # (sum C,) float64
+    volume: torch.Tensor       # (sum C,) float64, signed, about the component's vertex of smallest index
+    bbox_lo: torch.Tensor      # (sum C, 3) fp32
+    bbox_hi: torch.Tensor      # (sum C, 3) fp32
+
+
+def _offsets(sizes, dev):
+    off = [0]
+    for s in sizes:
+        off.append(off[-1] + int(s))
+    return off, torch.tensor(off, dtype=torch.int64).to(dev)
+
+
+def mesh_components(verts, faces, n_verts, n_faces):
+    """The connected components of a packed mesh (include/supnerf_hip.h, "Mesh components"): ``verts`` (sum V, 3) fp32 and ``faces``
+    (sum F, 3) int32 with indices local to each object, ``n_verts`` / ``n_faces`` the V and F per object (host lists), as ``iso_extract``
+    returns them.  ``snr_mesh_hook`` (lock-free union-find over the faces) -> ``snr_mesh_flatten`` -> one ``torch.cumsum`` per object ->
+    ``snr_mesh_label``; counts and boxes by ``snr_mesh_boxes``; area and volume by a stable sort of the faces by component,
+    ``snr_mesh_face_terms`` and ``snr_mesh_segment_sum`` (fixed order: the same bits from run to run).  One host read: the component
+    counts together with the bad-index flag; a face index outside its object raises.  Returns a ``MeshComponents``."""
+    _need_gpu(verts, faces)
+    n_verts, n_faces = [int(x) for x in n_verts], [int(x) for x in n_faces]
+    B = len(n_verts)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise SnrError(f"a packed mesh is verts (sum V, 3) fp32 and faces (sum F, 3) int32, got {tuple(verts.shape)} {verts.dtype} and "
+                       f"{tuple(faces.shape)} {faces.dtype}")
+    if len(n_faces) != B or min(n_verts + n_faces + [0]) < 0 or sum(n_verts) != verts.shape[0] or sum(n_faces) != faces.shape[0]:
+        raise SnrError(f"n_verts {n_verts} and n_faces {n_faces} do not add up to {verts.shape[0]} vertices and {faces.shape[0]} faces")
+    if max(n_verts + [0]) > 2 ** 31 - 1:
+        raise SnrError("an object has more than 2^31 - 1 vertices")
+    verts, faces = _f32c(verts.detach()), faces.contiguous()
+    dev = verts.device
+    nV, nF = verts.shape[0], faces.shape[0]
+    lib, st = _lib.lib(), _stream(dev)
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    voff_h, voff = _offsets(n_verts, dev)
+    _, foff = _offsets(n_faces, dev)
+    with torch.cuda.device(dev):
+        parent = torch.empty(nV, dtype=i32, device=dev)
+        root = torch.empty(nV, dtype=i32, device=dev)
+        is_root = torch.empty(nV, dtype=torch.uint8, device=dev)
+        bad = torch.zeros(1, dtype=i32, device=dev)
+        check(lib.snr_mesh_hook(_ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), B, nV, nF, _ptr(parent, i32), _ptr(bad, i32), st),
+              "snr_mesh_hook")
+        check(lib.snr_mesh_flatten(_ptr(parent, i32), _ptr(voff, i64), B, nV, _ptr(root, i32), _ptr(is_root, torch.uint8), st),
+              "snr_mesh_flatten")
+        root_scan = torch.empty(nV, dtype=i32, device=dev)
+        for b in range(B):
+            if n_verts[b]:
+                torch.cumsum(is_root[voff_h[b]:voff_h[b + 1]], 0, dtype=i32, out=root_scan[voff_h[b]:voff_h[b + 1]])
+        full = [b for b in range(B) if n_verts[b]]
+        last = torch.tensor([voff_h[b + 1] - 1 for b in full], dtype=i64).to(dev)
+        host = torch.cat([bad.long(), root_scan[last].long()]).cpu().tolist()          # the one host read
+        if host[0]:
+            raise SnrError("mesh_components: a face index lies outside its object's vertices")
+        n_comps = [0] * B
+        for b, c in zip(full, host[1:]):
+            n_comps[b] = c
+        coff_h, coff = _offsets(n_comps, dev)
+        nC = coff_h[-1]
+        if nC > 2 ** 31 - 1:
+            raise SnrError("more than 2^31 - 1 components in one call")
+        vert_label = torch.empty(nV, dtype=i32, device=dev)
+        face_label = torch.empty(nF, dtype=i32, device=dev)
+        check(lib.snr_mesh_label(_ptr(root, i32), _ptr(root_scan, i32), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), B, nV, nF,
+                                 _ptr(vert_label, i32), _ptr(face_label, i32), st), "snr_mesh_label")
+        comp_verts = torch.empty(nC, dtype=i64, device=dev)
+        bbox_lo, bbox_hi = torch.empty(nC, 3, device=dev), torch.empty(nC, 3, device=dev)
+        check(lib.snr_mesh_boxes(_ptr(verts), _ptr(vert_label, i32), _ptr(voff, i64), _ptr(coff, i64), B, nV, nC, _ptr(comp_verts, i64),
+                                 _ptr(bbox_lo), _ptr(bbox_hi), st), "snr_mesh_boxes")
+        area, volume = torch.zeros(nC, dtype=f64, device=dev), torch.zeros(nC, dtype=f64, device=dev)
+        comp_faces = torch.zeros(nC, dtype=i64, device=dev)
+        if nF and nC:
+            key = face_label
+            if B > 1:       # component ids of the whole call: the object's first id added to every face of the object
+                key = face_label + torch.repeat_interleave(coff[:-1].to(i32), torch.tensor(n_faces, dtype=i64).to(dev), output_size=nF)
+            key, order = torch.sort(key, stable=True)
+            seg_start = torch.searchsorted(key, torch.arange(nC + 1, dtype=i32, device=dev))
+            comp_faces = seg_start[1:] - seg_start[:-1]
+            slab_off = torch.zeros(nC + 1, dtype=i64, device=dev)
+            torch.cumsum((comp_faces + (MESH_SLAB - 1)) // MESH_SLAB, 0, out=slab_off[1:])
+            area_t, vol_t = torch.empty(nF, dtype=f64, device=dev), torch.empty(nF, dtype=f64, device=dev)
+            check(lib.snr_mesh_face_terms(_ptr(verts), _ptr(faces, i32), _ptr(root, i32), _ptr(order, i64), _ptr(voff, i64), _ptr(foff, i64),
+                                          B, nV, nF, _ptr(area_t, f64), _ptr(vol_t, f64), st), "snr_mesh_face_terms")
+            n_slabs = int(lib.snr_mesh_slab_bound(nC, nF))
+            partial = torch.empty(n_slabs, 2, dtype=f64, device=dev)
+            check(lib.snr_mesh_segment_sum(_ptr(area_t, f64), _ptr(vol_t, f64), _ptr(seg_start, i64), _ptr(slab_off, i64), nC, nF,
+                                           _ptr(partial, f64), n_slabs, _ptr(area, f64), _ptr(volume, f64), st), "snr_mesh_segment_sum")
+    return MeshComponents(vert_label, face_label, n_comps, coff_h, comp_verts, comp_faces, area, volume, bbox_lo, bbox_hi)
+
+
 # ------------------------------------------------------------------------------------ ray-cast surfaces
 def _ray_shapes(rays_o, rays_d, *per_ray):
     """R of rays_o, rays_d (R, 3) and any number of per-ray (R,) tensors: the sizes the ray kernels index by."""
