@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 14
+#define SNR_ABI_VERSION 15
 
 enum {
     SNR_OK = 0,
@@ -529,6 +529,57 @@ int snr_mesh_face_terms(const float* verts, const int32_t* faces, const int32_t*
 int64_t snr_mesh_slab_bound(int64_t n_comps, int64_t n_faces);
 int snr_mesh_segment_sum(const double* area_terms, const double* volume_terms, const int64_t* seg_start, const int64_t* slab_offset,
                          int64_t n_comps, int64_t n_faces, double* partial, int64_t n_slabs, double* area, double* volume, void* stream);
+
+/* Mesh rasteriser: which face of a packed triangle mesh each pixel of a pinhole camera sees, at which depth and with which barycentric
+ * weights.  The mesh is the packed form of "Mesh components" above (verts, object-local int32 faces, vert_offset and face_offset DEVICE
+ * arrays).  Each object b has one row-major 3x4 fp32 matrix M_b (obj_to_cam (n_objects, 3, 4), DEVICE) that maps its stored vertices to
+ * the camera frame (x right, y down, z forward); the camera is fx, fy, cx, cy.  All fp32 steps round once per written operation (no fma);
+ * tests/raster_restatement.py restates every rule step by step.
+ *   1. Projection of a vertex (x, y, z): per axis k, Xc_k = ((M[k][0] x + M[k][1] y) + M[k][2] z) + M[k][3]; its screen vertex is
+ *      u = fx (Xc_0 / Xc_2) + cx, v = fy (Xc_1 / Xc_2) + cy, with the camera depth Xc_2 kept beside it.  Pixel centres lie at INTEGER
+ *      (u, v): pixel (px, py) looks along ((px - cx) / fx, (py - cy) / fy, 1).
+ *   2. Snapping: xs = rint(256 u), ys = rint(256 v) (round half to even), integers with 8 sub-pixel bits.  A face is dropped when one of
+ *      its vertices has a non-finite u, v or depth, a depth < z_near (z_near > 0), or |u| or |v| >= 2^22 pixels; so is a face with a vertex
+ *      index outside its object, or of an object whose image index is outside [0, n_images).  Faces are NOT clipped against the near
+ *      plane: a face that reaches behind z_near disappears whole.  The objects this is for lie in front of the camera.
+ *   3. Orientation, exact in int64: A = (xs1 - xs0)(ys2 - ys0) - (xs2 - xs0)(ys1 - ys0); a face with A = 0 is dropped; s = sign(A).  The
+ *      iso rules wind faces counter-clockwise seen from outside in a right-handed frame, so under an M_b of positive determinant a face
+ *      seen from outside has A < 0 (y points down).  cull_sign (n_objects) int32, nullable: a face with A cull_sign[b] > 0 is dropped;
+ *      sign(det M_b[:, :3]) there drops the faces seen from inside, 0 (or a null array) draws both sides.
+ *   4. Coverage, exact in int64, of the pixel centre P = (256 px, 256 py): edge i runs from vertex a = i + 1 to b = i + 2 (mod 3), the edge
+ *      opposite vertex i; (dx, dy) = s (b - a); E_i = dx (P_y - a_y) - dy (P_x - a_x).  The pixel is covered iff for all three edges
+ *      E_i > 0, or E_i = 0 and the edge owns its ties: dy > 0, or dy = 0 and dx < 0.  Two faces on opposite sides of a shared edge see it
+ *      in opposite directions, so exactly one of them owns a centre on it.  Candidates are the pixels of the snapped bounding box inside
+ *      [0, W - 1] x [0, H - 1].  (Coordinates stay within 2^30, differences within 2^31: every product fits int64.)
+ *   5. Depth of a covered pixel: iz_i = 1.0f / z_i; q = (float(E_0) iz_0 + float(E_1) iz_1) + float(E_2) iz_2; depth = float(s A) / q, int64
+ *      to float rounding to nearest even.  It is the perspective-correct camera z; every term is positive (E_0 + E_1 + E_2 = s A).
+ *   6. Visibility: per pixel the covering face of smallest depth wins, ties to the smallest packed face index: the 64-bit key
+ *      (bits(depth) << 32) | packed face (depth > 0: its bits order like its value), combined by UNSIGNED integer atomic min into keys
+ *      (n_images, H, W), preset by the caller to all ones.  The result does not depend on the order of the threads.  Object b is drawn
+ *      into image image_of_object[b] (int32, DEVICE): all zeros = one scene image, 0, 1, 2 ... = one image per object.
+ *   7. Resolve, per pixel: face = the packed index (int32), -1 where empty; depth, 0 where empty; weights_i = (float(E_i) iz_i) / q
+ *      recomputed for the winning face, the perspective-correct barycentric weights, 0 where empty.
+ *   8. Interpolation of per-vertex attributes (sum V, C) fp32, 1 <= C <= 16: out_c = (w_0 a_0c + w_1 a_1c) + w_2 a_2c with a_i the row of
+ *      the winning face's vertex i; an empty pixel gets `background`.
+ *
+ * snr_raster_project: screen (sum V, 3) = (u, v, Xc_2) of every vertex (rule 1), a thread per vertex.
+ * snr_raster_faces: rules 2 - 6, a thread per face walking its candidate box; a face with 64 candidates or more is walked by its whole wave,
+ *   64 pixels at a time.  Vector integer atomics only; no key is read in this launch (the L2s of the eight XCDs are not coherent
+ *   within one).
+ * snr_raster_resolve (a later launch: plain loads of keys): face (n_images, H, W) int32, depth (n_images, H, W), weights (n_images, H, W, 3).
+ * snr_raster_interpolate: out (n_pixels, C) from face (n_pixels) and weights (n_pixels, 3), a thread per pixel and channel.
+ * A null pointer, a negative size, z_near <= 0 or C outside [1, 16]: SNR_E_ARG; n_images H W >= 2^31 or sum F >= 2^31: SNR_E_UNSUPPORTED. */
+int snr_raster_project(const float* verts, const int64_t* vert_offset, int64_t n_objects, int64_t n_verts, const float* obj_to_cam, float fx,
+                       float fy, float cx, float cy, float* screen, void* stream);
+int snr_raster_faces(const float* screen, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset,
+                     const int32_t* image_of_object, const int32_t* cull_sign, int64_t n_objects, int64_t n_verts, int64_t n_faces,
+                     int64_t n_images, int height, int width, float z_near, uint64_t* keys, void* stream);
+int snr_raster_resolve(const uint64_t* keys, const float* screen, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset,
+                       int64_t n_objects, int64_t n_verts, int64_t n_faces, int64_t n_images, int height, int width, int32_t* face,
+                       float* depth, float* weights, void* stream);
+int snr_raster_interpolate(const int32_t* face, const float* weights, const int32_t* faces, const int64_t* vert_offset,
+                           const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, const float* attributes,
+                           int n_channels, int64_t n_pixels, float background, float* out, void* stream);
 
 #ifdef __cplusplus
 }

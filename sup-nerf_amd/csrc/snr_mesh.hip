@@ -22,29 +22,6 @@ constexpr int MESH_SLAB = 4096;                      // faces of one component s
 
 #define SNR_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-// entry b of the (n + 1) ascending offsets `off` that holds item i: the largest b < n with off[b] <= i (empty entries are skipped)
-__device__ __forceinline__ long long mesh_entry_of(const long long* __restrict__ off, long long n, long long i) {
-    long long lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const long long mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct MeshObject {
-    long long v0;                // where the object's vertices start
-    long long V;                 // how many it has; 0 when the offsets are not usable
-};
-__device__ __forceinline__ MeshObject mesh_object(const long long* __restrict__ voff, long long b, long long nV) {
-    MeshObject o;
-    o.v0 = voff[b];
-    o.V = voff[b + 1] - o.v0;
-    if (o.v0 < 0 || o.V < 0 || o.V > 0x7fffffffll || o.v0 + o.V > nV) o.V = 0;
-    return o;
-}
-__device__ __forceinline__ bool mesh_index_ok(int i, long long V) { return i >= 0 && (long long)i < V; }
-
 __global__ void mesh_identity_kernel(const long long* __restrict__ voff, long long B, long long nV, int* __restrict__ parent) {
     const long long g = grid_thread();
     if (g >= nV) return;

@@ -25,6 +25,11 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     ``select_components(mesh, components, keep)``: the sub-mesh of some components, with the index maps back to the full mesh;
     ``largest_component(meshes, by=..., drop_cavities=...)``: the object without its floaters (and, by default, without the closed pockets
     inside it); ``extract_mesh(..., keep="largest")`` does it in one call;
+  * ``rasterize(meshes, obj_to_cam, K, size)``: the meshes as a pinhole camera sees them -- per pixel the nearest face, the object it belongs
+    to, its depth and barycentric weights, all objects in one scene image or one image each (``ops.rasterize``: ``snr_raster_*``);
+    ``interpolate(raster, attributes)``: per-vertex normals, colours or any data of up to 16 channels at the pixels;
+    ``mesh_view(mesh, cam_pose, obj_diag, K, roi)``: one object on the pixel grid of ``utils.get_rays``, metric depth comparable with
+    ``surface_depth``; ``scene_view(meshes, obj_poses, obj_diags, K, H, W)``: a whole scene with depth and instance ids;
   * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
     ``to_decoder_frame``: its inverse;
   * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
@@ -36,7 +41,9 @@ include/supnerf_hip.h, restated in tests/iso_restatement.py.  The density backwa
 branch): d xyz and the shape-code gradient are bit for bit those of the full backward with a zero colour gradient.  The ray rules (march,
 first crossing, refinement, depth, implicit gradient) are the header's too, restated in tests/ray_restatement.py; a ray search reads nothing
 back to the host.  The component rules (connectivity by vertex index, ids in the order of the smallest vertex index, float64 measures
-summed in a fixed order) are the header's as well, restated in tests/mesh_restatement.py.  There is no CPU path: CPU tensors raise
+summed in a fixed order) are the header's as well, restated in tests/mesh_restatement.py; so are the rasteriser's (projection, snapping
+to 1/256 pixel, exact integer coverage with a tie rule, perspective-correct depth, the nearest face by an integer atomic min), restated in
+tests/raster_restatement.py: no host read, no autograd, the same bits from run to run.  There is no CPU path: CPU tensors raise
 ``SnrError``."""
 from typing import NamedTuple
 
@@ -553,6 +560,201 @@ def to_decoder_frame(points, obj_diag, family="a", shapenet_obj_cood=False, kitt
     if direction:
         return v @ m.T
     return (v / scale) @ m.T
+
+
+class Raster(NamedTuple):
+    face: torch.Tensor       # (n_images, H, W) int32: the packed index of the face each pixel sees; -1 where empty
+    obj: torch.Tensor        # (n_images, H, W) int32: the object that face belongs to; -1 where empty
+    depth: torch.Tensor      # (n_images, H, W): camera z of the surface at the pixel centre; 0 where empty
+    weights: torch.Tensor    # (n_images, H, W, 3): perspective-correct barycentric weights of the face's three vertices; 0 where empty
+    mesh: ops.PackedMesh     # the packed mesh ``face`` indexes
+
+
+def _camera(K):
+    """(fx, fy, cx, cy) as host floats from a 3x3 intrinsic matrix or from the four numbers themselves.  The camera travels to the kernels
+    by value, so ``K`` is a host value (numpy, a tuple, a CPU tensor); a ``K`` on the GPU costs one synchronising copy, as in
+    ``utils._cam_table``."""
+    k = K.detach().cpu() if torch.is_tensor(K) else K
+    k = np.asarray(k, dtype=np.float64)
+    if k.shape == (3, 3):
+        return float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+    if k.shape == (4,):
+        return tuple(float(v) for v in k)
+    raise SnrError(f"K is a 3x3 intrinsic matrix or (fx, fy, cx, cy), got shape {k.shape}")
+
+
+def _det3(m):
+    """Determinant of (..., 3, 3+) matrices' left 3x3 blocks by the rule of Sarrus' cofactors (plain arithmetic: no host read)."""
+    a, b, c = m[..., 0, 0], m[..., 0, 1], m[..., 0, 2]
+    d, e, f = m[..., 1, 0], m[..., 1, 1], m[..., 1, 2]
+    g, h, i = m[..., 2, 0], m[..., 2, 1], m[..., 2, 2]
+    return a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g)
+
+
+def _pack(meshes):
+    ms, single = _one_or_many(meshes)
+    for _, f in ms:
+        if f.dtype != torch.int32:
+            raise SnrError(f"faces are int32, got {f.dtype}")
+    if not ms:
+        raise SnrError("no mesh to draw")
+    if len(ms) == 1:
+        verts, faces = ms[0][0].detach(), ms[0][1]
+    else:
+        verts, faces = torch.cat([v.detach().float() for v, _ in ms]), torch.cat([f for _, f in ms])
+    return ops.pack_mesh(verts, faces, [v.shape[0] for v, _ in ms], [f.shape[0] for _, f in ms])
+
+
+def rasterize(meshes, obj_to_cam, K, size, *, cull=None, z_near=1e-3, per_object=False):
+    """Draw ``meshes`` -- the list ``extract_mesh`` returns, or one (verts, faces) pair -- as a pinhole camera sees them: per pixel the
+    nearest face, its depth and barycentric weights (include/supnerf_hip.h, "Mesh rasteriser"; ``snr_raster_*``).
+
+    ``obj_to_cam``: (B, 3, 4), one matrix per object that maps its stored vertices to the camera frame (x right, y down, z forward); a
+    (3, 4) matrix with one mesh.  ``K``: the 3x3 intrinsic matrix or (fx, fy, cx, cy); pixel centres lie at integer coordinates, pixel
+    (px, py) looks along ((px - cx) / fx, (py - cy) / fy, 1) as in ``utils.get_rays``.  ``size = (H, W)``.  ``per_object=False``: all
+    objects into one scene image (n_images = 1); ``True``: one image per object.  ``cull="back"`` drops the faces seen from inside
+    (``extract_mesh`` winds faces counter-clockwise seen from outside; a mirroring ``obj_to_cam`` is accounted for by the sign of its
+    determinant); ``None`` draws both sides.
+
+    Vertices are snapped to 1/256 pixel; coverage is exact with a tie rule that gives a pixel centre on a shared edge to exactly one
+    face; of the covering faces the nearest wins, ties to the lowest face index: the same bits from run to run.  A face with a vertex
+    nearer than ``z_near``, not finite, or 2^22 pixels or more off the image origin is dropped WHOLE: nothing is clipped against the near
+    plane, the objects this is for lie in front of the camera.  No anti-aliasing.
+
+    Returns a ``Raster``.  The outputs carry no autograd (hard visibility gives the silhouette no gradient; ``ray_surface`` is the
+    differentiable depth).  ``K``, ``size`` and ``z_near`` are host values (a ``K`` on the GPU is copied to the host first, one
+    synchronising read); with those on the host the call is asynchronous on the current stream and reads nothing back: meshes and
+    ``obj_to_cam`` stay on the device.  CPU meshes raise ``SnrError``."""
+    mesh = _pack(meshes)
+    B, dev = len(mesh.n_verts), mesh.verts.device
+    if cull not in (None, "back"):
+        raise SnrError(f"cull is None or 'back', got {cull!r}")
+    if not float(z_near) > 0:
+        raise SnrError(f"z_near must be positive, got {z_near}")
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise SnrError(f"size is (H, W) with at least one pixel each way, got {tuple(size)}")
+    m = torch.as_tensor(obj_to_cam).detach()
+    if m.dim() == 2 and B == 1:
+        m = m.unsqueeze(0)
+    if tuple(m.shape) != (B, 3, 4):
+        raise SnrError(f"obj_to_cam must be ({B}, 3, 4), one matrix per object, got {tuple(m.shape)}")
+    cull_sign = None
+    if cull == "back":
+        cull_sign = torch.sign(_det3(m.double())).to(torch.int32).to(dev)
+    n_images = B if per_object else 1
+    image_of = torch.arange(B, dtype=torch.int32).to(dev) if per_object else torch.zeros(B, dtype=torch.int32, device=dev)
+    face, depth, weights, _ = ops.rasterize(mesh, m.float().to(dev), _camera(K), image_of, n_images, H, W, z_near, cull_sign)
+    obj = torch.bucketize(face, mesh.face_offset[1:], right=True, out_int32=True)
+    return Raster(face, torch.where(face < 0, face, obj), depth, weights, mesh)
+
+
+def interpolate(raster, attributes, background=0.0):
+    """Per-vertex ``attributes`` of the meshes of a ``Raster`` -- a per-object list of (V, C) tensors, or one packed (sum V, C) tensor, C
+    up to 16 (normals, colours ...) -- interpolated to its pixels with the perspective-correct weights: (n_images, H, W, C), ``background``
+    where no face is seen.  No autograd."""
+    a = attributes
+    if not torch.is_tensor(a):
+        a = [_gpu(x, "attributes") for x in a]
+        if len(a) != len(raster.mesh.n_verts) or any(x.dim() != 2 or x.shape[0] != n for x, n in zip(a, raster.mesh.n_verts)):
+            raise SnrError(f"attributes are one (V, C) tensor per object, V = {raster.mesh.n_verts}")
+        a = torch.cat([x.detach().float() for x in a]) if len(a) > 1 else a[0]
+    return ops.raster_interpolate(raster.mesh, raster.face, raster.weights, _gpu(a, "attributes"), background)
+
+
+class MeshView(NamedTuple):
+    depth: torch.Tensor      # (H, W): metres along the unit view direction of the pixel, as ``surface_depth``; 0 where empty
+    mask: torch.Tensor       # (H, W) bool: a face is seen
+    face: torch.Tensor       # (H, W) int32: its packed index; -1 where empty
+    normal: torch.Tensor     # (H, W, 3) unit, object frame (None without ``normals``); 0 where empty
+    color: torch.Tensor      # (H, W, 3) (None without ``colors``); 0 where empty
+
+
+def _frame_matrix(shapenet_obj_cood, kitti2nusc, like):
+    """(3, 3) float64 F^T with x_object = scale F^T p for decoder-frame p: ``to_object_frame`` as a matrix, on ``like``'s device."""
+    return torch.tensor(U._frame(False, kitti2nusc, shapenet_obj_cood), dtype=torch.float64, device=like.device).view(3, 3).T
+
+
+def _inverse3(r):
+    """Inverse of a (3, 3) matrix by cofactors (plain arithmetic: no host read)."""
+    c = torch.stack([torch.linalg.cross(r[1], r[2]), torch.linalg.cross(r[2], r[0]), torch.linalg.cross(r[0], r[1])], dim=1)
+    return c / (r[0] * torch.linalg.cross(r[1], r[2])).sum()
+
+
+def mesh_view(meshes, cam_pose, obj_diag, K, roi, *, im_sz=None, cull="back", family="a", shapenet_obj_cood=False, kitti2nusc=False,
+              normals=None, colors=None, z_near=1e-3):
+    """One object's decoder-frame mesh (a (verts, faces) pair, or a list of pieces that share the pose) on the pixel grid of
+    ``utils.get_rays(K, cam_pose, roi, uv_steps)``: the mesh-speed mirror of ``surface_depth``.  ``cam_pose``: the camera in the object's
+    frame, (3, 4).  Pixel (i, j) of the result is the pixel ``get_rays`` shoots ray i nx + j through; ``im_sz``: an ``im_sz`` x ``im_sz``
+    grid over ``roi`` instead of one ray per pixel.
+
+    The decoder -> object map of ``to_object_frame`` (frame matrix and scale), the inverse of ``cam_pose`` and the affine pixel grid
+    (offset x0, y0 and the step of ``im_sz``) are composed in float64 into one matrix and one effective (fx, fy, cx, cy), then
+    ``rasterize`` draws.  Returns a ``MeshView``: depth in metres along the unit view direction (camera z times
+    |((px - cx) / fx, (py - cy) / fy, 1)|), comparable with ``surface_depth``; the hit mask; the face index; with ``normals`` / ``colors``
+    (per-vertex, as ``vertex_normals`` / ``vertex_colors`` return them) the interpolated normals, renormalised and mapped to the object's
+    frame with ``to_object_frame(direction=True)``, and colours.  ``obj_diag``, ``K``, ``roi`` and ``im_sz`` are host values; ``cam_pose``
+    stays on its device.  No autograd."""
+    scale = _frame_scale(obj_diag, family)
+    pose = torch.as_tensor(cam_pose).detach().double()[:3]
+    if tuple(pose.shape) != (3, 4):
+        raise SnrError(f"cam_pose is (3, 4) or (4, 4), got {tuple(torch.as_tensor(cam_pose).shape)}")
+    r_inv = _inverse3(pose[:, :3])
+    m = torch.cat([r_inv @ _frame_matrix(shapenet_obj_cood, kitti2nusc, pose) * scale, -(r_inv @ pose[:, 3:4])], dim=1)
+    fx, fy, cx, cy = _camera(K)
+    x0, y0, x1, y1 = [int(v) for v in roi]
+    nx, ny = (int(im_sz), int(im_sz)) if im_sz is not None else (x1 - x0, y1 - y0)
+    sx = (x1 - 1 - x0) / (nx - 1) if nx > 1 else 1.0
+    sy = (y1 - 1 - y0) / (ny - 1) if ny > 1 else 1.0
+    cam = (fx / sx, fy / sy, (cx - x0) / sx, (cy - y0) / sy)
+    ms, single = _one_or_many(meshes)
+    r = rasterize(ms, m.unsqueeze(0).expand(len(ms), 3, 4), cam, (ny, nx), cull=cull, z_near=z_near)
+    dev = r.depth.device
+    px = (torch.arange(nx, dtype=torch.float64, device=dev) - cam[2]) / cam[0]
+    py = (torch.arange(ny, dtype=torch.float64, device=dev) - cam[3]) / cam[1]
+    length = torch.sqrt(px[None, :] ** 2 + py[:, None] ** 2 + 1.0).float()
+    normal = color = None
+    if normals is not None:
+        n = torch.nn.functional.normalize(interpolate(r, [normals] if single else list(normals))[0], dim=-1)
+        normal = to_object_frame(n, obj_diag, family, shapenet_obj_cood, kitti2nusc, direction=True)
+    if colors is not None:
+        color = interpolate(r, [colors] if single else list(colors))[0]
+    return MeshView(r.depth[0] * length, r.face[0] >= 0, r.face[0], normal, color)
+
+
+class SceneView(NamedTuple):
+    depth: torch.Tensor      # (H, W): camera z of the nearest surface; 0 where empty
+    obj: torch.Tensor        # (H, W) int32: the instance (index into ``meshes``) each pixel sees; -1 where empty
+    face: torch.Tensor       # (H, W) int32: packed face index; -1 where empty
+    normal: torch.Tensor     # (H, W, 3) unit, CAMERA frame (None without ``normals``)
+    color: torch.Tensor      # (H, W, 3) (None without ``colors``)
+
+
+def scene_view(meshes, obj_poses, obj_diags, K, H, W, *, cull="back", family="a", shapenet_obj_cood=False, kitti2nusc=False, normals=None,
+               colors=None, z_near=1e-3):
+    """All objects of a scene in one full H x W image: the mesh-speed counterpart of ``scene.vis_scene``.  ``meshes``: one decoder-frame
+    mesh per object; ``obj_poses`` (B, 3, 4): object -> camera, ``scene``'s convention; ``obj_diags`` (B,): each object's diagonal
+    (``to_object_frame``'s scale).  Returns a ``SceneView``: z-buffer depth (camera z, metres), the instance id per pixel, the face index
+    and, with per-object lists ``normals`` / ``colors``, the interpolated normals (renormalised, rotated to the camera frame) and colours.
+    ``K``, ``H`` and ``W`` are host values; poses and diagonals may live on either side.  No autograd."""
+    ms = _meshes(meshes)
+    poses = torch.as_tensor(obj_poses).detach().double()
+    diags = torch.as_tensor(obj_diags).detach().double().to(poses.device).reshape(-1)
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4) or poses.shape[0] != len(ms) or diags.shape[0] != len(ms):
+        raise SnrError(f"{len(ms)} meshes take obj_poses ({len(ms)}, 3, 4) and {len(ms)} obj_diags, got {tuple(poses.shape)} and "
+                       f"{tuple(diags.shape)}")
+    rot = poses[:, :, :3] @ _frame_matrix(shapenet_obj_cood, kitti2nusc, poses)
+    m = torch.cat([rot * (diags * _frame_scale(1.0, family)).view(-1, 1, 1), poses[:, :, 3:4]], dim=2)
+    r = rasterize(ms, m, K, (H, W), cull=cull, z_near=z_near)
+    normal = color = None
+    if normals is not None:
+        # rotate each object's normals to the camera frame before they are interpolated: one attribute pass for the whole scene
+        rot = rot.float().to(r.depth.device)
+        cam_n = [_gpu(n, "normals").detach().float() @ rot[b].T for b, n in enumerate(normals)]
+        normal = torch.nn.functional.normalize(interpolate(r, cam_n)[0], dim=-1)
+    if colors is not None:
+        color = interpolate(r, list(colors))[0]
+    return SceneView(r.depth[0], r.obj[0], r.face[0], normal, color)
 
 
 class RayHits(NamedTuple):

@@ -989,13 +989,19 @@ def _offsets(sizes, dev):
     return off, torch.tensor(off, dtype=torch.int64).to(dev)
 
 
-def mesh_components(verts, faces, n_verts, n_faces):
-    """The connected components of a packed mesh (include/supnerf_hip.h, "Mesh components"): ``verts`` (sum V, 3) fp32 and ``faces``
-    (sum F, 3) int32 with indices local to each object, ``n_verts`` / ``n_faces`` the V and F per object (host lists), as ``iso_extract``
-    returns them.  ``snr_mesh_hook`` (lock-free union-find over the faces) -> ``snr_mesh_flatten`` -> one ``torch.cumsum`` per object ->
-    ``snr_mesh_label``; counts and boxes by ``snr_mesh_boxes``; area and volume by a stable sort of the faces by component,
-    ``snr_mesh_face_terms`` and ``snr_mesh_segment_sum`` (fixed order: the same bits from run to run).  One host read: the component
-    counts together with the bad-index flag; a face index outside its object raises.  Returns a ``MeshComponents``."""
+class PackedMesh(NamedTuple):
+    """Several objects' meshes in the form the ``snr_mesh_*`` and ``snr_raster_*`` entry points take."""
+    verts: torch.Tensor        # (sum V, 3) fp32, object after object
+    faces: torch.Tensor        # (sum F, 3) int32, indices local to each object
+    vert_offset: torch.Tensor  # (B + 1,) int64 on the device: where each object's vertices start
+    face_offset: torch.Tensor  # (B + 1,) int64 on the device
+    n_verts: list              # V per object
+    n_faces: list              # F per object
+
+
+def pack_mesh(verts, faces, n_verts, n_faces) -> PackedMesh:
+    """Check ``verts`` (sum V, 3) fp32 and ``faces`` (sum F, 3) int32 against the per-object counts ``n_verts`` / ``n_faces`` (host lists)
+    and put the offsets on the device."""
     _need_gpu(verts, faces)
     n_verts, n_faces = [int(x) for x in n_verts], [int(x) for x in n_faces]
     B = len(n_verts)
@@ -1007,12 +1013,23 @@ def mesh_components(verts, faces, n_verts, n_faces):
     if max(n_verts + [0]) > 2 ** 31 - 1:
         raise SnrError("an object has more than 2^31 - 1 vertices")
     verts, faces = _f32c(verts.detach()), faces.contiguous()
-    dev = verts.device
+    return PackedMesh(verts, faces, _offsets(n_verts, verts.device)[1], _offsets(n_faces, verts.device)[1], n_verts, n_faces)
+
+
+def mesh_components(verts, faces, n_verts, n_faces):
+    """The connected components of a packed mesh (include/supnerf_hip.h, "Mesh components"): ``verts`` (sum V, 3) fp32 and ``faces``
+    (sum F, 3) int32 with indices local to each object, ``n_verts`` / ``n_faces`` the V and F per object (host lists), as ``iso_extract``
+    returns them.  ``snr_mesh_hook`` (lock-free union-find over the faces) -> ``snr_mesh_flatten`` -> one ``torch.cumsum`` per object ->
+    ``snr_mesh_label``; counts and boxes by ``snr_mesh_boxes``; area and volume by a stable sort of the faces by component,
+    ``snr_mesh_face_terms`` and ``snr_mesh_segment_sum`` (fixed order: the same bits from run to run).  One host read: the component
+    counts together with the bad-index flag; a face index outside its object raises.  Returns a ``MeshComponents``."""
+    mesh = pack_mesh(verts, faces, n_verts, n_faces)
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    B, dev = len(n_verts), verts.device
     nV, nF = verts.shape[0], faces.shape[0]
     lib, st = _lib.lib(), _stream(dev)
     i32, i64, f64 = torch.int32, torch.int64, torch.float64
-    voff_h, voff = _offsets(n_verts, dev)
-    _, foff = _offsets(n_faces, dev)
+    voff_h = [sum(n_verts[:b]) for b in range(B + 1)]
     with torch.cuda.device(dev):
         parent = torch.empty(nV, dtype=i32, device=dev)
         root = torch.empty(nV, dtype=i32, device=dev)
@@ -1065,6 +1082,92 @@ def mesh_components(verts, faces, n_verts, n_faces):
             check(lib.snr_mesh_segment_sum(_ptr(area_t, f64), _ptr(vol_t, f64), _ptr(seg_start, i64), _ptr(slab_off, i64), nC, nF,
                                            _ptr(partial, f64), n_slabs, _ptr(area, f64), _ptr(volume, f64), st), "snr_mesh_segment_sum")
     return MeshComponents(vert_label, face_label, n_comps, coff_h, comp_verts, comp_faces, area, volume, bbox_lo, bbox_hi)
+
+
+# ------------------------------------------------------------------------------------ mesh rasteriser
+RASTER_MAX_CHANNELS = 16
+
+
+def _mesh_args(mesh):
+    """What every rasteriser entry point takes of its mesh beside the arrays: both offsets, B, sum V and sum F."""
+    i64 = torch.int64
+    return (_ptr(mesh.vert_offset, i64), _ptr(mesh.face_offset, i64), len(mesh.n_verts), mesh.verts.shape[0], mesh.faces.shape[0])
+
+
+def raster_project(mesh, obj_to_cam, camera):
+    """screen (sum V, 3) = (u, v, camera z) of every vertex of the ``PackedMesh`` (``snr_raster_project``; header rule 1): ``obj_to_cam``
+    (B, 3, 4) fp32 on the device maps each object's stored vertices to the camera frame, ``camera`` = (fx, fy, cx, cy) host floats."""
+    dev, B = mesh.verts.device, len(mesh.n_verts)
+    if tuple(obj_to_cam.shape) != (B, 3, 4):
+        raise SnrError(f"obj_to_cam must be ({B}, 3, 4), one matrix per object, got {tuple(obj_to_cam.shape)}")
+    fx, fy, cx, cy = [float(v) for v in camera]
+    screen = torch.empty(mesh.verts.shape[0], 3, device=dev)
+    voff, _, _, nV, _ = _mesh_args(mesh)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_raster_project(_ptr(mesh.verts), voff, B, nV, _ptr(_f32c(obj_to_cam)), fx, fy, cx, cy, _ptr(screen),
+                                            _stream(dev)), "snr_raster_project")
+    return screen
+
+
+def raster_faces(mesh, screen, image_of_object, n_images, H, W, z_near, cull_sign=None):
+    """keys (n_images, H, W) int64: per pixel the unsigned minimum of (bits(depth) << 32) | packed face over the faces that cover it, all
+    ones where none does (``snr_raster_faces``; header rules 2 - 6).  The buffer is allocated and preset here.  ``image_of_object`` (B,)
+    int32 on the device: the image each object is drawn into; ``cull_sign`` (B,) int32 or None: a face with A cull_sign > 0 is dropped."""
+    dev, i32 = mesh.verts.device, torch.int32
+    n_images, H, W = int(n_images), int(H), int(W)
+    if min(n_images, H, W) < 0:
+        raise SnrError(f"n_images, H and W must not be negative, got {n_images}, {H}, {W}")
+    if n_images * H * W >= 2 ** 31:
+        raise SnrError(f"{n_images} images of {H} x {W} pixels: the rasteriser takes fewer than 2^31 pixels per call")
+    keys = torch.full((n_images, H, W), -1, dtype=torch.int64, device=dev)
+    voff, foff, B, nV, nF = _mesh_args(mesh)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_raster_faces(_ptr(screen), _ptr(mesh.faces, i32), voff, foff, _ptr(image_of_object, i32), _ptr(cull_sign, i32), B,
+                                          nV, nF, n_images, H, W, float(z_near), _ptr(keys, torch.int64), _stream(dev)), "snr_raster_faces")
+    return keys
+
+
+def raster_resolve(mesh, screen, keys):
+    """(face (n_images, H, W) int32, -1 where empty; depth (n_images, H, W), 0 where empty; weights (n_images, H, W, 3)) of the keys of
+    ``raster_faces`` (``snr_raster_resolve``; header rule 7)."""
+    dev, i32 = mesh.verts.device, torch.int32
+    n_images, H, W = keys.shape
+    face = torch.empty(n_images, H, W, dtype=i32, device=dev)
+    depth = torch.empty(n_images, H, W, device=dev)
+    weights = torch.empty(n_images, H, W, 3, device=dev)
+    voff, foff, B, nV, nF = _mesh_args(mesh)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_raster_resolve(_ptr(keys, torch.int64), _ptr(screen), _ptr(mesh.faces, i32), voff, foff, B, nV, nF, n_images, H, W,
+                                            _ptr(face, i32), _ptr(depth), _ptr(weights), _stream(dev)), "snr_raster_resolve")
+    return face, depth, weights
+
+
+def raster_interpolate(mesh, face, weights, attributes, background=0.0):
+    """out (..., C): per pixel of ``face`` (...) / ``weights`` (..., 3) the winning face's per-vertex ``attributes`` (sum V, C) fp32 weighed
+    by the barycentric weights, ``background`` where empty (``snr_raster_interpolate``; header rule 8)."""
+    dev, i32 = mesh.verts.device, torch.int32
+    nV = mesh.verts.shape[0]
+    if attributes.dim() != 2 or attributes.shape[0] != nV or not 1 <= attributes.shape[1] <= RASTER_MAX_CHANNELS:
+        raise SnrError(f"attributes must be ({nV}, C) with 1 <= C <= {RASTER_MAX_CHANNELS}, got {tuple(attributes.shape)}")
+    if tuple(weights.shape) != tuple(face.shape) + (3,) or face.dtype != i32:
+        raise SnrError(f"face (...) int32 and weights (..., 3) do not match: {tuple(face.shape)} {face.dtype}, {tuple(weights.shape)}")
+    _need_gpu(attributes)
+    C_ = attributes.shape[1]
+    out = torch.empty(tuple(face.shape) + (C_,), device=dev)
+    voff, foff, B, _, nF = _mesh_args(mesh)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_raster_interpolate(_ptr(face.contiguous(), i32), _ptr(_f32c(weights)), _ptr(mesh.faces, i32), voff, foff, B, nV,
+                                                nF, _ptr(_f32c(attributes.detach())), C_, face.numel(), float(background), _ptr(out),
+                                                _stream(dev)), "snr_raster_interpolate")
+    return out
+
+
+def rasterize(mesh, obj_to_cam, camera, image_of_object, n_images, H, W, z_near, cull_sign=None):
+    """``raster_project`` -> ``raster_faces`` -> ``raster_resolve`` on the current stream: (face, depth, weights, screen).  Nothing is read
+    back to the host."""
+    screen = raster_project(mesh, obj_to_cam, camera)
+    keys = raster_faces(mesh, screen, image_of_object, n_images, H, W, z_near, cull_sign)
+    return raster_resolve(mesh, screen, keys) + (screen,)
 
 
 # ------------------------------------------------------------------------------------ ray-cast surfaces
