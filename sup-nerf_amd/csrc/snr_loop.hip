@@ -14,6 +14,12 @@ namespace snr {
 
 struct Pose { float Rc[9]; float tc[3]; };
 
+// 1 - cos t without the cancellation: just above the series threshold cosf(t) rounds to 1 or its neighbour and 1 - cosf(t) keeps no digits
+__device__ __forceinline__ float one_minus_cos(float t) {
+    const float s = sinf(0.5f * t);
+    return 2.f * s * s;
+}
+
 // R = I + a K + b K^2 (Rodrigues), a = sin(t)/t, b = (1 - cos t)/t^2, series below t^2 = 1e-8 (driver.axis_angle_to_matrix)
 __device__ __forceinline__ void rodrigues(const float v[3], float R[9], float* a_, float* b_, float* t2_) {
     const float x = v[0], y = v[1], z = v[2];
@@ -21,7 +27,7 @@ __device__ __forceinline__ void rodrigues(const float v[3], float R[9], float* a
     const float t = sqrtf(fmaxf(t2, 1e-24f));
     const bool small = t2 < 1e-8f;
     const float a = small ? 1.f - t2 / 6.f : sinf(t) / t;
-    const float b = small ? 0.5f - t2 / 24.f : (1.f - cosf(t)) / fmaxf(t2, 1e-24f);
+    const float b = small ? 0.5f - t2 / 24.f : one_minus_cos(t) / fmaxf(t2, 1e-24f);
     const float K[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
     float K2[9];
 #pragma unroll
@@ -238,7 +244,7 @@ __global__ void __launch_bounds__(1024) pose_rays_bwd_kernel(const float* __rest
     const bool small = t2 < 1e-8f;
     const float th = sqrtf(fmaxf(t2, 1e-24f));
     const float da = small ? -1.f / 3.f : (th * cosf(th) - sinf(th)) / (th * t2);                      // (da/dv_k) / v_k
-    const float db = small ? -1.f / 12.f : (th * sinf(th) - 2.f * (1.f - cosf(th))) / (t2 * t2);       // (db/dv_k) / v_k
+    const float db = small ? -1.f / 12.f : (th * sinf(th) - 2.f * one_minus_cos(th)) / (t2 * t2);       // (db/dv_k) / v_k
     const float e[3] = {G[7] - G[5], G[2] - G[6], G[3] - G[1]};
     const float m[3] = {M[7] - M[5], M[2] - M[6], M[3] - M[1]};
 #pragma unroll
@@ -460,7 +466,8 @@ int snr_adamw_step(float* const* params, const float* const* grads, float* const
     const double b1 = 1.0 - pow((double)beta1, (double)step), b2 = 1.0 - pow((double)beta2, (double)step);
     for (int i = 0; i < 4; ++i) {
         const bool on = i < n_groups;
-        if (on && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] < 0)) return SNR_E_ARG;
+        // (an empty group has no storage: null is what its tensors' addresses are)
+        if (on && (numel[i] < 0 || (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i])))) return SNR_E_ARG;
         a.p[i] = on ? params[i] : nullptr; a.g[i] = on ? grads[i] : nullptr; a.m[i] = on ? exp_avg[i] : nullptr; a.v[i] = on ? exp_avg_sq[i] : nullptr;
         a.n[i] = on ? numel[i] : 0;
         a.decay[i] = on ? (float)(1.0 - (double)lr[i] * (double)weight_decay) : 1.f;

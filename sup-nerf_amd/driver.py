@@ -62,12 +62,14 @@ def load_hpams(path: Optional[str] = None, dataset: str = "nusc") -> dict:
 
 # ------------------------------------------------------------------ rotations (restated, quaternion-free Rodrigues)
 def axis_angle_to_matrix(v: torch.Tensor) -> torch.Tensor:
-    """(...,3) rotation vector -> (...,3,3).  R = I + sin(t)/t K + (1-cos t)/t^2 K^2, series near t = 0."""
+    """(...,3) rotation vector -> (...,3,3).  R = I + sin(t)/t K + (1-cos t)/t^2 K^2, series near t = 0.  1 - cos t is taken as
+    2 sin^2(t/2): in float32 cos t rounds to 1 or its neighbour just above the series threshold and the difference keeps no digits."""
     t2 = (v * v).sum(-1, keepdim=True)
     t = torch.sqrt(t2.clamp_min(1e-24))
     small = t2 < 1e-8
     a = torch.where(small, 1 - t2 / 6, torch.sin(t) / t)
-    b = torch.where(small, 0.5 - t2 / 24, (1 - torch.cos(t)) / t2.clamp_min(1e-24))
+    s = torch.sin(0.5 * t)
+    b = torch.where(small, 0.5 - t2 / 24, 2 * s * s / t2.clamp_min(1e-24))
     x, y, z = v[..., 0], v[..., 1], v[..., 2]
     zero = torch.zeros_like(x)
     K = torch.stack([zero, -z, y, z, zero, -x, -y, x, zero], -1).reshape(*v.shape[:-1], 3, 3)

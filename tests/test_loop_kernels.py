@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import supnerf_oracle as O
+from loop_reference import pose_rays as torch_pose_rays
 from oracle_bands import amd, dev, md, rel  # noqa: F401  (amd, dev: fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -47,27 +48,6 @@ def test_loss_tail_rejects_partial_objects(amd, dev):
 
 
 # ------------------------------------------------------------------ pose -> rays (src/optimizer_nuscenes.py:685-699, src/utils.py:107-135,159-164,468-469)
-def torch_pose_rays(D, U, rot_vec, trans_vec, cam, half, jit, S, opt_cam_pose):
-    R = D.axis_angle_to_matrix(rot_vec)
-    t = trans_vec.unsqueeze(-1)
-    if not opt_cam_pose:
-        Rc = R.transpose(-2, -1)
-        c2o = torch.cat([Rc, -Rc @ t], -1)
-    else:
-        c2o = torch.cat([R, t], -1)
-    world = (cam[:, :, None, :] * c2o[:, None, :3, :3]).sum(-1)
-    unit = world / torch.norm(world, dim=-1, keepdim=True)
-    origin = c2o[:, None, :3, 3].expand(world.shape)
-    dist = c2o[:, :, 3].detach().norm(dim=-1)
-    near, far = (dist - half)[:, None], (dist + half)[:, None]
-    idx = torch.arange(S, dtype=cam.dtype)[None, :]
-    hw = (far - near) / (2 * S)
-    start, end = near + hw, far - hw
-    step = (end - start) / max(S - 1, 1)
-    z = torch.where(idx < S // 2, start + step * idx, end - step * (S - 1 - idx)) + jit * hw
-    return c2o, origin.reshape(-1, 3), unit.reshape(-1, 3), z
-
-
 @pytest.mark.parametrize("opt_cam_pose", [0, 1])
 @pytest.mark.parametrize("B,n,S", [(1, 4096, 64), (3, 100, 32), (2, 1, 7)])
 def test_pose_rays_forward_backward(amd, dev, B, n, S, opt_cam_pose):
@@ -80,7 +60,7 @@ def test_pose_rays_forward_backward(amd, dev, B, n, S, opt_cam_pose):
     jit = torch.rand(B, S, generator=g, dtype=torch.float64)
     w_o, w_d, w_c = [torch.randn(*s, generator=g, dtype=torch.float64) for s in ((B * n, 3), (B * n, 3), (B, 3, 4))]
     rot_r, tr_r = rot.clone().requires_grad_(), tr.clone().requires_grad_()
-    ref = torch_pose_rays(D, U, rot_r, tr_r, cam, half, jit, S, opt_cam_pose)         # float64 reference of the driver's formulas
+    ref = torch_pose_rays(rot_r, tr_r, cam, half, jit, S, opt_cam_pose)         # float64 reference of the driver's formulas
     ((ref[1] * w_o).sum() + (ref[2] * w_d).sum() + (ref[0] * w_c).sum()).backward()
     f = lambda t: t.float().to(dev)
     rot_d, tr_d = f(rot).requires_grad_(), f(tr).requires_grad_()
@@ -102,7 +82,7 @@ def test_pose_rays_small_angle(amd, dev):
     half, jit = torch.tensor([2.5, 2.7], dtype=torch.float64), torch.rand(2, 16, generator=g, dtype=torch.float64)
     w_d = torch.randn(100, 3, generator=g, dtype=torch.float64)
     rot_r, tr_r = rot.clone().requires_grad_(), tr.clone().requires_grad_()
-    ref = torch_pose_rays(D, U, rot_r, tr_r, cam, half, jit, 16, 0)
+    ref = torch_pose_rays(rot_r, tr_r, cam, half, jit, 16, 0)
     (ref[2] * w_d).sum().backward()
     f = lambda t: t.float().to(dev)
     rot_d, tr_d = f(rot).requires_grad_(), f(tr).requires_grad_()
