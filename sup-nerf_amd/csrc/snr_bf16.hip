@@ -779,23 +779,7 @@ bf16_fwd_kernel(DecoderIO io, Layout L, const float* __restrict__ xyz, const flo
             c[0] = my_sigma; c[1] = my_r; c[2] = my_g; c[3] = my_b;      // c[4] = composite depth, parked there at the start
         }
         __syncthreads();
-        const int S = g.S;
-        const int rays_here = 128 / S;
-        const bool white = g.flags & SNR_WHITE_BKGD;
-        for (int r = wave; r < rays_here; r += 4) {
-            const long long ray = tile128 * rays_here + r;
-            if (ray >= g.n_rays) break;
-            const float* c0 = comp + r * S * COMP_STRIDE;
-            RayOut o = composite_ray_fwd(S, lane_t, white, [&](int k, float& s_, float& r_, float& g_, float& b_, float& z_, float& zn_) {
-                const float* c = c0 + k * COMP_STRIDE;
-                s_ = c[0]; r_ = c[1]; g_ = c[2]; b_ = c[3]; z_ = c[4];
-                zn_ = (k < S - 1) ? c[COMP_STRIDE + 4] : 0.f;
-            });
-            if (lane_t == 0) {
-                out_rgb[ray * 3] = o.r; out_rgb[ray * 3 + 1] = o.g; out_rgb[ray * 3 + 2] = o.b;
-                out_depth[ray] = o.depth; out_acc[ray] = o.acc;
-            }
-        }
+        composite_rays_fwd<128, 4>(comp, g.S, g.flags & SNR_WHITE_BKGD, g.n_rays, tile128, wave, lane_t, out_rgb, out_depth, out_acc);
     }
     SNR_STAMP(14);
 }
@@ -1077,6 +1061,8 @@ bf16_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float
             if (io.d_rgbs) { gr = io.d_rgbs[gp * 3]; gg = io.d_rgbs[gp * 3 + 1]; gb = io.d_rgbs[gp * 3 + 2]; }
         }
     } else {
+        // The composite seed: a copy in each of snr_mlp_bwd.hip, snr_mlp16_bwd.hip and snr_bf16.hip.  Sharing it, whole or in parts, changes the
+        // code of these kernels (register allocation, instruction selection: DESIGN.md 4, "the seed"), so the three copies are kept in step by hand.
         if (lane < 32) comp[(wave * 32 + p) * COMP_STRIDE + 5] = zc;
         __syncthreads();
         const int S = g.S;
@@ -1122,7 +1108,7 @@ bf16_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float
     // private to the wave from here on: LDS operations of one wave execute in order)
     if (lane < 32) {
         float* c = comp + (wave * 32 + p) * COMP_STRIDE;
-        c[0] = gs * -expm1f(-sig_gp); c[1] = gr; c[2] = gg; c[3] = gb;      // softplus'(pre) = -expm1(-sigma) (snr_mlp_bwd.hip)
+        c[0] = gs * softplus_grad(sig_gp); c[1] = gr; c[2] = gg; c[3] = gb;
     }
     float dpre2[2], gr2[2], gg2[2], gb2[2];
 #pragma unroll
@@ -1241,9 +1227,10 @@ bf16_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float
 #pragma unroll
             for (int r = 0; r < 4; ++r) scw[(16 * cb + n16) * PE_ROWF + 16 * T + 4 * gq + r] = accA[cb][T][r];
     float gx = 0.f, gy = 0.f, gz = 0.f, hx = 0.f, hy = 0.f, hz = 0.f;
-    auto pe_grad = [&](int q, int n_freq, float vx, float vy, float vz, float sn, float cs, float& ax, float& ay, float& az) {
-        const int a = q % 3, f = q / 3;
-        const float v = ldexpf(sc[3 + q] * cs - sc[3 + 3 * n_freq + q] * sn, f);
+    // (the axis sums stay written out in each of snr_mlp_bwd.hip, snr_mlp16_bwd.hip and snr_bf16.hip: one function for term and sums changes two of the kernels' code)
+    auto pe_grad = [&](int q, int n_freq, float sn, float cs, float& ax, float& ay, float& az) {
+        const int a = q % 3;
+        const float v = pe_grad_term(sc, q, n_freq, sn, cs);
         ax += a == 0 ? v : 0.f; ay += a == 1 ? v : 0.f; az += a == 2 ? v : 0.f;
     };
 #pragma unroll 1
@@ -1251,14 +1238,14 @@ bf16_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float
         const int q = 15 * h + i;
         f32x2 sn, cs;
         pe_sincos2(f32x2{ldexpf(pick3(px_, py_, pz_, q % 3), q / 3), ldexpf(pick3(px_, py_, pz_, (q + 1) % 3), (q + 1) / 3)}, &sn, &cs);
-        pe_grad(q, XYZ_FREQ, px_, py_, pz_, sn[0], cs[0], gx, gy, gz);
-        pe_grad(q + 1, XYZ_FREQ, px_, py_, pz_, sn[1], cs[1], gx, gy, gz);
+        pe_grad(q, XYZ_FREQ, sn[0], cs[0], gx, gy, gz);
+        pe_grad(q + 1, XYZ_FREQ, sn[1], cs[1], gx, gy, gz);
     }
     {
         const int q = 15 * h + 14;
         float sn, cs;
         pe_sincos(ldexpf(pick3(px_, py_, pz_, q % 3), q / 3), &sn, &cs);
-        pe_grad(q, XYZ_FREQ, px_, py_, pz_, sn, cs, gx, gy, gz);
+        pe_grad(q, XYZ_FREQ, sn, cs, gx, gy, gz);
     }
     if (h == 0) { gx += sc[0]; gy += sc[1]; gz += sc[2]; }
 #pragma unroll
@@ -1272,8 +1259,8 @@ bf16_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float
         const int q = 6 * h + i;
         f32x2 sn, cs;
         pe_sincos2(f32x2{ldexpf(pick3(dx, dy, dz, q % 3), q / 3), ldexpf(pick3(dx, dy, dz, (q + 1) % 3), (q + 1) / 3)}, &sn, &cs);
-        pe_grad(q, DIR_FREQ, dx, dy, dz, sn[0], cs[0], hx, hy, hz);
-        pe_grad(q + 1, DIR_FREQ, dx, dy, dz, sn[1], cs[1], hx, hy, hz);
+        pe_grad(q, DIR_FREQ, sn[0], cs[0], hx, hy, hz);
+        pe_grad(q + 1, DIR_FREQ, sn[1], cs[1], hx, hy, hz);
     }
     if (h == 0) { hx += sc[0]; hy += sc[1]; hz += sc[2]; }
     gx = sum_halves(gx); gy = sum_halves(gy); gz = sum_halves(gz);
@@ -1287,7 +1274,7 @@ bf16_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const float
         }
         return;
     }
-    ray_grad_tail(g, io.d_rays_o, io.d_rays_d, io.d_t, comp, tile128, ray, gp, live, tval, uval, zc, gx, gy, gz, hx, hy, hz, gzc);
+    ray_grad_tail(g, io.d_rays_o, io.d_rays_d, io.d_t, comp, tile128, ray, ray / g.rays_per_obj, gp, live, tval, uval, zc, gx, gy, gz, hx, hy, hz, gzc);
     SNR_BSTAMP(14);
 }
 

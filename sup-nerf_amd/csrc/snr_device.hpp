@@ -345,6 +345,32 @@ __device__ __forceinline__ RayOut composite_ray_fwd(int S, int lane, bool white,
     return o;
 }
 
+// Row of a point in the fused render kernels' composite scratch (LDS)
+constexpr int COMP_STRIDE = 8;        // sigma r g b zc + pad (the backward kernels park zc in slot 5: slots 0..4 receive the composite's gradients)
+
+// Last step of the fused render forwards.  The workgroup's WGP consecutive points lie in the LDS scratch `comp`, COMP_STRIDE floats per
+// point: sigma, r, g, b, composite depth.  S divides WGP; wave `wave` of NW composites rays wave, wave + NW, .. of the workgroup's WGP / S
+// and lane 0 stores their five outputs.  Call behind the barrier that follows the scratch writes.
+template <int WGP, int NW>
+__device__ __forceinline__ void composite_rays_fwd(const float* comp, int S, bool white, long long n_rays, long long tile_wg, int wave, int lane,
+                                                   float* __restrict__ out_rgb, float* __restrict__ out_depth, float* __restrict__ out_acc) {
+    const int rays_here = WGP / S;
+    for (int r = wave; r < rays_here; r += NW) {
+        const long long ray = tile_wg * rays_here + r;
+        if (ray >= n_rays) break;
+        const float* c0 = comp + r * S * COMP_STRIDE;
+        RayOut o = composite_ray_fwd(S, lane, white, [&](int k, float& s_, float& r_, float& g_, float& b_, float& z_, float& zn_) {
+            const float* c = c0 + k * COMP_STRIDE;
+            s_ = c[0]; r_ = c[1]; g_ = c[2]; b_ = c[3]; z_ = c[4];
+            zn_ = (k < S - 1) ? c[COMP_STRIDE + 4] : 0.f;
+        });
+        if (lane == 0) {
+            out_rgb[ray * 3] = o.r; out_rgb[ray * 3 + 1] = o.g; out_rgb[ray * 3 + 2] = o.b;
+            out_depth[ray] = o.depth; out_acc[ray] = o.acc;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ alpha composite, backward
 // Analytic gradient of the above for S <= 64*NCH.  `fetch` as before; `emit(k, d_sigma, d_cr, d_cg,
 // d_cb, d_z)` receives the per-sample gradients (d_z includes both the depth and the delta paths).
@@ -405,6 +431,18 @@ __device__ __forceinline__ void composite_ray_bwd(int S, int lane, bool white, f
     }
 }
 
+// ------------------------------------------------------------------ pieces of the decoder backward kernels
+// softplus'(pre) = sigmoid(pre) = 1 - exp(-sigma) with sigma = softplus(pre), formed as -expm1(-sigma): 1 - expf(-sigma) is exactly 0
+// for sigma below ~6e-8 (pre below ~-16.6), where sigmoid(pre) ~ sigma still matters (the last, 1e10-wide interval turns sigma ~ 1e-10
+// into an alpha of order 1); exact 1 in fp32 past the threshold
+__device__ __forceinline__ float softplus_grad(float sigma) { return -expm1f(-sigma); }
+
+// Positional-encoding backward, pair q = 3 f + a of an encoding of n_freq frequencies: `row` holds the gradients wrt the encoding's features
+// (the vector itself, 3 n_freq sines, 3 n_freq cosines), (sn, cs) = sin / cos of 2^f v[a].  Returns the pair's term of the gradient wrt v[a].
+__device__ __forceinline__ float pe_grad_term(const float* row, int q, int n_freq, float sn, float cs) {
+    return ldexpf(row[3 + q] * cs - row[3 + 3 * n_freq + q] * sn, q / 3);
+}
+
 // ------------------------------------------------------------------ sample point -> ray, backward
 // One thread finishes one ray: c[0..2] = gradient wrt the sampling-frame origin, c[3..5] wrt the direction, c[6], c[7] = gradient wrt the
 // box bounds near / far (SNR_Z_BOX, summed over the ray's samples).  SNR_Z_BOX: the bounds' gradient goes back through the slab test
@@ -445,16 +483,17 @@ __device__ __forceinline__ void ray_finish(const RayGeom& g, long long ray, floa
     if (d_rays_d) { d_rays_d[ray * 3] = c[3]; d_rays_d[ray * 3 + 1] = c[4]; d_rays_d[ray * 3 + 2] = c[5]; }
 }
 
-// Tail of the render-mode backward kernels, called by all 256 threads of the workgroup (128 consecutive sample points, S divides 128; both
-// half-waves of a wave hold the same 32 points): per lane the gradient wrt the decoder-frame point (gx, gy, gz) and direction
-// (hx, hy, hz) and the composite's gradient wrt the depth it was given (gzc) -> d_t per sample, d_rays_o / d_rays_d per ray
+// Tail of the render-mode backward kernels, called by all 256 threads of the workgroup: four waves of PW points each (32: one wave per SIMD,
+// both half-waves hold the same points; 16: two waves per SIMD, the four lane groups do), 4 PW consecutive sample points, S divides 4 PW.
+// Per lane the gradient wrt the decoder-frame point (gx, gy, gz) and direction (hx, hy, hz) and the composite's gradient wrt the depth it
+// was given (gzc) -> d_t per sample, d_rays_o / d_rays_d per ray
 // (p' = M (((o + t d) / div) mul), dir' = M d; segmented wave sums over the samples of a ray, LDS combine across waves, no atomics).
-// `part`: 64 floats of LDS nobody else uses any more.
+// `tile`: the workgroup's index; `obj` = ray / rays_per_obj; `part`: 64 floats of LDS nobody else uses any more.
+template <int PW = 32>
 __device__ __forceinline__ void ray_grad_tail(const RayGeom& g, float* __restrict__ d_rays_o, float* __restrict__ d_rays_d, float* __restrict__ d_t,
-                                              float* part, long long tile128, long long ray, long long gp, bool live, float tval, float u,
+                                              float* part, long long tile, long long ray, long long obj, long long gp, bool live, float tval, float u,
                                               float zc, float gx, float gy, float gz, float hx, float hy, float hz, float gzc) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31, h = lane >> 5;
-    const long long obj = ray / g.rays_per_obj;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & (PW - 1), h = lane / PW;
     const bool box = g.z_mode == SNR_Z_BOX;
     const float sc_ = box ? g.xyz_mul : g.xyz_mul / g.xyz_div[obj];
     // M^T g
@@ -486,11 +525,11 @@ __device__ __forceinline__ void ray_grad_tail(const RayGeom& g, float* __restric
 #endif
     if (!(d_rays_o || d_rays_d)) return;
     const int S = g.S;
-    const int G = S < 32 ? S : 32;      // lanes of this wave that share a ray (S divides 128)
+    const int G = S < PW ? S : PW;      // lanes of this wave that share a ray
 #pragma unroll
     for (int i = 0; i < 6; ++i) c[i] = group_sum(c[i], G);
     if (box) { c[6] = group_sum(c[6], G); c[7] = group_sum(c[7], G); }
-    if (S <= 32) {
+    if (S <= PW) {
         if (live && h == 0 && (p % S) == 0) ray_finish(g, ray, c, d_rays_o, d_rays_d);
         return;
     }
@@ -500,10 +539,10 @@ __device__ __forceinline__ void ray_grad_tail(const RayGeom& g, float* __restric
         for (int i = 0; i < 8; ++i) part[wave * 8 + i] = c[i];
     }
     __syncthreads();
-    const int waves_per_ray = S / 32;              // 2 or 4
-    const int rays_here = 128 / S;
+    const int waves_per_ray = S / PW;              // 2 or 4
+    const int rays_here = 4 * PW / S;
     if (tid < rays_here) {
-        const long long rr = tile128 * rays_here + tid;
+        const long long rr = tile * rays_here + tid;
         if (rr < g.n_rays) {
             float s[8];
 #pragma unroll

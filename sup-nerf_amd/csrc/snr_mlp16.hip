@@ -25,6 +25,7 @@
 // 8 + r, 12 + r}, the 32x32x2 form k = 32 c + 8 j + {e, 4 + e}): both are exact fp32 fma chains over the same products, results agree
 // to fp32 round-off, not bit for bit.
 #include <atomic>
+#include <type_traits>
 
 #include "snr_mlp16_core.hpp"
 #include "snr_host.hpp"
@@ -450,23 +451,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
             c[0] = o_sigma; c[1] = o_r; c[2] = o_g; c[3] = o_b; c[4] = zc;
         }
         __syncthreads();
-        const int S = gm.S;
-        const int rays_here = WGP / S;           // host guarantees WGP % S == 0
-        const bool white = gm.flags & SNR_WHITE_BKGD;
-        for (int r = wave; r < rays_here; r += WAVES) {
-            const long long ray = tile_wg * rays_here + r;
-            if (ray >= gm.n_rays) break;
-            const float* c0 = comp + r * S * COMP_STRIDE;
-            RayOut o = composite_ray_fwd(S, lane, white, [&](int k, float& s_, float& r_, float& g_, float& b_, float& z_, float& zn_) {
-                const float* c = c0 + k * COMP_STRIDE;
-                s_ = c[0]; r_ = c[1]; g_ = c[2]; b_ = c[3]; z_ = c[4];
-                zn_ = (k < S - 1) ? c[COMP_STRIDE + 4] : 0.f;
-            });
-            if (lane == 0) {
-                out_rgb[ray * 3] = o.r; out_rgb[ray * 3 + 1] = o.g; out_rgb[ray * 3 + 2] = o.b;
-                out_depth[ray] = o.depth; out_acc[ray] = o.acc;
-            }
-        }
+        composite_rays_fwd<WGP, WAVES>(comp, gm.S, gm.flags & SNR_WHITE_BKGD, gm.n_rays, tile_wg, wave, lane, out_rgb, out_depth, out_acc);      // (the host guarantees WGP % S == 0)
     }
     SNR16_STAMP(7);
 }
@@ -502,55 +487,60 @@ static int launch16(const DecoderIO& io, const Layout& L, const Lds16& lo, const
     return snr_check_launch_();
 }
 
-template <int WAVES>
-static int launch16_w(int mode, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
-                      float* depth, float* acc, hipStream_t st) {
-    const bool latlds = (io.points_per_obj % (WAVES * 16)) == 0 && L.n_lat <= LDS_LAT_ROWS;
-    const bool masks = io.masks != nullptr;
-    const Lds16 lo = make_lds16(WAVES, L.n_mfma_layers, latlds ? L.n_lat : LDS_LAT_ROWS + 1);
-#define SNR_L16(M, LL, MK) launch16<M, WAVES, LL, MK>(io, L, lo, xyz, viewdir, g, rgb, depth, acc, st)
-    if (mode == MODE_POINTS) {
-        if (latlds) return masks ? SNR_L16(0, true, true) : SNR_L16(0, true, false);
-        return masks ? SNR_L16(0, false, true) : SNR_L16(0, false, false);
-    }
-    if (latlds) return masks ? SNR_L16(1, true, true) : SNR_L16(1, true, false);
-    return masks ? SNR_L16(1, false, true) : SNR_L16(1, false, false);
-#undef SNR_L16
+// The shape of a launch (see above), decided here for every launcher of this file: four waves whenever the map fits two workgroups per CU
+// and a render's ray lies inside 64 points, else eight; the latent rows in LDS or not; the LDS map of that choice.
+struct Shape16 { int waves; bool latlds; Lds16 lo; };
+static Shape16 launch_shape16(int mode, const DecoderIO& io, const Layout& L, int S) {
+    auto with = [&](int waves) {
+        Shape16 s;
+        s.waves = waves;
+        s.latlds = (io.points_per_obj % (waves * 16)) == 0 && L.n_lat <= LDS_LAT_ROWS;
+        s.lo = make_lds16(waves, L.n_mfma_layers, s.latlds ? L.n_lat : LDS_LAT_ROWS + 1);
+        return s;
+    };
+    const Shape16 four = with(4);
+    const bool fits = four.lo.total * 4 <= 80 * 1024 && (mode != MODE_RENDER || (S <= 64 && 64 % S == 0));
+    return fits ? four : with(8);
+}
+
+// The one dispatch over (MODE, WAVES, LATLDS, MASKS): the launchers below name MODE and the shape's WAVES, this picks the instantiation for the
+// shape's LATLDS and for MASKS (io.masks set; modes 3 and 4 save no ReLU bits and have no such kernels).  The order in which the instantiations
+// are first named is the order of the kernels in the code object, and it is kept as it has been: that is why WAVES is chosen by the callers
+// (modes 0 and 1 alternate inside each WAVES) and why the nesting of the two flags differs between the families.
+template <int MODE, int WAVES>
+static int launch16_flags(const Shape16& s, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const typename PointSrc<MODE>::T& src,
+                          float* rgb, float* depth, float* acc, hipStream_t st) {
+    auto go = [&](auto latlds, auto masks) {
+        return launch16<MODE, WAVES, decltype(latlds)::value, decltype(masks)::value>(io, L, s.lo, xyz, viewdir, src, rgb, depth, acc, st);
+    };
+    constexpr std::true_type Y{};
+    constexpr std::false_type N{};
+    const bool ll = s.latlds, mk = io.masks != nullptr;
+    if constexpr (MODE == MODE_POINTS || MODE == MODE_RENDER) return ll ? (mk ? go(Y, Y) : go(Y, N)) : (mk ? go(N, Y) : go(N, N));
+    else if constexpr (MODE == MODE_DENSITY) return mk ? (ll ? go(Y, Y) : go(N, Y)) : (ll ? go(Y, N) : go(N, N));
+    else return ll ? go(Y, N) : go(N, N);
 }
 
 int snr_fp32_fwd16_launch_(int mode, const DecoderIO& io, const Layout& L, const float* xyz, const float* viewdir, const RayGeom& g, float* rgb,
                            float* depth, float* acc, void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
     if (io.act) return SNR_E_UNSUPPORTED;          // (training dumps: snr_mlp.hip's kernel, whose dump stores are staged through LDS; this one has none)
-    const bool lat4 = (io.points_per_obj % 64) == 0 && L.n_lat <= LDS_LAT_ROWS;
-    const Lds16 lo4 = make_lds16(4, L.n_mfma_layers, lat4 ? L.n_lat : LDS_LAT_ROWS + 1);
-    const bool four = lo4.total * 4 <= 80 * 1024 && (mode == MODE_POINTS || (g.S <= 64 && 64 % g.S == 0));
-    return four ? launch16_w<4>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st) : launch16_w<8>(mode, io, L, xyz, viewdir, g, rgb, depth, acc, st);
+    const Shape16 s = launch_shape16(mode, io, L, g.S);
+    if (s.waves == 4) return mode == MODE_POINTS ? launch16_flags<MODE_POINTS, 4>(s, io, L, xyz, viewdir, g, rgb, depth, acc, st)
+                                                 : launch16_flags<MODE_RENDER, 4>(s, io, L, xyz, viewdir, g, rgb, depth, acc, st);
+    return mode == MODE_POINTS ? launch16_flags<MODE_POINTS, 8>(s, io, L, xyz, viewdir, g, rgb, depth, acc, st)
+                               : launch16_flags<MODE_RENDER, 8>(s, io, L, xyz, viewdir, g, rgb, depth, acc, st);
 }
 
 // density only (modes 2, 3 and 4): the shapes and the latent staging of mode 0, no dumps.  Mode 2 saves the ReLU bits of enc_xyz and the shape
 // layers when io.masks is set (the slots snr_decoder_fwd writes for them; the texture-branch slots are left as they are)
-template <int MODE, int WAVES>
-static int launch16_dens(const DecoderIO& io, const Layout& L, const float* xyz, const typename PointSrc<MODE>::T& src, hipStream_t st) {
-    const bool latlds = (io.points_per_obj % (WAVES * 16)) == 0 && L.n_lat <= LDS_LAT_ROWS;
-    const Lds16 lo = make_lds16(WAVES, L.n_mfma_layers, latlds ? L.n_lat : LDS_LAT_ROWS + 1);
-    if constexpr (MODE == MODE_DENSITY) {
-        if (io.masks) {
-            if (latlds) return launch16<MODE, WAVES, true, true>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
-            return launch16<MODE, WAVES, false, true>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
-        }
-    }
-    if (latlds) return launch16<MODE, WAVES, true, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
-    return launch16<MODE, WAVES, false, false>(io, L, lo, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
-}
-
 template <int MODE>
 static int density_launch(const DecoderIO& io, const float* xyz, const typename PointSrc<MODE>::T& src, void* stream_) {
     const Layout L = make_layout(io.sb, io.tb);
-    const bool lat4 = (io.points_per_obj % 64) == 0 && L.n_lat <= LDS_LAT_ROWS;
-    const bool four = make_lds16(4, L.n_mfma_layers, lat4 ? L.n_lat : LDS_LAT_ROWS + 1).total * 4 <= 80 * 1024;      // as snr_fp32_fwd16_launch_, mode 0
+    const Shape16 s = launch_shape16(MODE, io, L, 0);
     hipStream_t st = (hipStream_t)stream_;
-    return four ? launch16_dens<MODE, 4>(io, L, xyz, src, st) : launch16_dens<MODE, 8>(io, L, xyz, src, st);
+    return s.waves == 4 ? launch16_flags<MODE, 4>(s, io, L, xyz, nullptr, src, nullptr, nullptr, nullptr, st)
+                        : launch16_flags<MODE, 8>(s, io, L, xyz, nullptr, src, nullptr, nullptr, nullptr, st);
 }
 
 int snr_density_points_launch_(const DecoderIO& io, const float* xyz, void* stream_) { return density_launch<MODE_DENSITY>(io, xyz, RayGeom{}, stream_); }

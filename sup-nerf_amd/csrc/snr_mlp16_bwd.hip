@@ -40,13 +40,6 @@ __device__ __forceinline__ void chunk_b(const Dma16& d, const float* __restrict_
         if (i * 32 < rows) piece_b(d, g, lds_dst, lds_base, rows, i);
 }
 
-struct RingB { int cur; int aoff[2]; };
-__device__ __forceinline__ void ring_turn_b(RingB& p) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    p.cur ^= 1;
-}
-
 // accumulator value -> operand value with the saved ReLU bit applied: bit (8 (T & 3) + r) of the lane's pre-shifted word T >> 2
 __device__ __forceinline__ float masked(float v, const uint32_t (&mw)[4], int T, int r) {
     const int keep = __builtin_amdgcn_sbfe((int)mw[T >> 2], 8 * (T & 3) + r, 1);
@@ -59,7 +52,7 @@ __device__ __forceinline__ float masked(float v, const uint32_t (&mw)[4], int T,
 // after_first_turn(): called behind the layer's first chunk rendezvous (the workgroup's latent-gradient rows of the layer before are complete then).
 struct Nothing { __device__ __forceinline__ void operator()() const {} };
 template <int NT, int NCH, bool FROM_ACC, class After = Nothing>
-__device__ __forceinline__ void layer_b(f32x4 (&accP)[18], const f32x4* xin, RingB& ring, float* lds, const uint32_t (&mw)[4], const Dma16& dm,
+__device__ __forceinline__ void layer_b(f32x4 (&accP)[18], const f32x4* xin, Ring16& ring, float* lds, const uint32_t (&mw)[4], const Dma16& dm,
                                         const float* base, const float* next_first, int next_rows, After&& after_first_turn = Nothing()) {
     f32x4 accC[18];
     f32x4 a0, a1;
@@ -101,7 +94,7 @@ __device__ __forceinline__ void layer_b(f32x4 (&accP)[18], const f32x4* xin, Rin
                 } else if (gi == 0) xa = xin[2 * ch + 2];
             });
         }
-        ring_turn_b(ring);
+        ring_turn(ring);
         if (ch == 0) after_first_turn();
     }
 }
@@ -109,7 +102,7 @@ __device__ __forceinline__ void layer_b(f32x4 (&accP)[18], const f32x4* xin, Rin
 // enc_xyz^T (256 -> 64 features: 4 output tiles, 8 chunks of 64 rows): four chunks at a time (one 32 KiB piece of the stream = one ring
 // buffer), so the layer has two ring turns instead of eight -- a 64-row chunk is 32 MFMAs per wave, less than the latency of its own DMA.
 template <class After>
-__device__ __forceinline__ void layer_xyz_b(f32x4 (&accP)[18], RingB& ring, float* lds, const uint32_t (&mw)[4], const Dma16& dm, const float* base,
+__device__ __forceinline__ void layer_xyz_b(f32x4 (&accP)[18], Ring16& ring, float* lds, const uint32_t (&mw)[4], const Dma16& dm, const float* base,
                                             After&& after_first_turn) {
     f32x4 accC[4];
     f32x4 a0, a1, xa, xb;
@@ -145,7 +138,7 @@ __device__ __forceinline__ void layer_xyz_b(f32x4 (&accP)[18], RingB& ring, floa
             if (ch == 7) tile_mma<4, TM_LAST>(accC, accP, xb, wc + ring.aoff[1], a0, a1, wn);
             else tile_mma<4, 0>(accC, accP, xb, wc + ring.aoff[1], a0, a1, wn, mask_a);
         }
-        ring_turn_b(ring);
+        ring_turn(ring);
         if (sc == 0) after_first_turn();
     }
 }
@@ -195,69 +188,6 @@ __device__ __forceinline__ void flush_latent_rows(const float* red /* lds + LB_R
     dst[tid] = s;
 }
 
-// Tail of the render-mode backward for 16 points per wave (all 256 threads; 64 consecutive sample points, S divides 64; the four lane groups
-// of a point hold the same values): snr_device.hpp's ray_grad_tail for this lane layout.
-__device__ __forceinline__ void ray_grad_tail16(const RayGeom& g, float* __restrict__ d_rays_o, float* __restrict__ d_rays_d, float* __restrict__ d_t,
-                                                float* part, long long tile64, long long ray, long long obj, long long gp, bool live, float tval, float u,
-                                                float zc, float gx, float gy, float gz, float hx, float hy, float hz, float gzc) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, gg = lane >> 4;
-    const bool box = g.z_mode == SNR_Z_BOX;
-    const float sc_ = box ? g.xyz_mul : g.xyz_mul / g.xyz_div[obj];
-    const float px = (g.m[0] * gx + g.m[3] * gy + g.m[6] * gz) * sc_;
-    const float py = (g.m[1] * gx + g.m[4] * gy + g.m[7] * gz) * sc_;
-    const float pz = (g.m[2] * gx + g.m[5] * gy + g.m[8] * gz) * sc_;
-    const float qx = g.m[0] * hx + g.m[3] * hy + g.m[6] * hz;
-    const float qy = g.m[1] * hx + g.m[4] * hy + g.m[7] * hz;
-    const float qz = g.m[2] * hx + g.m[5] * hy + g.m[8] * hz;
-    const float rdx = g.rays_d[ray * 3], rdy = g.rays_d[ray * 3 + 1], rdz = g.rays_d[ray * 3 + 2];
-    float c[8] = {px, py, pz, tval * px + qx, tval * py + qy, tval * pz + qz, 0.f, 0.f};
-    float dt = rdx * px + rdy * py + rdz * pz;
-    if (g.flags & SNR_METRIC_Z) {
-        const float zs = g.z_scale[obj];
-        const float k = zc > 0.f ? gzc * zs * zs * tval / zc : 0.f;
-        dt += k * (rdx * rdx + rdy * rdy + rdz * rdz);
-        c[3] += k * tval * rdx; c[4] += k * tval * rdy; c[5] += k * tval * rdz;
-    } else {
-        dt += gzc;
-    }
-    if (box) { c[6] = dt * (1.f - u); c[7] = dt * u; }
-    if (!(live && gg == 0)) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c[i] = 0.f;
-    }
-    if (d_t && !box && live && gg == 0) d_t[gp] = dt;
-    if (!(d_rays_o || d_rays_d)) return;
-    const int S = g.S;
-    const int G = S < 16 ? S : 16;      // lanes of group 0 of this wave that share a ray (S divides 64)
-#pragma unroll
-    for (int i = 0; i < 6; ++i) c[i] = group_sum(c[i], G);
-    if (box) { c[6] = group_sum(c[6], G); c[7] = group_sum(c[7], G); }
-    if (S <= 16) {
-        if (live && gg == 0 && (n % S) == 0) ray_finish(g, ray, c, d_rays_o, d_rays_d);
-        return;
-    }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) part[wave * 8 + i] = c[i];
-    }
-    __syncthreads();
-    const int waves_per_ray = S / 16;              // 2 or 4
-    const int rays_here = 64 / S;
-    if (tid < rays_here) {
-        const long long rr = tile64 * rays_here + tid;
-        if (rr < g.n_rays) {
-            float s[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                s[i] = 0.f;
-                for (int w = 0; w < waves_per_ray; ++w) s[i] += part[(tid * waves_per_ray + w) * 8 + i];
-            }
-            ray_finish(g, rr, s, d_rays_o, d_rays_d);
-        }
-    }
-}
-
 #ifdef SNR_STAMPS   /* diagnostic build: s_memtime at phase boundaries into the d_t buffer, 8 per 16-point wave tile (tools/_diag/stamps16.py) */
 #define SNR16_BSTAMP(i) do { if (io.d_t && lane == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
         reinterpret_cast<unsigned long long*>(io.d_t)[tile16 * 8 + (i)] = t_; } } while (0)
@@ -293,7 +223,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     dm.voff = lane * 16u + 4096u;
     dm.lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)lds);
     dm.wave = __builtin_amdgcn_readfirstlane(wave);
-    RingB ring;
+    Ring16 ring;
     ring.cur = 0;
     {
         const int sw = (n >> 1) & 7;
@@ -341,6 +271,8 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
         if (io.partial)           // texture rows of this workgroup's partials: nothing reaches them
             for (int t = 0; t < tb; ++t) io.partial[(tile64 * L.n_lat + sb + t) * 256 + tid] = 0.f;
     } else {
+        // The composite seed: a copy in each of snr_mlp_bwd.hip, snr_mlp16_bwd.hip and snr_bf16.hip.  Sharing it, whole or in parts, changes the
+        // code of these kernels (register allocation, instruction selection: DESIGN.md 4, "the seed"), so the three copies are kept in step by hand.
         float* comp = lds + LB_RING1;            // (over ring buffer 1: chunk 1 is requested behind the barriers below)
         if (g == 0) comp[(wave * 16 + n) * COMP_STRIDE + 5] = zc;
         __syncthreads();
@@ -373,10 +305,7 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
             gs = c[0]; gr = c[1]; ggr = c[2]; gb = c[3]; gzc = c[4];
         }
     }
-    // softplus'(pre) = sigmoid(pre) = 1 - exp(-sigma) with sigma = softplus(pre), formed as -expm1(-sigma): 1 - expf(-sigma) is exactly 0
-    // for sigma below ~6e-8 (pre below ~-16.6), where sigmoid(pre) ~ sigma still matters (the last, 1e10-wide interval turns sigma ~ 1e-10
-    // into an alpha of order 1); exact 1 in fp32 past the threshold
-    const float dpre = gs * -expm1f(-io.sigmas[gp]);
+    const float dpre = gs * softplus_grad(io.sigmas[gp]);
 
     // the lane's ReLU bits of a layer, pre-shifted so that feature 16 T + 4 g + r is bit 8 (T & 3) + r of word T >> 2 (snr_mlp16.hip, store_masks16x4)
     auto load_bits = [&](int slot, uint32_t (&mw)[4]) {
@@ -475,9 +404,10 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
     }
     __syncthreads();
     float gx = 0.f, gy = 0.f, gz = 0.f, hx = 0.f, hy = 0.f, hz = 0.f;
+    // (the axis sums stay written out in each of snr_mlp_bwd.hip, snr_mlp16_bwd.hip and snr_bf16.hip: one function for term and sums changes two of the kernels' code)
     auto pe_grad = [&](const float* row, int q, int n_freq, float sn, float cs, float& ax, float& ay, float& az) {
-        const int a = q % 3, f = q / 3;
-        const float v = ldexpf(row[3 + q] * cs - row[3 + 3 * n_freq + q] * sn, f);
+        const int a = q % 3;
+        const float v = pe_grad_term(row, q, n_freq, sn, cs);
         ax += a == 0 ? v : 0.f; ay += a == 1 ? v : 0.f; az += a == 2 ? v : 0.f;
     };
 #pragma unroll 1
@@ -523,12 +453,8 @@ decoder_bwd16_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const fl
         }
         return;
     }
-#ifdef SNR_STAMPS
-    ray_grad_tail16(gm, io.d_rays_o, io.d_rays_d, nullptr, lds + LB_PART, tile64, ray, obj, gp, live, tval, uval, zc, gx, gy, gz, hx, hy, hz, gzc);
+    ray_grad_tail<16>(gm, io.d_rays_o, io.d_rays_d, io.d_t, lds + LB_PART, tile64, ray, obj, gp, live, tval, uval, zc, gx, gy, gz, hx, hy, hz, gzc);
     SNR16_BSTAMP(7);
-#else
-    ray_grad_tail16(gm, io.d_rays_o, io.d_rays_d, io.d_t, lds + LB_PART, tile64, ray, obj, gp, live, tval, uval, zc, gx, gy, gz, hx, hy, hz, gzc);
-#endif
 }
 
 }  // namespace snr

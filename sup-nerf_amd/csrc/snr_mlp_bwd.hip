@@ -152,6 +152,8 @@ decoder_bwd_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const floa
             if (io.d_rgbs) { gr = io.d_rgbs[gp * 3]; gg = io.d_rgbs[gp * 3 + 1]; gb = io.d_rgbs[gp * 3 + 2]; }
         }
     } else {
+        // The composite seed: a copy in each of snr_mlp_bwd.hip, snr_mlp16_bwd.hip and snr_bf16.hip.  Sharing it, whole or in parts, changes the
+        // code of these kernels (register allocation, instruction selection: DESIGN.md 4, "the seed"), so the three copies are kept in step by hand.
         float* comp = lds + LDS_COMP;
         if (lane < 32) comp[(wave * 32 + p) * COMP_STRIDE + 5] = zc;
         __syncthreads();
@@ -194,10 +196,7 @@ decoder_bwd_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const floa
             gs = c[0]; gr = c[1]; gg = c[2]; gb = c[3]; gzc = c[4];
         }
     }
-    // softplus'(pre) = sigmoid(pre) = 1 - exp(-sigma) with sigma = softplus(pre), formed as -expm1(-sigma): 1 - expf(-sigma) is exactly 0
-    // for sigma below ~6e-8 (pre below ~-16.6), where sigmoid(pre) ~ sigma still matters (the last, 1e10-wide interval turns sigma ~ 1e-10
-    // into an alpha of order 1); exact 1 in fp32 past the threshold
-    const float dpre = gs * -expm1f(-io.sigmas[gp]);
+    const float dpre = gs * softplus_grad(io.sigmas[gp]);
 
     float in[9][16];
     f32x16 acc[9];
@@ -308,12 +307,13 @@ decoder_bwd_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const floa
     for (int r = 0; r < 16; ++r) sc[64 + 8 * (r >> 2) + 4 * h + (r & 3)] = gdir[r];
     __syncthreads();
     float gx = 0.f, gy = 0.f, gz = 0.f, hx = 0.f, hy = 0.f, hz = 0.f;
+    // (the axis sums stay written out in each of snr_mlp_bwd.hip, snr_mlp16_bwd.hip and snr_bf16.hip: one function for term and sums changes two of the kernels' code)
 #pragma unroll 1
     for (int i = 0; i < 15; ++i) {
         const int q = 15 * h + i, a = q % 3, f = q / 3;
         float sn, cs;
         pe_sincos(ldexpf(pick3(x, y, z, a), f), &sn, &cs);
-        const float v = ldexpf(sc[3 + q] * cs - sc[3 + 3 * XYZ_FREQ + q] * sn, f);
+        const float v = pe_grad_term(sc, q, XYZ_FREQ, sn, cs);
         gx += a == 0 ? v : 0.f; gy += a == 1 ? v : 0.f; gz += a == 2 ? v : 0.f;
     }
 #pragma unroll 1
@@ -321,7 +321,7 @@ decoder_bwd_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const floa
         const int q = 6 * h + i, a = q % 3, f = q / 3;
         float sn, cs;
         pe_sincos(ldexpf(pick3(dx, dy, dz, a), f), &sn, &cs);
-        const float v = ldexpf(sc[64 + 3 + q] * cs - sc[64 + 3 + 3 * DIR_FREQ + q] * sn, f);
+        const float v = pe_grad_term(sc + 64, q, DIR_FREQ, sn, cs);
         hx += a == 0 ? v : 0.f; hy += a == 1 ? v : 0.f; hz += a == 2 ? v : 0.f;
     }
     if (h == 0) { gx += sc[0]; gy += sc[1]; gz += sc[2]; hx += sc[64]; hy += sc[65]; hz += sc[66]; }
@@ -338,8 +338,8 @@ decoder_bwd_kernel(BwdIO io, Layout L, const float* __restrict__ xyz, const floa
 
     // ---- sample point -> ray: p' = M (((o + t d) / div) mul), dir' = M d
     SNR32_BSTAMP(13);
-    ray_grad_tail(g, io.d_rays_o, io.d_rays_d, io.d_t, lds + LDS_COMP /* the composite scratch is free by now */, tile128, ray, gp, live, tval, uval, zc,
-                  gx, gy, gz, hx, hy, hz, gzc);
+    ray_grad_tail(g, io.d_rays_o, io.d_rays_d, io.d_t, lds + LDS_COMP /* the composite scratch is free by now */, tile128, ray, ray / g.rays_per_obj, gp, live, tval,
+                  uval, zc, gx, gy, gz, hx, hy, hz, gzc);
 }
 
 }  // namespace snr

@@ -9,7 +9,6 @@ constexpr int WBUF = K_VIEW_PAD * KC;               // floats per weight buffer 
 constexpr int PE_ROW = 97;                          // per-point scratch row: 64 xyz features + 32 dir features + 1
 constexpr int PE_WAVE = 32 * PE_ROW;
 constexpr int LDS_SCRATCH = 2 * WBUF;               // 4 waves x PE_WAVE
-constexpr int COMP_STRIDE = 8;                      // sigma r g b zc + pad
 constexpr int LDS_COMP = LDS_SCRATCH + 4 * PE_WAVE;
 constexpr int LDS_BIAS = LDS_COMP + 128 * COMP_STRIDE;    // forward: every MFMA layer's bias (n_mfma_layers x 256) and, right behind them as in
                                                           // the packed stream, the two small heads (648 floats), staged once per workgroup
