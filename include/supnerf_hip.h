@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 15
+#define SNR_ABI_VERSION 16
 
 enum {
     SNR_OK = 0,
@@ -199,6 +199,25 @@ int snr_render_bwd(const snr_render_args* a, const float* sigmas, const float* r
  * ---------------------------------------------------------------------------------- */
 int snr_scene_composite_fwd(const float* sigmas, const float* rgbs, const float* z_vals, int64_t n_pixels, int n_per_pixel, int run_length,
                             int flags, float* rgb, float* depth, float* acc_trans, void* stream);
+/* Backward of the above.  Per pixel, with n = n_per_pixel samples i = 0..n-1 in memory order:
+ *   lt_i = #{j : z_j < z_i},  eb_i = #{j < i : z_j == z_i},  ea_i = #{j > i : z_j == z_i};
+ *   sample i owns slot pos_i = lt_i + eb_i (a permutation) and the sorted depth row is zs[pos_i] = z_i;
+ *   slot lt_i receives (sigma_i, rgb_i) from its group's survivor, the member with ea_i == 0 (the last in memory order); the group's
+ *   other slots hold sigma 0 and rgb 0;
+ *   the sorted rows are composited like every ray here: relu on sigma, last interval 1e10, transmittance + 1e-10, white background.
+ * Given d_rgb (P,3), d_depth (P) and d_acc (P) [the last two nullable = zero]:
+ *   1. the analytic composite backward runs on the sorted rows and gives every slot (d_sigma, d_r, d_g, d_b, d_z);
+ *   2. sample i receives the d_sigma and d_rgb of slot lt_i if it is its group's survivor, and exact zeros otherwise;
+ *   3. sample i receives the d_z of its own slot pos_i;
+ *   4. at an exact tie the survivor's interval has width 0, so its weight and its sigma gradient are 0 by the formulas: only d_z tells
+ *      tied members apart, and rule 3 fixes it;
+ *   5. every output element is written exactly once by one lane, without atomics: the same bits from run to run;
+ *   6. run_length only changes how the ranks are found (verified per pixel as in the forward): the same bits for 0 and S.
+ * -> d_sigmas (P,n), d_rgbs (P,n,3), d_z (P,n) [nullable].  flags: SNR_WHITE_BKGD.  n_per_pixel <= 512 (8 objects x 64 samples), more is
+ * SNR_E_UNSUPPORTED.  One launch; tests/scene_grad_restatement.py states the same rules in a few lines of torch. */
+int snr_scene_composite_bwd(const float* sigmas, const float* rgbs, const float* z_vals, int64_t n_pixels, int n_per_pixel, int run_length,
+                            int flags, const float* d_rgb, const float* d_depth, const float* d_acc,
+                            float* d_sigmas, float* d_rgbs, float* d_z, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Alpha composite alone: replaces volume_rendering2 / volume_rendering_batch

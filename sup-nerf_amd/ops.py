@@ -223,6 +223,65 @@ def scene_composite(sigmas, rgbs, z_vals, white_bkgd=True, run_length=0):
     return rgb, depth, acc
 
 
+SCENE_BWD_MAX_N = 512       # snr_scene_composite_bwd: samples per pixel (8 objects x 64 samples)
+
+
+def _scene_shapes(name, sigmas, rgbs, z_vals):
+    if sigmas.dim() != 2 or rgbs.shape != (*sigmas.shape, 3) or z_vals.shape != sigmas.shape:
+        raise SnrError(f"{name}: expected sigmas/z (P,n) and rgbs (P,n,3), got {tuple(sigmas.shape)}, {tuple(z_vals.shape)}, {tuple(rgbs.shape)}")
+    return sigmas.shape
+
+
+def scene_composite_bwd(sigmas, rgbs, z_vals, white_bkgd, run_length, d_rgb, d_depth=None, d_acc=None, need_dz=True):
+    """Backward of ``scene_composite`` in one launch (rules: include/supnerf_hip.h): d_rgb (P,3), d_depth (P) / d_acc (P) or None
+    -> d_sigmas (P,n), d_rgbs (P,n,3), d_z (P,n) or None.  n <= 512."""
+    sigmas, rgbs, z_vals = _f32c(sigmas), _f32c(rgbs), _f32c(z_vals)
+    # dense copies are NAMED so that they live until the launch is enqueued (see composite_bwd)
+    d_rgb, d_depth, d_acc = _f32c(d_rgb), _f32c(d_depth), _f32c(d_acc)
+    _need_gpu(sigmas, rgbs, z_vals, d_rgb, d_depth, d_acc)
+    P, n = _scene_shapes("scene_composite_bwd", sigmas, rgbs, z_vals)
+    if d_rgb is None or d_rgb.shape != (P, 3) or any(g is not None and g.numel() != P for g in (d_depth, d_acc)):
+        raise SnrError(f"scene_composite_bwd: expected d_rgb ({P},3) and d_depth / d_acc ({P},) or None")
+    if n > SCENE_BWD_MAX_N:
+        raise SnrError(f"scene_composite_bwd: {n} samples per pixel, the backward takes at most {SCENE_BWD_MAX_N}")
+    dev = sigmas.device
+    d_sig = torch.empty(P, n, device=dev)
+    d_rgbs = torch.empty(P, n, 3, device=dev)
+    d_z = torch.empty(P, n, device=dev) if need_dz else None
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_scene_composite_bwd(_p(sigmas), _p(rgbs), _p(z_vals), P, n, int(run_length), WHITE_BKGD if white_bkgd else 0,
+                                                 _p(d_rgb), _p(d_depth), _p(d_acc), _p(d_sig), _p(d_rgbs), _p(d_z), _stream(dev)),
+              "snr_scene_composite_bwd")
+    return d_sig, d_rgbs, d_z
+
+
+class SceneComposite(torch.autograd.Function):
+    """``scene_composite`` with gradients: to sigmas (P,n) and rgbs (P,n,3) always, to z_vals (P,n) when it needs one.  At most 512
+    samples per pixel when any input requires grad."""
+
+    @staticmethod
+    def forward(ctx, sigmas, rgbs, z_vals, white_bkgd, run_length):
+        sigmas, rgbs, z_vals = _f32c(sigmas), _f32c(rgbs), _f32c(z_vals)
+        if any(ctx.needs_input_grad[:3]) and sigmas.dim() == 2 and sigmas.shape[1] > SCENE_BWD_MAX_N:
+            raise SnrError(f"SceneComposite: {sigmas.shape[1]} samples per pixel, the backward takes at most {SCENE_BWD_MAX_N} "
+                           "(ops.scene_composite renders more, without gradients)")
+        out = scene_composite(sigmas, rgbs, z_vals, white_bkgd, run_length)
+        ctx.save_for_backward(sigmas, rgbs, z_vals)
+        ctx.cfg = (bool(white_bkgd), int(run_length))
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_acc):
+        sigmas, rgbs, z_vals = ctx.saved_tensors
+        white, run_length = ctx.cfg
+        need_dz = ctx.needs_input_grad[2]
+        if d_rgb is None:
+            d_rgb = torch.zeros(sigmas.shape[0], 3, device=sigmas.device)
+        d_sig, d_rgbs, d_z = scene_composite_bwd(sigmas, rgbs, z_vals, white, run_length, d_rgb, d_depth, d_acc, need_dz)
+        return d_sig, d_rgbs, d_z, None, None
+
+
 def composite_bwd(sigmas, rgbs, z_vals, z_mode, white_bkgd, rays_per_obj, d_rgb, d_depth, d_acc, need_dz):
     sigmas, rgbs, z_vals = _f32c(sigmas), _f32c(rgbs), _f32c(z_vals)
     # dense copies are NAMED so that they live until the launch is enqueued: `_p(_f32c(t))` inside the argument list frees the temporary before

@@ -7,6 +7,9 @@ pixel); the samples of all objects are decoded in ONE batched-code decoder launc
 
 The method's attributes (``self.obj_poses``, ``self.obj_wlh``, ``self.shapecodes`` ...) are function arguments here;
 the ray table is built on the host exactly like the reference does (python loop over a handful of objects).
+
+``vis_scene`` makes pictures.  ``render_scene`` renders listed pixels with autograd to the codes and the object poses: its rows come from
+``scene_ray_rows`` (torch ops on the device) and its composite from ``ops.SceneComposite`` (HIP forward and backward).
 """
 from typing import Optional, Sequence
 
@@ -84,7 +87,10 @@ def render_scene_batch(model, device, batch_rays, diags, shapecodes, texturecode
     rays = batch_rays.reshape(-1, 8)
     step = 1.0 / n_samples
     t = torch.linspace(0, 1 - step, n_samples)[None, :].repeat(rays.shape[0], 1)
-    t = t + (torch.rand_like(t) if jitter is None else jitter.cpu()) * step            # CPU draw, like the reference's CPU ray table
+    if jitter is not None and jitter.device.type == dev.type and dev.index in (None, jitter.device.index):
+        t = t.to(dev) + jitter * step                                                  # a draw that lives on the device stays there
+    else:
+        t = t + (torch.rand_like(t) if jitter is None else jitter.cpu()) * step        # CPU draw, like the reference's CPU ray table
     rays, t = rays.to(dev), t.to(dev)
     z_coarse = rays[:, 6:7] * (1 - t) + rays[:, 7:8] * t
     empty = z_coarse == -1
@@ -103,7 +109,71 @@ def render_scene_batch(model, device, batch_rays, diags, shapecodes, texturecode
     empty = empty.view(Nr, Nb * n_samples)
     rgb = torch.where(empty[..., None], torch.ones_like(rgb), rgb)                       # empty space: white, zero density
     sig = torch.where(empty, torch.zeros_like(sig), sig)
-    return ops.scene_composite(sig, rgb, z_vals.view(Nr, Nb * n_samples), white_bkgd=True, run_length=n_samples)
+    z_vals = z_vals.view(Nr, Nb * n_samples)
+    if torch.is_grad_enabled() and (sig.requires_grad or rgb.requires_grad or z_vals.requires_grad):
+        return ops.SceneComposite.apply(sig, rgb, z_vals, True, n_samples)              # gradients to the codes and, through the rows, to poses
+    return ops.scene_composite(sig, rgb, z_vals, white_bkgd=True, run_length=n_samples)
+
+
+def scene_ray_rows(obj_poses, obj_wlh, K, pixels, H, W, manipulation=(0.0, 0.0, 0.0), rend_aabb=True):
+    """rows (Nr, Nb, 8), valid (Nr,): the rows ``scene_rays`` writes for the integer pixels ``pixels`` (Nr, 2) = (x, y), made with torch
+    ops on the device and in the dtype of ``obj_poses`` (Nb,3,4) and differentiable with respect to it.
+
+    Every object's roi is the truncated projection of its box corners clamped to the image, computed in fp32 on the host exactly as
+    ``scene_rays`` does and treated as a constant: that is this function's ONE host read of the poses.  A pixel outside an object's roi
+    gets the all -1 row; inside it the row holds origin / (diag/2) and direction, and near / far from the slab test
+    (``utils._slab_guarded``), -1 / -1 where the ray misses the box, or the sphere bounds when ``rend_aabb`` is False.  Rays are those of
+    ``utils.get_rays_specified`` for the object-from-camera pose.  ``valid``: some object's far - near is positive, like ``scene_rays``' mask."""
+    dev, dt = obj_poses.device, obj_poses.dtype
+    Nb = obj_poses.shape[0]
+    pixels = torch.as_tensor(pixels).to(dev)
+    poses = torch.cat([obj_poses[:, :, :3], obj_poses[:, :, 3:4] + torch.tensor(manipulation, dtype=dt, device=dev).view(1, 3, 1)], dim=2)
+    p32, wlh32, K32 = poses.detach().cpu().float(), obj_wlh.detach().cpu().float(), K.detach().cpu().float()       # the one host read
+    uv = view_points_batch(corners_of_box_batch(p32, wlh32), K32.unsqueeze(0).repeat(Nb, 1, 1))
+    rois = torch.stack([uv[:, 0].min(dim=1)[0], uv[:, 1].min(dim=1)[0], uv[:, 0].max(dim=1)[0], uv[:, 1].max(dim=1)[0]], dim=1).type(torch.int32)
+    lo = torch.stack([rois[:, 0].clamp(min=0), rois[:, 1].clamp(min=0)], 1)                                         # roi_process(roi, H, W, 0, False)
+    hi = torch.stack([rois[:, 2].clamp(max=W - 1), rois[:, 3].clamp(max=H - 1)], 1)
+    live = (hi[:, 0] > lo[:, 0]) & (hi[:, 1] > lo[:, 1])
+    lo, hi, live = lo.to(dev), hi.to(dev), live.to(dev)
+    px, py = pixels[:, 0], pixels[:, 1]
+    in_roi = live[:, None] & (px[None, :] >= lo[:, 0:1]) & (px[None, :] < hi[:, 0:1]) & (py[None, :] >= lo[:, 1:2]) & (py[None, :] < hi[:, 1:2])   # (Nb,Nr)
+
+    wlh, Kd = obj_wlh.detach().to(dev, dt), K.detach().to(dev, dt)
+    diag = torch.linalg.norm(wlh, dim=1)                                                                           # (Nb,)
+    R_c2o = poses[:, :3, :3].transpose(1, 2)
+    origin = -(R_c2o @ poses[:, :3, 3:4]).squeeze(-1)                                                              # (Nb,3): the camera in the object frame
+    fx, fy = px.to(torch.float32).to(dt), py.to(torch.float32).to(dt)
+    cam = torch.stack([(fx - Kd[0, 2]) / Kd[0, 0], (fy - Kd[1, 2]) / Kd[1, 1], torch.ones_like(fx)], -1)          # (Nr,3)
+    world = (cam[None, :, None, :] * R_c2o[:, None, :, :]).sum(-1)                                                 # (Nb,Nr,3)
+    unit = world / torch.norm(world, dim=-1, keepdim=True)
+    o_n = (origin / (diag / 2)[:, None])[:, None, :].expand_as(unit)
+    if rend_aabb:
+        half = torch.stack([wlh[:, 1] / diag, wlh[:, 0] / diag, wlh[:, 2] / diag], 1)[:, None, :].expand_as(unit)
+        t_near, t_far, hit = U._slab_guarded(o_n, unit, -half, half)
+        hit = hit & in_roi
+        near = torch.where(hit, t_near, torch.full_like(t_near, -1.0))
+        far = torch.where(hit, t_far, torch.full_like(t_far, -1.0))
+    else:
+        dist = torch.linalg.norm(origin, dim=1)
+        near = ((dist - diag / 2) / (diag / 2))[:, None].expand(Nb, pixels.shape[0])
+        far = ((dist + diag / 2) / (diag / 2))[:, None].expand(Nb, pixels.shape[0])
+    rows = torch.cat([o_n, unit, near[..., None], far[..., None]], dim=-1)                                         # (Nb,Nr,8)
+    rows = torch.where(in_roi[..., None], rows, torch.full_like(rows, -1.0)).permute(1, 0, 2)
+    valid = (rows[:, :, 7] - rows[:, :, 6]).max(-1)[0] > 0
+    return rows, valid.detach()
+
+
+def render_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, pixels, H, W, n_samples, jitter=None,
+                 manipulation=(0.0, 0.0, 0.0), rend_aabb=True, shapenet_obj_cood=True, adjust_scale=1.0):
+    """rgb (Nr,3), depth (Nr,), acc_trans (Nr,) of the scene at the listed integer pixels (Nr,2) = (x, y), with autograd to
+    ``shapecodes``, ``texturecodes`` and ``obj_poses``: ``render_scene_batch`` of ``scene_ray_rows``.  ``jitter``: (Nr*Nb, S) draws in
+    [0,1), default ``torch.rand_like``.  Every listed pixel is rendered; one that no object covers comes out white."""
+    if obj_poses.shape[0] != shapecodes.shape[0] or obj_poses.shape[0] != texturecodes.shape[0] or obj_poses.shape[0] != obj_wlh.shape[0]:
+        raise SnrError("render_scene: obj_poses, obj_wlh, shapecodes and texturecodes must describe the same number of objects")
+    dev = torch.device(device)
+    rows, _ = scene_ray_rows(obj_poses.to(dev), obj_wlh, K, pixels, H, W, manipulation, rend_aabb)
+    diags = torch.linalg.norm(obj_wlh.detach().float(), dim=1)
+    return render_scene_batch(model, device, rows.float(), diags, shapecodes, texturecodes, n_samples, jitter, adjust_scale, shapenet_obj_cood)
 
 
 def vis_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, H, W, n_samples, manipulation=(0.0, 0.0, 0.0),
