@@ -44,6 +44,9 @@ def test_kernel_against_restatement(amd, dev, Nb, S, P, quarters):
     gS = kernel_grads(amd, dev, sig, rgb, z, w, True, S)
     for a, b in zip(g0, gS):
         assert torch.equal(a, b)                      # the hint only changes how the ranks are found
+    if P > 8192 * 4:                                  # the grid-stride launch: the values under grad mode are the plain forward's
+        assert all(torch.equal(a, b) for a, b in zip(amd.ops.SceneComposite.apply(*[t.to(dev).requires_grad_() for t in (sig, rgb, z)], True, S),
+                                                     amd.ops.scene_composite(sig.to(dev), rgb.to(dev), z.to(dev), True, S)))
     against_restatement(amd, dev, sig, rgb, z, w, True, g0, f"({Nb},{S},{P}){' quarters' if quarters else ''}")
 
 
