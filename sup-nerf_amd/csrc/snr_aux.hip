@@ -601,75 +601,38 @@ int snr_pack_weights(const float* const* t, int n_tensors, int sb, int tb, float
     for (int i = 0; i < n_tensors; ++i) if (!t[i]) return SNR_E_ARG;
     hipStream_t st = (hipStream_t)stream_;
     const Layout L = make_layout(sb, tb);
-    // tensor index helpers (weight, bias pairs in reference order without the latent layers)
-    int ti = 0;
-    auto Wp = [&](int i) { return t[2 * i]; };
-    auto Bp = [&](int i) { return t[2 * i + 1]; };
-    const int i_xyz = ti++;
-    int i_shape[MAX_BLOCKS]; for (int j = 0; j < sb; ++j) i_shape[j] = ti++;
-    const int i_encshape = ti++;
-    const int i_sigma = ti++;
-    const int i_view = ti++;
-    int i_tex[MAX_BLOCKS]; for (int j = 0; j < tb; ++j) i_tex[j] = ti++;
-    const int i_rgb0 = ti++;
-    const int i_rgb2 = ti++;
+    const LayerTable T = layer_table(sb, tb);
+    auto Wp = [&](const Layer& l) { return t[2 * l.tensor]; };
+    auto Bp = [&](const Layer& l) { return t[2 * l.tensor + 1]; };
 
     // ---- forward stream
     float* f = packed + L.fwd;
-    auto fwd = [&](const float* Wsrc, int n_out, int k_in, int n_chunks) {
-        pack_fwd_kernel<<<grid_for((long long)n_chunks * n_out * KC), 256, 0, st>>>(Wsrc, n_out, k_in, n_chunks, f);
-        f += (long long)n_chunks * n_out * KC;
-    };
-    fwd(Wp(i_xyz), 256, D_XYZ, 2);
-    for (int j = 0; j < sb; ++j) fwd(Wp(i_shape[j]), 256, 256, 8);
-    fwd(Wp(i_encshape), 256, 256, 8);
-    fwd(Wp(i_view), 256, 256 + D_DIR, 9);
-    for (int j = 0; j < tb; ++j) fwd(Wp(i_tex[j]), 256, 256, 8);
-    fwd(Wp(i_rgb0), 128, 256, 8);
-    if (f - (packed + L.fwd) != L.fwd_floats) return SNR_E_SHAPE;
-
+    for (int li = 0; li < T.n; ++li) {
+        const Layer& l = T.mfma[li];
+        pack_fwd_kernel<<<grid_for(stream_floats(l)), 256, 0, st>>>(Wp(l), l.n_out, l.k_in, k_pad(l) / KC, f);
+        f += stream_floats(l);
+    }
     // ---- backward stream (reverse consumption order)
     float* b = packed + L.bwd;
-    auto bwd = [&](const float* Wsrc, int n_out, int k_in, int rows_pad) {
-        const int n_chunks = n_out / KC;
-        pack_bwd_kernel<<<grid_for((long long)n_chunks * rows_pad * KC), 256, 0, st>>>(Wsrc, n_out, k_in, rows_pad, b);
-        b += (long long)n_chunks * rows_pad * KC;
-    };
-    bwd(Wp(i_rgb0), 128, 256, 256);
-    for (int j = tb - 1; j >= 0; --j) bwd(Wp(i_tex[j]), 256, 256, 256);
-    bwd(Wp(i_view), 256, 256 + D_DIR, K_VIEW_PAD);
-    bwd(Wp(i_encshape), 256, 256, 256);
-    for (int j = sb - 1; j >= 0; --j) bwd(Wp(i_shape[j]), 256, 256, 256);
-    bwd(Wp(i_xyz), 256, D_XYZ, K_XYZ_PAD);
-    if (b - (packed + L.bwd) != L.bwd_floats) return SNR_E_SHAPE;
-
-    // ---- vectors
+    for (int li = T.n - 1; li >= 0; --li) {
+        const Layer& l = T.mfma[li];
+        pack_bwd_kernel<<<grid_for(stream_floats(l)), 256, 0, st>>>(Wp(l), l.n_out, l.k_in, k_pad(l), b);
+        b += stream_floats(l);
+    }
+    // ---- vectors: one bias row per layer, the two heads
     auto vec = [&](const float* src, int n, long long off, int n_pad) {
         copy_pad_kernel<<<(n_pad + 255) / 256, 256, 0, st>>>(src, n, packed + off, n_pad);
     };
-    vec(Bp(i_xyz), 256, L.bias + 256ll * layer_enc_xyz(), 256);
-    for (int j = 0; j < sb; ++j) vec(Bp(i_shape[j]), 256, L.bias + 256ll * layer_shape(j), 256);
-    vec(Bp(i_encshape), 256, L.bias + 256ll * layer_enc_shape(sb), 256);
-    vec(Bp(i_view), 256, L.bias + 256ll * layer_viewdir(sb), 256);
-    for (int j = 0; j < tb; ++j) vec(Bp(i_tex[j]), 256, L.bias + 256ll * layer_texture(sb, j), 256);
-    vec(Bp(i_rgb0), 128, L.bias + 256ll * layer_rgb0(sb, tb), 256);
-    vec(Wp(i_sigma), 256, L.sigma_w, 256);
-    vec(Bp(i_sigma), 1, L.sigma_b, 4);
-    vec(Wp(i_rgb2), 3 * 128, L.rgb2_w, 3 * 128);
-    vec(Bp(i_rgb2), 3, L.rgb2_b, 4);
+    for (int li = 0; li < T.n; ++li) vec(Bp(T.mfma[li]), T.mfma[li].n_out, L.bias + (long long)W * li, W);
+    auto head = [&](const Layer& h, long long off_w, long long off_b) {
+        vec(Wp(h), h.n_out * h.k_in, off_w, h.n_out * h.k_in);
+        vec(Bp(h), h.n_out, off_b, 4);
+    };
+    head(T.sigma, L.sigma_w, L.sigma_b);
+    head(T.rgb2, L.rgb2_w, L.rgb2_b);
     // ---- split-bf16 streams (same weights as hi/lo bf16 pairs, output-tile-major chunks)
-    {
-        const float* Wl[MAX_BLOCKS * 2 + 4];
-        int n = 0;
-        Wl[n++] = Wp(i_xyz);
-        for (int j = 0; j < sb; ++j) Wl[n++] = Wp(i_shape[j]);
-        Wl[n++] = Wp(i_encshape);
-        Wl[n++] = Wp(i_view);
-        for (int j = 0; j < tb; ++j) Wl[n++] = Wp(i_tex[j]);
-        Wl[n++] = Wp(i_rgb0);
-        int rc = snr_bf16_pack_(Wl, sb, tb, packed, stream_);
-        if (rc != SNR_OK) return rc;
-    }
+    const int rc = snr_bf16_pack_(t, sb, tb, packed, stream_);
+    if (rc != SNR_OK) return rc;
     return snr_check_launch_();
 }
 

@@ -1330,48 +1330,41 @@ int snr_bf16_supported_(int sb, int tb, long long points_per_obj) {
     return (sb + tb + 4 <= bf::MAX_LAYERS) && (sb + tb <= bf::MAX_LAT) && (points_per_obj % 32 == 0);
 }
 
-int snr_bf16_pack_(const float* const* W /* per-point weight tensors in MFMA-layer order */, int sb, int tb, float* packed, void* stream_) {
+int snr_bf16_pack_(const float* const* t /* snr_pack_weights' tensor list */, int sb, int tb, float* packed, void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
     const Layout L = make_layout(sb, tb);
-    auto launch = [&](const float* w, int n_out, int k_in, int transpose, int n_tiles, int KS, __bf16* dst, int tile0 = 0, int k_off = 0) {
+    const LayerTable T = layer_table(sb, tb);
+    auto launch = [&](const float* w, int n_out, int k_in, int transpose, int n_tiles, int KS, char* dst, int tile0 = 0, int k_off = 0) {
         const long long total = (long long)n_tiles * KS * 512;
         int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
-        bf::pack_bf16_kernel<<<grid, 256, 0, st>>>(w, n_out, k_in, transpose, n_tiles, KS, tile0, k_off, dst);
+        bf::pack_bf16_kernel<<<grid, 256, 0, st>>>(w, n_out, k_in, transpose, n_tiles, KS, tile0, k_off, reinterpret_cast<__bf16*>(dst));
     };
-    const int n_layers = sb + tb + 4;
-    // forward stream (16x16x32 image): k32-steps of 16-row tiles; enc_viewdir = 8 steps over the 256 hidden units + one step over the
-    // direction features
+    // forward stream (16x16x32 image): k32-steps of 16-row tiles of output features; the steps past the hidden width (enc_viewdir's
+    // direction features) are one more piece, a chunk of its own
     char* f = reinterpret_cast<char*>(packed + L.bf_fwd);
-    for (int li = 0; li < n_layers; ++li) {
-        const bool is_xyz = li == 0, is_view = li == sb + 2, is_rgb0 = li == n_layers - 1;
-        const int n_out = is_rgb0 ? 128 : 256;
-        const int k_in = is_xyz ? D_XYZ : (is_view ? 256 + D_DIR : 256);
-        const int KS = is_xyz ? 2 : 8;
-        const int n_tiles = n_out / 16;
-        launch(W[li], n_out, is_view ? 256 + D_DIR : k_in, 0, n_tiles, KS, reinterpret_cast<__bf16*>(f));
-        f += (long long)n_tiles * 2 * KS * 1024;
-        if (is_view) {                                             // the direction features: one more k32-step, a chunk of its own
-            launch(W[li], n_out, k_in, 0, n_tiles, 1, reinterpret_cast<__bf16*>(f), 0, 256);
-            f += (long long)n_tiles * 2 * 1024;
+    for (int li = 0; li < T.n; ++li) {
+        const Layer& l = T.mfma[li];
+        const int n_tiles = l.n_out / 16, steps = bf_fwd_steps(l), hidden = steps < W / KC ? steps : W / KC;
+        launch(t[2 * l.tensor], l.n_out, l.k_in, 0, n_tiles, hidden, f);
+        f += bf_fwd_bytes(l, hidden);
+        if (steps > hidden) {
+            launch(t[2 * l.tensor], l.n_out, l.k_in, 0, n_tiles, steps - hidden, f, 0, hidden * KC);
+            f += bf_fwd_bytes(l, steps - hidden);
         }
     }
-    if (f - reinterpret_cast<char*>(packed + L.bf_fwd) != L.bf_fwd_bytes) return SNR_E_SHAPE;
-    // backward stream: rgb.0^T, texture^T (reverse), enc_viewdir^T, enc_shape^T, shape^T (reverse), enc_xyz^T
+    // backward stream, reverse order: k32-steps over the layer's outputs of 16-row tiles of input features; the tiles past the hidden
+    // width (enc_viewdir's tiles 16, 17) are a chunk of their own
     char* b = reinterpret_cast<char*>(packed + L.bf_bwd);
-    for (int li = n_layers - 1; li >= 0; --li) {
-        const bool is_xyz = li == 0, is_view = li == sb + 2, is_rgb0 = li == n_layers - 1;
-        const int n_out = is_rgb0 ? 128 : 256;
-        const int k_in = is_xyz ? D_XYZ : (is_view ? 256 + D_DIR : 256);
-        const int KS = n_out / 32;                                 // k32-steps over the layer's outputs
-        const int n_tiles = is_xyz ? 4 : 16;                       // tiles of 16 input features
-        launch(W[li], n_out, k_in, 2, n_tiles, KS, reinterpret_cast<__bf16*>(b));
-        b += (long long)n_tiles * 2 * KS * 1024;
-        if (is_view) {                                             // the direction features: tiles 16, 17, a chunk of their own
-            launch(W[li], n_out, k_in, 2, 2, KS, reinterpret_cast<__bf16*>(b), 16);
-            b += 2ll * 2 * KS * 1024;
+    for (int li = T.n - 1; li >= 0; --li) {
+        const Layer& l = T.mfma[li];
+        const int KS = l.n_out / KC, tiles = bf_bwd_tiles(l), hidden = tiles < W / 16 ? tiles : W / 16;
+        launch(t[2 * l.tensor], l.n_out, l.k_in, 2, hidden, KS, b);
+        b += bf_bwd_bytes(l, hidden);
+        if (tiles > hidden) {
+            launch(t[2 * l.tensor], l.n_out, l.k_in, 2, tiles - hidden, KS, b, hidden);
+            b += bf_bwd_bytes(l, tiles - hidden);
         }
     }
-    if (b - reinterpret_cast<char*>(packed + L.bf_bwd) != L.bf_bwd_bytes) return SNR_E_SHAPE;
     return snr_check_launch_();
 }
 

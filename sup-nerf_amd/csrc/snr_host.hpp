@@ -32,7 +32,7 @@ long long snr_reduce_scratch_floats_(long long tiles_per_obj, int n_lat, long lo
 int snr_launch_reduce_latent_(const float* partial, float* scratch, long long tiles_per_obj, int n_lat, long long n_obj, float* d_latent, void* stream);
 // ---- snr_bf16.hip: the split ("bf16x3") arithmetic, modes 0 and 1; partial rows of 32 points
 int snr_bf16_supported_(int sb, int tb, long long points_per_obj);
-int snr_bf16_pack_(const float* const* W /* per-point weight tensors in MFMA-layer order */, int sb, int tb, float* packed, void* stream_);
+int snr_bf16_pack_(const float* const* t /* snr_pack_weights' tensor list */, int sb, int tb, float* packed, void* stream_);
 int snr_bf16_launch_fwd_(int mode, const snr::DecoderIO& io, const snr::Layout& L, const float* xyz, const float* viewdir, const snr::RayGeom& g, float* rgb,
                          float* depth, float* acc, void* stream_);
 int snr_bf16_launch_bwd_(int mode, const snr::BwdIO& io, const snr::Layout& L, const float* xyz, const float* viewdir, const snr::RayGeom& g, void* stream_);

@@ -59,29 +59,68 @@ struct Layout {
 constexpr int BF_CHUNK = 32768;          // bytes of every chunk except the forward enc_viewdir ones
 constexpr int BF_CHUNK_VIEW = 36864;     // 18 k16-steps
 
-SNR_HD inline Layout make_layout(int sb, int tb) {
+// ---- the layer table (host side) -----------------------------------------------------------------------
+// The one description of the per-point layers.  Everything the packed buffer is made of follows from it: make_layout sums the per-layer
+// sizes below, and the packers (snr_pack_weights, snr_bf16_pack_) walk the same table with the same size functions.  A layer's index
+// (bias row, activation slot) is its place in `mfma`.  ops.decoder_layers is the Python twin (tests/test_host_logic.py ties the two).
+struct Layer {
+    int n_out, k_in;
+    bool relu;
+    int tensor;          // place of its (weight, bias) pair in snr_pack_weights' tensor list: reference order
+};
+struct LayerTable {
+    int n;                                   // MFMA layers, in the order the kernels consume them
+    Layer mfma[2 * MAX_BLOCKS + 4];
+    Layer sigma, rgb2;                       // the two narrow heads (plain fp32 vectors behind the bias rows)
+};
+inline LayerTable layer_table(int sb, int tb) {
+    LayerTable T;
+    int n = 0, t = 0;
+    T.mfma[n++] = {W, D_XYZ, true, t++};                                 // encoding_xyz
+    for (int j = 0; j < sb; ++j) T.mfma[n++] = {W, W, true, t++};        // shape_layer_1..sb
+    T.mfma[n++] = {W, W, false, t++};                                    // encoding_shape
+    T.sigma = {1, W, false, t++};                                        // sigma.0
+    T.mfma[n++] = {W, W + D_DIR, true, t++};                             // encoding_viewdir: hidden units, then the direction features
+    for (int j = 0; j < tb; ++j) T.mfma[n++] = {W, W, true, t++};        // texture_layer_1..tb
+    T.mfma[n++] = {W_RGB, W, true, t++};                                 // rgb.0
+    T.rgb2 = {3, W_RGB, false, t++};                                     // rgb.2
+    T.n = n;
+    return T;
+}
+
+inline int k_pad(const Layer& l) { return (l.k_in + KC - 1) / KC * KC; }          // 64, 288 or 256
+// fp32 streams: forward k_pad / KC chunks of n_out x KC floats, backward n_out / KC chunks of k_pad x KC floats -- n_out x k_pad either way
+inline int64_t stream_floats(const Layer& l) { return (int64_t)l.n_out * k_pad(l); }
+// split streams, 1 KiB per (tile, plane): forward n_out / 16 tiles x 2 planes per k32-step, backward 2 planes x n_out / KC steps per tile
+// of 16 input features.  What lies past the hidden width (encoding_viewdir's direction features: forward step 8, backward tiles 16 and
+// 17) is packed as a piece of its own behind the layer's other steps / tiles, hence the count argument.
+inline int bf_fwd_steps(const Layer& l) { return k_pad(l) / KC; }
+inline int bf_bwd_tiles(const Layer& l) { return (l.k_in + 15) / 16; }
+inline int64_t bf_fwd_bytes(const Layer& l, int steps) { return (int64_t)(l.n_out / 16) * 2 * steps * 1024; }
+inline int64_t bf_bwd_bytes(const Layer& l, int tiles) { return (int64_t)tiles * 2 * (l.n_out / KC) * 1024; }
+
+inline Layout make_layout(int sb, int tb) {
+    const LayerTable T = layer_table(sb, tb);
     Layout L;
     L.sb = sb; L.tb = tb;
-    L.n_mfma_layers = sb + tb + 4;
+    L.n_mfma_layers = T.n;
     L.n_lat = sb + tb;
-    const int64_t c256 = 256 * KC;
-    // forward: enc_xyz 2 chunks, (sb+1) 256-layers x 8, viewdir 9, tb x 8 (all 256 rows), rgb0 8 chunks of 128 rows
-    L.fwd_floats = 2 * c256 + (int64_t)(sb + 1) * 8 * c256 + 9 * c256 + (int64_t)tb * 8 * c256 + 8 * (128 * KC);
-    // backward: rgb0^T 4 chunks of 256 rows, tb x 8 x 256 rows, viewdir^T 8 chunks of 288 rows,
-    //           (sb+1) x 8 x 256 rows, enc_xyz^T 8 chunks of 64 rows
-    L.bwd_floats = 4 * c256 + (int64_t)tb * 8 * c256 + 8 * (288 * KC) + (int64_t)(sb + 1) * 8 * c256 + 8 * (64 * KC);
+    L.fwd_floats = L.bwd_floats = L.bf_fwd_bytes = L.bf_bwd_bytes = 0;
+    for (int li = 0; li < T.n; ++li) {
+        const Layer& l = T.mfma[li];
+        L.fwd_floats += stream_floats(l);
+        L.bwd_floats += stream_floats(l);
+        L.bf_fwd_bytes += bf_fwd_bytes(l, bf_fwd_steps(l));
+        L.bf_bwd_bytes += bf_bwd_bytes(l, bf_bwd_tiles(l));
+    }
     int64_t o = 0;
     L.fwd = o; o += L.fwd_floats;
     L.bwd = o; o += L.bwd_floats;
-    L.bias = o; o += (int64_t)L.n_mfma_layers * 256;
-    L.sigma_w = o; o += 256;
+    L.bias = o; o += (int64_t)T.n * W;
+    L.sigma_w = o; o += T.sigma.n_out * T.sigma.k_in;
     L.sigma_b = o; o += 4;
-    L.rgb2_w = o; o += 3 * 128;
+    L.rgb2_w = o; o += T.rgb2.n_out * T.rgb2.k_in;
     L.rgb2_b = o; o += 4;
-    // forward: enc_xyz 2 chunks (4 tiles each, K=64), 8 per 256-layer, 8 x enc_viewdir (K=288), rgb.0 4 chunks
-    L.bf_fwd_bytes = 2ll * BF_CHUNK + (int64_t)(sb + 1 + tb) * 8 * BF_CHUNK + 8ll * BF_CHUNK_VIEW + 4ll * BF_CHUNK;
-    // backward: rgb.0^T 4 chunks (one k32-step of 16 tiles each, K=128), 8 per 256-layer, enc_viewdir^T 8 + 1 (its two direction tiles), enc_xyz^T 2 (four steps of 4 tiles each)
-    L.bf_bwd_bytes = 4ll * BF_CHUNK + (int64_t)tb * 8 * BF_CHUNK + 9ll * BF_CHUNK + (int64_t)(sb + 1) * 8 * BF_CHUNK + 2ll * BF_CHUNK;
     o = (o + 3) & ~3ll;                       // 16-byte alignment for the LDS-DMA source
     L.bf_fwd = o; o += L.bf_fwd_bytes / 4;
     L.bf_bwd = o; o += L.bf_bwd_bytes / 4;
@@ -95,14 +134,6 @@ SNR_HD inline Layout make_layout(int sb, int tb) {
 // lanes of a read group land on 16 distinct 16-byte slots of the 256-byte bank row) and lets the
 // staging be a linear LDS-DMA copy.
 SNR_HD inline int chunk_pos(int row, int kk) { return row * KC + ((((kk >> 2) ^ ((row >> 1) & 7)) << 2) | (kk & 3)); }
-
-// index of the MFMA layers in consumption order
-SNR_HD inline int layer_enc_xyz() { return 0; }
-SNR_HD inline int layer_shape(int j /*0-based*/) { return 1 + j; }
-SNR_HD inline int layer_enc_shape(int sb) { return 1 + sb; }
-SNR_HD inline int layer_viewdir(int sb) { return 2 + sb; }
-SNR_HD inline int layer_texture(int sb, int j) { return 3 + sb + j; }
-SNR_HD inline int layer_rgb0(int sb, int tb) { return 3 + sb + tb; }
 
 // ReLU masks saved by the forward pass for the backward pass: one bit per hidden unit of every
 // ReLU layer, stored per 32-point wave tile as [layer][lane] uint4 (128 bits: the lane's 8 tiles x 16

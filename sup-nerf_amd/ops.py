@@ -4,6 +4,7 @@ Everything here requires fp32 tensors on an AMD GPU (``tensor.is_cuda`` under Py
 There is no CPU/eager fallback -- a CPU tensor raises."""
 import copy
 import ctypes as C
+import functools
 import math
 import threading
 import warnings
@@ -148,27 +149,34 @@ def _stream(dev):
 
 
 # ------------------------------------------------------------------------------------ weights
+class DecoderLayer(NamedTuple):
+    stem: str                # state-dict key without ".weight" / ".bias" (reference naming, src/model_supnerf.py:184-199)
+    n_out: int
+    n_in: int
+    slot: Optional[int]      # place among the MFMA layers in the order the kernels consume them; None: one of the two narrow heads
+
+
+@functools.lru_cache(maxsize=None)
+def decoder_layers(shape_blocks: int, texture_blocks: int) -> Sequence[DecoderLayer]:
+    """The per-point layers in the order snr_pack_weights expects their tensors: the Python twin of csrc/snr_layout.h's layer table
+    (tests/test_host_logic.py ties the two).  The kernels are built for the decoder of every shipped config: W = latent = 256,
+    L_xyz = 10, L_dir = 4."""
+    rows = [("encoding_xyz.0", 256, 63, True)] + [(f"shape_layer_{j}.0", 256, 256, True) for j in range(1, shape_blocks + 1)]
+    rows += [("encoding_shape", 256, 256, True), ("sigma.0", 1, 256, False), ("encoding_viewdir.0", 256, 256 + 27, True)]
+    rows += [(f"texture_layer_{j}.0", 256, 256, True) for j in range(1, texture_blocks + 1)]
+    rows += [("rgb.0", 128, 256, True), ("rgb.2", 3, 128, False)]
+    slots = iter(range(len(rows)))
+    return tuple(DecoderLayer(stem, n_out, n_in, next(slots) if mfma else None) for stem, n_out, n_in, mfma in rows)
+
+
 def per_point_tensor_names(shape_blocks: int, texture_blocks: int) -> Sequence[str]:
-    """State-dict keys (reference naming, src/model_supnerf.py:184-199) of the per-point layers in the
-    order snr_pack_weights expects them."""
-    names = ["encoding_xyz.0"] + [f"shape_layer_{j}.0" for j in range(1, shape_blocks + 1)]
-    names += ["encoding_shape", "sigma.0", "encoding_viewdir.0"]
-    names += [f"texture_layer_{j}.0" for j in range(1, texture_blocks + 1)] + ["rgb.0", "rgb.2"]
-    out = []
-    for n in names:
-        out += [n + ".weight", n + ".bias"]
-    return out
+    """State-dict keys of the per-point layers in the order snr_pack_weights expects them."""
+    return [l.stem + q for l in decoder_layers(shape_blocks, texture_blocks) for q in (".weight", ".bias")]
 
 
 def check_decoder_shapes(params: Dict[str, torch.Tensor], shape_blocks: int, texture_blocks: int):
-    """The kernels are built for the decoder of every shipped config: W = latent = 256, L_xyz = 10, L_dir = 4."""
-    want = {"encoding_xyz.0.weight": (256, 63), "encoding_shape.weight": (256, 256), "sigma.0.weight": (1, 256),
-            "encoding_viewdir.0.weight": (256, 283), "rgb.0.weight": (128, 256), "rgb.2.weight": (3, 128)}
-    for j in range(1, shape_blocks + 1):
-        want[f"shape_layer_{j}.0.weight"] = (256, 256)
-    for j in range(1, texture_blocks + 1):
-        want[f"texture_layer_{j}.0.weight"] = (256, 256)
-    for k, shp in want.items():
+    for l in decoder_layers(shape_blocks, texture_blocks):
+        k, shp = l.stem + ".weight", (l.n_out, l.n_in)
         if k not in params or tuple(params[k].shape) != shp:
             got = tuple(params[k].shape) if k in params else None
             raise SnrError(f"unsupported decoder: {k} is {got}, the gfx950 kernels need {shp} "
@@ -1459,7 +1467,7 @@ class DecoderPointsTrain(torch.autograd.Function):
         names = per_point_tensor_names(shape_blocks, texture_blocks)
         packed = _packed_for(names, weights, shape_blocks, texture_blocks)
         P, dev = xyz.shape[0], xyz.device
-        n_slots = shape_blocks + texture_blocks + 4
+        n_slots = sum(l.slot is not None for l in decoder_layers(shape_blocks, texture_blocks))
         act = torch.empty(n_slots, P, 256, device=dev)
         sig, rgb, masks = decoder_fwd(xyz, viewdir, latent, packed, shape_blocks, texture_blocks, save_masks=True, precision=prec,
                                       activations=act)
@@ -1474,7 +1482,8 @@ class DecoderPointsTrain(torch.autograd.Function):
         xyz, viewdir, latent, packed, masks, sig, act, *weights = ctx.saved_tensors
         sb, tb, wprec, prec = ctx.cfg
         P, dev = xyz.shape[0], xyz.device
-        n_slots = sb + tb + 4
+        layers = decoder_layers(sb, tb)
+        n_slots = sum(l.slot is not None for l in layers)
         G = torch.empty(n_slots, P, 256, device=dev)
         d_sig, d_rgb = _f32c(d_sig), _f32c(d_rgb)
         B_, n_, n_pad = ctx.pad
@@ -1487,34 +1496,29 @@ class DecoderPointsTrain(torch.autograd.Function):
         # reduction per layer; X of layer 0 and the direction features are the positional encodings, one launch of snr_pe_points (``pe``:
         # columns 0..63 PE(xyz), 64..95 PE(dir); round 2 recomputed them with torch.sin / cos / cat: 0.3 ms a step)
         pe = pe_points(xyz, viewdir)
-        li_view, li_rgb0 = sb + 2, sb + tb + 3
         ws = torch.empty(_lib.lib().snr_weight_grad_ws_bytes(P, 256, 256), dtype=torch.uint8, device=dev)
-        by_layer = {}
-        for li in range(n_slots):              # MFMA layers in order; the two small heads follow
-            n_out = 128 if li == li_rgb0 else 256
-            if li == 0:
-                by_layer[li] = weight_grad(G[li], n_out, pe[:, :64], 64, ws=ws, precision=wprec)
-                by_layer[li] = (by_layer[li][0][:, :63].contiguous(), by_layer[li][1])
-            elif li == li_view:
-                dW = torch.empty(256, 256 + 28, device=dev)
-                _, db = weight_grad(G[li], 256, act[li - 1], 256, out=(dW[:, :256], torch.empty(256, device=dev)), ws=ws, precision=wprec)
-                weight_grad(G[li], 256, pe[:, 64:], 28, out=(dW[:, 256:], None), ws=ws, precision=wprec)
-                by_layer[li] = (dW[:, :283].contiguous(), db)
+        grads = {}
+        for l in layers:                       # MFMA layers in order; the two small heads follow
+            if l.slot is None:
+                continue
+            li, n_pe = l.slot, l.n_in % 256    # n_in = the 256 columns of the activation before it (not the first layer) + positional-encoding columns
+            k_pe = (n_pe + 3) // 4 * 4         # (as pe_points pads them: 63 -> 64, 27 -> 28)
+            if l.n_in < 256:                   # encoding_xyz: PE(xyz)
+                dW, db = weight_grad(G[li], l.n_out, pe[:, :64], k_pe, ws=ws, precision=wprec)
+                grads[l.stem] = (dW[:, :n_pe].contiguous(), db)
+            elif n_pe:                         # encoding_viewdir: act || PE(dir)
+                dW = torch.empty(l.n_out, 256 + k_pe, device=dev)
+                _, db = weight_grad(G[li], l.n_out, act[li - 1], 256, out=(dW[:, :256], torch.empty(l.n_out, device=dev)), ws=ws, precision=wprec)
+                weight_grad(G[li], l.n_out, pe[:, 64:], k_pe, out=(dW[:, 256:], None), ws=ws, precision=wprec)
+                grads[l.stem] = (dW[:, :l.n_in].contiguous(), db)
             else:
-                by_layer[li] = weight_grad(G[li], n_out, act[li - 1], 256, ws=ws, precision=wprec)
-        # sigma head: pre = w . y4 + b with y4 = input of enc_viewdir
-        dpre = sigma_pre_grad(d_sig, sig).reshape(P, 1)
-        d_sigma_w, d_sigma_b = weight_grad(dpre, 1, act[li_view - 1], 256, ws=ws)
-        d_rgb2_w, d_rgb2_b = weight_grad(d_rgb.reshape(P, 3), 3, act[n_slots - 1], 128, ws=ws)
-        out = []
-        order = [0] + list(range(1, sb + 1)) + [sb + 1, "sigma", li_view] + list(range(sb + 3, sb + 3 + tb)) + [li_rgb0, "rgb2"]
-        for k in order:
-            if k == "sigma":
-                out += [d_sigma_w, d_sigma_b]
-            elif k == "rgb2":
-                out += [d_rgb2_w, d_rgb2_b]
-            else:
-                out += list(by_layer[k])
+                grads[l.stem] = weight_grad(G[li], l.n_out, act[li - 1], 256, ws=ws, precision=wprec)
+        # the heads read the output of the layer before them: sigma.0 (pre = w . y + b) the input of enc_viewdir, rgb.2 that of rgb.0
+        upstream = {"sigma.0": sigma_pre_grad(d_sig, sig).reshape(P, 1), "rgb.2": d_rgb.reshape(P, 3)}
+        for before, l in zip(layers, layers[1:]):
+            if l.slot is None:
+                grads[l.stem] = weight_grad(upstream[l.stem], l.n_out, act[before.slot], l.n_in, ws=ws)
+        out = [g for l in layers for g in grads[l.stem]]
         if n_pad:
             d_xyz, d_dir = _unpad_rows(d_xyz, B_, n_, n_pad), _unpad_rows(d_dir, B_, n_, n_pad)
         return (d_xyz, d_dir, d_lat, None, None, None, *out)

@@ -37,6 +37,86 @@ def test_library_exports_every_declared_symbol(amd):
     assert lib.snr_mask_bytes(262144, 3, 1) == 262144 // 32 * 7 * 1024
 
 
+PACKED_BYTES = {(0, 0): 3021344, (2, 1): 6170144, (3, 1): 7219744, (5, 5): 13517344, (8, 8): 19814944}
+
+
+def test_packed_bytes_recorded_values(amd):
+    lib = amd._lib.lib()
+    for blocks, nbytes in PACKED_BYTES.items():
+        assert lib.snr_packed_bytes(*blocks) == nbytes, blocks
+    assert lib.snr_packed_bytes(9, 1) == 0 and lib.snr_packed_bytes(-1, 0) == 0
+
+
+def _table_bytes(layers):
+    """The packed size by the rules of csrc/snr_layout.h, from the PYTHON layer table: per MFMA layer ceil(k / 32) forward chunks of
+    n_out x 32 floats, n_out / 32 backward chunks of round_up(k, 32) x 32 floats, (n_out / 16) x 2 x ceil(k / 32) KiB of split forward
+    image and ceil(k / 16) x 2 x (n_out / 32) KiB of split backward image; then the scalar section."""
+    mfma = [l for l in layers if l.slot is not None]
+    up = lambda n, m: (n + m - 1) // m
+    floats = sum(up(l.n_in, 32) * l.n_out * 32 + (l.n_out // 32) * up(l.n_in, 32) * 32 * 32 for l in mfma)
+    split = sum((l.n_out // 16) * 2 * up(l.n_in, 32) * 1024 + up(l.n_in, 16) * 2 * (l.n_out // 32) * 1024 for l in mfma)
+    return 4 * (floats + len(mfma) * 256 + 256 + 4 + 384 + 4) + split
+
+
+def test_layer_tables_agree_at_every_block_count(amd):
+    """The tie between csrc/snr_layout.h's layer table, its Python twin ``ops.decoder_layers`` and the numpy restatement of the format."""
+    import pack_restatement as R
+    lib = amd._lib.lib()
+    for sb in range(9):
+        for tb in range(9):
+            layers = amd.ops.decoder_layers(sb, tb)
+            assert [l.slot for l in layers if l.slot is not None] == list(range(sb + tb + 4))
+            assert _table_bytes(layers) == lib.snr_packed_bytes(sb, tb), (sb, tb)
+            assert R.packed_image(R.zero_params(sb, tb), sb, tb).size == lib.snr_packed_bytes(sb, tb), (sb, tb)
+
+
+def test_per_point_tensor_names_literal(amd):
+    pairs = lambda stems: [s + q for s in stems for q in (".weight", ".bias")]
+    assert amd.ops.per_point_tensor_names(0, 0) == pairs(["encoding_xyz.0", "encoding_shape", "sigma.0", "encoding_viewdir.0", "rgb.0", "rgb.2"])
+    assert amd.ops.per_point_tensor_names(3, 1) == pairs(["encoding_xyz.0", "shape_layer_1.0", "shape_layer_2.0", "shape_layer_3.0",
+                                                          "encoding_shape", "sigma.0", "encoding_viewdir.0", "texture_layer_1.0", "rgb.0",
+                                                          "rgb.2"])
+
+
+def test_check_decoder_shapes_messages(amd):
+    """The exception text, recorded before the shapes came from ``ops.decoder_layers``."""
+    tail = " (W=256, latent_dim=256, num_xyz_freq=10, num_dir_freq=4)"
+    params = O.init_decoder_params(3, 1, seed=0)
+    amd.ops.check_decoder_shapes(params, 3, 1)
+    missing = {k: v for k, v in params.items() if k != "shape_layer_2.0.weight"}
+    with pytest.raises(amd.SnrError) as e:
+        amd.ops.check_decoder_shapes(missing, 3, 1)
+    assert str(e.value) == "unsupported decoder: shape_layer_2.0.weight is None, the gfx950 kernels need (256, 256)" + tail
+    wrong = dict(params)
+    wrong["encoding_viewdir.0.weight"] = torch.zeros(256, 295)
+    with pytest.raises(amd.SnrError) as e:
+        amd.ops.check_decoder_shapes(wrong, 3, 1)
+    assert str(e.value) == "unsupported decoder: encoding_viewdir.0.weight is (256, 295), the gfx950 kernels need (256, 283)" + tail
+    wrong = dict(params)
+    wrong["rgb.2.weight"] = torch.zeros(4, 128)
+    with pytest.raises(amd.SnrError) as e:
+        amd.ops.check_decoder_shapes(wrong, 3, 1)
+    assert str(e.value) == "unsupported decoder: rgb.2.weight is (4, 128), the gfx950 kernels need (3, 128)" + tail
+
+
+def test_pack_weights_return_codes(amd):
+    """snr_pack_weights' checks and their order, with dummy addresses the host never dereferences: nothing is launched."""
+    import ctypes as C
+    lib = amd._lib.lib()
+    E_ARG, E_SHAPE = -1, -2
+    dst = C.c_void_p(0x1000)
+    full = (C.c_void_p * 20)(*[0x1000] * 20)                 # 3 / 1 blocks: 2 * (3 + 1 + 6) tensors
+    holed = (C.c_void_p * 20)(*([0x1000] * 7 + [None] + [0x1000] * 12))
+    assert lib.snr_pack_weights(None, 20, 3, 1, dst, None) == E_ARG
+    assert lib.snr_pack_weights(full, 20, 3, 1, None, None) == E_ARG
+    assert lib.snr_pack_weights(full, 20, 9, 1, dst, None) == E_ARG
+    assert lib.snr_pack_weights(full, 19, 3, 1, dst, None) == E_SHAPE
+    assert lib.snr_pack_weights(full, 20, 3, 2, dst, None) == E_SHAPE
+    assert lib.snr_pack_weights(holed, 20, 3, 1, dst, None) == E_ARG
+    assert lib.snr_pack_weights(holed, 18, 3, 1, dst, None) == E_SHAPE          # the count is checked before the entries
+    assert lib.snr_pack_weights(None, 18, 3, 1, dst, None) == E_ARG             # and the list before the count
+
+
 def test_graft_entry_build(amd):
     """__graft_entry__.build() is what the driver runs on the CPU box: it must compile (or find up to date) the library, load it,
     resolve every symbol and agree with the header on the ABI version."""
