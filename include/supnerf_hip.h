@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 16
+#define SNR_ABI_VERSION 17
 
 enum {
     SNR_OK = 0,
@@ -218,6 +218,55 @@ int snr_scene_composite_fwd(const float* sigmas, const float* rgbs, const float*
 int snr_scene_composite_bwd(const float* sigmas, const float* rgbs, const float* z_vals, int64_t n_pixels, int n_per_pixel, int run_length,
                             int flags, const float* d_rgb, const float* d_depth, const float* d_acc,
                             float* d_sigmas, float* d_rgbs, float* d_z, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Scene rows and samples: what scene.scene_ray_rows and the sample lines of scene.render_scene_batch make with ~65 torch launches, in
+ * one launch each way (tests/scene_rows_restatement.py states the same rules in a few lines of torch).
+ *   cam2obj (Nb,3,4) camera-in-object poses [R | t] = [R_obj^T | -R_obj^T t_obj];  wlh (Nb,3);  rois (Nb,4) int32 [x0,y0,x1,y1], already
+ *   clamped to the image (a pixel outside the image is therefore outside every roi), dead when x1 <= x0 or y1 <= y0;  pixels (Nr,2) int32
+ *   (x, y);  jitter (Nr*Nb, S), row r*Nb + b, nullable = 0.  With diag = |wlh|, per pair (pixel r, object b):
+ *   coverage   b is live and x0 <= x < x1, y0 <= y < y1;
+ *   direction  w = R [(x - cx)/fx, (y - cy)/fy, 1],  u = w / |w|;      origin  o = t / (diag/2);
+ *   bounds     rend_aabb: the slab test of (o, u) against +-(l, w, h)/diag -- near = the largest entry, far = the smallest exit; an axis with
+ *              u_a == 0 bounds nothing when o_a lies strictly inside its slab and makes the ray a miss otherwise (rules 1, 3, 4 of
+ *              SNR_Z_BOX above).  Otherwise the sphere bounds (|t| -/+ diag/2) / (diag/2);
+ *   hit        covered and far > near and far > 0 (strict);
+ *   depths     z_k = near (1 - tau_k) + far tau_k,  tau_k = k/S + jitter (1/S);
+ *   point      (o + z_k u) adjust_scale; shapenet_obj_cood applies (x,y,z) -> (-y,x,z) to the point and to the direction;
+ *   metric depth  |z_k u| diag/2.
+ * The pair's arithmetic runs in double from the fp32 inputs and every output is rounded to fp32 once.
+ * -> xyz, viewdir (Nb*Nr, S, 3) object-major (the decoder's layout), z_vals (Nr, Nb*S) pixel-major (the composite's), hit (Nr,Nb) uint8,
+ *    valid (Nr) uint8 [nullable]: some object is hit.  A pair that is not hit holds z_vals = -1 exactly for all S samples, xyz = 0 and
+ *    viewdir = (0,0,1): finite inputs for the decoder, whose values there snr_scene_gather_fwd throws away.
+ * The lists are only ever compared and converted, never used as an index: the kernels write inside their buffers whatever they hold.
+ * Every output element is written once; no host synchronisation; n_pixels == 0 returns at once.  n_objects <= 65535.
+ * ---------------------------------------------------------------------------------- */
+int snr_scene_samples_fwd(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx, float cy,
+                          const float* jitter, int64_t n_pixels, int64_t n_objects, int n_samples, float adjust_scale, int rend_aabb,
+                          int shapenet_obj_cood, float* xyz, float* viewdir, float* z_vals, uint8_t* hit, uint8_t* valid, void* stream);
+/* Backward of the above to the poses: d_xyz, d_viewdir (Nb*Nr,S,3), d_z (Nr,Nb*S), each nullable = zero -> d_cam2obj (Nb,3,4) = [dL/dR | dL/dt].
+ *   1. pairs that are not hit contribute exact zeros; the roi is a constant; jitter, pixels and wlh are data;
+ *   2. near and far carry the gradient of the one slab plane that gives them, (plane - o_a)/u_a: an axis with u_a == 0 never bounds a hit
+ *      and adds nothing (no 0 * inf).  Which plane takes it when two axes give exactly the same parameter is unspecified;
+ *   3. the metric depth's gradient to u lies along u and vanishes in u = w/|w|; to z_k it is sign(z_k) diag/2;
+ *   4. the same bits from run to run: per-sample arithmetic and all sums in double, no floating-point atomics -- every thread adds its samples
+ *      in index order, a workgroup adds its threads' sums in thread order (LDS), and a second launch adds the per-slice rows (256 pixels of
+ *      one object each) in slice order.
+ * ws: snr_scene_samples_bwd_ws_bytes(n_pixels, n_objects) bytes, 8-byte aligned.  Two launches on the stream. */
+size_t snr_scene_samples_bwd_ws_bytes(int64_t n_pixels, int64_t n_objects);
+int snr_scene_samples_bwd(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx, float cy,
+                          const float* jitter, int64_t n_pixels, int64_t n_objects, int n_samples, float adjust_scale, int rend_aabb,
+                          int shapenet_obj_cood, const float* d_xyz, const float* d_viewdir, const float* d_z, float* d_cam2obj, void* ws,
+                          size_t ws_bytes, void* stream);
+/* The decoder's object-major outputs as the composite's pixel-major rows: sigmas (Nb*Nr*S), rgbs (Nb*Nr*S,3), hit (Nr,Nb) from
+ * snr_scene_samples_fwd -> sigma_rows (Nr, Nb*S), rgb_rows (Nr, Nb*S, 3); a pair that is not hit holds sigma 0 and white (1,1,1).  Pure
+ * copies: the two permutes and two torch.where of scene.render_scene_batch bit for bit.  Either output (with its input) may be NULL. */
+int snr_scene_gather_fwd(const float* sigmas, const float* rgbs, const uint8_t* hit, int64_t n_pixels, int64_t n_objects, int n_samples,
+                         float* sigma_rows, float* rgb_rows, void* stream);
+/* The inverse scatter: d_sigma_rows (Nr, Nb*S), d_rgb_rows (Nr, Nb*S, 3) -> d_sigmas (Nb*Nr*S), d_rgbs (Nb*Nr*S,3), exact zeros on pairs
+ * that are not hit.  Either pair may be NULL. */
+int snr_scene_gather_bwd(const float* d_sigma_rows, const float* d_rgb_rows, const uint8_t* hit, int64_t n_pixels, int64_t n_objects, int n_samples,
+                         float* d_sigmas, float* d_rgbs, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Alpha composite alone: replaces volume_rendering2 / volume_rendering_batch

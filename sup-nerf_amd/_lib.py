@@ -62,6 +62,13 @@ _SIGS = {
     "snr_render_bwd": (C.c_int, [C.POINTER(RenderArgs), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "snr_scene_composite_fwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "snr_scene_composite_bwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "snr_scene_samples_fwd": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_int,
+                                        C.c_int, _P, _P, _P, _P, _P, _P]),
+    "snr_scene_samples_bwd_ws_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "snr_scene_samples_bwd": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_int,
+                                        C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "snr_scene_gather_fwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
+    "snr_scene_gather_bwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "snr_composite_fwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P]),
     "snr_composite_bwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "snr_encode_fwd": (C.c_int, [C.POINTER(RenderArgs), _P, _P, _P, _P, _P, _P, _P]),

@@ -485,6 +485,127 @@ def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, 
     return metrics.permute(1, 0, 2).contiguous(), shapecode.detach(), texturecode.detach(), pose
 
 
+# ------------------------------------------------------------------ all objects of a frame, jointly against the frame
+def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texturecodes0, pose_noise=(0.05, 0.3), seed=0, jitter=None,
+                   pixels=None, info: Optional[dict] = None):
+    """Fit the codes and poses of all Nb objects of one frame JOINTLY against the frame: every listed pixel is rendered through all objects
+    (``scene.render_scene``'s fused route) and compared with the image, so objects that occlude each other share their pixels' loss.
+
+    ``frame``: K (3,3), H, W, img (H,W,3), occ (H,W) in {-1,0,1} (1 on any object, -1 known background, 0 unknown), obj_poses (Nb,3,4)
+    (the ground truth: the metrics and the noise-perturbed start), obj_wlh (Nb,3).  ``pixels`` (Nr,2) int (x, y), fixed over the loop;
+    default: the pixels inside the union of the start poses' rois.  ``jitter`` (T, Nr*Nb, S); default: one seeded CPU generator.
+
+    One iteration, without a host round trip: pose parameters -> camera-in-object poses (``ops.PoseRays``), ``scene.scene_rois`` on the device
+    from the detached poses, ``ops.SceneSamples``, the decoder on the object-major points, ``ops.SceneGather``, ``ops.SceneComposite``,
+    ``ops.LossTail`` with the scene as one "object", backward, ``ops.DeviceAdamW`` over the four groups (every iteration; rates halved every
+    ``lr_half_interval``).  The decoder's weights are constants of the loop.  ``info`` receives ``pixels`` and ``hit_share`` (T,), the share of
+    (pixel, object) pairs that hit per iteration.
+
+    Returns metrics (T,Nb,2) = rotation / translation error of every object at the poses iteration t rendered, losses (T,4) = [loss,
+    loss_rgb, loss_occ, mse_fg], shape codes, texture codes and the object poses (Nb,3,4) after the last update."""
+    from . import scene
+    ops = U.ops
+    dev = torch.device(device)
+    opt = hpams["optimize"]
+    S, T = int(hpams["n_samples"]), int(opt["num_opts"])
+    gt = torch.as_tensor(frame["obj_poses"], dtype=torch.float32)
+    wlh = torch.as_tensor(frame["obj_wlh"], dtype=torch.float32)
+    Nb = gt.shape[0]
+    if tuple(gt.shape) != (Nb, 3, 4) or tuple(wlh.shape) != (Nb, 3) or shapecodes0.shape[0] != Nb or texturecodes0.shape[0] != Nb:
+        raise U.SnrError("optimize_scene: obj_poses (Nb,3,4), obj_wlh (Nb,3), shapecodes0 and texturecodes0 must describe the same number of objects")
+    if Nb * S > ops.SCENE_BWD_MAX_N:
+        raise U.SnrError(f"optimize_scene: {Nb} objects x {S} samples per pixel, the composite backward takes at most {ops.SCENE_BWD_MAX_N}")
+    if not U._is_native(model):
+        raise U.SnrError("optimize_scene needs the package's own decoder")
+    if hpams.get("sym_aug", 0):
+        raise U.SnrError("optimize_scene: sym_aug is a per-object, per-call coin; it has no meaning for a jointly rendered frame")
+    if opt.get("opt_cam_pose", 0):
+        raise U.SnrError("optimize_scene optimises object poses in one camera (opt_cam_pose = 0)")
+    H, W = int(frame["H"]), int(frame["W"])
+    K = torch.as_tensor(frame["K"], dtype=torch.float32).cpu()
+    Kvec = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
+    rs = np.random.RandomState(seed)
+    rot0 = matrix_to_axis_angle(gt[:, :, :3]) + torch.from_numpy(rs.randn(Nb, 3).astype(np.float32)) * pose_noise[0]
+    tr0 = gt[:, :, 3] + torch.from_numpy(rs.randn(Nb, 3).astype(np.float32)) * pose_noise[1]
+    if pixels is None:
+        r0 = scene.scene_rois(torch.cat([axis_angle_to_matrix(rot0), tr0[:, :, None]], dim=2), wlh, K, H, W)
+        cover = torch.zeros(H, W, dtype=torch.bool)
+        for x0, y0, x1, y1 in r0.tolist():
+            if x1 > x0 and y1 > y0:
+                cover[y0:y1, x0:x1] = True
+        ys, xs = torch.nonzero(cover, as_tuple=True)
+        pixels = torch.stack([xs, ys], 1)
+    pixels = torch.as_tensor(pixels).reshape(-1, 2).to(torch.int32)
+    Nr = pixels.shape[0]
+    if Nr == 0:
+        raise U.SnrError("optimize_scene: no pixel to render (the start poses project outside the image)")
+    if bool((pixels[:, 0] < 0).any() | (pixels[:, 0] >= W).any() | (pixels[:, 1] < 0).any() | (pixels[:, 1] >= H).any()):
+        raise U.SnrError("optimize_scene: the pixel list leaves the image")
+    if jitter is None:
+        jitter = torch.rand(T, Nr * Nb, S, generator=torch.Generator().manual_seed(int(seed)))
+    if tuple(jitter.shape) != (T, Nr * Nb, S):
+        raise U.SnrError(f"optimize_scene: jitter must be (T, Nr*Nb, S) = ({T}, {Nr * Nb}, {S}), got {tuple(jitter.shape)}")
+    jitter = jitter.to(dev, torch.float32).contiguous()
+    px = pixels.long()
+    tgt = torch.as_tensor(frame["img"], dtype=torch.float32)[px[:, 1], px[:, 0]].reshape(Nr, 3).to(dev).contiguous()
+    occ = torch.as_tensor(frame["occ"], dtype=torch.float32)[px[:, 1], px[:, 0]].reshape(Nr).to(dev).contiguous()
+    pixels, wlh_d, K_d, gt_d = pixels.to(dev), wlh.to(dev), K.to(dev), gt.to(dev)
+    rot_vec, trans_vec = rot0.to(dev).contiguous().requires_grad_(), tr0.to(dev).contiguous().requires_grad_()
+    shapecode = shapecodes0.detach().clone().to(dev).contiguous().requires_grad_()
+    texturecode = texturecodes0.detach().clone().to(dev).contiguous().requires_grad_()
+    lr = {k: float(opt[k]) for k in ("lr_shape", "lr_texture", "lr_pose")}
+    optim = ops.DeviceAdamW([(shapecode, lr["lr_shape"]), (texturecode, lr["lr_texture"]), (rot_vec, lr["lr_pose"]), (trans_vec, lr["lr_pose"])])
+    sb, tb = model.shape_blocks, model.texture_blocks
+    coef = float(hpams["loss_occ_coef"])
+    shapenet = bool(hpams["shapenet_obj_cood"])
+    one_dir = torch.tensor([0.0, 0.0, 1.0], device=dev).expand(Nb, 1, 3).contiguous()      # PoseRays' ray outputs go unused: one ray is enough
+    half = (wlh_d.norm(dim=1) / 2).contiguous()
+    pose_log = torch.zeros(T, Nb, 3, 4, device=dev)
+    loss_log = torch.zeros(T, 4, device=dev)
+    hit_log = torch.zeros(T, device=dev)
+    ones = torch.ones(1, device=dev)
+    packed = model.packed_weights()
+    prec = model.precision
+    frozen = [p for p in model.parameters() if p.requires_grad]     # the decoder is a constant of this loop, as in _optimize_fused
+    for p in frozen:
+        p.requires_grad_(False)
+    try:
+        for it in range(T):
+            cam2obj = ops.PoseRays.apply(rot_vec, trans_vec, one_dir, half, None, 1, 0)[0]
+            with torch.no_grad():
+                R_obj = cam2obj[:, :, :3].transpose(1, 2)
+                pose_log[it] = torch.cat([R_obj, -(R_obj @ cam2obj[:, :, 3:])], dim=2)
+                rois = scene.scene_rois(pose_log[it], wlh_d, K_d, H, W)
+            xyz, viewdir, z, hit, _ = ops.SceneSamples.apply(cam2obj, wlh_d, rois, pixels, Kvec, jitter[it], S, 1.0, True, shapenet)
+            lat = model.latent_terms(shapecode, texturecode)
+            x3, d3 = xyz.view(-1, 3), viewdir.view(-1, 3)
+            if it == 0:         # which arithmetic the loop runs in: "auto" is decided (and range-checked) once, like CodeNeRF.forward does
+                ppo, probe_pts = model._points_shape(x3.detach(), d3.detach(), lat, pad=sb + tb > 0)
+                prec = model._auto_precision(model.precision, ppo, lambda p_: ops.decoder_fwd(*probe_pts(), lat.detach(), packed, sb, tb, precision=p_)[:2])
+            sig, rgbs = ops.DecoderPoints.apply(x3, d3, lat, packed, sb, tb, prec)
+            sig, rgbs = ops.SceneGather.apply(sig, rgbs, hit, S)
+            rgb, _, acc = ops.SceneComposite.apply(sig, rgbs, z, True, S)
+            loss, lm = ops.LossTail.apply(rgb, acc, tgt, occ, coef, Nr)
+            torch.autograd.backward(loss, ones)
+            with torch.no_grad():
+                loss_log[it, 0:1] = loss.detach()
+                loss_log[it, 1:] = lm[0]
+                hit_log[it] = hit.float().mean()
+            optim.step()
+            optim.zero_grad()
+            if (it + 1) % opt["lr_half_interval"] == 0:
+                optim.restart(2.0 ** (-((it + 1) // opt["lr_half_interval"])))
+    finally:
+        for p in frozen:
+            p.requires_grad_(True)
+    with torch.no_grad():
+        metrics = torch.stack([rot_dist(pose_log[:, :, :, :3], gt_d[None, :, :, :3]), (pose_log[:, :, :, 3] - gt_d[None, :, :, 3]).norm(dim=-1)], dim=-1)
+        poses = torch.cat([axis_angle_to_matrix(rot_vec.detach()), trans_vec.detach()[:, :, None]], dim=2)
+    if info is not None:
+        info["pixels"], info["hit_share"] = pixels, hit_log
+    return metrics, loss_log, shapecode.detach(), texturecode.detach(), poses
+
+
 def make_objects(ids: Sequence[int], im_sz: int, lidar: bool = False) -> List[Dict]:
     """Synthetic nuScenes-like objects.  ``lidar``: also a synthetic set of lidar returns on the foreground (``lidar_xy`` (n,2) crop pixels,
     ``lidar_depth`` (n,) metres; n differs from object to object like real sweeps), which switches the loop's depth metric to the reference's."""

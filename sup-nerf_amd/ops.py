@@ -290,6 +290,115 @@ class SceneComposite(torch.autograd.Function):
         return d_sig, d_rgbs, d_z, None, None
 
 
+def _scene_lists(name, cam2obj, wlh, rois, pixels, jitter, S):
+    """Shapes and types of the scene sample kernels' operands -> (Nr, Nb)."""
+    Nb = cam2obj.shape[0] if cam2obj.dim() == 3 else -1
+    if Nb < 1 or cam2obj.shape != (Nb, 3, 4) or wlh.shape != (Nb, 3) or rois.shape != (Nb, 4) or pixels.dim() != 2 or pixels.shape[1] != 2:
+        raise SnrError(f"{name}: expected cam2obj (Nb,3,4), wlh (Nb,3), rois (Nb,4), pixels (Nr,2), got {tuple(cam2obj.shape)}, {tuple(wlh.shape)}, "
+                       f"{tuple(rois.shape)}, {tuple(pixels.shape)}")
+    if rois.dtype != torch.int32 or pixels.dtype != torch.int32:
+        raise SnrError(f"{name}: rois and pixels are int32 tensors, got {rois.dtype} and {pixels.dtype}")
+    Nr = pixels.shape[0]
+    if int(S) < 1 or (jitter is not None and jitter.shape != (Nr * Nb, int(S))):
+        raise SnrError(f"{name}: expected n_samples >= 1 and jitter (Nr*Nb, S) = ({Nr * Nb}, {int(S)}) or None")
+    return Nr, Nb
+
+
+class SceneSamples(torch.autograd.Function):
+    """Rays, bounds and samples of every (pixel, object) pair of a scene in one launch (snr_scene_samples_fwd; rules: include/supnerf_hip.h):
+    cam2obj (Nb,3,4) [differentiable], wlh (Nb,3), rois (Nb,4) int32, pixels (Nr,2) int32, Kvec = (fx, fy, cx, cy) host numbers, jitter
+    (Nr*Nb,S) or None -> xyz, viewdir (Nb*Nr,S,3) object-major, z_vals (Nr,Nb*S) pixel-major, hit (Nr,Nb) uint8, valid (Nr) uint8.
+    Backward to cam2obj: two launches, the same bits from run to run."""
+
+    @staticmethod
+    def forward(ctx, cam2obj, wlh, rois, pixels, Kvec, jitter, S, adjust_scale, rend_aabb, shapenet_obj_cood):
+        cam2obj, wlh, jitter = _f32c(cam2obj), _f32c(wlh), _f32c(jitter)
+        Nr, Nb = _scene_lists("scene_samples", cam2obj, wlh, rois, pixels, jitter, S)
+        if len(Kvec) != 4:
+            raise SnrError("scene_samples: Kvec is (fx, fy, cx, cy)")
+        _need_gpu(cam2obj, wlh, rois, pixels, jitter)
+        rois, pixels = rois.contiguous(), pixels.contiguous()
+        cfg = (*[float(v) for v in Kvec], int(S), float(adjust_scale), int(bool(rend_aabb)), int(bool(shapenet_obj_cood)))
+        fx, fy, cx, cy, S = cfg[:5]
+        dev = cam2obj.device
+        ctx.set_materialize_grads(False)        # (the kernel takes null for the gradients of outputs that were not used)
+        xyz, viewdir = torch.empty(Nb * Nr, S, 3, device=dev), torch.empty(Nb * Nr, S, 3, device=dev)
+        z = torch.empty(Nr, Nb * S, device=dev)
+        hit = torch.empty(Nr, Nb, dtype=torch.uint8, device=dev)
+        valid = torch.empty(Nr, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_scene_samples_fwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, cfg[5], cfg[6],
+                                                   cfg[7], _p(xyz), _p(viewdir), _p(z), _p(hit), _p(valid), _stream(dev)), "snr_scene_samples_fwd")
+        ctx.save_for_backward(cam2obj, wlh, rois, pixels, jitter)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(hit, valid)
+        return xyz, viewdir, z, hit, valid
+
+    @staticmethod
+    def backward(ctx, d_xyz, d_viewdir, d_z, _d_hit, _d_valid):
+        cam2obj, wlh, rois, pixels, jitter = ctx.saved_tensors
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[5]:
+            raise SnrError("scene_samples: the box sizes and the jitter are data, no gradient is provided")
+        if not ctx.needs_input_grad[0] or (d_xyz is None and d_viewdir is None and d_z is None):
+            return (None,) * 10
+        fx, fy, cx, cy, S, scale, aabb, shapenet = ctx.cfg
+        Nr, Nb = pixels.shape[0], cam2obj.shape[0]
+        dev = cam2obj.device
+        d_xyz, d_viewdir, d_z = _f32c(d_xyz), _f32c(d_viewdir), _f32c(d_z)
+        if Nr == 0:
+            return (torch.zeros_like(cam2obj),) + (None,) * 9
+        d_cam2obj = torch.empty_like(cam2obj)
+        n_ws = int(_lib.lib().snr_scene_samples_bwd_ws_bytes(Nr, Nb))
+        ws = torch.empty(n_ws // 8, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_scene_samples_bwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, scale, aabb,
+                                                   shapenet, _p(d_xyz), _p(d_viewdir), _p(d_z), _p(d_cam2obj), _p(ws), n_ws, _stream(dev)),
+                  "snr_scene_samples_bwd")
+        return (d_cam2obj,) + (None,) * 9
+
+
+class SceneGather(torch.autograd.Function):
+    """The decoder's object-major sigmas (Nb*Nr*S values) and rgbs (Nb*Nr*S,3) as the composite's pixel-major rows (Nr,Nb*S) / (Nr,Nb*S,3),
+    sigma 0 and white where ``hit`` (Nr,Nb) uint8 is 0: the permutes and ``torch.where`` of ``scene.render_scene_batch`` in one launch, bit for
+    bit; backward the inverse scatter in one launch."""
+
+    @staticmethod
+    def forward(ctx, sigmas, rgbs, hit, S):
+        sigmas, rgbs = _f32c(sigmas), _f32c(rgbs)
+        S = int(S)
+        if hit.dim() != 2 or hit.dtype != torch.uint8 or S < 1 or sigmas.numel() != hit.numel() * S or rgbs.numel() != 3 * sigmas.numel():
+            raise SnrError(f"scene_gather: expected sigmas (Nb*Nr*S), rgbs (Nb*Nr*S,3) and hit (Nr,Nb) uint8, got {tuple(sigmas.shape)}, "
+                           f"{tuple(rgbs.shape)}, {tuple(hit.shape)} {hit.dtype}, S = {S}")
+        _need_gpu(sigmas, rgbs, hit)
+        hit = hit.contiguous()
+        Nr, Nb = hit.shape
+        dev = sigmas.device
+        ctx.set_materialize_grads(False)
+        sig_rows, rgb_rows = torch.empty(Nr, Nb * S, device=dev), torch.empty(Nr, Nb * S, 3, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_scene_gather_fwd(_p(sigmas), _p(rgbs), _p(hit), Nr, Nb, S, _p(sig_rows), _p(rgb_rows), _stream(dev)),
+                  "snr_scene_gather_fwd")
+        ctx.save_for_backward(hit)
+        ctx.cfg = (S, sigmas.shape, rgbs.shape)
+        return sig_rows, rgb_rows
+
+    @staticmethod
+    def backward(ctx, d_sig_rows, d_rgb_rows):
+        hit, = ctx.saved_tensors
+        S, sig_shape, rgb_shape = ctx.cfg
+        Nr, Nb = hit.shape
+        dev = hit.device
+        d_sig_rows = _f32c(d_sig_rows) if ctx.needs_input_grad[0] else None
+        d_rgb_rows = _f32c(d_rgb_rows) if ctx.needs_input_grad[1] else None
+        d_sig = torch.empty(sig_shape, device=dev) if d_sig_rows is not None else None
+        d_rgb = torch.empty(rgb_shape, device=dev) if d_rgb_rows is not None else None
+        if d_sig is not None or d_rgb is not None:
+            with torch.cuda.device(dev):
+                check(_lib.lib().snr_scene_gather_bwd(_p(d_sig_rows), _p(d_rgb_rows), _p(hit), Nr, Nb, S, _p(d_sig), _p(d_rgb), _stream(dev)),
+                      "snr_scene_gather_bwd")
+        return d_sig, d_rgb, None, None
+
+
 def composite_bwd(sigmas, rgbs, z_vals, z_mode, white_bkgd, rays_per_obj, d_rgb, d_depth, d_acc, need_dz):
     sigmas, rgbs, z_vals = _f32c(sigmas), _f32c(rgbs), _f32c(z_vals)
     # dense copies are NAMED so that they live until the launch is enqueued: `_p(_f32c(t))` inside the argument list frees the temporary before

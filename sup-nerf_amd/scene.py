@@ -79,6 +79,36 @@ def scene_rays(obj_poses, obj_wlh, K, H, W, manipulation=(0.0, 0.0, 0.0), rend_a
     return table, valid, diags
 
 
+_BOX_SIGNS = {}
+
+
+def _box_signs(dev):
+    """(3,8) corner signs of ``corners_of_box_batch``, one copy per device."""
+    key = str(dev)
+    if key not in _BOX_SIGNS:
+        _BOX_SIGNS[key] = torch.tensor([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]],
+                                       dtype=torch.float32, device=dev)
+    return _BOX_SIGNS[key]
+
+
+def scene_rois(obj_poses, obj_wlh, K, H, W, manipulation=(0.0, 0.0, 0.0)):
+    """(Nb,4) int32 [x0, y0, x1, y1]: every object's roi as ``scene_rays`` and ``scene_ray_rows`` take it -- the truncated projection of the box
+    corners at the (manipulated) pose, clamped to the image like ``roi_process(roi, H, W, 0, False)`` -- in fp32 on the device of
+    ``obj_poses``, without gradient.  An object whose roi has x1 <= x0 or y1 <= y0 covers no pixel."""
+    with torch.no_grad():
+        dev = obj_poses.device
+        poses = obj_poses.detach().float()
+        if any(float(m) != 0.0 for m in manipulation):
+            poses = poses.clone()
+            poses[:, :, 3] += torch.tensor(manipulation, dtype=torch.float32, device=dev).unsqueeze(0)
+        wlh, K32 = obj_wlh.detach().to(dev, torch.float32), K.detach().to(dev, torch.float32)
+        # corners_of_box_batch with its sign table kept on the device: a call inside an optimise loop uploads nothing
+        local = torch.stack([wlh[:, 1] / 2, wlh[:, 0] / 2, wlh[:, 2] / 2], dim=1)[:, :, None] * _box_signs(dev)[None]
+        uv = view_points_batch(torch.matmul(poses[:, :, :3], local) + poses[:, :, 3:4], K32.unsqueeze(0).repeat(poses.shape[0], 1, 1))
+        rois = torch.stack([uv[:, 0].min(dim=1)[0], uv[:, 1].min(dim=1)[0], uv[:, 0].max(dim=1)[0], uv[:, 1].max(dim=1)[0]], dim=1).type(torch.int32)
+        return torch.stack([rois[:, 0].clamp(min=0), rois[:, 1].clamp(min=0), rois[:, 2].clamp(max=W - 1), rois[:, 3].clamp(max=H - 1)], 1)
+
+
 def render_scene_batch(model, device, batch_rays, diags, shapecodes, texturecodes, n_samples, jitter=None, adjust_scale=1.0,
                        shapenet_obj_cood=True):
     """One ray batch (Nr, Nb, 8) -> rgb (Nr,3), depth (Nr,), acc_trans (Nr,)  (scripts/demo.py:527-566)."""
@@ -164,16 +194,46 @@ def scene_ray_rows(obj_poses, obj_wlh, K, pixels, H, W, manipulation=(0.0, 0.0, 
 
 
 def render_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, pixels, H, W, n_samples, jitter=None,
-                 manipulation=(0.0, 0.0, 0.0), rend_aabb=True, shapenet_obj_cood=True, adjust_scale=1.0):
+                 manipulation=(0.0, 0.0, 0.0), rend_aabb=True, shapenet_obj_cood=True, adjust_scale=1.0, fused=False):
     """rgb (Nr,3), depth (Nr,), acc_trans (Nr,) of the scene at the listed integer pixels (Nr,2) = (x, y), with autograd to
     ``shapecodes``, ``texturecodes`` and ``obj_poses``: ``render_scene_batch`` of ``scene_ray_rows``.  ``jitter``: (Nr*Nb, S) draws in
-    [0,1), default ``torch.rand_like``.  Every listed pixel is rendered; one that no object covers comes out white."""
+    [0,1), default ``torch.rand_like``.  Every listed pixel is rendered; one that no object covers comes out white.
+    ``fused`` (native decoders): rows and samples in one launch (``ops.SceneSamples``) and the decoder's outputs regrouped in one
+    (``ops.SceneGather``), each with a one-launch backward, instead of ~65 torch launches each way; same rois, same jitter draw."""
     if obj_poses.shape[0] != shapecodes.shape[0] or obj_poses.shape[0] != texturecodes.shape[0] or obj_poses.shape[0] != obj_wlh.shape[0]:
         raise SnrError("render_scene: obj_poses, obj_wlh, shapecodes and texturecodes must describe the same number of objects")
     dev = torch.device(device)
+    if fused:
+        return _render_scene_fused(model, dev, obj_poses.to(dev), obj_wlh, shapecodes, texturecodes, K, pixels, H, W, n_samples, jitter, manipulation,
+                                   rend_aabb, shapenet_obj_cood, adjust_scale)
     rows, _ = scene_ray_rows(obj_poses.to(dev), obj_wlh, K, pixels, H, W, manipulation, rend_aabb)
     diags = torch.linalg.norm(obj_wlh.detach().float(), dim=1)
     return render_scene_batch(model, device, rows.float(), diags, shapecodes, texturecodes, n_samples, jitter, adjust_scale, shapenet_obj_cood)
+
+
+def _render_scene_fused(model, dev, obj_poses, obj_wlh, shapecodes, texturecodes, K, pixels, H, W, n_samples, jitter, manipulation, rend_aabb,
+                        shapenet_obj_cood, adjust_scale):
+    """``render_scene`` with the rows, samples and regrouping on the HIP kernels; the decoder and the composite as on the default route."""
+    if not U._is_native(model):
+        raise SnrError("render_scene(fused=True) needs the package's own decoder; a foreign decoder renders on the default route")
+    Nb = obj_poses.shape[0]
+    pixels = torch.as_tensor(pixels).to(dev, torch.int32)
+    Nr = pixels.shape[0]
+    poses = torch.cat([obj_poses[:, :, :3], obj_poses[:, :, 3:4] + torch.tensor(manipulation, dtype=obj_poses.dtype, device=dev).view(1, 3, 1)], dim=2)
+    rois = scene_rois(poses.detach().cpu(), obj_wlh.detach().cpu(), K.detach().cpu(), H, W).to(dev)     # the one host read, as in scene_ray_rows
+    R_c2o = poses[:, :3, :3].transpose(1, 2)
+    cam2obj = torch.cat([R_c2o, -(R_c2o @ poses[:, :3, 3:4])], dim=2)
+    if jitter is None:
+        jitter = torch.rand(Nr * Nb, n_samples)                                                      # CPU draw, like render_scene_batch
+    Kc = K.detach().cpu().float()
+    xyz, viewdir, z_vals, hit, _ = ops.SceneSamples.apply(cam2obj.float(), obj_wlh.detach().to(dev), rois, pixels,
+                                                          (Kc[0, 0], Kc[1, 1], Kc[0, 2], Kc[1, 2]), jitter.to(dev), n_samples, adjust_scale, rend_aabb,
+                                                          shapenet_obj_cood)
+    sig, rgb = model(xyz, viewdir, shapecodes.to(dev), texturecodes.to(dev))                         # object-major, Nb codes
+    sig, rgb = ops.SceneGather.apply(sig, rgb, hit, n_samples)
+    if torch.is_grad_enabled() and (sig.requires_grad or rgb.requires_grad or z_vals.requires_grad):
+        return ops.SceneComposite.apply(sig, rgb, z_vals, True, n_samples)
+    return ops.scene_composite(sig, rgb, z_vals, white_bkgd=True, run_length=n_samples)
 
 
 def vis_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, H, W, n_samples, manipulation=(0.0, 0.0, 0.0),

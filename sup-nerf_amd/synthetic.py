@@ -138,3 +138,48 @@ def synthetic_lidar(index, mask, ob):
     dist = float(np.linalg.norm(ob["cam_pose"][:, 3].numpy()))
     depth = dist - 0.3 * float(ob["obj_diag"]) * (1.0 - 0.5 * r2) + 0.02 * rs.randn(n)
     return np.stack([x, y], axis=1).astype(np.int64), depth.astype(np.float32)
+
+
+# ------------------------------------------------------------------ several objects in one camera (driver.optimize_scene)
+def synthetic_frame(ids, H, W, focal=None, model=None, device=None, shapecodes=None, texturecodes=None, n_samples=32):
+    """The synthetic objects ``ids`` side by side in ONE camera of H x W pixels: dict(K, H, W, obj_poses (Nb,3,4) object poses in the camera
+    frame, obj_wlh (Nb,3), img (H,W,3), occ (H,W) in {-1,0,1}).  Sizes and yaws are ``synthetic_object``'s; the objects stand in a row across
+    the image at depths 10, 12, 14, 10, ... on the optical axis' height.  With ``model`` (and codes) the target is ``scene.render_scene`` at
+    these poses without jitter -- occ 1 where the transmittance is below 0.3, -1 above 0.7, 0 between; without, a random image and the rois'
+    inner ellipses."""
+    from . import scene
+    n = len(ids)
+    focal = 0.3 * W if focal is None else float(focal)
+    K = torch.tensor([[focal, 0.0, W / 2.0], [0.0, focal, H / 2.0], [0.0, 0.0, 1.0]])
+    poses, wlhs = [], []
+    for j, i in enumerate(ids):
+        ob = synthetic_object(i)
+        R_obj = ob["cam_pose"][:, :3].T
+        depth = 10.0 + 2.0 * (j % 3)
+        u = W * (j + 0.5) / n
+        poses.append(torch.cat([R_obj, torch.tensor([[(u - W / 2.0) * depth / focal], [0.0], [depth]])], dim=1))
+        wlhs.append(torch.from_numpy(ob["wlh"]))
+    obj_poses, obj_wlh = torch.stack(poses), torch.stack(wlhs)
+    rois = scene.scene_rois(obj_poses, obj_wlh, K, H, W)
+    img, occ = torch.ones(H, W, 3), -torch.ones(H, W)
+    if model is None:
+        img = torch.rand(H, W, 3, generator=torch.Generator().manual_seed(3000 + int(ids[0]) if n else 0))
+        yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+        for x0, y0, x1, y1 in rois.tolist():
+            if x1 > x0 and y1 > y0:
+                r = ((xx - (x0 + x1) / 2) / (0.4 * (x1 - x0))) ** 2 + ((yy - (y0 + y1) / 2) / (0.3 * (y1 - y0))) ** 2
+                occ = torch.where(r < 1.0, torch.ones_like(occ), occ)
+    else:
+        cover = torch.zeros(H, W, dtype=torch.bool)
+        for x0, y0, x1, y1 in rois.tolist():
+            if x1 > x0 and y1 > y0:
+                cover[y0:y1, x0:x1] = True
+        ys, xs = torch.nonzero(cover, as_tuple=True)
+        with torch.no_grad():
+            for part in torch.split(torch.stack([xs, ys], 1), 8192):
+                rgb, _, acc = scene.render_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, part, H, W, n_samples,
+                                                 jitter=torch.zeros(part.shape[0] * n, n_samples))
+                img[part[:, 1], part[:, 0]] = rgb.cpu()
+                a = acc.cpu()
+                occ[part[:, 1], part[:, 0]] = torch.where(a < 0.3, torch.ones_like(a), torch.where(a > 0.7, -torch.ones_like(a), torch.zeros_like(a)))
+    return dict(K=K, H=H, W=W, obj_poses=obj_poses, obj_wlh=obj_wlh, img=img, occ=occ)
