@@ -17,6 +17,7 @@ No dataset is available offline: objects come from ``synthetic.py`` (SURVEY.md 8
 (pytorch3d ``axis_angle_to_matrix`` / ``matrix_to_axis_angle`` in the reference, un-pinned and not installed) is
 restated here via Rodrigues' formula; parity for it is pinned only by self-consistency tests.
 """
+import contextlib
 import json
 import math
 from typing import Dict, List, Optional, Sequence
@@ -24,7 +25,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import synthetic, utils as U
+from . import scene, synthetic, utils as U
 
 DEFAULT_HPAMS = {     # the keys of jsonfiles/supnerf.nusc.vehicle.car.json that the loop reads
     "n_samples": 64, "render_im_sz": 32, "roi_margin": 5, "shapenet_obj_cood": 1, "sym_aug": 0, "loss_occ_coef": 0.1,
@@ -134,24 +135,14 @@ def gather_metric_rows(rows: torch.Tensor, ids: torch.Tensor, n_items: int, grou
 
 
 # ------------------------------------------------------------------ the stock pose head in the loop (src/optimizer_nuscenes.py:451-551)
-def _box_corners(obj_pose, wlh):
-    """(B,3,8) box corners in the camera frame: ``corners_of_box_batch(obj_pose, wlh)`` (src/utils.py:1110-1148, nuScenes order: x
-    forward, y left, z up)."""
-    sx = torch.tensor([1, 1, 1, 1, -1, -1, -1, -1], dtype=wlh.dtype, device=wlh.device)
-    sy = torch.tensor([1, -1, -1, 1, 1, -1, -1, 1], dtype=wlh.dtype, device=wlh.device)
-    sz = torch.tensor([1, 1, -1, -1, 1, 1, -1, -1], dtype=wlh.dtype, device=wlh.device)
-    local = torch.stack([wlh[:, 1:2] / 2 * sx, wlh[:, 0:1] / 2 * sy, wlh[:, 2:3] / 2 * sz], dim=1)
-    return torch.matmul(obj_pose[:, :, :3], local) + obj_pose[:, :, 3:4]
-
-
 def fw_pose_one_step(model, im_feat, src_pose, wlh, roi, K, K_inv):
     """One step of the feed-forward pose refiner, ``OptimizerNuScenes.fw_pose_one_step`` (src/optimizer_nuscenes.py:509-551): project
-    the current box (``corners_of_box_batch`` + ``view_points_batch(normalize=True)``), normalise the 8 corners by the roi
+    the current box (``scene.corners_of_box_batch`` + ``view_points_batch(normalize=True)``), normalise the 8 corners by the roi
     (``normalize_by_roi(need_square=True)``, src/utils.py:1175-1197), let the STOCK pose head ``model.pose_update`` (plain PyTorch,
     src/model_supnerf.py:226-239) regress a 6-vector, and apply it: rotation vector += 2 pi d[:3]; projected centre += d[3:5] * roi size;
     depth *= (d[5] + 1).  (B,3,4) object poses in, (B,3,4) out.  Rotation conversions: Rodrigues (``axis_angle_to_matrix`` above; the
     reference calls pytorch3d, un-pinned)."""
-    uvw = torch.matmul(K, _box_corners(src_pose, wlh))
+    uvw = torch.matmul(K, scene.corners_of_box_batch(src_pose, wlh))
     uv = (uvw / uvw[:, 2:3, :])[:, :2, :]
     w_, h_ = roi[:, 2] - roi[:, 0], roi[:, 3] - roi[:, 1]
     cx, cy = (roi[:, 2] + roi[:, 0]) / 2, (roi[:, 3] + roi[:, 1]) / 2
@@ -239,10 +230,8 @@ def optimize_object_api(model, device, obj: Dict, hpams: dict, shapecode0, textu
     K, roi, obj_diag = obj["K"], obj["roi"], obj["obj_diag"]
     img, mask = obj["img"], obj["mask"]
     # ground-truth OBJECT pose in the camera frame and a perturbed start
-    R_c2o, t_c2o = obj["cam_pose"][:, :3], obj["cam_pose"][:, 3:]
-    R_gt = R_c2o.T
-    t_gt = (-R_gt @ t_c2o)
-    gt_pose = torch.cat([R_gt, t_gt], -1)
+    gt_pose = U.invert_pose(obj["cam_pose"])
+    R_gt, t_gt = gt_pose[:, :3], gt_pose[:, 3:]
     rot_vec = (matrix_to_axis_angle(R_gt[None]) + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[0]).to(dev)
     trans_vec = (t_gt.T + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[1]).to(dev)
     if pose_per_iter is not None:          # the pose head's table: start from its last pose (src/optimizer_nuscenes.py:652,664-666)
@@ -267,15 +256,10 @@ def optimize_object_api(model, device, obj: Dict, hpams: dict, shapecode0, textu
         if jitter is not None:                                   # (num_opts, 2, S): the two draws of this iteration (tests)
             U.JITTER_OVERRIDE = jitter[it, 0]
         if pose_per_iter is not None and it <= reg_iters:        # "the first a few to load pre-computed poses" (:684-689)
-            R, t = pose_per_iter[it, :3, :3], pose_per_iter[it, :3, 3:]
+            pose = pose_per_iter[it]
         else:
-            R = axis_angle_to_matrix(rot_vec[0])
-            t = trans_vec[0].unsqueeze(-1)
-        if not opt.get("opt_cam_pose", 0):                       # object pose is optimised: invert to camera-in-object
-            Rc = R.transpose(-2, -1)
-            cam2opt = torch.cat([Rc, -Rc @ t], -1)
-        else:
-            cam2opt = torch.cat([R, t], -1)
+            pose = torch.cat([axis_angle_to_matrix(rot_vec[0]), trans_vec[0].unsqueeze(-1)], -1)
+        cam2opt = pose if opt.get("opt_cam_pose", 0) else U.invert_pose(pose)      # object pose is optimised: invert to camera-in-object
         rgb, depth, acc, rgb_tgt, occ = U.render_rays_v2(model, dev, img, mask, cam2opt, obj_diag, K, roi, S, shapecode, texturecode,
                                                          hpams["shapenet_obj_cood"], hpams["sym_aug"], im_sz=im_sz, n_rays=None)
         loss, mse_fg = losses(rgb, acc, rgb_tgt, occ, hpams["loss_occ_coef"])
@@ -287,8 +271,8 @@ def optimize_object_api(model, device, obj: Dict, hpams: dict, shapecode0, textu
                                                         shapecode, texturecode, hpams["shapenet_obj_cood"], hpams["sym_aug"])
             if depth0 is None:
                 depth0 = d_vec.clone()
-            pred_R = cam2opt[:, :3].detach().T if not opt.get("opt_cam_pose", 0) else cam2opt[:, :3].detach()
-            pred_t = (-pred_R @ cam2opt[:, 3:].detach()) if not opt.get("opt_cam_pose", 0) else cam2opt[:, 3:].detach()
+            pred = cam2opt.detach() if opt.get("opt_cam_pose", 0) else U.invert_pose(cam2opt.detach())
+            pred_R, pred_t = pred[:, :3], pred[:, 3:]
             row = torch.stack([-10 * torch.log10(mse_fg.detach()), (d_vec - depth0).abs().sum() / (len(x_vec) + 1e-8),     # (log_eval_depth_v2, :1736-1741)
                                rot_dist(pred_R, gt_dev[:, :3]), (pred_t - gt_dev[:, 3:]).norm()])
         metrics[it] = row
@@ -353,8 +337,8 @@ def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=Non
     rot0, tr0, gtR, gtT, cam, lid, lid_d, tgt, occ = [], [], [], [], [], [], [], [], []
     for ob, seed in zip(objs, seeds):
         rs = np.random.RandomState(seed)
-        R_gt = ob["cam_pose"][:, :3].T
-        t_gt = -R_gt @ ob["cam_pose"][:, 3:]
+        gt = U.invert_pose(ob["cam_pose"])
+        R_gt, t_gt = gt[:, :3], gt[:, 3:]
         rot0.append(matrix_to_axis_angle(R_gt[None]) + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[0])
         tr0.append(t_gt.T + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[1])
         if pose_per_iter is not None:      # (the draws above still happen: the lidar pixels below come from the same RandomState)
@@ -390,6 +374,36 @@ def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=Non
                 tgt=st(tgt), occ=st(occ), diag=torch.tensor([float(ob["obj_diag"]) for ob in objs], device=dev), n_lidar=n_l)
 
 
+@contextlib.contextmanager
+def _decoder_frozen(model):
+    """The decoder is a constant of the fused loops (the reference leaves its weights trainable and pays for unused weight gradients): inside
+    the block none of its parameters requires a gradient; those that did are handed back trainable, also when the loop raises."""
+    frozen = [p for p in model.parameters() if p.requires_grad]
+    for p in frozen:
+        p.requires_grad_(False)
+    try:
+        yield
+    finally:
+        for p in frozen:
+            p.requires_grad_(True)
+
+
+def _leaves_and_adamw(shapecodes0, texturecodes0, rot0, tr0, opt, dev):
+    """The four leaves of a fused loop on the device -- clones of the start codes, the start rotation and translation vectors -- and
+    ``ops.DeviceAdamW`` over them with the three learning rates (src/optimizer_nuscenes.py:1762-1769)."""
+    shapecode, texturecode = [t.detach().clone().to(dev).contiguous().requires_grad_() for t in (shapecodes0, texturecodes0)]
+    rot_vec, trans_vec = [t.to(dev).contiguous().requires_grad_() for t in (rot0, tr0)]
+    lr_shape, lr_texture, lr_pose = [float(opt[k]) for k in ("lr_shape", "lr_texture", "lr_pose")]
+    optim = U.ops.DeviceAdamW([(shapecode, lr_shape), (texturecode, lr_texture), (rot_vec, lr_pose), (trans_vec, lr_pose)])
+    return shapecode, texturecode, rot_vec, trans_vec, optim
+
+
+def _halve_rates(optim, it, opt):
+    """After every ``lr_half_interval`` iterations: AdamW as re-created with its rates scaled down (src/optimizer_nuscenes.py:1771-1775)."""
+    if (it + 1) % opt["lr_half_interval"] == 0:
+        optim.restart(2.0 ** (-((it + 1) // opt["lr_half_interval"])))
+
+
 def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, pose_noise, reg_iters, n_lidar, jitter, info=None,
                     pose_per_iter=None):
     """The iteration as ~30 launches for any number of objects: pose -> rays + depths (one launch), the per-object layers (two GEMMs),
@@ -401,15 +415,11 @@ def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, 
     B, n = len(objs), im_sz * im_sz
     c = _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter)
     n_l = c["n_lidar"]
-    rot_vec, trans_vec = c["rot0"].requires_grad_(), c["tr0"].requires_grad_()
-    shapecode = shapecodes0.detach().clone().to(dev).contiguous().requires_grad_()
-    texturecode = texturecodes0.detach().clone().to(dev).contiguous().requires_grad_()
+    shapecode, texturecode, rot_vec, trans_vec, optim = _leaves_and_adamw(shapecodes0, texturecodes0, c["rot0"], c["tr0"], opt, dev)
     if jitter is None:
         gens = [torch.Generator().manual_seed(int(s_)) for s_ in seeds]
         jitter = torch.stack([torch.rand(T, 2, S, generator=g) for g in gens], dim=2)
     jitter = jitter.to(dev).contiguous()
-    lr = {k: float(opt[k]) for k in ("lr_shape", "lr_texture", "lr_pose")}
-    optim = ops.DeviceAdamW([(shapecode, lr["lr_shape"]), (texturecode, lr["lr_texture"]), (rot_vec, lr["lr_pose"]), (trans_vec, lr["lr_pose"])])
     frame = U._frame(False, False, hpams["shapenet_obj_cood"])
     sb, tb = model.shape_blocks, model.texture_blocks
     half = (c["diag"] / 2).contiguous()
@@ -427,17 +437,11 @@ def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, 
     packed = model.packed_weights()
     table = None
     if pose_per_iter is not None:
-        # the render-only iterations' camera poses, made once: cam2opt = [R^T | -R^T t] of the table's object poses unless the camera pose
-        # itself is what is optimised (src/optimizer_nuscenes.py:684-699); (reg_iters + 1, B, 3, 4) on the device
+        # the render-only iterations' camera poses, made once: the inverses of the table's object poses unless the camera pose itself is
+        # what is optimised (src/optimizer_nuscenes.py:684-699); (reg_iters + 1, B, 3, 4) on the device
         P = pose_per_iter.to(dev).permute(1, 0, 2, 3)
-        if not opt_cam:
-            Rt = P[..., :3].transpose(-1, -2)
-            P = torch.cat([Rt, -Rt @ P[..., 3:]], dim=-1)
-        table = P.contiguous()
-    frozen = [p for p in model.parameters() if p.requires_grad]     # the decoder is a constant of this loop (the reference leaves its
-    for p in frozen:                                                 # weights trainable and pays for unused weight gradients)
-        p.requires_grad_(False)
-    try:
+        table = (P if opt_cam else U.invert_pose(P)).contiguous()
+    with _decoder_frozen(model):
         for it in range(T):
             from_table = table is not None and it <= reg_iters
             if from_table:      # a pre-computed pose per object: rays straight from the (3,4) camera poses (snr_cam_rays_fwd), nothing to differentiate
@@ -477,11 +481,7 @@ def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, 
             if it > reg_iters:
                 optim.step()
             optim.zero_grad()
-            if (it + 1) % opt["lr_half_interval"] == 0:
-                optim.restart(2.0 ** (-((it + 1) // opt["lr_half_interval"])))
-    finally:
-        for p in frozen:
-            p.requires_grad_(True)
+            _halve_rates(optim, it, opt)
     return metrics.permute(1, 0, 2).contiguous(), shapecode.detach(), texturecode.detach(), pose
 
 
@@ -496,14 +496,13 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
     default: the pixels inside the union of the start poses' rois.  ``jitter`` (T, Nr*Nb, S); default: one seeded CPU generator.
 
     One iteration, without a host round trip: pose parameters -> camera-in-object poses (``ops.PoseRays``), ``scene.scene_rois`` on the device
-    from the detached poses, ``ops.SceneSamples``, the decoder on the object-major points, ``ops.SceneGather``, ``ops.SceneComposite``,
-    ``ops.LossTail`` with the scene as one "object", backward, ``ops.DeviceAdamW`` over the four groups (every iteration; rates halved every
-    ``lr_half_interval``).  The decoder's weights are constants of the loop.  ``info`` receives ``pixels`` and ``hit_share`` (T,), the share of
-    (pixel, object) pairs that hit per iteration.
+    from the detached poses, ``scene.render_pairs`` (``ops.SceneSamples``, the decoder on the object-major points, ``ops.SceneGather``,
+    ``ops.SceneComposite``), ``ops.LossTail`` with the scene as one "object", backward, ``ops.DeviceAdamW`` over the four groups (every
+    iteration; rates halved every ``lr_half_interval``).  The decoder's weights are constants of the loop.  ``info`` receives ``pixels`` and
+    ``hit_share`` (T,), the share of (pixel, object) pairs that hit per iteration.
 
     Returns metrics (T,Nb,2) = rotation / translation error of every object at the poses iteration t rendered, losses (T,4) = [loss,
     loss_rgb, loss_occ, mse_fg], shape codes, texture codes and the object poses (Nb,3,4) after the last update."""
-    from . import scene
     ops = U.ops
     dev = torch.device(device)
     opt = hpams["optimize"]
@@ -523,18 +522,12 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
         raise U.SnrError("optimize_scene optimises object poses in one camera (opt_cam_pose = 0)")
     H, W = int(frame["H"]), int(frame["W"])
     K = torch.as_tensor(frame["K"], dtype=torch.float32).cpu()
-    Kvec = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
+    Kvec = scene.K_vector(K)
     rs = np.random.RandomState(seed)
     rot0 = matrix_to_axis_angle(gt[:, :, :3]) + torch.from_numpy(rs.randn(Nb, 3).astype(np.float32)) * pose_noise[0]
     tr0 = gt[:, :, 3] + torch.from_numpy(rs.randn(Nb, 3).astype(np.float32)) * pose_noise[1]
     if pixels is None:
-        r0 = scene.scene_rois(torch.cat([axis_angle_to_matrix(rot0), tr0[:, :, None]], dim=2), wlh, K, H, W)
-        cover = torch.zeros(H, W, dtype=torch.bool)
-        for x0, y0, x1, y1 in r0.tolist():
-            if x1 > x0 and y1 > y0:
-                cover[y0:y1, x0:x1] = True
-        ys, xs = torch.nonzero(cover, as_tuple=True)
-        pixels = torch.stack([xs, ys], 1)
+        pixels = scene.roi_pixels(scene.scene_rois(torch.cat([axis_angle_to_matrix(rot0), tr0[:, :, None]], dim=2), wlh, K, H, W), H, W)
     pixels = torch.as_tensor(pixels).reshape(-1, 2).to(torch.int32)
     Nr = pixels.shape[0]
     if Nr == 0:
@@ -550,11 +543,7 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
     tgt = torch.as_tensor(frame["img"], dtype=torch.float32)[px[:, 1], px[:, 0]].reshape(Nr, 3).to(dev).contiguous()
     occ = torch.as_tensor(frame["occ"], dtype=torch.float32)[px[:, 1], px[:, 0]].reshape(Nr).to(dev).contiguous()
     pixels, wlh_d, K_d, gt_d = pixels.to(dev), wlh.to(dev), K.to(dev), gt.to(dev)
-    rot_vec, trans_vec = rot0.to(dev).contiguous().requires_grad_(), tr0.to(dev).contiguous().requires_grad_()
-    shapecode = shapecodes0.detach().clone().to(dev).contiguous().requires_grad_()
-    texturecode = texturecodes0.detach().clone().to(dev).contiguous().requires_grad_()
-    lr = {k: float(opt[k]) for k in ("lr_shape", "lr_texture", "lr_pose")}
-    optim = ops.DeviceAdamW([(shapecode, lr["lr_shape"]), (texturecode, lr["lr_texture"]), (rot_vec, lr["lr_pose"]), (trans_vec, lr["lr_pose"])])
+    shapecode, texturecode, rot_vec, trans_vec, optim = _leaves_and_adamw(shapecodes0, texturecodes0, rot0, tr0, opt, dev)
     sb, tb = model.shape_blocks, model.texture_blocks
     coef = float(hpams["loss_occ_coef"])
     shapenet = bool(hpams["shapenet_obj_cood"])
@@ -565,26 +554,23 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
     hit_log = torch.zeros(T, device=dev)
     ones = torch.ones(1, device=dev)
     packed = model.packed_weights()
-    prec = model.precision
-    frozen = [p for p in model.parameters() if p.requires_grad]     # the decoder is a constant of this loop, as in _optimize_fused
-    for p in frozen:
-        p.requires_grad_(False)
-    try:
+    prec = None
+
+    def decode(xyz, viewdir):
+        nonlocal prec
+        lat = model.latent_terms(shapecode, texturecode)
+        x3, d3 = xyz.view(-1, 3), viewdir.view(-1, 3)
+        if prec is None:    # iteration 0 -- which arithmetic the loop runs in: "auto" is decided (and range-checked) once, like CodeNeRF.forward does
+            ppo, probe_pts = model._points_shape(x3.detach(), d3.detach(), lat, pad=sb + tb > 0)
+            prec = model._auto_precision(model.precision, ppo, lambda p_: ops.decoder_fwd(*probe_pts(), lat.detach(), packed, sb, tb, precision=p_)[:2])
+        return ops.DecoderPoints.apply(x3, d3, lat, packed, sb, tb, prec)
+    with _decoder_frozen(model):
         for it in range(T):
             cam2obj = ops.PoseRays.apply(rot_vec, trans_vec, one_dir, half, None, 1, 0)[0]
             with torch.no_grad():
-                R_obj = cam2obj[:, :, :3].transpose(1, 2)
-                pose_log[it] = torch.cat([R_obj, -(R_obj @ cam2obj[:, :, 3:])], dim=2)
+                pose_log[it] = U.invert_pose(cam2obj)
                 rois = scene.scene_rois(pose_log[it], wlh_d, K_d, H, W)
-            xyz, viewdir, z, hit, _ = ops.SceneSamples.apply(cam2obj, wlh_d, rois, pixels, Kvec, jitter[it], S, 1.0, True, shapenet)
-            lat = model.latent_terms(shapecode, texturecode)
-            x3, d3 = xyz.view(-1, 3), viewdir.view(-1, 3)
-            if it == 0:         # which arithmetic the loop runs in: "auto" is decided (and range-checked) once, like CodeNeRF.forward does
-                ppo, probe_pts = model._points_shape(x3.detach(), d3.detach(), lat, pad=sb + tb > 0)
-                prec = model._auto_precision(model.precision, ppo, lambda p_: ops.decoder_fwd(*probe_pts(), lat.detach(), packed, sb, tb, precision=p_)[:2])
-            sig, rgbs = ops.DecoderPoints.apply(x3, d3, lat, packed, sb, tb, prec)
-            sig, rgbs = ops.SceneGather.apply(sig, rgbs, hit, S)
-            rgb, _, acc = ops.SceneComposite.apply(sig, rgbs, z, True, S)
+            rgb, _, acc, hit = scene.render_pairs(decode, cam2obj, wlh_d, rois, pixels, Kvec, jitter[it], S, 1.0, True, shapenet)
             loss, lm = ops.LossTail.apply(rgb, acc, tgt, occ, coef, Nr)
             torch.autograd.backward(loss, ones)
             with torch.no_grad():
@@ -593,11 +579,7 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
                 hit_log[it] = hit.float().mean()
             optim.step()
             optim.zero_grad()
-            if (it + 1) % opt["lr_half_interval"] == 0:
-                optim.restart(2.0 ** (-((it + 1) // opt["lr_half_interval"])))
-    finally:
-        for p in frozen:
-            p.requires_grad_(True)
+            _halve_rates(optim, it, opt)
     with torch.no_grad():
         metrics = torch.stack([rot_dist(pose_log[:, :, :, :3], gt_d[None, :, :, :3]), (pose_log[:, :, :, 3] - gt_d[None, :, :, 3]).norm(dim=-1)], dim=-1)
         poses = torch.cat([axis_angle_to_matrix(rot_vec.detach()), trans_vec.detach()[:, :, None]], dim=2)
@@ -636,8 +618,7 @@ def make_kitti_objects(ids: Sequence[int], hpams: dict) -> List[Dict]:
         ob = synthetic.synthetic_kitti_object(i, K=synthetic.WAYMO_K, im_w=synthetic.WAYMO_IM_W, im_h=synthetic.WAYMO_IM_H) if waymo \
             else synthetic.synthetic_kitti_object(i)
         pose_nusc = U.obj_pose_kitti2nusc(ob["obj_pose"][None].clone(), torch.tensor([float(ob["wlh"][2])]))[0]
-        R_c2o = pose_nusc[:, :3].T
-        cam_pose = torch.cat([R_c2o, -R_c2o @ pose_nusc[:, 3:]], -1)
+        cam_pose = U.invert_pose(pose_nusc)
         roi = U.roi_process(ob["box2d"], ob["im_h"], ob["im_w"], margin, sq_pad=True)
         h, w = int(roi[3] - roi[1]), int(roi[2] - roi[0])
         img, mask = synthetic.synthetic_crop_targets(i, h, w)

@@ -9,7 +9,14 @@ The method's attributes (``self.obj_poses``, ``self.obj_wlh``, ``self.shapecodes
 the ray table is built on the host exactly like the reference does (python loop over a handful of objects).
 
 ``vis_scene`` makes pictures.  ``render_scene`` renders listed pixels with autograd to the codes and the object poses: its rows come from
-``scene_ray_rows`` (torch ops on the device) and its composite from ``ops.SceneComposite`` (HIP forward and backward).
+``scene_ray_rows`` (torch ops on the device) and its composite from ``ops.SceneComposite`` (HIP forward and backward); with ``fused=True``
+rows, samples and regrouping are HIP launches too (``render_pairs``).
+
+What lies between the object poses and the kernels is stated once, here: the box corners (``corners_of_box_batch``), the roi (``scene_rois``,
+which ``scene_rays``, ``scene_ray_rows`` and the fused route all call), the pixels the live rois cover (``roi_pixels``), the intrinsics as host
+floats (``K_vector``), the fused chain SceneSamples -> decoder -> SceneGather -> composite (``render_pairs``: ``render_scene(fused=True)`` and
+``driver.optimize_scene`` differ only in the decoder call they hand it) and the choice between the composite with and without a backward
+(``_composite``).  The rigid inverse [R^T | -(R^T t)] is ``utils.invert_pose``.
 """
 from typing import Optional, Sequence
 
@@ -21,12 +28,18 @@ from . import utils as U
 from ._lib import SnrError
 
 
+_BOX_SIGNS = {}
+
+
 def corners_of_box_batch(obj_poses: torch.Tensor, wlh: torch.Tensor) -> torch.Tensor:
-    """(Nb,3,8) box corners in the camera frame, nuScenes convention (src/utils.py:1110-1148, is_kitti=False)."""
-    sx = torch.tensor([1, 1, 1, 1, -1, -1, -1, -1], dtype=wlh.dtype, device=wlh.device)
-    sy = torch.tensor([1, -1, -1, 1, 1, -1, -1, 1], dtype=wlh.dtype, device=wlh.device)
-    sz = torch.tensor([1, 1, -1, -1, 1, 1, -1, -1], dtype=wlh.dtype, device=wlh.device)
-    local = torch.stack([wlh[:, 1:2] / 2 * sx, wlh[:, 0:1] / 2 * sy, wlh[:, 2:3] / 2 * sz], dim=1)
+    """(Nb,3,8) box corners in the camera frame, nuScenes convention (src/utils.py:1110-1148, is_kitti=False): x forward, y left, z up.
+    The (3,8) sign table is kept per device and dtype, so a call inside an optimise loop uploads nothing."""
+    key = (wlh.device, wlh.dtype)
+    if key not in _BOX_SIGNS:
+        _BOX_SIGNS[key] = torch.tensor([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]],
+                                       dtype=wlh.dtype, device=wlh.device)
+    half = wlh / 2
+    local = torch.stack([half[:, 1], half[:, 0], half[:, 2]], dim=1)[:, :, None] * _BOX_SIGNS[key]
     return torch.matmul(obj_poses[:, :, :3], local) + obj_poses[:, :, 3:4]
 
 
@@ -44,14 +57,11 @@ def scene_rays(obj_poses, obj_wlh, K, H, W, manipulation=(0.0, 0.0, 0.0), rend_a
     table = torch.full((H, W, Nb, 8), -1.0)
     poses = obj_poses.clone()
     poses[:, :, 3] += torch.tensor(manipulation, dtype=torch.float32).unsqueeze(0)
-    uv = view_points_batch(corners_of_box_batch(poses, obj_wlh), K.unsqueeze(0).repeat(Nb, 1, 1))
-    rois = torch.stack([uv[:, 0].min(dim=1)[0], uv[:, 1].min(dim=1)[0], uv[:, 0].max(dim=1)[0], uv[:, 1].max(dim=1)[0]], dim=1).type(torch.int32)
+    rois = scene_rois(poses, obj_wlh, K, H, W).tolist()
     diags = []
     for i in range(Nb):
-        x0, y0 = max(int(rois[i, 0]), 0), max(int(rois[i, 1]), 0)                    # roi_process(roi, H, W, 0, False)
-        x1, y1 = min(int(rois[i, 2]), W - 1), min(int(rois[i, 3]), H - 1)
-        R_c2o = poses[i, :3, :3].transpose(0, 1)
-        cam_pose = torch.cat([R_c2o, -R_c2o @ poses[i, :3, 3:4]], dim=1)
+        x0, y0, x1, y1 = rois[i]
+        cam_pose = U.invert_pose(poses[i])
         wlh = obj_wlh[i].numpy()
         diag = np.linalg.norm(wlh).astype(np.float32)
         diags.append(diag)
@@ -79,22 +89,10 @@ def scene_rays(obj_poses, obj_wlh, K, H, W, manipulation=(0.0, 0.0, 0.0), rend_a
     return table, valid, diags
 
 
-_BOX_SIGNS = {}
-
-
-def _box_signs(dev):
-    """(3,8) corner signs of ``corners_of_box_batch``, one copy per device."""
-    key = str(dev)
-    if key not in _BOX_SIGNS:
-        _BOX_SIGNS[key] = torch.tensor([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]],
-                                       dtype=torch.float32, device=dev)
-    return _BOX_SIGNS[key]
-
-
 def scene_rois(obj_poses, obj_wlh, K, H, W, manipulation=(0.0, 0.0, 0.0)):
-    """(Nb,4) int32 [x0, y0, x1, y1]: every object's roi as ``scene_rays`` and ``scene_ray_rows`` take it -- the truncated projection of the box
-    corners at the (manipulated) pose, clamped to the image like ``roi_process(roi, H, W, 0, False)`` -- in fp32 on the device of
-    ``obj_poses``, without gradient.  An object whose roi has x1 <= x0 or y1 <= y0 covers no pixel."""
+    """(Nb,4) int32 [x0, y0, x1, y1]: every object's roi, THE roi of ``scene_rays``, ``scene_ray_rows`` and the fused route -- the truncated
+    projection of the box corners at the (manipulated) pose, clamped to the image like ``roi_process(roi, H, W, 0, False)`` -- in fp32 on the
+    device of ``obj_poses``, without gradient.  An object whose roi has x1 <= x0 or y1 <= y0 covers no pixel."""
     with torch.no_grad():
         dev = obj_poses.device
         poses = obj_poses.detach().float()
@@ -102,11 +100,38 @@ def scene_rois(obj_poses, obj_wlh, K, H, W, manipulation=(0.0, 0.0, 0.0)):
             poses = poses.clone()
             poses[:, :, 3] += torch.tensor(manipulation, dtype=torch.float32, device=dev).unsqueeze(0)
         wlh, K32 = obj_wlh.detach().to(dev, torch.float32), K.detach().to(dev, torch.float32)
-        # corners_of_box_batch with its sign table kept on the device: a call inside an optimise loop uploads nothing
-        local = torch.stack([wlh[:, 1] / 2, wlh[:, 0] / 2, wlh[:, 2] / 2], dim=1)[:, :, None] * _box_signs(dev)[None]
-        uv = view_points_batch(torch.matmul(poses[:, :, :3], local) + poses[:, :, 3:4], K32.unsqueeze(0).repeat(poses.shape[0], 1, 1))
+        uv = view_points_batch(corners_of_box_batch(poses, wlh), K32.unsqueeze(0).repeat(poses.shape[0], 1, 1))
         rois = torch.stack([uv[:, 0].min(dim=1)[0], uv[:, 1].min(dim=1)[0], uv[:, 0].max(dim=1)[0], uv[:, 1].max(dim=1)[0]], dim=1).type(torch.int32)
         return torch.stack([rois[:, 0].clamp(min=0), rois[:, 1].clamp(min=0), rois[:, 2].clamp(max=W - 1), rois[:, 3].clamp(max=H - 1)], 1)
+
+
+def _host_rois(poses, obj_wlh, K, H, W):
+    """``scene_rois`` of the (already manipulated) poses in fp32 on the host, whatever their dtype and device: the ONE host read of the poses
+    that ``scene_ray_rows`` and the fused route make, so both see the same pixels."""
+    return scene_rois(poses.detach().cpu().float(), obj_wlh.detach().cpu(), K.detach().cpu(), H, W)
+
+
+def roi_pixels(rois, H, W):
+    """(Nr,2) int64 (x, y): the pixels of an H x W image inside the union of the live rois (x1 > x0 and y1 > y0; upper bounds exclusive), row-major."""
+    cover = torch.zeros(H, W, dtype=torch.bool)
+    for x0, y0, x1, y1 in torch.as_tensor(rois).tolist():
+        if x1 > x0 and y1 > y0:
+            cover[y0:y1, x0:x1] = True
+    ys, xs = torch.nonzero(cover, as_tuple=True)
+    return torch.stack([xs, ys], 1)
+
+
+def K_vector(K):
+    """(fx, fy, cx, cy) of the intrinsics as host floats (fp32 values): one host copy, what ``ops.SceneSamples`` takes."""
+    Kc = torch.as_tensor(K).detach().cpu().float()
+    return float(Kc[0, 0]), float(Kc[1, 1]), float(Kc[0, 2]), float(Kc[1, 2])
+
+
+def _composite(sig, rgb, z_vals, n_samples):
+    """The merge-composite against white of pixel-major rows: ``ops.SceneComposite`` when a gradient is wanted, else the forward launch alone."""
+    if torch.is_grad_enabled() and (sig.requires_grad or rgb.requires_grad or z_vals.requires_grad):
+        return ops.SceneComposite.apply(sig, rgb, z_vals, True, n_samples)              # gradients to the codes and, through the rows, to poses
+    return ops.scene_composite(sig, rgb, z_vals, white_bkgd=True, run_length=n_samples)
 
 
 def render_scene_batch(model, device, batch_rays, diags, shapecodes, texturecodes, n_samples, jitter=None, adjust_scale=1.0,
@@ -140,17 +165,15 @@ def render_scene_batch(model, device, batch_rays, diags, shapecodes, texturecode
     rgb = torch.where(empty[..., None], torch.ones_like(rgb), rgb)                       # empty space: white, zero density
     sig = torch.where(empty, torch.zeros_like(sig), sig)
     z_vals = z_vals.view(Nr, Nb * n_samples)
-    if torch.is_grad_enabled() and (sig.requires_grad or rgb.requires_grad or z_vals.requires_grad):
-        return ops.SceneComposite.apply(sig, rgb, z_vals, True, n_samples)              # gradients to the codes and, through the rows, to poses
-    return ops.scene_composite(sig, rgb, z_vals, white_bkgd=True, run_length=n_samples)
+    return _composite(sig, rgb, z_vals, n_samples)
 
 
 def scene_ray_rows(obj_poses, obj_wlh, K, pixels, H, W, manipulation=(0.0, 0.0, 0.0), rend_aabb=True):
     """rows (Nr, Nb, 8), valid (Nr,): the rows ``scene_rays`` writes for the integer pixels ``pixels`` (Nr, 2) = (x, y), made with torch
     ops on the device and in the dtype of ``obj_poses`` (Nb,3,4) and differentiable with respect to it.
 
-    Every object's roi is the truncated projection of its box corners clamped to the image, computed in fp32 on the host exactly as
-    ``scene_rays`` does and treated as a constant: that is this function's ONE host read of the poses.  A pixel outside an object's roi
+    Every object's roi is ``scene_rois`` of the manipulated poses, in fp32 on the host like ``scene_rays``' and treated as a constant: that
+    is this function's ONE host read of the poses.  A pixel outside an object's roi
     gets the all -1 row; inside it the row holds origin / (diag/2) and direction, and near / far from the slab test
     (``utils._slab_guarded``), -1 / -1 where the ray misses the box, or the sphere bounds when ``rend_aabb`` is False.  Rays are those of
     ``utils.get_rays_specified`` for the object-from-camera pose.  ``valid``: some object's far - near is positive, like ``scene_rays``' mask."""
@@ -158,20 +181,14 @@ def scene_ray_rows(obj_poses, obj_wlh, K, pixels, H, W, manipulation=(0.0, 0.0, 
     Nb = obj_poses.shape[0]
     pixels = torch.as_tensor(pixels).to(dev)
     poses = torch.cat([obj_poses[:, :, :3], obj_poses[:, :, 3:4] + torch.tensor(manipulation, dtype=dt, device=dev).view(1, 3, 1)], dim=2)
-    p32, wlh32, K32 = poses.detach().cpu().float(), obj_wlh.detach().cpu().float(), K.detach().cpu().float()       # the one host read
-    uv = view_points_batch(corners_of_box_batch(p32, wlh32), K32.unsqueeze(0).repeat(Nb, 1, 1))
-    rois = torch.stack([uv[:, 0].min(dim=1)[0], uv[:, 1].min(dim=1)[0], uv[:, 0].max(dim=1)[0], uv[:, 1].max(dim=1)[0]], dim=1).type(torch.int32)
-    lo = torch.stack([rois[:, 0].clamp(min=0), rois[:, 1].clamp(min=0)], 1)                                         # roi_process(roi, H, W, 0, False)
-    hi = torch.stack([rois[:, 2].clamp(max=W - 1), rois[:, 3].clamp(max=H - 1)], 1)
-    live = (hi[:, 0] > lo[:, 0]) & (hi[:, 1] > lo[:, 1])
-    lo, hi, live = lo.to(dev), hi.to(dev), live.to(dev)
+    rois = _host_rois(poses, obj_wlh, K, H, W).to(dev)                                                            # the one host read
     px, py = pixels[:, 0], pixels[:, 1]
-    in_roi = live[:, None] & (px[None, :] >= lo[:, 0:1]) & (px[None, :] < hi[:, 0:1]) & (py[None, :] >= lo[:, 1:2]) & (py[None, :] < hi[:, 1:2])   # (Nb,Nr)
+    in_roi = (px[None, :] >= rois[:, 0:1]) & (px[None, :] < rois[:, 2:3]) & (py[None, :] >= rois[:, 1:2]) & (py[None, :] < rois[:, 3:4])   # (Nb,Nr); a dead roi holds no pixel
 
     wlh, Kd = obj_wlh.detach().to(dev, dt), K.detach().to(dev, dt)
     diag = torch.linalg.norm(wlh, dim=1)                                                                           # (Nb,)
-    R_c2o = poses[:, :3, :3].transpose(1, 2)
-    origin = -(R_c2o @ poses[:, :3, 3:4]).squeeze(-1)                                                              # (Nb,3): the camera in the object frame
+    cam2obj = U.invert_pose(poses)
+    R_c2o, origin = cam2obj[:, :, :3], cam2obj[:, :, 3]                                                            # origin (Nb,3): the camera in the object frame
     fx, fy = px.to(torch.float32).to(dt), py.to(torch.float32).to(dt)
     cam = torch.stack([(fx - Kd[0, 2]) / Kd[0, 0], (fy - Kd[1, 2]) / Kd[1, 1], torch.ones_like(fx)], -1)          # (Nr,3)
     world = (cam[None, :, None, :] * R_c2o[:, None, :, :]).sum(-1)                                                 # (Nb,Nr,3)
@@ -220,20 +237,22 @@ def _render_scene_fused(model, dev, obj_poses, obj_wlh, shapecodes, texturecodes
     pixels = torch.as_tensor(pixels).to(dev, torch.int32)
     Nr = pixels.shape[0]
     poses = torch.cat([obj_poses[:, :, :3], obj_poses[:, :, 3:4] + torch.tensor(manipulation, dtype=obj_poses.dtype, device=dev).view(1, 3, 1)], dim=2)
-    rois = scene_rois(poses.detach().cpu(), obj_wlh.detach().cpu(), K.detach().cpu(), H, W).to(dev)     # the one host read, as in scene_ray_rows
-    R_c2o = poses[:, :3, :3].transpose(1, 2)
-    cam2obj = torch.cat([R_c2o, -(R_c2o @ poses[:, :3, 3:4])], dim=2)
+    rois = _host_rois(poses, obj_wlh, K, H, W).to(dev)                                              # as in scene_ray_rows
     if jitter is None:
         jitter = torch.rand(Nr * Nb, n_samples)                                                      # CPU draw, like render_scene_batch
-    Kc = K.detach().cpu().float()
-    xyz, viewdir, z_vals, hit, _ = ops.SceneSamples.apply(cam2obj.float(), obj_wlh.detach().to(dev), rois, pixels,
-                                                          (Kc[0, 0], Kc[1, 1], Kc[0, 2], Kc[1, 2]), jitter.to(dev), n_samples, adjust_scale, rend_aabb,
-                                                          shapenet_obj_cood)
-    sig, rgb = model(xyz, viewdir, shapecodes.to(dev), texturecodes.to(dev))                         # object-major, Nb codes
+    return render_pairs(lambda x, d: model(x, d, shapecodes.to(dev), texturecodes.to(dev)), U.invert_pose(poses).float(), obj_wlh.detach().to(dev),
+                        rois, pixels, K_vector(K), jitter.to(dev), n_samples, adjust_scale, rend_aabb, shapenet_obj_cood)[:3]
+
+
+def render_pairs(decode, cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood):
+    """THE fused chain of the scene path, all operands on the GPU: rows and samples of every (pixel, object) pair (``ops.SceneSamples``; cam2obj
+    (Nb,3,4) differentiable, rois (Nb,4) and pixels (Nr,2) int32, Kvec from ``K_vector``, jitter (Nr*Nb,S) or None), ``decode(xyz, viewdir)
+    -> (sigmas, rgbs)`` on the object-major points, ``ops.SceneGather``, the merge-composite.  -> rgb (Nr,3), depth (Nr,), acc_trans (Nr,), hit
+    (Nr,Nb) uint8."""
+    xyz, viewdir, z_vals, hit, _ = ops.SceneSamples.apply(cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood)
+    sig, rgb = decode(xyz, viewdir)                                                                  # object-major, Nb codes
     sig, rgb = ops.SceneGather.apply(sig, rgb, hit, n_samples)
-    if torch.is_grad_enabled() and (sig.requires_grad or rgb.requires_grad or z_vals.requires_grad):
-        return ops.SceneComposite.apply(sig, rgb, z_vals, True, n_samples)
-    return ops.scene_composite(sig, rgb, z_vals, white_bkgd=True, run_length=n_samples)
+    return (*_composite(sig, rgb, z_vals, n_samples), hit)
 
 
 def vis_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, H, W, n_samples, manipulation=(0.0, 0.0, 0.0),

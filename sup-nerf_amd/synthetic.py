@@ -170,13 +170,8 @@ def synthetic_frame(ids, H, W, focal=None, model=None, device=None, shapecodes=N
                 r = ((xx - (x0 + x1) / 2) / (0.4 * (x1 - x0))) ** 2 + ((yy - (y0 + y1) / 2) / (0.3 * (y1 - y0))) ** 2
                 occ = torch.where(r < 1.0, torch.ones_like(occ), occ)
     else:
-        cover = torch.zeros(H, W, dtype=torch.bool)
-        for x0, y0, x1, y1 in rois.tolist():
-            if x1 > x0 and y1 > y0:
-                cover[y0:y1, x0:x1] = True
-        ys, xs = torch.nonzero(cover, as_tuple=True)
         with torch.no_grad():
-            for part in torch.split(torch.stack([xs, ys], 1), 8192):
+            for part in torch.split(scene.roi_pixels(rois, H, W), 8192):
                 rgb, _, acc = scene.render_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, part, H, W, n_samples,
                                                  jitter=torch.zeros(part.shape[0] * n, n_samples))
                 img[part[:, 1], part[:, 0]] = rgb.cpu()

@@ -71,6 +71,13 @@ def _cam_table(K, px, py, like, key=None):
     return cam if key is None else _cache_put(_CAM_CACHE, key, cam)
 
 
+def invert_pose(P):
+    """(...,3,4) rigid poses [R | t] -> their inverses [R^T | -(R^T t)]: object-in-camera <-> camera-in-object.  Plain torch in the dtype and on
+    the device of ``P``, differentiable."""
+    Rt = P[..., :3].transpose(-1, -2)
+    return torch.cat([Rt, -(Rt @ P[..., 3:])], dim=-1)
+
+
 def _fusable_pose(c2w):
     """The one-launch ray kernels take a single fp32 (3,4) pose that lives on the GPU.  A (4,4) pose takes the torch formulation: the
     reference's sphere bounds are the norm of the WHOLE last column (``cam_pose[:, -1]``, src/utils.py:468), which for a homogeneous pose

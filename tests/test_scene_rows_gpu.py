@@ -1,5 +1,5 @@
 """GPU tests of the scene sample kernels (snr_scene_samples_fwd / bwd, snr_scene_gather_fwd / bwd) behind ``ops.SceneSamples`` /
-``ops.SceneGather``, and of ``scene.render_scene(fused=True)``.
+``ops.SceneGather``, of ``scene.render_pairs`` (the one fused chain) and of ``scene.render_scene(fused=True)``.
 
 The oracle of record is the float64 run of tests/scene_rows_restatement.py.  No band below is fixed in advance and no code under test enters
 one: per output it is 4 x the worst absolute error of the EXISTING fp32 torch route (``scene.scene_ray_rows`` + the sample lines of
@@ -358,6 +358,58 @@ def test_abi_writes_every_element_and_nothing_else(amd, dev):
         assert getattr(lib, name)(ops._p(sig), ops._p(rgb), ops._p(want[3]), 0, Nb, S, ops._p(g_s), ops._p(g_r), ops._stream(dev)) == 0
         torch.cuda.synchronize()
         assert torch.equal(g_s, keep) and bool((g_r == CAN).all())
+
+
+# ------------------------------------------------------------------------------------------------ render_pairs
+def test_render_pairs_is_the_four_ops_by_hand(amd, dev, oracle_params):
+    """``scene.render_pairs`` against SceneSamples -> decoder -> SceneGather -> composite written out here, bit for bit: 257 pixels (one more
+    than a 256-pair slice), two objects of which one has a dead roi, 4 samples; under ``no_grad`` (``ops.scene_composite``) and with
+    ``cam2obj`` and both codes requiring a gradient (``ops.SceneComposite``), there with the three gradients of one backward."""
+    ops = amd.ops
+    Nb, Nr, S = 2, 257, 4
+    c = make_case(amd, Nb, Nr, S, seed=21)
+    rois = c["rois"].clone()
+    assert bool(((rois[:, 2] > rois[:, 0]) & (rois[:, 3] > rois[:, 1])).all())
+    rois[1] = torch.tensor([40, 10, 40, 30], dtype=torch.int32)                  # dead: x1 == x0
+    model = make_model(amd, dev, oracle_params, "fp32")
+    gen = torch.Generator().manual_seed(22)
+    sc0, tc0 = torch.randn(Nb, 256, generator=gen) * 0.3, torch.randn(Nb, 256, generator=gen) * 0.3
+    w = (torch.randn(Nr, 3, generator=gen).to(dev), torch.randn(Nr, generator=gen).to(dev), torch.randn(Nr, generator=gen).to(dev))
+    wlh, rois, pixels, jitter = c["wlh"].to(dev), rois.to(dev), c["pixels"].to(dev), c["jitter"].to(dev)
+
+    def leaves(grad):
+        return [t.to(dev).requires_grad_(grad) for t in (R.cam2obj_of(c["poses"]), sc0, tc0)]
+
+    def by_hand(cam2obj, sc, tc, composite):
+        xyz, viewdir, z, hit, _ = ops.SceneSamples.apply(cam2obj, wlh, rois, pixels, c["Kvec"], jitter, S, c["scale"], c["rend_aabb"], c["shapenet"])
+        sig, rgb = model(xyz, viewdir, sc, tc)
+        sig, rgb = ops.SceneGather.apply(sig, rgb, hit, S)
+        return (*composite(sig, rgb, z), hit)
+
+    def pairs(cam2obj, sc, tc):
+        return amd.scene.render_pairs(lambda x, d: model(x, d, sc, tc), cam2obj, wlh, rois, pixels, c["Kvec"], jitter, S, c["scale"], c["rend_aabb"],
+                                      c["shapenet"])
+    with torch.no_grad():
+        want = by_hand(*leaves(False), lambda sig, rgb, z: ops.scene_composite(sig, rgb, z, white_bkgd=True, run_length=S))
+        got = pairs(*leaves(False))
+    assert len(got) == 4 and got[3].shape == (Nr, Nb) and got[3].dtype == torch.uint8
+    assert bool(got[3][:, 0].any()) and not bool(got[3][:, 1].any())             # the live object is hit, the dead roi never
+    for name, a, b in zip(("rgb", "depth", "acc", "hit"), got, want):
+        assert not a.requires_grad and a.shape == b.shape and torch.equal(a, b), name
+    plain = got
+    res = []
+    for fn in (lambda *l: by_hand(*l, lambda sig, rgb, z: ops.SceneComposite.apply(sig, rgb, z, True, S)), pairs):
+        lv = leaves(True)
+        out = fn(*lv)
+        assert out[0].requires_grad and not out[3].requires_grad
+        sum((o * wi).sum() for o, wi in zip(out[:3], w)).backward()
+        res.append([t.detach() for t in out] + [t.grad for t in lv])
+    for name, a, b in zip(("rgb", "depth", "acc", "hit", "d_cam2obj", "d_shapecodes", "d_texturecodes"), res[1], res[0]):
+        assert a.shape == b.shape and torch.equal(a, b), name
+    assert all(torch.equal(a, b) for a, b in zip(res[1][:4], plain))             # either composite branch: the same values
+    g_cam, g_sc, g_tc = res[1][4:]
+    assert float(g_cam[0].abs().max()) > 0 and float(g_sc[0].abs().max()) > 0 and float(g_tc[0].abs().max()) > 0
+    assert float(g_cam[1].abs().max()) == 0 and float(g_sc[1].abs().max()) == 0 and float(g_tc[1].abs().max()) == 0
 
 
 # ------------------------------------------------------------------------------------------------ render_scene(fused=True)

@@ -16,7 +16,7 @@ import torch
 import geometry_common as C
 from conftest import load_golden
 from ray_surface_time import in_turn
-from supnerf_amd import driver, ops, scene, synthetic
+from supnerf_amd import driver, ops, scene, synthetic, utils
 
 
 def render_pair(model, dev, poses, wlh, sc0, tc0, K, pixels, H, W, S, reps):
@@ -54,20 +54,14 @@ def frame_rows(model, a, dev):
     frame = synthetic.synthetic_frame(list(range(Nb)), H, W, focal=0.35 * W, model=model, device=dev, shapecodes=sc0, texturecodes=tc0, n_samples=S)
     K, poses, wlh = frame["K"], frame["obj_poses"], frame["obj_wlh"]
     rois = scene.scene_rois(poses, wlh, K, H, W)
-    cover = torch.zeros(H, W, dtype=torch.bool)
-    for x0, y0, x1, y1 in rois.tolist():
-        cover[y0:max(y0, y1), x0:max(x0, x1)] = True
-    ys, xs = torch.nonzero(cover, as_tuple=True)
-    pixels = torch.stack([xs, ys], 1)
+    pixels = scene.roi_pixels(rois, H, W)
     Nr = pixels.shape[0]
     render = render_pair(model, dev, poses, wlh, sc0, tc0, K, pixels, H, W, S, a.reps)
     render["roi_pixels_per_object"] = [int((r[2] - r[0]) * (r[3] - r[1])) for r in rois.tolist()]
 
     # the two launches alone
-    Kvec = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]))
-    R = poses[:, :, :3].transpose(1, 2)
-    cam2obj = torch.cat([R, -(R @ poses[:, :, 3:])], 2).to(dev).requires_grad_()
-    args = (wlh.to(dev), rois.to(dev), pixels.to(dev, torch.int32), Kvec, torch.rand(Nr * Nb, S, device=dev), S, 1.0, True, True)
+    cam2obj = utils.invert_pose(poses).to(dev).requires_grad_()
+    args = (wlh.to(dev), rois.to(dev), pixels.to(dev, torch.int32), scene.K_vector(K), torch.rand(Nr * Nb, S, device=dev), S, 1.0, True, True)
     xyz, viewdir, z, hit, _ = ops.SceneSamples.apply(cam2obj, *args)
     g = [torch.randn_like(t) for t in (xyz, viewdir, z)]
 
