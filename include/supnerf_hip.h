@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 17
+#define SNR_ABI_VERSION 18
 
 enum {
     SNR_OK = 0,
@@ -267,6 +267,49 @@ int snr_scene_gather_fwd(const float* sigmas, const float* rgbs, const uint8_t* 
  * that are not hit.  Either pair may be NULL. */
 int snr_scene_gather_bwd(const float* d_sigma_rows, const float* d_rgb_rows, const uint8_t* hit, int64_t n_pixels, int64_t n_objects, int n_samples,
                          float* d_sigmas, float* d_rgbs, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Scene rows, compact: the same chain with only the (pixel, object) pairs that hit handed to the decoder, `capacity` = C slots per object
+ * (tests/scene_compact_restatement.py states the same rules in a few lines of torch).  C >= 1 and C % 32 == 0, so that C * S points are
+ * whole 32-point decoder tiles for every S; any other capacity returns SNR_E_ARG before a launch.
+ *   hit        per pair exactly what snr_scene_samples_fwd decides (the same code, the same bits): snr_scene_pair_hits writes the flags alone;
+ *   scan       hit_scan (Nr,Nb) int32, the CALLER's inclusive prefix sum of hit along the pixel list, per object;
+ *   slot       scan[r][b] - 1: the rank of the pair among its object's hits in list order (deterministic, no atomics);
+ *   kept       hit and 0 <= slot < C.  A hit pair with slot >= C is DROPPED: every output treats it as a pair that is not hit;
+ *   count[b]   scan[Nr-1][b] still tells the true number of hits: max(0, count - C) pairs of object b were dropped;
+ *   samples    a kept pair's S points and directions are the bits snr_scene_samples_fwd writes for that pair, at row b*C + slot of xyz and
+ *              viewdir (Nb*C, S, 3);  z_vals (Nr, Nb*S) stays pixel-major and dense and holds -1 exactly, for all S samples, on every pair
+ *              that is not kept;
+ *   padding    slots count[b] .. C-1 of an object: xyz = 0, viewdir = (0,0,1);
+ *   pair_of_slot (Nb,C) int32: the pixel index of each slot, -1 on padding;
+ *   gather     forward: a kept pair's rows come from its slot, every other pair gets sigma 0 and white.  Backward: written in the
+ *              destination's order through pair_of_slot, padding slots get exact zeros;
+ *   backward to cam2obj: every kept pair's samples added in the order snr_scene_samples_bwd adds them (the same slice grid, the same
+ *              sweep e = thread + i*256, the same LDS meeting order, the same second launch), d_xyz and d_viewdir read at the slot, d_z at
+ *              the pair: the same bits as the dense backward of the scattered upstream.  The upstream of padding slots is never read.
+ * scan, kept and pair_of_slot are only compared and range-checked, never trusted as an index: the kernels write inside their buffers
+ * whatever the lists hold.  Every output element is written once; no host synchronisation and no floating-point atomic; the same bits
+ * from run to run.
+ * ---------------------------------------------------------------------------------- */
+int snr_scene_pair_hits(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx, float cy,
+                        int64_t n_pixels, int64_t n_objects, int rend_aabb, uint8_t* hit, void* stream);
+/* -> xyz, viewdir (Nb*C, S, 3), z_vals (Nr, Nb*S), kept (Nr,Nb) uint8, pair_of_slot (Nb,C) int32.  n_pixels == 0: padding only. */
+int snr_scene_samples_compact_fwd(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx,
+                                  float cy, const float* jitter, int64_t n_pixels, int64_t n_objects, int n_samples, float adjust_scale,
+                                  int rend_aabb, int shapenet_obj_cood, const int32_t* hit_scan, int64_t capacity, float* xyz, float* viewdir,
+                                  float* z_vals, uint8_t* kept, int32_t* pair_of_slot, void* stream);
+/* d_xyz, d_viewdir (Nb*C, S, 3), d_z (Nr, Nb*S), each nullable = zero -> d_cam2obj (Nb,3,4).  ws: snr_scene_samples_bwd_ws_bytes(n_pixels,
+ * n_objects) bytes, 8-byte aligned.  Two launches on the stream. */
+int snr_scene_samples_compact_bwd(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx,
+                                  float cy, const float* jitter, int64_t n_pixels, int64_t n_objects, int n_samples, float adjust_scale,
+                                  int rend_aabb, int shapenet_obj_cood, const int32_t* hit_scan, int64_t capacity, const float* d_xyz,
+                                  const float* d_viewdir, const float* d_z, float* d_cam2obj, void* ws, size_t ws_bytes, void* stream);
+/* sigmas (Nb*C*S), rgbs (Nb*C*S,3) -> sigma_rows (Nr, Nb*S), rgb_rows (Nr, Nb*S, 3).  Either output (with its input) may be NULL. */
+int snr_scene_gather_compact_fwd(const float* sigmas, const float* rgbs, const int32_t* hit_scan, const uint8_t* kept, int64_t n_pixels,
+                                 int64_t n_objects, int n_samples, int64_t capacity, float* sigma_rows, float* rgb_rows, void* stream);
+/* d_sigma_rows (Nr, Nb*S), d_rgb_rows (Nr, Nb*S, 3) -> d_sigmas (Nb*C*S), d_rgbs (Nb*C*S,3).  Either pair may be NULL. */
+int snr_scene_gather_compact_bwd(const float* d_sigma_rows, const float* d_rgb_rows, const int32_t* pair_of_slot, int64_t n_pixels, int64_t n_objects,
+                                 int n_samples, int64_t capacity, float* d_sigmas, float* d_rgbs, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Alpha composite alone: replaces volume_rendering2 / volume_rendering_batch

@@ -69,6 +69,13 @@ _SIGS = {
                                         C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "snr_scene_gather_fwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "snr_scene_gather_bwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
+    "snr_scene_pair_hits": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int64, C.c_int, _P, _P]),
+    "snr_scene_samples_compact_fwd": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_int64, C.c_int64, C.c_int, C.c_float,
+                                                C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "snr_scene_samples_compact_bwd": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_int64, C.c_int64, C.c_int, C.c_float,
+                                                C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "snr_scene_gather_compact_fwd": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int64, _P, _P, _P]),
+    "snr_scene_gather_compact_bwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int64, _P, _P, _P]),
     "snr_composite_fwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P]),
     "snr_composite_bwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "snr_encode_fwd": (C.c_int, [C.POINTER(RenderArgs), _P, _P, _P, _P, _P, _P, _P]),

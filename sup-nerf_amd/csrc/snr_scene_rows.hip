@@ -3,7 +3,9 @@
 //   * scene_samples_fwd: camera-in-object poses + rois + listed pixels -> every (pixel, object) pair's ray (scene.scene_ray_rows), its box or
 //                        sphere bounds and its S samples in the decoder's layout and the composite's (scene.render_scene_batch);
 //   * scene_samples_bwd: d(points), d(directions), d(metric depths) -> d(poses), through the bounds; two launches, fixed association;
-//   * scene_gather_fwd / bwd: the decoder's object-major outputs <-> the composite's pixel-major rows, (0, white) on pairs that are not hit.
+//   * scene_gather_fwd / bwd: the decoder's object-major outputs <-> the composite's pixel-major rows, (0, white) on pairs that are not hit;
+//   * scene_pair_hits, scene_samples_compact_fwd / bwd, scene_gather_compact_fwd / bwd: the same chain with only the pairs that hit handed to
+//     the decoder, `capacity` slots per object, a pair's slot its rank among its object's hits (the caller's prefix sum of the flags).
 // All HBM-bound.  One workgroup owns PAIRS consecutive pixels of one object: its threads first set the pairs up (one pair each, in double:
 // a few dozen flops against S samples of traffic), park what the samples need in LDS, then sweep the samples in memory order.
 #include "snr_device.hpp"
@@ -97,6 +99,33 @@ __device__ __forceinline__ double pick3(const double v[3], int a) { return a == 
 // what the sweeps read per pair from LDS
 struct PairLds { double u[3], near, far; };
 
+// sample k of a pair that is hit: point, direction and metric depth, each rounded to fp32 once
+__device__ __forceinline__ void sample_fwd(const ObjFrame& f, const double o[3], const PairLds& p, int k, const float* __restrict__ jitter, long long ip,
+                                           double inv_s, double scale, int shapenet, float px[3], float dv[3], float& z) {
+    const double tau = ((double)k + (jitter ? (double)jitter[ip] : 0.0)) * inv_s;
+    const double zk = p.near * (1.0 - tau) + p.far * tau;
+    const double pt[3] = {(o[0] + zk * p.u[0]) * scale, (o[1] + zk * p.u[1]) * scale, (o[2] + zk * p.u[2]) * scale};
+    if (shapenet) {
+        px[0] = (float)-pt[1]; px[1] = (float)pt[0]; px[2] = (float)pt[2];
+        dv[0] = (float)-p.u[1]; dv[1] = (float)p.u[0]; dv[2] = (float)p.u[2];
+    } else {
+        px[0] = (float)pt[0]; px[1] = (float)pt[1]; px[2] = (float)pt[2];
+        dv[0] = (float)p.u[0]; dv[1] = (float)p.u[1]; dv[2] = (float)p.u[2];
+    }
+    z = (float)(fabs(zk) * sqrt(p.u[0] * p.u[0] + p.u[1] * p.u[1] + p.u[2] * p.u[2]) * f.hd);
+}
+
+// what a pair that is not hit holds: finite inputs for the decoder, depth -1
+__device__ __forceinline__ void sample_miss(float px[3], float dv[3], float& z) {
+    px[0] = px[1] = px[2] = 0.f;
+    dv[0] = dv[1] = 0.f; dv[2] = 1.f;
+    z = -1.f;
+}
+
+__device__ __forceinline__ void park_pair(PairLds& q, const PairRay& p) {
+    q.u[0] = p.u[0]; q.u[1] = p.u[1]; q.u[2] = p.u[2]; q.near = p.near; q.far = p.far;
+}
+
 __global__ void __launch_bounds__(PAIRS) scene_samples_fwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
                                                                   const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels, SceneCam cam,
                                                                   const float* __restrict__ jitter, long long Nr, int Nb, int S, float adjust_scale,
@@ -113,10 +142,7 @@ __global__ void __launch_bounds__(PAIRS) scene_samples_fwd_kernel(const float* _
         const int x = pixels[2 * r], y = pixels[2 * r + 1];
         const PairRay p = make_pair(f, x, y, cam, rend_aabb != 0);
         hits[threadIdx.x] = p.hit;
-        if (p.hit) {
-            PairLds& q = prm[threadIdx.x];
-            q.u[0] = p.u[0]; q.u[1] = p.u[1]; q.u[2] = p.u[2]; q.near = p.near; q.far = p.far;
-        }
+        if (p.hit) park_pair(prm[threadIdx.x], p);
         hit[r * Nb + b] = p.hit ? 1 : 0;
         if (valid && b == 0) {       // some object is hit: the workgroups of object 0 look at the others too
             bool any = p.hit;
@@ -134,24 +160,8 @@ __global__ void __launch_bounds__(PAIRS) scene_samples_fwd_kernel(const float* _
         const long long io = ((b * Nr + r) * S + k) * 3;        // object-major: the decoder's layout
         const long long ip = (r * Nb + b) * S + k;              // pixel-major: the composite's (and the jitter's)
         float px[3], dv[3], z;
-        if (hits[q]) {
-            const PairLds& p = prm[q];
-            const double tau = ((double)k + (jitter ? (double)jitter[ip] : 0.0)) * inv_s;
-            const double zk = p.near * (1.0 - tau) + p.far * tau;
-            const double pt[3] = {(o[0] + zk * p.u[0]) * scale, (o[1] + zk * p.u[1]) * scale, (o[2] + zk * p.u[2]) * scale};
-            if (shapenet) {
-                px[0] = (float)-pt[1]; px[1] = (float)pt[0]; px[2] = (float)pt[2];
-                dv[0] = (float)-p.u[1]; dv[1] = (float)p.u[0]; dv[2] = (float)p.u[2];
-            } else {
-                px[0] = (float)pt[0]; px[1] = (float)pt[1]; px[2] = (float)pt[2];
-                dv[0] = (float)p.u[0]; dv[1] = (float)p.u[1]; dv[2] = (float)p.u[2];
-            }
-            z = (float)(fabs(zk) * sqrt(p.u[0] * p.u[0] + p.u[1] * p.u[1] + p.u[2] * p.u[2]) * f.hd);
-        } else {
-            px[0] = px[1] = px[2] = 0.f;
-            dv[0] = dv[1] = 0.f; dv[2] = 1.f;
-            z = -1.f;
-        }
+        if (hits[q]) sample_fwd(f, o, prm[q], k, jitter, ip, inv_s, scale, shapenet, px, dv, z);
+        else sample_miss(px, dv, z);
 #pragma unroll
         for (int c = 0; c < 3; ++c) { xyz[io + c] = px[c]; viewdir[io + c] = dv[c]; }
         z_vals[ip] = z;
@@ -162,6 +172,79 @@ __global__ void __launch_bounds__(PAIRS) scene_samples_fwd_kernel(const float* _
 // upstream gradients with coefficients of its pair, so a thread applies the pair's map to each of its samples and keeps 12 double sums of its
 // own: no reduction per pair.  The sums meet in LDS in thread order (pose_rays_bwd_kernel's scheme) and leave as one row of `partial`.
 struct PairBwd { double u[3], c[2], inv_n, near, far, gn[2], gf[2]; int a_near, a_far; };
+
+__device__ __forceinline__ void park_pair_bwd(PairBwd& q, const PairRay& p) {
+    q.u[0] = p.u[0]; q.u[1] = p.u[1]; q.u[2] = p.u[2]; q.c[0] = p.c[0]; q.c[1] = p.c[1];
+    q.inv_n = p.inv_n; q.near = p.near; q.far = p.far; q.a_near = p.a_near; q.a_far = p.a_far;
+    // near = (plane - o_a) / u_a on its axis a: d near / d o_a = -1 / u_a, d near / d u_a = -near / u_a (far likewise).  An axis with
+    // u_a == 0 is never the one that bounds a hit, so it adds nothing.
+    const double un = pick3(p.u, p.a_near), uf = pick3(p.u, p.a_far);
+    if (p.a_near >= 0) { q.gn[0] = -1.0 / un; q.gn[1] = -p.near / un; } else { q.gn[0] = q.gn[1] = 0.0; }
+    if (p.a_far >= 0) { q.gf[0] = -1.0 / uf; q.gf[1] = -p.far / uf; } else { q.gf[0] = q.gf[1] = 0.0; }
+}
+
+// sample k of a pair that is hit, added to the thread's 12 sums; io: its row in d_xyz / d_viewdir, ip: in d_z and the jitter
+__device__ __forceinline__ void sample_bwd(const ObjFrame& f, const PairBwd& p, int k, const float* __restrict__ jitter, long long io, long long ip,
+                                           double inv_s, double scale, int rend_aabb, int shapenet, double dist, const float* __restrict__ d_xyz,
+                                           const float* __restrict__ d_viewdir, const float* __restrict__ d_z, double gR[9], double gt[3]) {
+    const double tau = ((double)k + (jitter ? (double)jitter[ip] : 0.0)) * inv_s;
+    const double zk = p.near * (1.0 - tau) + p.far * tau;
+    double G[3] = {0., 0., 0.}, gu[3] = {0., 0., 0.};
+    if (d_xyz) {             // gradient of (o + z u): the frame swap (x,y,z) -> (-y,x,z) undone, times the scale
+        const double g0 = d_xyz[io], g1 = d_xyz[io + 1], g2 = d_xyz[io + 2];
+        if (shapenet) { G[0] = g1 * scale; G[1] = -g0 * scale; G[2] = g2 * scale; }
+        else { G[0] = g0 * scale; G[1] = g1 * scale; G[2] = g2 * scale; }
+    }
+    if (d_viewdir) {
+        const double g0 = d_viewdir[io], g1 = d_viewdir[io + 1], g2 = d_viewdir[io + 2];
+        if (shapenet) { gu[0] = g1; gu[1] = -g0; gu[2] = g2; } else { gu[0] = g0; gu[1] = g1; gu[2] = g2; }
+    }
+    // the metric depth |z| |u| diag/2: its gradient to u lies along u and the normalisation below removes it
+    double gz = G[0] * p.u[0] + G[1] * p.u[1] + G[2] * p.u[2];
+    if (d_z) gz += (double)d_z[ip] * (zk > 0.0 ? f.hd : (zk < 0.0 ? -f.hd : 0.0));
+    const double g_near = gz * (1.0 - tau), g_far = gz * tau;
+    double go[3] = {G[0], G[1], G[2]};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        gu[a] += zk * G[a];
+        if (a == p.a_near) { go[a] += g_near * p.gn[0]; gu[a] += g_near * p.gn[1]; }
+        if (a == p.a_far) { go[a] += g_far * p.gf[0]; gu[a] += g_far * p.gf[1]; }
+    }
+    // u = w / |w|, w = R c: the part of gu along u is projected off
+    const double dot = p.u[0] * gu[0] + p.u[1] * gu[1] + p.u[2] * gu[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double gw = (gu[i] - p.u[i] * dot) * p.inv_n;
+        gR[3 * i] += gw * p.c[0]; gR[3 * i + 1] += gw * p.c[1]; gR[3 * i + 2] += gw;
+        // o = t / (diag/2); the sphere bounds move with |t|
+        double g = go[i] / f.hd;
+        if (!rend_aabb) g += (g_near + g_far) * f.t[i] / (dist * f.hd);
+        gt[i] += g;
+    }
+}
+
+// the threads' 12 sums meet in LDS in thread order and leave as the workgroup's row of `partial`
+__device__ __forceinline__ void meet_slice(double (&part)[12][PAIRS], double (&part2)[12][16], const double gR[9], const double gt[3],
+                                           double* __restrict__ row) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) part[i][threadIdx.x] = gR[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) part[9 + i][threadIdx.x] = gt[i];
+    __syncthreads();
+    if (threadIdx.x < 12 * 16) {
+        const int q = threadIdx.x >> 4, seg = threadIdx.x & 15;
+        double sum = 0.;
+        for (int k = 0; k < PAIRS / 16; ++k) sum += part[q][seg * (PAIRS / 16) + k];
+        part2[q][seg] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        double sum = 0.;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) sum += part2[threadIdx.x][k];
+        row[threadIdx.x] = sum;
+    }
+}
 
 __global__ void __launch_bounds__(PAIRS) scene_samples_bwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
                                                                   const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels, SceneCam cam,
@@ -181,16 +264,7 @@ __global__ void __launch_bounds__(PAIRS) scene_samples_bwd_kernel(const float* _
         const long long r = r0 + threadIdx.x;
         const PairRay p = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0);
         hits[threadIdx.x] = p.hit;
-        if (p.hit) {
-            PairBwd& q = prm[threadIdx.x];
-            q.u[0] = p.u[0]; q.u[1] = p.u[1]; q.u[2] = p.u[2]; q.c[0] = p.c[0]; q.c[1] = p.c[1];
-            q.inv_n = p.inv_n; q.near = p.near; q.far = p.far; q.a_near = p.a_near; q.a_far = p.a_far;
-            // near = (plane - o_a) / u_a on its axis a: d near / d o_a = -1 / u_a, d near / d u_a = -near / u_a (far likewise).  An axis with
-            // u_a == 0 is never the one that bounds a hit, so it adds nothing.
-            const double un = pick3(p.u, p.a_near), uf = pick3(p.u, p.a_far);
-            if (p.a_near >= 0) { q.gn[0] = -1.0 / un; q.gn[1] = -p.near / un; } else { q.gn[0] = q.gn[1] = 0.0; }
-            if (p.a_far >= 0) { q.gf[0] = -1.0 / uf; q.gf[1] = -p.far / uf; } else { q.gf[0] = q.gf[1] = 0.0; }
-        }
+        if (p.hit) park_pair_bwd(prm[threadIdx.x], p);
     }
     __syncthreads();
     const double scale = (double)adjust_scale, inv_s = 1.0 / (double)S;
@@ -201,63 +275,11 @@ __global__ void __launch_bounds__(PAIRS) scene_samples_bwd_kernel(const float* _
     for (long long e = threadIdx.x; e < n; e += PAIRS) {
         const int q = (int)(e / S), k = (int)(e - (long long)q * S);
         if (!hits[q]) continue;                                  // pairs that are not hit contribute exact zeros
-        const PairBwd& p = prm[q];
         const long long r = r0 + q;
-        const long long io = ((b * Nr + r) * S + k) * 3;
-        const long long ip = (r * Nb + b) * S + k;
-        const double tau = ((double)k + (jitter ? (double)jitter[ip] : 0.0)) * inv_s;
-        const double zk = p.near * (1.0 - tau) + p.far * tau;
-        double G[3] = {0., 0., 0.}, gu[3] = {0., 0., 0.};
-        if (d_xyz) {             // gradient of (o + z u): the frame swap (x,y,z) -> (-y,x,z) undone, times the scale
-            const double g0 = d_xyz[io], g1 = d_xyz[io + 1], g2 = d_xyz[io + 2];
-            if (shapenet) { G[0] = g1 * scale; G[1] = -g0 * scale; G[2] = g2 * scale; }
-            else { G[0] = g0 * scale; G[1] = g1 * scale; G[2] = g2 * scale; }
-        }
-        if (d_viewdir) {
-            const double g0 = d_viewdir[io], g1 = d_viewdir[io + 1], g2 = d_viewdir[io + 2];
-            if (shapenet) { gu[0] = g1; gu[1] = -g0; gu[2] = g2; } else { gu[0] = g0; gu[1] = g1; gu[2] = g2; }
-        }
-        // the metric depth |z| |u| diag/2: its gradient to u lies along u and the normalisation below removes it
-        double gz = G[0] * p.u[0] + G[1] * p.u[1] + G[2] * p.u[2];
-        if (d_z) gz += (double)d_z[ip] * (zk > 0.0 ? f.hd : (zk < 0.0 ? -f.hd : 0.0));
-        const double g_near = gz * (1.0 - tau), g_far = gz * tau;
-        double go[3] = {G[0], G[1], G[2]};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            gu[a] += zk * G[a];
-            if (a == p.a_near) { go[a] += g_near * p.gn[0]; gu[a] += g_near * p.gn[1]; }
-            if (a == p.a_far) { go[a] += g_far * p.gf[0]; gu[a] += g_far * p.gf[1]; }
-        }
-        // u = w / |w|, w = R c: the part of gu along u is projected off
-        const double dot = p.u[0] * gu[0] + p.u[1] * gu[1] + p.u[2] * gu[2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double gw = (gu[i] - p.u[i] * dot) * p.inv_n;
-            gR[3 * i] += gw * p.c[0]; gR[3 * i + 1] += gw * p.c[1]; gR[3 * i + 2] += gw;
-            // o = t / (diag/2); the sphere bounds move with |t|
-            double g = go[i] / f.hd;
-            if (!rend_aabb) g += (g_near + g_far) * f.t[i] / (dist * f.hd);
-            gt[i] += g;
-        }
+        sample_bwd(f, prm[q], k, jitter, ((b * Nr + r) * S + k) * 3, (r * Nb + b) * S + k, inv_s, scale, rend_aabb, shapenet, dist, d_xyz, d_viewdir,
+                   d_z, gR, gt);
     }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) part[i][threadIdx.x] = gR[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) part[9 + i][threadIdx.x] = gt[i];
-    __syncthreads();
-    if (threadIdx.x < 12 * 16) {
-        const int q = threadIdx.x >> 4, seg = threadIdx.x & 15;
-        double sum = 0.;
-        for (int k = 0; k < PAIRS / 16; ++k) sum += part[q][seg * (PAIRS / 16) + k];
-        part2[q][seg] = sum;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double sum = 0.;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) sum += part2[threadIdx.x][k];
-        partial[(b * gridDim.x + blockIdx.x) * 12 + threadIdx.x] = sum;
-    }
+    meet_slice(part, part2, gR, gt, partial + (b * gridDim.x + blockIdx.x) * 12);
 }
 
 // Stage 2: the slices of every object added in slice order; element (i, j) of d_cam2obj (Nb,3,4) = [dL/dR | dL/dt]
@@ -309,11 +331,176 @@ __global__ void __launch_bounds__(256) scene_gather_bwd_kernel(const float* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------ compact route
+// the hit flags alone: what scene_samples_fwd_kernel decides, for the caller's prefix sum
+__global__ void __launch_bounds__(PAIRS) scene_pair_hits_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
+                                                                const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels, SceneCam cam,
+                                                                long long Nr, int Nb, int rend_aabb, uint8_t* __restrict__ hit) {
+    const long long b = blockIdx.y;
+    const long long r = (long long)blockIdx.x * PAIRS + threadIdx.x;
+    if (r >= Nr) return;
+    const ObjFrame f = load_object(cam2obj, wlh, rois, b);
+    hit[r * Nb + b] = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0).hit ? 1 : 0;
+}
+
+// the slot of a hit pair, -1 when it is not kept: scan is only compared, a value outside [1, C] keeps nothing
+__device__ __forceinline__ int slot_of(bool hit, int32_t scan, int C) { return hit && scan >= 1 && scan <= C ? scan - 1 : -1; }
+
+// how many of an object's C slots are taken: its true count, clamped
+__device__ __forceinline__ int slots_taken(const int32_t* __restrict__ scan, long long Nr, int Nb, long long b, int C) {
+    if (Nr <= 0) return 0;
+    const int32_t n = scan[(Nr - 1) * Nb + b];
+    return n < 0 ? 0 : (n > C ? C : n);
+}
+
+// scene_samples_fwd_kernel with the points and directions of kept pairs at their slots; the workgroups of an object share its padding slots
+__global__ void __launch_bounds__(PAIRS) scene_samples_compact_fwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
+                                                                          const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels,
+                                                                          SceneCam cam, const float* __restrict__ jitter, long long Nr, int Nb, int S,
+                                                                          float adjust_scale, int rend_aabb, int shapenet,
+                                                                          const int32_t* __restrict__ scan, int C, float* __restrict__ xyz,
+                                                                          float* __restrict__ viewdir, float* __restrict__ z_vals,
+                                                                          uint8_t* __restrict__ kept, int32_t* __restrict__ pair_of_slot) {
+    __shared__ PairLds prm[PAIRS];
+    __shared__ int slots[PAIRS];
+    const long long b = blockIdx.y;
+    const long long r0 = (long long)blockIdx.x * PAIRS;
+    const long long left = Nr - r0;
+    const int np = (int)(left < 0 ? 0 : (left < PAIRS ? left : PAIRS));
+    const ObjFrame f = load_object(cam2obj, wlh, rois, b);
+    if ((int)threadIdx.x < np) {
+        const long long r = r0 + threadIdx.x;
+        const PairRay p = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0);
+        const int slot = slot_of(p.hit, scan[r * Nb + b], C);
+        slots[threadIdx.x] = slot;
+        kept[r * Nb + b] = slot >= 0 ? 1 : 0;
+        if (slot >= 0) {
+            park_pair(prm[threadIdx.x], p);
+            pair_of_slot[b * C + slot] = (int32_t)r;
+        }
+    }
+    __syncthreads();
+    const double o[3] = {f.t[0] / f.hd, f.t[1] / f.hd, f.t[2] / f.hd};
+    const double scale = (double)adjust_scale, inv_s = 1.0 / (double)S;
+    const long long n = (long long)np * S;
+    for (long long e = threadIdx.x; e < n; e += PAIRS) {
+        const int q = (int)(e / S), k = (int)(e - (long long)q * S);
+        const long long ip = ((r0 + q) * Nb + b) * S + k;
+        const int slot = slots[q];
+        float px[3], dv[3], z;
+        if (slot >= 0) {
+            sample_fwd(f, o, prm[q], k, jitter, ip, inv_s, scale, shapenet, px, dv, z);
+            const long long io = ((b * C + slot) * S + k) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { xyz[io + c] = px[c]; viewdir[io + c] = dv[c]; }
+        } else {
+            sample_miss(px, dv, z);
+        }
+        z_vals[ip] = z;
+    }
+    // padding: slots taken .. C-1 of this object, an equal run of them per workgroup
+    const int taken = slots_taken(scan, Nr, Nb, b, C);
+    const int run = (C + (int)gridDim.x - 1) / (int)gridDim.x;
+    const long long lo0 = (long long)blockIdx.x * run, hi0 = lo0 + run;
+    const int lo = (int)(lo0 < taken ? taken : (lo0 > C ? C : lo0)), hi = (int)(hi0 > C ? C : hi0);
+    if (hi <= lo) return;
+    for (int sl = lo + (int)threadIdx.x; sl < hi; sl += PAIRS) pair_of_slot[b * C + sl] = -1;
+    float px[3], dv[3], z;
+    sample_miss(px, dv, z);
+    const long long m = (long long)(hi - lo) * S;
+    for (long long e = threadIdx.x; e < m; e += PAIRS) {
+        const long long io = ((b * C + lo) * S + e) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { xyz[io + c] = px[c]; viewdir[io + c] = dv[c]; }
+    }
+}
+
+// scene_samples_bwd_kernel reading d_xyz and d_viewdir at the slot: the same pairs per slice, the same sweep, the same meeting order
+__global__ void __launch_bounds__(PAIRS) scene_samples_compact_bwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
+                                                                          const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels,
+                                                                          SceneCam cam, const float* __restrict__ jitter, long long Nr, int Nb, int S,
+                                                                          float adjust_scale, int rend_aabb, int shapenet,
+                                                                          const int32_t* __restrict__ scan, int C, const float* __restrict__ d_xyz,
+                                                                          const float* __restrict__ d_viewdir, const float* __restrict__ d_z,
+                                                                          double* __restrict__ partial) {
+    __shared__ PairBwd prm[PAIRS];
+    __shared__ int slots[PAIRS];
+    __shared__ double part[12][PAIRS];
+    __shared__ double part2[12][16];
+    const long long b = blockIdx.y;
+    const long long r0 = (long long)blockIdx.x * PAIRS;
+    const int np = (int)(Nr - r0 < PAIRS ? Nr - r0 : PAIRS);
+    const ObjFrame f = load_object(cam2obj, wlh, rois, b);
+    if ((int)threadIdx.x < np) {
+        const long long r = r0 + threadIdx.x;
+        const PairRay p = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0);
+        const int slot = slot_of(p.hit, scan[r * Nb + b], C);
+        slots[threadIdx.x] = slot;
+        if (slot >= 0) park_pair_bwd(prm[threadIdx.x], p);
+    }
+    __syncthreads();
+    const double scale = (double)adjust_scale, inv_s = 1.0 / (double)S;
+    double dist = 1.0;
+    if (!rend_aabb) dist = sqrt(f.t[0] * f.t[0] + f.t[1] * f.t[1] + f.t[2] * f.t[2]);
+    double gR[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.}, gt[3] = {0., 0., 0.};
+    const long long n = (long long)np * S;
+    for (long long e = threadIdx.x; e < n; e += PAIRS) {
+        const int q = (int)(e / S), k = (int)(e - (long long)q * S);
+        const int slot = slots[q];
+        if (slot < 0) continue;                                  // not hit, or dropped: exact zeros
+        sample_bwd(f, prm[q], k, jitter, ((b * C + slot) * S + k) * 3, ((r0 + q) * Nb + b) * S + k, inv_s, scale, rend_aabb, shapenet, dist, d_xyz,
+                   d_viewdir, d_z, gR, gt);
+    }
+    meet_slice(part, part2, gR, gt, partial + (b * gridDim.x + blockIdx.x) * 12);
+}
+
+// pixel-major rows of the decoder's compact outputs: a kept pair's rows from its slot, (0, white) on every other pair
+__global__ void __launch_bounds__(256) scene_gather_compact_fwd_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                                       const int32_t* __restrict__ scan, const uint8_t* __restrict__ kept,
+                                                                       long long Nr, int Nb, int S, int C, float* __restrict__ sig_out,
+                                                                       float* __restrict__ rgb_out) {
+    const long long n = Nr * Nb * S;
+    for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const long long pair = e / S;
+        const int k = (int)(e - pair * S);
+        const long long b = pair % Nb;
+        const int slot = slot_of(kept[pair] != 0, scan[pair], C);
+        const long long src = ((b * C + (slot < 0 ? 0 : slot)) * S + k);
+        if (sig_out) sig_out[e] = slot >= 0 ? sigmas[src] : 0.f;
+        if (rgb_out) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rgb_out[3 * e + c] = slot >= 0 ? rgbs[3 * src + c] : 1.f;
+        }
+    }
+}
+
+// the inverse scatter in the destination's order: slot (b, s) takes the gradients of pixel pair_of_slot[b][s], padding exact zeros
+__global__ void __launch_bounds__(256) scene_gather_compact_bwd_kernel(const float* __restrict__ d_sig_rows, const float* __restrict__ d_rgb_rows,
+                                                                       const int32_t* __restrict__ pair_of_slot, long long Nr, int Nb, int S, int C,
+                                                                       float* __restrict__ d_sigmas, float* __restrict__ d_rgbs) {
+    const long long n = (long long)Nb * C * S;
+    for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const long long row = e / S;                 // row = b * C + slot
+        const int k = (int)(e - row * S);
+        const long long b = row / C;
+        const long long r = pair_of_slot[row];
+        const bool h = r >= 0 && r < Nr;
+        const long long src = ((h ? r : 0) * Nb + b) * S + k;
+        if (d_sigmas) d_sigmas[e] = h ? d_sig_rows[src] : 0.f;
+        if (d_rgbs) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d_rgbs[3 * e + c] = h ? d_rgb_rows[3 * src + c] : 0.f;
+        }
+    }
+}
+
 inline long long scene_slices(long long Nr) { return (Nr + PAIRS - 1) / PAIRS; }
 // sizes the kernels' 64-bit indices and grids take: Nb objects in gridDim.y, Nr * Nb * S * 3 elements
 inline bool scene_sizes_ok(long long Nr, long long Nb, int S) {
     return Nr >= 0 && Nb >= 1 && Nb <= 65535 && S >= 1 && Nr <= (1ll << 40) / (Nb * (long long)S) && scene_slices(Nr) <= 0x7fffffffll;
 }
+// a capacity the compact kernels take: whole 32-point tiles per object for every S, Nb * C * S * 3 elements within the same limit
+inline bool scene_capacity_ok(long long C, long long Nb, int S) { return C >= 1 && C <= 0x7fffffffll && C % 32 == 0 && scene_sizes_ok(C, Nb, S); }
 
 }  // namespace snr
 
@@ -381,6 +568,72 @@ int snr_scene_gather_bwd(const float* d_sigma_rows, const float* d_rgb_rows, con
     if (!hit || (d_sigmas && !d_sigma_rows) || (d_rgbs && !d_rgb_rows) || (!d_sigmas && !d_rgbs)) return SNR_E_ARG;
     scene_gather_bwd_kernel<<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(d_sigma_rows, d_rgb_rows, hit, n_pixels,
                                                                                                           (int)n_objects, n_samples, d_sigmas, d_rgbs);
+    return snr_check_launch_();
+}
+
+int snr_scene_pair_hits(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx, float cy,
+                        int64_t n_pixels, int64_t n_objects, int rend_aabb, uint8_t* hit, void* stream) {
+    if (n_pixels == 0) return SNR_OK;
+    if (!scene_sizes_ok(n_pixels, n_objects, 1)) return SNR_E_ARG;
+    if (!cam2obj || !wlh || !rois || !pixels || !hit) return SNR_E_ARG;
+    const SceneCam cam = {fx, fy, cx, cy};
+    scene_pair_hits_kernel<<<dim3((unsigned)scene_slices(n_pixels), (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
+        cam2obj, wlh, rois, pixels, cam, n_pixels, (int)n_objects, rend_aabb, hit);
+    return snr_check_launch_();
+}
+
+int snr_scene_samples_compact_fwd(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx,
+                                  float cy, const float* jitter, int64_t n_pixels, int64_t n_objects, int n_samples, float adjust_scale,
+                                  int rend_aabb, int shapenet_obj_cood, const int32_t* hit_scan, int64_t capacity, float* xyz, float* viewdir,
+                                  float* z_vals, uint8_t* kept, int32_t* pair_of_slot, void* stream) {
+    if (!scene_sizes_ok(n_pixels, n_objects, n_samples) || !scene_capacity_ok(capacity, n_objects, n_samples)) return SNR_E_ARG;
+    if (!cam2obj || !wlh || !rois || !xyz || !viewdir || !pair_of_slot) return SNR_E_ARG;
+    if (n_pixels > 0 && (!pixels || !hit_scan || !z_vals || !kept)) return SNR_E_ARG;
+    const SceneCam cam = {fx, fy, cx, cy};
+    const long long slices = scene_slices(n_pixels);
+    scene_samples_compact_fwd_kernel<<<dim3((unsigned)(slices < 1 ? 1 : slices), (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
+        cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, hit_scan,
+        (int)capacity, xyz, viewdir, z_vals, kept, pair_of_slot);
+    return snr_check_launch_();
+}
+
+int snr_scene_samples_compact_bwd(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx,
+                                  float cy, const float* jitter, int64_t n_pixels, int64_t n_objects, int n_samples, float adjust_scale,
+                                  int rend_aabb, int shapenet_obj_cood, const int32_t* hit_scan, int64_t capacity, const float* d_xyz,
+                                  const float* d_viewdir, const float* d_z, float* d_cam2obj, void* ws, size_t ws_bytes, void* stream) {
+    if (!scene_sizes_ok(n_pixels, n_objects, n_samples) || !scene_capacity_ok(capacity, n_objects, n_samples)) return SNR_E_ARG;
+    if (n_pixels == 0) return SNR_OK;
+    if (!cam2obj || !wlh || !rois || !pixels || !hit_scan || !d_cam2obj || !ws) return SNR_E_ARG;
+    if (((uintptr_t)ws & 7) != 0) return SNR_E_ARG;
+    if (ws_bytes < snr_scene_samples_bwd_ws_bytes(n_pixels, n_objects)) return SNR_E_WORKSPACE;
+    const SceneCam cam = {fx, fy, cx, cy};
+    const long long slices = scene_slices(n_pixels);
+    scene_samples_compact_bwd_kernel<<<dim3((unsigned)slices, (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
+        cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, hit_scan,
+        (int)capacity, d_xyz, d_viewdir, d_z, (double*)ws);
+    const int rc = snr_check_launch_();
+    if (rc != SNR_OK) return rc;
+    scene_samples_sum_kernel<<<(unsigned)n_objects, 64, 0, (hipStream_t)stream>>>((const double*)ws, slices, d_cam2obj);
+    return snr_check_launch_();
+}
+
+int snr_scene_gather_compact_fwd(const float* sigmas, const float* rgbs, const int32_t* hit_scan, const uint8_t* kept, int64_t n_pixels,
+                                 int64_t n_objects, int n_samples, int64_t capacity, float* sigma_rows, float* rgb_rows, void* stream) {
+    if (!scene_sizes_ok(n_pixels, n_objects, n_samples) || !scene_capacity_ok(capacity, n_objects, n_samples)) return SNR_E_ARG;
+    if (n_pixels == 0) return SNR_OK;
+    if (!hit_scan || !kept || (sigma_rows && !sigmas) || (rgb_rows && !rgbs) || (!sigma_rows && !rgb_rows)) return SNR_E_ARG;
+    scene_gather_compact_fwd_kernel<<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(
+        sigmas, rgbs, hit_scan, kept, n_pixels, (int)n_objects, n_samples, (int)capacity, sigma_rows, rgb_rows);
+    return snr_check_launch_();
+}
+
+int snr_scene_gather_compact_bwd(const float* d_sigma_rows, const float* d_rgb_rows, const int32_t* pair_of_slot, int64_t n_pixels, int64_t n_objects,
+                                 int n_samples, int64_t capacity, float* d_sigmas, float* d_rgbs, void* stream) {
+    if (!scene_sizes_ok(n_pixels, n_objects, n_samples) || !scene_capacity_ok(capacity, n_objects, n_samples)) return SNR_E_ARG;
+    if (!pair_of_slot || (!d_sigmas && !d_rgbs)) return SNR_E_ARG;
+    if (n_pixels > 0 && ((d_sigmas && !d_sigma_rows) || (d_rgbs && !d_rgb_rows))) return SNR_E_ARG;
+    scene_gather_compact_bwd_kernel<<<gather_grid(n_objects * capacity * n_samples), 256, 0, (hipStream_t)stream>>>(
+        d_sigma_rows, d_rgb_rows, pair_of_slot, n_pixels, (int)n_objects, n_samples, (int)capacity, d_sigmas, d_rgbs);
     return snr_check_launch_();
 }
 

@@ -20,6 +20,7 @@ restated here via Rodrigues' formula; parity for it is pinned only by self-consi
 import contextlib
 import json
 import math
+import warnings
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -487,7 +488,7 @@ def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, 
 
 # ------------------------------------------------------------------ all objects of a frame, jointly against the frame
 def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texturecodes0, pose_noise=(0.05, 0.3), seed=0, jitter=None,
-                   pixels=None, info: Optional[dict] = None):
+                   pixels=None, info: Optional[dict] = None, compact=False, capacity=None, capacity_margin=1.5):
     """Fit the codes and poses of all Nb objects of one frame JOINTLY against the frame: every listed pixel is rendered through all objects
     (``scene.render_scene``'s fused route) and compared with the image, so objects that occlude each other share their pixels' loss.
 
@@ -500,6 +501,13 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
     ``ops.SceneComposite``), ``ops.LossTail`` with the scene as one "object", backward, ``ops.DeviceAdamW`` over the four groups (every
     iteration; rates halved every ``lr_half_interval``).  The decoder's weights are constants of the loop.  ``info`` receives ``pixels`` and
     ``hit_share`` (T,), the share of (pixel, object) pairs that hit per iteration.
+
+    ``compact``: ``render_pairs``' compact chain, the decoder on ``capacity`` slots per object instead of all Nr pixels.  The default
+    capacity is measured ONCE before the loop (one host read of Nb counts): the fullest object's hit count at the start poses times
+    ``capacity_margin``, through ``ops.scene_capacity``, at most ``ops.scene_capacity(Nr)``.  Inside the loop nothing is read: an object whose
+    hits outgrow the capacity has the surplus pairs rendered as misses, their number summed on the device into ``info["dropped_pairs"]``
+    (0-dim int64), and a ``RuntimeWarning`` is raised after the loop when it is not zero.  ``info["capacity"]`` holds the capacity;
+    ``hit_share`` stays the geometric share, dropped pairs included.
 
     Returns metrics (T,Nb,2) = rotation / translation error of every object at the poses iteration t rendered, losses (T,4) = [loss,
     loss_rgb, loss_occ, mse_fg], shape codes, texture codes and the object poses (Nb,3,4) after the last update."""
@@ -555,6 +563,16 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
     ones = torch.ones(1, device=dev)
     packed = model.packed_weights()
     prec = None
+    if compact:
+        if capacity is None:    # the fullest object at the start poses, with room to grow: the one host read of the compact route
+            with torch.no_grad():
+                start = torch.cat([axis_angle_to_matrix(rot0), tr0[:, :, None]], dim=2).to(dev)
+                hit0 = ops.scene_pair_hits(U.invert_pose(start), wlh_d, scene.scene_rois(start, wlh_d, K_d, H, W), pixels, Kvec, True)
+                capacity = ops.scene_capacity(math.ceil(int(hit0.sum(0, dtype=torch.int32).max()) * float(capacity_margin)))
+        capacity = min(int(capacity), ops.scene_capacity(Nr))
+        dropped = torch.zeros((), dtype=torch.int64, device=dev)
+    elif capacity is not None:
+        raise U.SnrError("optimize_scene: capacity belongs to compact=True")
 
     def decode(xyz, viewdir):
         nonlocal prec
@@ -570,13 +588,20 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
             with torch.no_grad():
                 pose_log[it] = U.invert_pose(cam2obj)
                 rois = scene.scene_rois(pose_log[it], wlh_d, K_d, H, W)
-            rgb, _, acc, hit = scene.render_pairs(decode, cam2obj, wlh_d, rois, pixels, Kvec, jitter[it], S, 1.0, True, shapenet)
+            if compact:
+                rgb, _, acc, _, count = scene.render_pairs(decode, cam2obj, wlh_d, rois, pixels, Kvec, jitter[it], S, 1.0, True, shapenet, capacity)
+            else:
+                rgb, _, acc, hit = scene.render_pairs(decode, cam2obj, wlh_d, rois, pixels, Kvec, jitter[it], S, 1.0, True, shapenet)
             loss, lm = ops.LossTail.apply(rgb, acc, tgt, occ, coef, Nr)
             torch.autograd.backward(loss, ones)
             with torch.no_grad():
                 loss_log[it, 0:1] = loss.detach()
                 loss_log[it, 1:] = lm[0]
-                hit_log[it] = hit.float().mean()
+                if compact:
+                    hit_log[it] = count.sum() / float(Nr * Nb)
+                    dropped += (count - capacity).clamp_min(0).sum()
+                else:
+                    hit_log[it] = hit.float().mean()
             optim.step()
             optim.zero_grad()
             _halve_rates(optim, it, opt)
@@ -585,6 +610,11 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
         poses = torch.cat([axis_angle_to_matrix(rot_vec.detach()), trans_vec.detach()[:, :, None]], dim=2)
     if info is not None:
         info["pixels"], info["hit_share"] = pixels, hit_log
+        if compact:
+            info["capacity"], info["dropped_pairs"] = capacity, dropped
+    if compact and int(dropped) > 0:
+        warnings.warn(f"optimize_scene: {int(dropped)} hit (pixel, object) pairs beyond the capacity of {capacity} per object were rendered as "
+                      "misses; pass a larger capacity or capacity_margin", RuntimeWarning, stacklevel=2)
     return metrics, loss_log, shapecode.detach(), texturecode.detach(), poses
 
 

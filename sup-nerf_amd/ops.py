@@ -6,6 +6,7 @@ import copy
 import ctypes as C
 import functools
 import math
+import operator
 import threading
 import warnings
 import weakref
@@ -397,6 +398,150 @@ class SceneGather(torch.autograd.Function):
                 check(_lib.lib().snr_scene_gather_bwd(_p(d_sig_rows), _p(d_rgb_rows), _p(hit), Nr, Nb, S, _p(d_sig), _p(d_rgb), _stream(dev)),
                       "snr_scene_gather_bwd")
         return d_sig, d_rgb, None, None
+
+
+def scene_capacity(n) -> int:
+    """Slots per object of the compact scene route that hold ``n`` pairs: ``n`` rounded up to a multiple of 32 (whole decoder tiles for every
+    sample count), at least 32."""
+    return max(32, 32 * ((int(n) + 31) // 32))
+
+
+def _scene_capacity_arg(name, capacity):
+    try:
+        cap = None if isinstance(capacity, bool) else operator.index(capacity)
+    except TypeError:
+        cap = None
+    if cap is None or cap < 1 or cap % 32 != 0:
+        raise SnrError(f"{name}: capacity is a positive multiple of 32 (ops.scene_capacity), got {capacity!r}")
+    return cap
+
+
+def _scene_scan(name, hit_scan, Nr, Nb):
+    if hit_scan.shape != (Nr, Nb) or hit_scan.dtype != torch.int32:
+        raise SnrError(f"{name}: expected hit_scan (Nr,Nb) = ({Nr},{Nb}) int32, got {tuple(hit_scan.shape)} {hit_scan.dtype}")
+    return hit_scan.contiguous()
+
+
+def scene_pair_hits(cam2obj, wlh, rois, pixels, Kvec, rend_aabb=True):
+    """hit (Nr,Nb) uint8 of every (pixel, object) pair, the flags of ``SceneSamples`` without its samples (snr_scene_pair_hits): what the
+    compact route scans, ``torch.cumsum(hit.to(torch.int32), 0)``."""
+    cam2obj, wlh = _f32c(cam2obj.detach()), _f32c(wlh)
+    Nr, Nb = _scene_lists("scene_pair_hits", cam2obj, wlh, rois, pixels, None, 1)
+    if len(Kvec) != 4:
+        raise SnrError("scene_pair_hits: Kvec is (fx, fy, cx, cy)")
+    _need_gpu(cam2obj, wlh, rois, pixels)
+    rois, pixels = rois.contiguous(), pixels.contiguous()
+    dev = cam2obj.device
+    hit = torch.empty(Nr, Nb, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_scene_pair_hits(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), *[float(v) for v in Kvec], Nr, Nb, int(bool(rend_aabb)),
+                                             _p(hit), _stream(dev)), "snr_scene_pair_hits")
+    return hit
+
+
+class SceneSamplesCompact(torch.autograd.Function):
+    """``SceneSamples`` with only the pairs that hit handed on (snr_scene_samples_compact_fwd; rules: include/supnerf_hip.h): ``hit_scan``
+    (Nr,Nb) int32 = ``torch.cumsum`` of ``scene_pair_hits`` along the pixels, ``capacity`` C slots per object (``scene_capacity``) -> xyz,
+    viewdir (Nb*C,S,3), a pair at row b*C + hit_scan - 1; z_vals (Nr,Nb*S) pixel-major and dense, -1 on pairs that are not kept; kept (Nr,Nb)
+    uint8; pair_of_slot (Nb,C) int32, -1 on padding.  A hit pair beyond the capacity is dropped.  Backward to cam2obj: two launches, the
+    bits of ``SceneSamples``' backward."""
+
+    @staticmethod
+    def forward(ctx, cam2obj, wlh, rois, pixels, Kvec, jitter, S, adjust_scale, rend_aabb, shapenet_obj_cood, hit_scan, capacity):
+        cam2obj, wlh, jitter = _f32c(cam2obj), _f32c(wlh), _f32c(jitter)
+        Nr, Nb = _scene_lists("scene_samples_compact", cam2obj, wlh, rois, pixels, jitter, S)
+        if len(Kvec) != 4:
+            raise SnrError("scene_samples_compact: Kvec is (fx, fy, cx, cy)")
+        cap = _scene_capacity_arg("scene_samples_compact", capacity)
+        hit_scan = _scene_scan("scene_samples_compact", hit_scan, Nr, Nb)
+        _need_gpu(cam2obj, wlh, rois, pixels, jitter, hit_scan)
+        rois, pixels = rois.contiguous(), pixels.contiguous()
+        cfg = (*[float(v) for v in Kvec], int(S), float(adjust_scale), int(bool(rend_aabb)), int(bool(shapenet_obj_cood)), cap)
+        fx, fy, cx, cy, S = cfg[:5]
+        dev = cam2obj.device
+        ctx.set_materialize_grads(False)
+        xyz, viewdir = torch.empty(Nb * cap, S, 3, device=dev), torch.empty(Nb * cap, S, 3, device=dev)
+        z = torch.empty(Nr, Nb * S, device=dev)
+        kept = torch.empty(Nr, Nb, dtype=torch.uint8, device=dev)
+        pair_of_slot = torch.empty(Nb, cap, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_scene_samples_compact_fwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, cfg[5],
+                                                           cfg[6], cfg[7], _p(hit_scan), cap, _p(xyz), _p(viewdir), _p(z), _p(kept),
+                                                           _p(pair_of_slot), _stream(dev)), "snr_scene_samples_compact_fwd")
+        ctx.save_for_backward(cam2obj, wlh, rois, pixels, jitter, hit_scan)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(kept, pair_of_slot)
+        return xyz, viewdir, z, kept, pair_of_slot
+
+    @staticmethod
+    def backward(ctx, d_xyz, d_viewdir, d_z, _d_kept, _d_slots):
+        cam2obj, wlh, rois, pixels, jitter, hit_scan = ctx.saved_tensors
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[5]:
+            raise SnrError("scene_samples_compact: the box sizes and the jitter are data, no gradient is provided")
+        if not ctx.needs_input_grad[0] or (d_xyz is None and d_viewdir is None and d_z is None):
+            return (None,) * 12
+        fx, fy, cx, cy, S, scale, aabb, shapenet, cap = ctx.cfg
+        Nr, Nb = pixels.shape[0], cam2obj.shape[0]
+        dev = cam2obj.device
+        d_xyz, d_viewdir, d_z = _f32c(d_xyz), _f32c(d_viewdir), _f32c(d_z)
+        if Nr == 0:
+            return (torch.zeros_like(cam2obj),) + (None,) * 11
+        d_cam2obj = torch.empty_like(cam2obj)
+        n_ws = int(_lib.lib().snr_scene_samples_bwd_ws_bytes(Nr, Nb))
+        ws = torch.empty(n_ws // 8, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_scene_samples_compact_bwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, scale,
+                                                           aabb, shapenet, _p(hit_scan), cap, _p(d_xyz), _p(d_viewdir), _p(d_z), _p(d_cam2obj),
+                                                           _p(ws), n_ws, _stream(dev)), "snr_scene_samples_compact_bwd")
+        return (d_cam2obj,) + (None,) * 11
+
+
+class SceneGatherCompact(torch.autograd.Function):
+    """``SceneGather`` from the compact layout: sigmas (Nb*C*S values) and rgbs (Nb*C*S,3) of the decoder -> rows (Nr,Nb*S) / (Nr,Nb*S,3), a
+    kept pair's rows from its slot (``hit_scan`` - 1), sigma 0 and white on every other pair; backward through ``pair_of_slot`` (Nb,C), exact
+    zeros on padding slots.  ``hit_scan``, ``kept`` and ``pair_of_slot`` as ``SceneSamplesCompact`` took and gave them."""
+
+    @staticmethod
+    def forward(ctx, sigmas, rgbs, hit_scan, kept, pair_of_slot, S):
+        sigmas, rgbs = _f32c(sigmas), _f32c(rgbs)
+        S = int(S)
+        ok = kept.dim() == 2 and kept.dtype == torch.uint8 and pair_of_slot.dim() == 2 and pair_of_slot.dtype == torch.int32 and S >= 1
+        if ok:
+            (Nr, Nb), cap = kept.shape, pair_of_slot.shape[1]
+            ok = pair_of_slot.shape[0] == Nb and Nb >= 1 and sigmas.numel() == Nb * cap * S and rgbs.numel() == 3 * sigmas.numel()
+        if not ok:
+            raise SnrError(f"scene_gather_compact: expected sigmas (Nb*C*S), rgbs (Nb*C*S,3), kept (Nr,Nb) uint8 and pair_of_slot (Nb,C) int32, got "
+                           f"{tuple(sigmas.shape)}, {tuple(rgbs.shape)}, {tuple(kept.shape)} {kept.dtype}, {tuple(pair_of_slot.shape)} "
+                           f"{pair_of_slot.dtype}, S = {S}")
+        cap = _scene_capacity_arg("scene_gather_compact", cap)
+        hit_scan = _scene_scan("scene_gather_compact", hit_scan, Nr, Nb)
+        _need_gpu(sigmas, rgbs, hit_scan, kept, pair_of_slot)
+        kept, pair_of_slot = kept.contiguous(), pair_of_slot.contiguous()
+        dev = sigmas.device
+        ctx.set_materialize_grads(False)
+        sig_rows, rgb_rows = torch.empty(Nr, Nb * S, device=dev), torch.empty(Nr, Nb * S, 3, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.lib().snr_scene_gather_compact_fwd(_p(sigmas), _p(rgbs), _p(hit_scan), _p(kept), Nr, Nb, S, cap, _p(sig_rows), _p(rgb_rows),
+                                                          _stream(dev)), "snr_scene_gather_compact_fwd")
+        ctx.save_for_backward(pair_of_slot)
+        ctx.cfg = (S, Nr, sigmas.shape, rgbs.shape)
+        return sig_rows, rgb_rows
+
+    @staticmethod
+    def backward(ctx, d_sig_rows, d_rgb_rows):
+        pair_of_slot, = ctx.saved_tensors
+        S, Nr, sig_shape, rgb_shape = ctx.cfg
+        Nb, cap = pair_of_slot.shape
+        dev = pair_of_slot.device
+        d_sig_rows = _f32c(d_sig_rows) if ctx.needs_input_grad[0] else None
+        d_rgb_rows = _f32c(d_rgb_rows) if ctx.needs_input_grad[1] else None
+        d_sig = torch.empty(sig_shape, device=dev) if d_sig_rows is not None else None
+        d_rgb = torch.empty(rgb_shape, device=dev) if d_rgb_rows is not None else None
+        if d_sig is not None or d_rgb is not None:
+            with torch.cuda.device(dev):
+                check(_lib.lib().snr_scene_gather_compact_bwd(_p(d_sig_rows), _p(d_rgb_rows), _p(pair_of_slot), Nr, Nb, S, cap, _p(d_sig), _p(d_rgb),
+                                                              _stream(dev)), "snr_scene_gather_compact_bwd")
+        return d_sig, d_rgb, None, None, None, None
 
 
 def composite_bwd(sigmas, rgbs, z_vals, z_mode, white_bkgd, rays_per_obj, d_rgb, d_depth, d_acc, need_dz):

@@ -15,7 +15,7 @@ rows, samples and regrouping are HIP launches too (``render_pairs``).
 What lies between the object poses and the kernels is stated once, here: the box corners (``corners_of_box_batch``), the roi (``scene_rois``,
 which ``scene_rays``, ``scene_ray_rows`` and the fused route all call), the pixels the live rois cover (``roi_pixels``), the intrinsics as host
 floats (``K_vector``), the fused chain SceneSamples -> decoder -> SceneGather -> composite (``render_pairs``: ``render_scene(fused=True)`` and
-``driver.optimize_scene`` differ only in the decoder call they hand it) and the choice between the composite with and without a backward
+``driver.optimize_scene`` differ only in the decoder call they hand it; with a ``capacity`` its compact form, which decodes only the pairs that hit) and the choice between the composite with and without a backward
 (``_composite``).  The rigid inverse [R^T | -(R^T t)] is ``utils.invert_pose``.
 """
 from typing import Optional, Sequence
@@ -211,25 +211,34 @@ def scene_ray_rows(obj_poses, obj_wlh, K, pixels, H, W, manipulation=(0.0, 0.0, 
 
 
 def render_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, pixels, H, W, n_samples, jitter=None,
-                 manipulation=(0.0, 0.0, 0.0), rend_aabb=True, shapenet_obj_cood=True, adjust_scale=1.0, fused=False):
+                 manipulation=(0.0, 0.0, 0.0), rend_aabb=True, shapenet_obj_cood=True, adjust_scale=1.0, fused=False, compact=False, capacity=None,
+                 info: Optional[dict] = None):
     """rgb (Nr,3), depth (Nr,), acc_trans (Nr,) of the scene at the listed integer pixels (Nr,2) = (x, y), with autograd to
     ``shapecodes``, ``texturecodes`` and ``obj_poses``: ``render_scene_batch`` of ``scene_ray_rows``.  ``jitter``: (Nr*Nb, S) draws in
     [0,1), default ``torch.rand_like``.  Every listed pixel is rendered; one that no object covers comes out white.
     ``fused`` (native decoders): rows and samples in one launch (``ops.SceneSamples``) and the decoder's outputs regrouped in one
-    (``ops.SceneGather``), each with a one-launch backward, instead of ~65 torch launches each way; same rois, same jitter draw."""
+    (``ops.SceneGather``), each with a one-launch backward, instead of ~65 torch launches each way; same rois, same jitter draw.
+    ``compact`` (with ``fused``): the decoder sees only the pairs that hit, ``capacity`` slots per object (a multiple of 32,
+    ``ops.scene_capacity``).  ``capacity=None`` reads the Nb hit counts once -- the route's SECOND host read, after the roi read -- and takes
+    ``ops.scene_capacity`` of the largest, so no pair is dropped; an int makes no read, and hit pairs of an object beyond it render as
+    misses.  ``info`` receives ``count`` (Nb,) int32, every object's true number of hits, and ``capacity``."""
     if obj_poses.shape[0] != shapecodes.shape[0] or obj_poses.shape[0] != texturecodes.shape[0] or obj_poses.shape[0] != obj_wlh.shape[0]:
         raise SnrError("render_scene: obj_poses, obj_wlh, shapecodes and texturecodes must describe the same number of objects")
     dev = torch.device(device)
+    if compact and not fused:
+        raise SnrError("render_scene(compact=True) is a variant of the fused route: pass fused=True")
+    if capacity is not None and not compact:
+        raise SnrError("render_scene: capacity belongs to compact=True")
     if fused:
         return _render_scene_fused(model, dev, obj_poses.to(dev), obj_wlh, shapecodes, texturecodes, K, pixels, H, W, n_samples, jitter, manipulation,
-                                   rend_aabb, shapenet_obj_cood, adjust_scale)
+                                   rend_aabb, shapenet_obj_cood, adjust_scale, compact, capacity, info)
     rows, _ = scene_ray_rows(obj_poses.to(dev), obj_wlh, K, pixels, H, W, manipulation, rend_aabb)
     diags = torch.linalg.norm(obj_wlh.detach().float(), dim=1)
     return render_scene_batch(model, device, rows.float(), diags, shapecodes, texturecodes, n_samples, jitter, adjust_scale, shapenet_obj_cood)
 
 
 def _render_scene_fused(model, dev, obj_poses, obj_wlh, shapecodes, texturecodes, K, pixels, H, W, n_samples, jitter, manipulation, rend_aabb,
-                        shapenet_obj_cood, adjust_scale):
+                        shapenet_obj_cood, adjust_scale, compact=False, capacity=None, info=None):
     """``render_scene`` with the rows, samples and regrouping on the HIP kernels; the decoder and the composite as on the default route."""
     if not U._is_native(model):
         raise SnrError("render_scene(fused=True) needs the package's own decoder; a foreign decoder renders on the default route")
@@ -240,19 +249,39 @@ def _render_scene_fused(model, dev, obj_poses, obj_wlh, shapecodes, texturecodes
     rois = _host_rois(poses, obj_wlh, K, H, W).to(dev)                                              # as in scene_ray_rows
     if jitter is None:
         jitter = torch.rand(Nr * Nb, n_samples)                                                      # CPU draw, like render_scene_batch
-    return render_pairs(lambda x, d: model(x, d, shapecodes.to(dev), texturecodes.to(dev)), U.invert_pose(poses).float(), obj_wlh.detach().to(dev),
-                        rois, pixels, K_vector(K), jitter.to(dev), n_samples, adjust_scale, rend_aabb, shapenet_obj_cood)[:3]
+    cam2obj, wlh, Kvec = U.invert_pose(poses).float(), obj_wlh.detach().to(dev), K_vector(K)
+    if compact and capacity is None:                                                                 # the second host read: Nb counts
+        capacity = ops.scene_capacity(int(ops.scene_pair_hits(cam2obj, wlh, rois, pixels, Kvec, rend_aabb).sum(0, dtype=torch.int32).max()) if Nr else 0)
+    out = render_pairs(lambda x, d: model(x, d, shapecodes.to(dev), texturecodes.to(dev)), cam2obj, wlh, rois, pixels, Kvec, jitter.to(dev), n_samples,
+                       adjust_scale, rend_aabb, shapenet_obj_cood, capacity)
+    if compact and info is not None:
+        info["count"], info["capacity"] = out[4], capacity
+    return out[:3]
 
 
-def render_pairs(decode, cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood):
+def render_pairs(decode, cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, capacity=None):
     """THE fused chain of the scene path, all operands on the GPU: rows and samples of every (pixel, object) pair (``ops.SceneSamples``; cam2obj
     (Nb,3,4) differentiable, rois (Nb,4) and pixels (Nr,2) int32, Kvec from ``K_vector``, jitter (Nr*Nb,S) or None), ``decode(xyz, viewdir)
     -> (sigmas, rgbs)`` on the object-major points, ``ops.SceneGather``, the merge-composite.  -> rgb (Nr,3), depth (Nr,), acc_trans (Nr,), hit
-    (Nr,Nb) uint8."""
-    xyz, viewdir, z_vals, hit, _ = ops.SceneSamples.apply(cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood)
-    sig, rgb = decode(xyz, viewdir)                                                                  # object-major, Nb codes
-    sig, rgb = ops.SceneGather.apply(sig, rgb, hit, n_samples)
-    return (*_composite(sig, rgb, z_vals, n_samples), hit)
+    (Nr,Nb) uint8.
+
+    ``capacity`` (an int, a multiple of 32): the compact chain -- the hit flags (``ops.scene_pair_hits``), their prefix sum along the pixels,
+    ``ops.SceneSamplesCompact``, ``decode`` on Nb * capacity * S points, ``ops.SceneGatherCompact``, the same composite; no host read.  -> rgb,
+    depth, acc_trans, kept (Nr,Nb) uint8, count (Nb,) int32: an object's hit pairs beyond ``capacity`` (count - capacity of them) render as
+    misses."""
+    if capacity is None:
+        xyz, viewdir, z_vals, hit, _ = ops.SceneSamples.apply(cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood)
+        sig, rgb = decode(xyz, viewdir)                                                              # object-major, Nb codes
+        sig, rgb = ops.SceneGather.apply(sig, rgb, hit, n_samples)
+        return (*_composite(sig, rgb, z_vals, n_samples), hit)
+    hit = ops.scene_pair_hits(cam2obj, wlh, rois, pixels, Kvec, rend_aabb)
+    scan = torch.cumsum(hit.to(torch.int32), 0, dtype=torch.int32)
+    count = scan[-1] if scan.shape[0] else scan.new_zeros(scan.shape[1])
+    xyz, viewdir, z_vals, kept, pair_of_slot = ops.SceneSamplesCompact.apply(cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale,
+                                                                              rend_aabb, shapenet_obj_cood, scan, capacity)
+    sig, rgb = decode(xyz, viewdir)                                                                  # object-major, Nb codes, capacity rows each
+    sig, rgb = ops.SceneGatherCompact.apply(sig, rgb, scan, kept, pair_of_slot, n_samples)
+    return (*_composite(sig, rgb, z_vals, n_samples), kept, count)
 
 
 def vis_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, H, W, n_samples, manipulation=(0.0, 0.0, 0.0),

@@ -6,7 +6,10 @@
   * the two new launches on their own at the frame's size against their least traffic: 28 bytes per sample out of the forward (points,
     directions, depth), 32 bytes per sample into the backward (their three gradients and the jitter);
   * one iteration of ``driver.optimize_scene`` on the frame: the difference of a 6- and a 2-iteration run over 4;
-  * the share of (pixel, object) pairs that hit, which sizes what decoding only the hit pairs would save.
+  * the share of (pixel, object) pairs that hit, which sizes what decoding only the hit pairs saves;
+  * the compact route (``compact=True``: the decoder on the pairs that hit) in turn with the rows above, in the same calls: forward + backward
+    on the fixture and on the frame (its default capacity, with the read of the counts that sets it) and one ``optimize_scene`` iteration;
+    the frame's per-object hit counts and the capacity they give.
 
 Prints one JSON line.
 
@@ -20,23 +23,29 @@ from supnerf_amd import driver, ops, scene, synthetic, utils
 
 
 def render_pair(model, dev, poses, wlh, sc0, tc0, K, pixels, H, W, S, reps):
-    """forward + backward of render_scene, default route and fused, in turn; the largest distance between their outputs."""
+    """forward + backward of render_scene, default route, fused and compact, in turn; the largest distance between their outputs."""
     Nb = poses.shape[0]
     jitter = torch.rand(pixels.shape[0] * Nb, S, generator=torch.Generator().manual_seed(2)).to(dev)
     sc, tc = sc0.to(dev).requires_grad_(), tc0.to(dev).requires_grad_()
     p = poses.to(dev).requires_grad_()
 
-    def run(fused):
+    def run(fused, compact=False):
         def fn():
-            rgb = scene.render_scene(model, dev, p, wlh, sc, tc, K, pixels, H, W, S, jitter=jitter, fused=fused)[0]
+            rgb = scene.render_scene(model, dev, p, wlh, sc, tc, K, pixels, H, W, S, jitter=jitter, fused=fused, compact=compact)[0]
             torch.autograd.grad(((rgb - 0.5) ** 2).mean(), (p, sc, tc))
         return fn
-    t_default, t_fused = in_turn([run(False), run(True)], reps)
+    t_default, t_fused, t_compact = in_turn([run(False), run(True), run(True, True)], reps)
+    info = {}
     with torch.no_grad():
         a = scene.render_scene(model, dev, p, wlh, sc, tc, K, pixels, H, W, S, jitter=jitter)
         b = scene.render_scene(model, dev, p, wlh, sc, tc, K, pixels, H, W, S, jitter=jitter, fused=True)
-    return {"pixels": int(pixels.shape[0]), "objects": int(Nb), "S": S, "default_ms": t_default, "fused_ms": t_fused,
-            "default_over_fused": round(t_default / t_fused, 3), "max_output_distance": max(float((x - y).abs().max()) for x, y in zip(a, b))}
+        c = scene.render_scene(model, dev, p, wlh, sc, tc, K, pixels, H, W, S, jitter=jitter, fused=True, compact=True, info=info)
+    return {"pixels": int(pixels.shape[0]), "objects": int(Nb), "S": S, "default_ms": t_default, "fused_ms": t_fused, "compact_ms": t_compact,
+            "default_over_fused": round(t_default / t_fused, 3), "fused_over_compact": round(t_fused / t_compact, 3),
+            "max_output_distance": max(float((x - y).abs().max()) for x, y in zip(a, b)),
+            "max_compact_distance": max(float((x - y).abs().max()) for x, y in zip(c, b)),
+            "hits_per_object": info["count"].tolist(), "capacity": info["capacity"],
+            "decoder_points": {"fused": int(pixels.shape[0]) * int(Nb) * S, "compact": info["capacity"] * int(Nb) * S}}
 
 
 def fixture_row(model, reps, dev):
@@ -79,13 +88,17 @@ def frame_rows(model, a, dev):
 
     jit = torch.rand(6, Nr * Nb, S, device=dev)       # (the default draw is a CPU generator's: host time that grows with the iterations)
 
-    def fit(T):
+    fit_info = {}
+
+    def fit(T, compact=False):
         def fn():
             hp["optimize"]["num_opts"] = T
-            driver.optimize_scene(model, dev, frame, hp, sc0, tc0, jitter=jit[:T], pixels=pixels)
+            driver.optimize_scene(model, dev, frame, hp, sc0, tc0, jitter=jit[:T], pixels=pixels, compact=compact, info=fit_info if compact else None)
         return fn
-    t2, t6 = in_turn([fit(2), fit(6)], max(1, a.reps // 2))
-    return render, launches, hit_share, {"pixels": Nr, "objects": Nb, "S": S, "iteration_ms": round((t6 - t2) / 4, 4), "run_2_ms": t2, "run_6_ms": t6}
+    t2, t6, c2, c6 = in_turn([fit(2), fit(6), fit(2, True), fit(6, True)], max(1, a.reps // 2))
+    return render, launches, hit_share, {"pixels": Nr, "objects": Nb, "S": S, "iteration_ms": round((t6 - t2) / 4, 4), "run_2_ms": t2, "run_6_ms": t6,
+                                         "compact_iteration_ms": round((c6 - c2) / 4, 4), "compact_run_2_ms": c2, "compact_run_6_ms": c6,
+                                         "compact_capacity": fit_info["capacity"], "compact_dropped_pairs": int(fit_info["dropped_pairs"])}
 
 
 def main():
