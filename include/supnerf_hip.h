@@ -109,6 +109,21 @@ int snr_pack_weights(const float* const* tensors, int n_tensors, int shape_block
  *                  used).  Needs relu_masks; both precisions.  Together with `layer_grads` of snr_decoder_bwd and the encodings of
  *                  snr_pe_points they are the X operands of the weight-gradient products dW_l = G_l^T X_l of snr_weight_grad (the weight
  *                  half of the backward of src/trainer_unified_nuscenes.py:334).
+ * Input range (measured on the MI355X, tests/test_decoder_range_gpu.py; both precisions, every kernel of this section and the
+ * density-only ones):
+ *   1. Coordinates of any finite size are encoded to fp32 accuracy: angles 2^f x up to 8192 by the kernels' own sin / cos (9.2e-8 of
+ *      float64), beyond by the library routine.  SNR_BF16X3 additionally clamps activations to +-65504 (they saturate, finite) and
+ *      carries what is smaller than 2^-3 with an absolute 2^-24 instead of 22 relative bits: fp16 subnormal pieces are kept, and a
+ *      decoder whose activations or weights are 2^-16 of the usual scale comes out 5e-5 .. 1.3e-4 off (finite).
+ *   2. A NaN or an infinity in xyz, viewdir or latent is NOT propagated the way torch.relu propagates it.  The ReLU is a v_med3 (fmaxf in
+ *      the fused exact-fp32 forward), which returns the smaller of the other two operands for a NaN: every NaN pre-activation becomes 0 at
+ *      the first ReLU behind the poison, and the point returns FINITE values -- those of the decoder with that layer's output forced to
+ *      0: encoding_xyz's for a coordinate (sigmas and rgbs both wrong), encoding_viewdir's for a direction (sigmas exact, rgbs wrong), the
+ *      next shape / texture layer's for a latent term (every point of that object).  The reference returns NaN there.  Both precisions
+ *      return the same values, so comparing them does not reveal the poison: callers that may hold diverged poses or codes check their
+ *      inputs themselves.
+ *   3. Whatever a poisoned point returns, it changes nothing else: the outputs, ReLU bits, activations and gradients of every other
+ *      point, and the d_latent rows of every other object, are bit-identical to those of the clean launch; no call fails.
  * ---------------------------------------------------------------------------------- */
 size_t snr_mask_bytes(int64_t n_points, int shape_blocks, int texture_blocks);
 int snr_decoder_fwd(const float* xyz, const float* viewdir, const float* latent, const float* packed,
@@ -138,6 +153,10 @@ int snr_decoder_bwd(const float* xyz, const float* viewdir, const float* latent,
  *                    (sym flip, kitti2nusc, shapenet_obj_cood: src/utils.py:475-495)
  *   z_scale        : (B,) metric scale for SNR_METRIC_Z (family B: obj_diag/2), else unused
  *   rgb (N,3), depth (N), acc_trans (N) outputs; sigmas (P) / rgbs (P,3) optional per-point outputs
+ * Input range: as for the decoder on points (above).  A NaN in a ray's origin reaches every sample of that ray and is erased at
+ * encoding_xyz's ReLU: the ray renders FINITE rgb, depth and acc_trans -- those of a ray whose samples all decode with that layer's
+ * output 0 -- where the reference returns NaN; every other ray of the launch is bit-identical to the clean launch (measured, SNR_Z_SHARED,
+ * both precisions).
  * ---------------------------------------------------------------------------------- */
 typedef struct snr_render_args {
     const float* rays_o;

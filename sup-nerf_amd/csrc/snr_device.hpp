@@ -85,8 +85,11 @@ __device__ __forceinline__ float wave_suffix_sum(float v, int lane) {
 // ------------------------------------------------------------------ positional-encoding sin / cos
 // sin and cos of one angle for the encodings (|angle| <= 512 * |x| with x an object-normalised coordinate): Cody-Waite
 // reduction by pi/2 in three fused steps, cephes minimax polynomials on [-pi/4, pi/4], quadrant fix-up -- ~25 VALU ops
-// against ~100 of the library sincosf (whose large-argument path is never needed here).  Measured against float64 over
-// |angle| <= 1024: max abs error 9.2e-8 (the correctly rounded fp32 result: 6.4e-8).  Beyond 8192 the library routine runs.
+// against ~100 of the library sincosf (whose large-argument path is never needed here).  Against float64 over the whole fast
+// branch, |angle| <= 8192 (every octave, every multiple of pi/2 and its neighbours, the seam itself): max abs error 9.2e-8 (the
+// correctly rounded fp32 result: 6.4e-8) -- a numpy restatement on the CPU (tests/test_split_restatement_cpu.py) and, on the device,
+// every call site forward and backward on coordinates up to 64 and 1e4 (tests/test_decoder_range_gpu.py).  Beyond 8192, and for a NaN
+// or an infinity, the library routine runs (NaN out); pe_sincos2 then sends BOTH angles of its pair through this scalar function.
 __device__ __forceinline__ void pe_sincos(float a, float* sn, float* cs) {
     if (__builtin_expect(!(fabsf(a) <= 8192.f), 0)) { sincosf(a, sn, cs); return; }
     const float k = rintf(a * 0.636619772367581343f);
