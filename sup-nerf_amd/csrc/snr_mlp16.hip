@@ -77,24 +77,25 @@ __device__ __forceinline__ void acc_from_bias(f32x4 (&acc)[16], const float* bia
 // base + 0 .. 7 of the stream.  `pre` (uniform; enc_viewdir): the layer also has a chunk of explicit operand tiles xe (the direction
 // features) -- chunk 8 of its stream, consumed FIRST, so that the last MFMA step of every layer is the same deposit into accP (with the
 // extra chunk behind the eight, the merge of the two ends of the layer cost 48 spilled registers).  On entry the layer's first chunk
-// (the direction chunk if `pre`) is in the current buffer; at its last chunk the layer requests `next_first` (next_rows rows; 0 = the
-// stream ends).  On return accP holds this layer's sums (bias included, no activation yet).
+// (the direction chunk if `pre`) is in the current buffer and its first fragment pair is requested into (a0, a1); at its last chunk the
+// layer requests `next_first` (next_rows rows; 0 = the stream ends) and, with the rendezvous taken inside the chunk's last MFMA group
+// (RingTurn), that chunk's first fragment pair: the pair is carried from chunk to chunk and from layer to layer.  Only the direction
+// chunk keeps the rendezvous behind its MFMAs.  On return accP holds this layer's sums (bias included, no activation yet).
 template <int NT, int WAVES, bool LATLDS, bool MASKS>
 __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, float* lds, const float* bias, const Epi& c, int g, const Dma16& dm,
                                                const float* base, bool pre, const f32x4 (&xe)[2], const float* next_first, int next_rows,
-                                               uint32_t (&mw)[4]) {
+                                               uint32_t (&mw)[4], f32x4& a0, f32x4& a1) {
     f32x4 accC[16];
-    f32x4 a0, a1;
     constexpr int rows_mid = NT * 16;
     constexpr int chunk_floats = rows_mid * KC;
     if (pre) {
         chunk_dma16<WAVES>(dm, base, lds + (ring.cur ^ 1) * WBUF16, lds, rows_mid);
         const float* wb = lds + ring.cur * WBUF16;
-        first_pair(a0, a1, wb + ring.aoff[0]);
         acc_from_bias<NT>(accC, bias, g);
         tile_mma<NT, false>(accC, accP, xe[0], wb + ring.aoff[0], a0, a1, wb + ring.aoff[1]);
         tile_mma<NT, false>(accC, accP, xe[1], wb + ring.aoff[1], a0, a1, nullptr);
         ring_turn(ring);
+        first_pair(a0, a1, lds + ring.cur * WBUF16 + ring.aoff[0]);
     } else {
         acc_from_bias<NT>(accC, bias, g);
     }
@@ -115,7 +116,9 @@ __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, 
         const int rows = (ch < 7) ? rows_mid : next_rows;
         float* const dst = lds + (ring.cur ^ 1) * WBUF16;
         const float* wb = lds + ring.cur * WBUF16;
-        first_pair(a0, a1, wb + ring.aoff[0]);
+        // the next chunk's first fragment pair, requested behind the early rendezvous.  The 256-row layers always have a successor in the
+        // full forward; in the density-only modes enc_shape's last chunk requests a pair nobody uses from a buffer nobody writes again.
+        const float* const wn = (ch < 7 || NT == 16) ? dst + ring.aoff[0] : nullptr;
         // first tile of the chunk (T = 2 ch) on xa; between its groups: the next chunk's DMA pieces and tile 2 ch + 1's operand
         tile_mma<NT, false>(accC, accP, xa, wb + ring.aoff[0], a0, a1, wb + ring.aoff[1], [&](int gi) {
             if (gi == 0) e = epi_load<LATLDS>(c, 2 * ch + 1, g);
@@ -127,15 +130,15 @@ __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, 
         if (ch & 1) { mw[ch >> 1] = m16; m16 = 0u; }
         // second tile (T = 2 ch + 1) on xb; between its groups: tile 2 ch + 2's operand (the next chunk's first tile)
         if (ch == 7) {
-            tile_mma<NT, true>(accC, accP, xb, wb + ring.aoff[1], a0, a1, nullptr);
+            tile_mma<NT, true>(accC, accP, xb, wb + ring.aoff[1], a0, a1, wn, NoBetween(), RingTurn());
         } else {
-            tile_mma<NT, false>(accC, accP, xb, wb + ring.aoff[1], a0, a1, nullptr, [&](int gi) {
+            tile_mma<NT, false>(accC, accP, xb, wb + ring.aoff[1], a0, a1, wn, [&](int gi) {
                 if (gi == 0) e = epi_load<LATLDS>(c, 2 * ch + 2, g);
 #pragma unroll
                 for (int k = (gi * 4) / NG; k < ((gi + 1) * 4) / NG; ++k) epi_value<MASKS>(accP[2 * ch + 2], xa, c, e, 3 - k, m16);
-            });
+            }, RingTurn());
         }
-        ring_turn(ring);
+        ring.cur ^= 1;
     }
 }
 
@@ -315,9 +318,9 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     SNR16_STAMP(1);
     // ---- enc_xyz: 64 -> 256 from explicit operand tiles (two chunks)
     f32x4 accP[16];
+    f32x4 a0, a1;                    // the fragment pair in flight: the first of the chunk about to be consumed
     {
         f32x4 accC[16];
-        f32x4 a0, a1;
         acc_from_bias<16>(accC, bias, g);
 #pragma unroll
         for (int ch = 0; ch < 2; ++ch) {
@@ -329,6 +332,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
             else tile_mma<16, false>(accC, accP, xin[2 * ch + 1], wb + ring.aoff[1], a0, a1, nullptr);
             ring_turn(ring);
         }
+        first_pair(a0, a1, lds + ring.cur * WBUF16 + ring.aoff[0]);       // layer 1's: from here on the pair is carried (layer_from_acc)
     }
 
     SNR16_STAMP(2);
@@ -373,7 +377,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
         }
         const bool end = DENS && li == li_stop;
         layer_from_acc<16, WAVES, LATLDS, MASKS>(accP, ring, lds, bias + li * 256, c, g, dm, layer_base(li), !DENS && li == li_view, xd,
-                                                       end ? nullptr : layer_first(li + 1), end ? 0 : (li == li_last) ? 128 : 256, mw);
+                                                       end ? nullptr : layer_first(li + 1), end ? 0 : (li == li_last) ? 128 : 256, mw, a0, a1);
         after_layer_input(lp);
     }
     if constexpr (DENS) {
@@ -400,7 +404,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
     SNR16_STAMP(4);
     {   // rgb.0: 256 -> 128
         const Epi c = epi_of(li_last);
-        layer_from_acc<8, WAVES, LATLDS, MASKS>(accP, ring, lds, bias + (li_last + 1) * 256, c, g, dm, layer_base(li_last + 1), false, xd, nullptr, 0, mw);
+        layer_from_acc<8, WAVES, LATLDS, MASKS>(accP, ring, lds, bias + (li_last + 1) * 256, c, g, dm, layer_base(li_last + 1), false, xd, nullptr, 0, mw, a0, a1);
         after_layer_input(li_last);
     }
 
@@ -445,7 +449,7 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
         if (io.rgbs) { io.rgbs[gp * 3] = o_r; io.rgbs[gp * 3 + 1] = o_g; io.rgbs[gp * 3 + 2] = o_b; }
     }
     if constexpr (MODE == 1) {
-        float* comp = lds + lo.comp;             // (WAVES = 4: over ring buffer 0 -- every wave is past the last chunk's barrier)
+        float* comp = lds + lo.comp;             // (WAVES = 4: over ring buffer 0 -- every wave is past the last chunk's barrier, reached with its last ring read returned: RingTurn)
         if (g == 0) {
             float* c = comp + (wave * 16 + n) * COMP_STRIDE;
             c[0] = o_sigma; c[1] = o_r; c[2] = o_g; c[3] = o_b; c[4] = zc;

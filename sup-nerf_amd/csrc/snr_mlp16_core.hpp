@@ -33,7 +33,7 @@ inline Lds16 make_lds16(int waves, int n_mfma_layers, int n_lat) {
 // per-lane VGPR offset (lane x 16 + 4096) is made once per kernel and the piece is selected by the immediate, which moves the global and
 // the LDS address together (-4096 .. +3072).  The builtin form computes a 64-bit per-lane address on the VALU for every piece -- and on
 // this chip VALU instructions compete with the fp32 MFMAs for the ALUs.  EVERY LDS-DMA of the kernel takes this form: the compiler must
-// never have a use of M0 of its own (it would assume M0 survives an asm statement).  Completion is counted by hand (ring_turn: vmcnt(0)).
+// never have a use of M0 of its own (it would assume M0 survives an asm statement).  Completion is counted by hand (ring_turn, RingTurn: vmcnt(0)).
 template <int K>
 __device__ __forceinline__ void dma_piece_imm(unsigned voff, const void* sbase, unsigned m0v) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" :: "v"(voff), "s"(sbase), "s"(m0v), "n"(1024 * K - 4096) : "memory");
@@ -109,13 +109,16 @@ struct Ring16 {
 // point only that pair is outstanding, requested a whole group (>= 256 cycles) earlier -- and the next pair (the next TILE's first pair from
 // `wnext` at the end) is requested before the group's eight MFMAs.  Left to the compiler, the request follows the MFMAs and the wait
 // (lgkmcnt(0), not a counted one) sits right behind the request: an LDS round trip exposed per group in both waves of the SIMD at once.
+// `turn` (RingTurn for the second tile of a chunk whose successor is already on its way) runs in the LAST group between the wait and the
+// `wnext` request: that is where the ring's rendezvous belongs, see RingTurn.
 struct NoBetween { __device__ __forceinline__ void operator()(int) const {} };
+struct NoTurn { __device__ __forceinline__ void operator()() const {} };
 // FLAGS: bit 0 (LAST): the finished sums go to accD; bit 1 (ZERO): the sums start from zero -- every tile's first MFMA takes the constant 0 as
 // its C operand, no zeroed register set.
 constexpr int TM_LAST = 1, TM_ZERO = 2;
-template <int NT, int FLAGS, class Between = NoBetween, int NA = 16, int ND = 16>
+template <int NT, int FLAGS, class Between = NoBetween, class Turn = NoTurn, int NA = 16, int ND = 16>
 __device__ __forceinline__ void tile_mma(f32x4 (&accC)[NA], f32x4 (&accD)[ND], const f32x4& x, const float* wrow /* chunk + aoff[dT] */,
-                                         f32x4& a0, f32x4& a1, const float* wnext, Between&& between = NoBetween()) {
+                                         f32x4& a0, f32x4& a1, const float* wnext, Between&& between = NoBetween(), Turn&& turn = Turn()) {
     constexpr bool LAST = FLAGS & TM_LAST, ZERO = FLAGS & TM_ZERO;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -125,9 +128,12 @@ __device__ __forceinline__ void tile_mma(f32x4 (&accC)[NA], f32x4 (&accD)[ND], c
         if (t + 2 < NT) {
             n0 = *reinterpret_cast<const f32x4*>(wrow + (t + 2) * 16 * KC);
             n1 = *reinterpret_cast<const f32x4*>(wrow + (t + 3) * 16 * KC);
-        } else if (wnext) {
-            n0 = *reinterpret_cast<const f32x4*>(wnext);
-            n1 = *reinterpret_cast<const f32x4*>(wnext + 16 * KC);
+        } else {
+            turn();
+            if (wnext) {
+                n0 = *reinterpret_cast<const f32x4*>(wnext);
+                n1 = *reinterpret_cast<const f32x4*>(wnext + 16 * KC);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -158,6 +164,26 @@ __device__ __forceinline__ void ring_turn(Ring16& p) {
     __syncthreads();
     p.cur ^= 1;
 }
+
+// The same rendezvous taken EARLY, as tile_mma's `turn` of the chunk's second tile: at the top of the chunk's last MFMA group, behind that
+// group's lgkmcnt(0) and ahead of the request of the NEXT chunk's first fragment pair (tile_mma's `wnext` = the other buffer + aoff[0]), so
+// the group's eight MFMAs cover the LDS round trip of that pair instead of every wave sitting through it behind the barrier.  The caller
+// flips ring.cur behind the tile and does NOT call first_pair for the next chunk: (a0, a1) arrive carried.
+//   * The next chunk is complete behind the barrier: a wave's DMA pieces of it went out between the groups of the chunk's FIRST tile (the
+//     last of them 7 groups = 56 MFMAs of this wave earlier in a 256-row layer, 3 groups in rgb.0), its vmcnt(0) here covers them, and the barrier collects every wave's.
+//   * Nobody reads the old buffer behind the barrier: a wave arrives with lgkmcnt(0) -- the last group's own pair, the last read it will
+//     ever make of that buffer, is in registers -- so when the barrier opens every wave's reads of the old buffer have returned.  The DMA
+//     that overwrites it (the chunk after next) is issued between the groups of the next chunk's first tile, behind this barrier in every
+//     wave's program order: as with ring_turn.
+//   * The same argument covers what is laid over the ring: whatever a wave writes there behind the stream's last rendezvous (the
+//     forward's composite scratch over buffer 0) is written behind a barrier that every wave reached with no ring read outstanding, and
+//     the stream's last chunk requests nothing (wnext = nullptr).
+struct RingTurn {
+    __device__ __forceinline__ void operator()() const {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+};
 
 
 }  // namespace snr

@@ -1,5 +1,8 @@
 """A/B timing of library variants (tools/build_variant.sh): forward, forward with ReLU bits and backward of the fused render at
-4096 x 64, device-event times.  usage: python tools/ab_time.py NAME [NAME ...]  -- min and median over interleaved rounds   (NAME 'shipped' = the in-tree library)"""
+4096 x 64, device-event times.  usage: python tools/ab_time.py NAME [NAME ...]  -- min and median over interleaved rounds   (NAME 'shipped' = the in-tree library)
+Environment: SNR_AB_ROUNDS (5) rounds of SNR_AB_N (20) launches per kernel and variant, after SNR_AB_WARM (0) forwards of every variant (the chip
+takes seconds to settle on its clock: without them the first rounds of every variant run 0.5 % slower); SNR_AB_PRECISION 1 = split-bf16 (default), 0 = exact fp32.
+Every round is printed per variant and kernel with mean, standard deviation and range."""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -81,9 +84,12 @@ def setup(name):
 names = list(dict.fromkeys(sys.argv[1:]))
 for n in names: libs[n] = setup(n)
 res = {n: [[], [], []] for n in names}
+for _ in range(int(os.environ.get("SNR_AB_WARM", "0"))):
+    for n in names: libs[n][0]()
+torch.cuda.synchronize()
 for rnd in range(int(os.environ.get("SNR_AB_ROUNDS", "5"))):          # interleaved rounds: clock drift hits every variant alike
     for n in names:
-        for k in range(3): res[n][k].append(timed(libs[n][k], 20))
+        for k in range(3): res[n][k].append(timed(libs[n][k], int(os.environ.get("SNR_AB_N", "20"))))
 for n in names[1:]:          # backward outputs against the first name's
     ref, got = libs[names[0]][5], libs[n][5]
     print(n, "backward vs", names[0], " ".join(f"{k} {float((g_ - r_).abs().max() / r_.abs().max()):.1e}" for k, r_, g_ in zip(("d_latent", "d_rays_o", "d_rays_d"), ref, got)), flush=True)
@@ -91,3 +97,8 @@ for n in names:
     r = res[n]
     print(f"{n:14s} fwd {min(r[0]):.4f} (med {sorted(r[0])[len(r[0]) // 2]:.4f})   fwd+bits {min(r[1]):.4f} (med {sorted(r[1])[len(r[1]) // 2]:.4f})   "
           f"bwd {min(r[2]):.4f} (med {sorted(r[2])[len(r[2]) // 2]:.4f}) ms   [{libs[n][3]}]", flush=True)
+import statistics
+for n in names:
+    for k, what in enumerate(("fwd", "fwd+bits", "bwd")):
+        r = res[n][k]
+        print(f"rounds {n:14s} {what:9s} " + " ".join(f"{v:.4f}" for v in r) + f"   mean {statistics.mean(r):.4f} sd {statistics.pstdev(r):.4f} range {max(r) - min(r):.4f}", flush=True)
