@@ -81,20 +81,54 @@ __device__ __forceinline__ void acc_from_bias(f32x4 (&acc)[16], const float* bia
 // layer requests `next_first` (next_rows rows; 0 = the stream ends) and, with the rendezvous taken inside the chunk's last MFMA group
 // (RingTurn), that chunk's first fragment pair: the pair is carried from chunk to chunk and from layer to layer.  Only the direction
 // chunk keeps the rendezvous behind its MFMAs.  On return accP holds this layer's sums (bias included, no activation yet).
-template <int NT, int WAVES, bool LATLDS, bool MASKS>
+// RAY (the fused render's instantiations) and `ray` (uniform: the workgroup is one ray): the direction chunk is summed once per workgroup,
+// see below; the layer BEFORE that one passes next_off = own_rows16 so that the pair it hands on is the wave's own.
+template <int NT, int WAVES, bool LATLDS, bool MASKS, bool RAY = false>
 __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, float* lds, const float* bias, const Epi& c, int g, const Dma16& dm,
                                                const float* base, bool pre, const f32x4 (&xe)[2], const float* next_first, int next_rows,
-                                               uint32_t (&mw)[4], f32x4& a0, f32x4& a1) {
+                                               uint32_t (&mw)[4], f32x4& a0, f32x4& a1, bool ray = false, int next_off = 0) {
     f32x4 accC[16];
     constexpr int rows_mid = NT * 16;
     constexpr int chunk_floats = rows_mid * KC;
     if (pre) {
         chunk_dma16<WAVES>(dm, base, lds + (ring.cur ^ 1) * WBUF16, lds, rows_mid);
-        const float* wb = lds + ring.cur * WBUF16;
-        acc_from_bias<NT>(accC, bias, g);
-        tile_mma<NT, false>(accC, accP, xe[0], wb + ring.aoff[0], a0, a1, wb + ring.aoff[1]);
-        tile_mma<NT, false>(accC, accP, xe[1], wb + ring.aoff[1], a0, a1, nullptr);
+        const bool once = RAY && NT == 16 && ray;
+        if (once) {
+            // The direction chunk when the workgroup is ONE ray (fused render, S = 16 WAVES): every column of every wave holds the same B
+            // operands xe, so the chunk's 256 sums are the same in all 16 WAVES columns -- computed once, by the workgroup together.  Wave w
+            // takes output tiles NTW w .. NTW w + NTW - 1 (NTW = 16 / WAVES): bias, xe[0]'s four k-steps, xe[1]'s four, the MFMAs the full form
+            // issues for those tiles on the same A fragments (rows 16 NTW w .. of the chunk: own_rows16; the pair carried in is already that
+            // wave's own, the layer before requested it at next_off) in the same order; column 0 (n = 0, one lane per g) writes the tile
+            // back IN PLACE into the layer's bias row, slot 16 t + 4 g: the layout acc_from_bias reads, as a broadcast over n.  Behind the
+            // chunk's rendezvous every wave starts its accumulators from that row and goes on with the 256 features as before.
+            //   * Bit for bit the full form's sums: an MFMA's column n depends on column n of B and C alone; B is the same in all columns
+            //     and C (the bias) is a broadcast over n, so column 0 of the tile IS every column of it -- the same instruction on the same
+            //     operand bits, NaN and infinite directions included.  The chain per output stays bias, xe[0], xe[1], then the eight chunks.
+            //   * Before the barrier a wave reads and writes only ITS tiles' slots of the row; the writes are complete (lgkmcnt(0)) when it
+            //     arrives, so behind the barrier every wave reads finished sums.  Nobody needs the plain biases again: the row is restaged
+            //     by every workgroup's prologue, and enc_viewdir is consumed once.
+            //   * No LDS, barrier or DMA the full form does not have; the accumulator start is the same 16 ds_read_b128, behind the barrier.
+            constexpr int NTW = 16 / WAVES;
+            const float* wb = lds + ring.cur * WBUF16 + own_rows16<WAVES>(dm);
+            float* own = const_cast<float*>(bias) + dm.wave * (NTW * 16) + 4 * g;
+            f32x4 accS[NTW];
+#pragma unroll
+            for (int t = 0; t < NTW; ++t) accS[t] = *reinterpret_cast<const f32x4*>(own + 16 * t);
+            tile_mma<NTW, 0, NoBetween, NoTurn, NTW>(accS, accP, xe[0], wb + ring.aoff[0], a0, a1, wb + ring.aoff[1]);
+            tile_mma<NTW, 0, NoBetween, NoTurn, NTW>(accS, accP, xe[1], wb + ring.aoff[1], a0, a1, nullptr);
+            if ((threadIdx.x & 15) == 0) {
+#pragma unroll
+                for (int t = 0; t < NTW; ++t) *reinterpret_cast<f32x4*>(own + 16 * t) = accS[t];
+            }
+            SNR16_WAIT_LDS();
+        } else {
+            const float* wb = lds + ring.cur * WBUF16;
+            acc_from_bias<NT>(accC, bias, g);
+            tile_mma<NT, false>(accC, accP, xe[0], wb + ring.aoff[0], a0, a1, wb + ring.aoff[1]);
+            tile_mma<NT, false>(accC, accP, xe[1], wb + ring.aoff[1], a0, a1, nullptr);
+        }
         ring_turn(ring);
+        if (once) acc_from_bias<NT>(accC, bias, g);
         first_pair(a0, a1, lds + ring.cur * WBUF16 + ring.aoff[0]);
     } else {
         acc_from_bias<NT>(accC, bias, g);
@@ -118,7 +152,7 @@ __device__ __forceinline__ void layer_from_acc(f32x4 (&accP)[16], Ring16& ring, 
         const float* wb = lds + ring.cur * WBUF16;
         // the next chunk's first fragment pair, requested behind the early rendezvous.  The 256-row layers always have a successor in the
         // full forward; in the density-only modes enc_shape's last chunk requests a pair nobody uses from a buffer nobody writes again.
-        const float* const wn = (ch < 7 || NT == 16) ? dst + ring.aoff[0] : nullptr;
+        const float* const wn = (ch < 7 || NT == 16) ? dst + ring.aoff[0] + ((RAY && ch == 7) ? next_off : 0) : nullptr;
         // first tile of the chunk (T = 2 ch) on xa; between its groups: the next chunk's DMA pieces and tile 2 ch + 1's operand
         tile_mma<NT, false>(accC, accP, xa, wb + ring.aoff[0], a0, a1, wb + ring.aoff[1], [&](int gi) {
             if (gi == 0) e = epi_load<LATLDS>(c, 2 * ch + 1, g);
@@ -354,6 +388,9 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
         if (MASKS && lp != li_encshape && tile_live) store_masks16x4(io.masks + (tile32 * n_relu + relu_slot(lp, sb)) * 64, mw, wave, lane);
     };
     const int li_stop = DENS ? li_encshape : li_last;       // density only: the stream ends with enc_shape
+    // enc_viewdir's direction chunk: once per workgroup when the workgroup is one ray of a fused render (uniform), else per point
+    bool one_ray = false;
+    if constexpr (MODE == 1) one_ray = gm.S == WGP;
 #pragma unroll 1
     for (int li = 1; li <= li_stop; ++li) {
         const int lp = li - 1;
@@ -376,6 +413,10 @@ decoder_fwd16_kernel(DecoderIO io, Layout L, Lds16 lo, const float* __restrict__
             o_sigma = pre > 20.f ? pre : log1pf(expf(pre));
         }
         const bool end = DENS && li == li_stop;
+        if constexpr (MODE == 1)
+            layer_from_acc<16, WAVES, LATLDS, MASKS, true>(accP, ring, lds, bias + li * 256, c, g, dm, layer_base(li), li == li_view, xd, layer_first(li + 1),
+                                                                 (li == li_last) ? 128 : 256, mw, a0, a1, one_ray, (one_ray && li + 1 == li_view) ? own_rows16<WAVES>(dm) : 0);
+        else
         layer_from_acc<16, WAVES, LATLDS, MASKS>(accP, ring, lds, bias + li * 256, c, g, dm, layer_base(li), !DENS && li == li_view, xd,
                                                        end ? nullptr : layer_first(li + 1), end ? 0 : (li == li_last) ? 128 : 256, mw, a0, a1);
         after_layer_input(lp);

@@ -96,6 +96,11 @@ __device__ __forceinline__ PointId point_id(const RayGeom& g, long long tile_wg,
     return p;
 }
 
+// A chunk whose operand tiles are the same for every point of the workgroup (the forward's direction chunk when the workgroup is one ray) is
+// summed once, wave w taking the 16 / WAVES output tiles from this row of the chunk on (float offset; snr_mlp16.hip: layer_from_acc).
+template <int WAVES>
+__device__ __forceinline__ int own_rows16(const Dma16& d) { return d.wave * ((16 / WAVES) * 16 * KC); }
+
 struct Ring16 {
     int cur;             // LDS buffer holding the chunk about to be consumed
     int aoff[2];         // this lane's float offset of the 16-byte slot (4 dT + kg) of row m in a chunk, swizzle applied (dT = 0, 1)
