@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 18
+#define SNR_ABI_VERSION 19
 
 enum {
     SNR_OK = 0,
@@ -710,6 +710,34 @@ int snr_raster_resolve(const uint64_t* keys, const float* screen, const int32_t*
 int snr_raster_interpolate(const int32_t* face, const float* weights, const int32_t* faces, const int64_t* vert_offset,
                            const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, const float* attributes,
                            int n_channels, int64_t n_pixels, float background, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Several views of one instance share one shape and one texture code (src/optimizer_nuscenes.py:796-1277): V rendered views, I <= V code
+ * rows, the views of an instance contiguous (instance-major).
+ *
+ * snr_view_pixels: one iteration's random pixels of every view's native-resolution roi (render_rays, src/utils.py:380-432).  The V crops
+ *   are concatenated row-major: view v's h_v x w_v pixels start at pixel crop_offset[v] of img (sum h w, 3) / occ (sum h w), which hold
+ *   crop_offset[V] pixels (a pick is also refused where it leaves its view's slice crop_offset[v] .. crop_offset[v+1]);
+ *   roi (V,4) int32 = x0 y0 x1 y1 with w = x1 - x0, h = y1 - y0; Kvec (V,4) = fx fy cx cy; picks (V,n) int32 = index y w + x into the
+ *   view's crop.  Pick id is pixel x = x0 + id % w, y = y0 + id / w (get_rays' linspace(x0, x1 - 1, w) pixels, exact integers):
+ *   cam_dirs (V,n,3) = ((x - cx) / fx, (y - cy) / fy, 1) with a correctly rounded fp32 division, rgb_tgt (V,n,3) and occ_out (V,n) gathered
+ *   from the crop.  A pick outside [0, h w) (-1 by convention) is a PADDING ray: nothing is read, cam_dirs = (0,0,1), rgb_tgt = 0,
+ *   occ_out = 0 -- which snr_loss_tail_* weighs with exactly 0 in every numerator and denominator, so a view with fewer than n pixels
+ *   rides in the rectangular launch.  A thread per ray, striding beyond 262144 rays.
+ * snr_instance_rows_fwd: src (I,C) -> dst (V,C), row v = the row of v's instance.  view_offset (I+1) int64 in DEVICE memory:
+ *   instance i owns the views view_offset[i] .. view_offset[i+1]-1.  view_offset_host [nullable]: the same I+1 numbers in HOST memory,
+ *   checked before the launch.
+ * snr_instance_rows_bwd: d_dst (V,C) -> d_src (I,C): d_src[i,c] = the sum over the instance's views in ASCENDING order with plain fp32
+ *   adds, starting from the first term; one thread per (i,c), no atomics: the same bits every run.
+ * Any C >= 1.  SNR_E_ARG: a null pointer, I < 1, V < I, or host offsets that do not start at 0, end at V and ascend strictly (an
+ * instance without a view).
+ * ---------------------------------------------------------------------------------- */
+int snr_view_pixels(const float* img, const float* occ, const int64_t* crop_offset, const int32_t* roi, const float* Kvec, const int32_t* picks,
+                    int64_t n_views, int64_t n, float* cam_dirs, float* rgb_tgt, float* occ_out, void* stream);
+int snr_instance_rows_fwd(const float* src, const int64_t* view_offset, const int64_t* view_offset_host, int64_t n_instances, int64_t n_views,
+                          int64_t n_cols, float* dst, void* stream);
+int snr_instance_rows_bwd(const float* d_dst, const int64_t* view_offset, const int64_t* view_offset_host, int64_t n_instances, int64_t n_views,
+                          int64_t n_cols, float* d_src, void* stream);
 
 #ifdef __cplusplus
 }

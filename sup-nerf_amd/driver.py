@@ -13,6 +13,12 @@ Objects are independent, so multi-GPU = one process per GPU, each taking a conti
 dropped) with no communication inside the loop; one ``all_gather`` of the per-object metric rows at the end (RCCL
 when the backend is nccl, gloo on CPU in the tests).
 
+Several views of one instance (``optimize_instances``; ``optimize_objs_multi_anns_w_pose`` :1050-1277 and ``optimize_objs_multi_anns``
+:796-1048): the I instances' codes are (I,256), their V >= I views lie instance-major and every view is one "object" of the same fused
+launches.  ``ops.InstanceRows`` copies an instance's latent row to its views and, backwards, adds its views' gradients in ascending view
+order with plain fp32 adds (no atomics: the same bits every run).  With random sampling every iteration picks ``n_rays`` pixels of each
+view's native roi (``ops.view_pixels``); a view with fewer pixels is padded with rays of occupancy 0, which weigh exactly 0 in its loss.
+
 No dataset is available offline: objects come from ``synthetic.py``.  The rotation parametrisation
 (pytorch3d ``axis_angle_to_matrix`` / ``matrix_to_axis_angle`` in the reference, un-pinned and not installed) is
 restated here via Rodrigues' formula; parity for it is pinned only by self-consistency tests.
@@ -329,11 +335,12 @@ def _lidar_pixels(ob, rs, n_lidar):
     return xs[pick], ys[pick], None
 
 
-def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=None):
+def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=None, grid=True):
     """Per-object constants of the loop, built once on the host and moved to the device: perturbed start pose, ground truth, the pixel
     direction tables [(px-cx)/fx, (py-cy)/fy, 1] of the render grid and of the lidar pixels (every object keeps ITS OWN count: the tables
     are padded to the largest, the metric kernel averages each object's first ``lid_cnt`` entries), measured depths when the objects
-    carry them, resized targets (the reference resizes the same crop again in every iteration, src/utils.py:447-456)."""
+    carry them, resized targets (the reference resizes the same crop again in every iteration, src/utils.py:447-456).  ``grid=False``
+    (a loop that samples native pixels anew every iteration, ``optimize_instances``): no render grid and no resized targets."""
     im_sz = hpams["render_im_sz"]
     rot0, tr0, gtR, gtT, cam, lid, lid_d, tgt, occ = [], [], [], [], [], [], [], [], []
     for ob, seed in zip(objs, seeds):
@@ -350,14 +357,16 @@ def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=Non
         x0, y0, x1, y1 = [int(v) for v in ob["roi"]]
         K = ob["K"]
         cx, cy, fx, fy = K[0, 2], K[1, 2], K[0, 0], K[1, 1]
-        gx, gy = torch.linspace(x0, x1 - 1, im_sz), torch.linspace(y0, y1 - 1, im_sz)
-        px, py = gx[None, :].expand(im_sz, im_sz).reshape(-1), gy[:, None].expand(im_sz, im_sz).reshape(-1)
-        cam.append(torch.stack([(px - cx) / fx, (py - cy) / fy, torch.ones_like(px)], -1))
+        if grid:
+            gx, gy = torch.linspace(x0, x1 - 1, im_sz), torch.linspace(y0, y1 - 1, im_sz)
+            px, py = gx[None, :].expand(im_sz, im_sz).reshape(-1), gy[:, None].expand(im_sz, im_sz).reshape(-1)
+            cam.append(torch.stack([(px - cx) / fx, (py - cy) / fy, torch.ones_like(px)], -1))
         lx, ly = torch.from_numpy(x_vec + x0), torch.from_numpy(y_vec + y0)         # integer pixels, like get_rays_specified
         lid.append(torch.stack([(lx - cx) / fx, (ly - cy) / fy, torch.ones_like(lx, dtype=torch.float32)], -1).float().reshape(-1, 3))
         lid_d.append(None if depth is None else torch.from_numpy(depth))
-        im, mk = U._resize(ob["img"], ob["mask"], im_sz)
-        tgt.append(im.reshape(-1, 3)); occ.append(mk.reshape(-1))
+        if grid:
+            im, mk = U._resize(ob["img"], ob["mask"], im_sz)
+            tgt.append(im.reshape(-1, 3)); occ.append(mk.reshape(-1))
     has_depth = [d is not None for d in lid_d]
     if any(has_depth) and not all(has_depth):
         raise U.SnrError("optimize_objects_batched: either every object of a batch carries lidar_xy / lidar_depth or none does")
@@ -370,9 +379,10 @@ def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=Non
     def pad(v, width):          # (the padding rays are rendered and ignored: a valid direction, depth 0)
         return torch.cat([v, (one_ray if width == 3 else torch.zeros(1)).expand(n_l - v.shape[0], *([3] if width == 3 else []))]) if v.shape[0] < n_l else v
     st = lambda xs_: torch.stack(xs_).to(dev).contiguous()
-    return dict(rot0=torch.cat(rot0).to(dev), tr0=torch.cat(tr0).to(dev), gtR=st(gtR), gtT=st(gtT), cam=st(cam), lid=st([pad(v, 3) for v in lid]),
+    return dict(rot0=torch.cat(rot0).to(dev), tr0=torch.cat(tr0).to(dev), gtR=st(gtR), gtT=st(gtT), cam=st(cam) if grid else None,
+                lid=st([pad(v, 3) for v in lid]),
                 lid_depth=st([pad(d, 1) for d in lid_d]) if all(has_depth) else None, lid_cnt=torch.tensor(cnt, dtype=torch.int32, device=dev),
-                tgt=st(tgt), occ=st(occ), diag=torch.tensor([float(ob["obj_diag"]) for ob in objs], device=dev), n_lidar=n_l)
+                tgt=st(tgt) if grid else None, occ=st(occ) if grid else None, diag=torch.tensor([float(ob["obj_diag"]) for ob in objs], device=dev), n_lidar=n_l)
 
 
 @contextlib.contextmanager
@@ -616,6 +626,226 @@ def optimize_scene(model, device, frame: Dict, hpams: dict, shapecodes0, texture
         warnings.warn(f"optimize_scene: {int(dropped)} hit (pixel, object) pairs beyond the capacity of {capacity} per object were rendered as "
                       "misses; pass a larger capacity or capacity_margin", RuntimeWarning, stacklevel=2)
     return metrics, loss_log, shapecode.detach(), texturecode.detach(), poses
+
+
+# ------------------------------------------------------------------ several views of one instance: shared codes
+def _flatten_instances(instances):
+    """Instance-major list of all views and the (I+1,) offsets of every instance's contiguous views."""
+    if not instances:
+        raise U.SnrError("optimize_instances: no instance")
+    counts = []
+    for i, inst in enumerate(instances):
+        views = inst.get("views") if isinstance(inst, dict) else None
+        if not views:
+            raise U.SnrError(f"optimize_instances: instance {i} has no view ('views' must be a non-empty list)")
+        counts.append(len(views))
+    return [v for inst in instances for v in inst["views"]], U.ops.view_offset_of(counts)
+
+
+def draw_view_picks(views, seeds, num_opts, n_rays):
+    """(num_opts, V, n_rays) int32 pixel picks of ``render_rays`` (src/utils.py:380-432), drawn up front: per view one
+    ``np.random.RandomState(seed)``, per iteration ``permutation(h w)[:n_rays]`` into the view's native roi, -1 where the roi has fewer
+    than ``n_rays`` pixels (the reference's ``n_rays = min(n_all, n_rays)``; a -1 is a padding ray of weight 0)."""
+    picks = np.full((num_opts, len(views), n_rays), -1, dtype=np.int32)
+    for v, (view, seed) in enumerate(zip(views, seeds)):
+        x0, y0, x1, y1 = [int(t) for t in view["roi"]]
+        n_all = (x1 - x0) * (y1 - y0)
+        rs = np.random.RandomState(seed)
+        for it in range(num_opts):
+            ids = rs.permutation(n_all)[:n_rays]
+            picks[it, v, :len(ids)] = ids
+    return torch.from_numpy(picks)
+
+
+def _view_crops(views, dev):
+    """The views' native crops as ``ops.view_pixels`` takes them: concatenated pixels, offsets, rois, intrinsics."""
+    img, occ, off, roi, Kv = [], [], [0], [], []
+    for v, view in enumerate(views):
+        x0, y0, x1, y1 = [int(t) for t in view["roi"]]
+        h, w = y1 - y0, x1 - x0
+        if h < 1 or w < 1 or tuple(view["img"].shape) != (h, w, 3) or view["mask"].numel() != h * w:
+            raise U.SnrError(f"optimize_instances: view {v}: img {tuple(view['img'].shape)} / mask {tuple(view['mask'].shape)} are not the "
+                             f"native {h} x {w} crop of its roi (random sampling reads the unresized crop)")
+        img.append(view["img"].reshape(-1, 3).float()); occ.append(view["mask"].reshape(-1).float())
+        off.append(off[-1] + h * w); roi.append([x0, y0, x1, y1])
+        K = view["K"]
+        Kv.append([float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])])
+    # (K's entries go through python floats and back: float32 -> double -> float32 is exact)
+    return (torch.cat(img).to(dev).contiguous(), torch.cat(occ).to(dev).contiguous(), torch.tensor(off, dtype=torch.int64, device=dev),
+            torch.tensor(roi, dtype=torch.int32, device=dev), torch.tensor(Kv, dtype=torch.float32, device=dev))
+
+
+def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapecodes0, texturecodes0, seeds: Sequence[int], opt_pose=True,
+                       sampling=None, n_rays=None, pose_noise=(0.05, 0.3), n_lidar=64, picks=None, jitter=None, info: Optional[dict] = None):
+    """Fit I instances, each seen in one or more views, with ONE shape code and ONE texture code per instance -- the reference's
+    ``optimize_objs_multi_anns_w_pose`` (``opt_pose=True``, src/optimizer_nuscenes.py:1050-1277: also one object pose per VIEW) and
+    ``optimize_objs_multi_anns`` (``opt_pose=False``, :796-1048: poses fixed at every view's ``cam_pose``) -- as the fused iteration of
+    ``optimize_objects_batched``: all V views of all instances ride in the same ~30 launches.
+
+    ``instances[i]["views"]``: a non-empty list of the dicts ``optimize_object`` consumes (img, mask, cam_pose, obj_diag, K, roi, optional
+    lidar_xy / lidar_depth).  Views are laid out instance-major; ``seeds`` holds one seed per view (start-pose noise and lidar pixels like
+    ``optimize_objects_batched``; picks and jitter by default).  Layout: codes (I,256) -> latent rows (I, n_lat, 256) by one
+    ``LatentLayers`` launch -> ``ops.InstanceRows`` copies every instance's row to its views (V, n_lat, 256); everything after that is per
+    view.  Backward: the gradient of an instance's row is the sum of its views' rows in ascending view order, plain fp32 adds (no atomics:
+    the same bits every run) -- the reference's successive ``loss.backward()`` calls accumulating into ``.grad``.  Every view has its own
+    loss ``loss_rgb + loss_occ_coef loss_occ`` over its own sum of |occ|; one backward of their sum; one AdamW step EVERY iteration (no
+    render-only iterations, no pose table): codes at lr_shape / lr_texture, and with ``opt_pose`` rot_vec / trans_vec (V,3) at lr_pose.
+
+    ``sampling``: "random" (default with ``opt_pose``) = ``render_rays``: every iteration ``n_rays`` (argument, else ``hpams["n_rays"]``)
+    random pixels of each view's NATIVE roi, targets from the unresized crop, by one ``ops.view_pixels`` launch on ``picks[it]``
+    (``picks`` (num_opts, V, n_rays) int32, default ``draw_view_picks``, uploaded once).  A view with fewer pixels than ``n_rays`` is padded
+    with -1 picks: rays with occupancy 0, which weigh exactly 0 in every sum of the loss, so its loss is the loss of its own pixels.
+    "grid" (default without ``opt_pose``) = ``render_rays_v2``: the ``render_im_sz``^2 resized grid, built once.
+    Learning rates are halved every ``lr_half_interval`` with ``opt_pose`` (:1266-1270) and never without (:1039-1040 is commented out).
+    ``jitter`` (num_opts, 2, V, S), default one seeded generator per view.  ``info`` receives ``view_offset`` (I+1,), ``lidar_count`` (V,),
+    ``rays_per_view`` (V,), ``loss`` (num_opts, V); with ``info["record_grads"]`` set also ``code_grads``: per iteration the
+    (shape, texture) code gradients as the optimiser step reads them.
+
+    Returns metrics (V, num_opts, 4) = [psnr, depth_err, rot_err, trans_err] per view, shape codes (I,256), texture codes (I,256), and the
+    camera-in-object poses (V,3,4) of the last iteration.  Not provided: ``sym_aug``, per-view texture residuals (``slack_tex``),
+    fine-tuning the decoder (``opt_model``)."""
+    ops = U.ops
+    dev = torch.device(device)
+    opt = hpams["optimize"]
+    if hpams.get("sym_aug", 0):
+        raise U.SnrError("optimize_instances: sym_aug draws one python coin per view and iteration; it is not provided here")
+    for key in ("slack_tex", "opt_model"):
+        if hpams.get(key, 0) or opt.get(key, 0):
+            raise U.SnrError(f"optimize_instances: the reference's {key} is not provided (codes and poses only, one texture code per instance)")
+    if not U._is_native(model):
+        raise U.SnrError("optimize_instances needs the package's own decoder")
+    views, offsets = _flatten_instances(instances)
+    I, V = len(instances), len(views)
+    S, T = int(hpams["n_samples"]), int(opt["num_opts"])
+    if not ops.fused_supported(S):
+        raise U.SnrError(f"optimize_instances: n_samples = {S} is not a divisor of 128 (the fused render)")
+    if len(seeds) != V:
+        raise U.SnrError(f"optimize_instances: one seed per view expected ({V}), got {len(seeds)}")
+    if shapecodes0.shape != (I, 256) or texturecodes0.shape != (I, 256):
+        raise U.SnrError(f"optimize_instances: shapecodes0 / texturecodes0 must be (I,256) = ({I},256), one row per instance")
+    if sampling is None:
+        sampling = "random" if opt_pose else "grid"
+    if sampling not in ("random", "grid"):
+        raise U.SnrError(f"optimize_instances: sampling is 'random' or 'grid', got {sampling!r}")
+    random_px = sampling == "random"
+    c = _loop_inputs(views, seeds, hpams, pose_noise, n_lidar, dev, grid=not random_px)
+    if random_px:
+        n = int(n_rays if n_rays is not None else hpams.get("n_rays", 0))
+        if n < 1:
+            raise U.SnrError("optimize_instances: random sampling needs n_rays (the argument, or the reference's hpams['n_rays'])")
+        if picks is None:
+            picks = draw_view_picks(views, seeds, T, n)
+        picks = torch.as_tensor(picks)
+        if tuple(picks.shape) != (T, V, n):
+            raise U.SnrError(f"optimize_instances: picks must be (num_opts, V, n_rays) = ({T}, {V}, {n}), got {tuple(picks.shape)}")
+        img_cat, occ_cat, crop_off, roi_d, Kvec = _view_crops(views, dev)
+        picks = picks.to(dev, torch.int32).contiguous()
+        rays_per_view = torch.tensor([min(n, int((v["roi"][2] - v["roi"][0]) * (v["roi"][3] - v["roi"][1]))) for v in views], dtype=torch.int32)
+    else:
+        if picks is not None:
+            raise U.SnrError("optimize_instances: picks belong to sampling='random'")
+        n = int(hpams["render_im_sz"]) ** 2
+        rays_per_view = torch.full((V,), n, dtype=torch.int32)
+    n_l = c["n_lidar"]
+    if jitter is None:
+        gens = [torch.Generator().manual_seed(int(s_)) for s_ in seeds]
+        jitter = torch.stack([torch.rand(T, 2, S, generator=g) for g in gens], dim=2)
+    if tuple(jitter.shape) != (T, 2, V, S):
+        raise U.SnrError(f"optimize_instances: jitter must be (num_opts, 2, V, S) = ({T}, 2, {V}, {S}), got {tuple(jitter.shape)}")
+    jitter = jitter.to(dev, torch.float32).contiguous()
+    shapecode, texturecode = [t.detach().clone().to(dev).contiguous().requires_grad_() for t in (shapecodes0, texturecodes0)]
+    groups = [(shapecode, float(opt["lr_shape"])), (texturecode, float(opt["lr_texture"]))]
+    opt_cam = int(bool(opt.get("opt_cam_pose", 0))) if opt_pose else 0
+    if opt_pose:
+        rot_vec, trans_vec = [t.to(dev).contiguous().requires_grad_() for t in (c["rot0"], c["tr0"])]
+        groups += [(rot_vec, float(opt["lr_pose"])), (trans_vec, float(opt["lr_pose"]))]
+    else:
+        fixed = torch.stack([torch.as_tensor(v["cam_pose"], dtype=torch.float32)[:3, :4] for v in views]).to(dev).contiguous()
+    optim = ops.DeviceAdamW(groups)
+    frame = U._frame(False, False, hpams["shapenet_obj_cood"])
+    sb, tb = model.shape_blocks, model.texture_blocks
+    half = (c["diag"] / 2).contiguous()
+    coef = float(hpams["loss_occ_coef"])
+    metrics = torch.zeros(T, V, 4, device=dev)
+    measured = c["lid_depth"] is not None
+    depth0 = c["lid_depth"] if measured else torch.zeros(V, n_l, device=dev)
+    record = info is not None and bool(info.get("record_grads"))
+    if info is not None:
+        info["view_offset"] = torch.tensor(offsets, dtype=torch.int64)
+        info["lidar_count"], info["rays_per_view"] = c["lid_cnt"].clone(), rays_per_view
+        info["loss"] = loss_log = torch.zeros(T, V, device=dev)
+        if record:
+            info["code_grads"] = []
+    ones = torch.ones(V, device=dev)
+    pose = torch.zeros(V, 3, 4, device=dev)
+    cfg = ops.RenderCfg(S, ops.Z_PER_OBJECT, n, sb, tb, frame=frame, precision=model.precision)
+    cfg_l = ops.RenderCfg(S, ops.Z_PER_OBJECT, n_l, sb, tb, frame=frame, precision=model.precision)
+    packed = model.packed_weights()
+    with _decoder_frozen(model):
+        for it in range(T):
+            if random_px:      # this iteration's pixels of every view: directions, targets and labels in one launch
+                cam, tgt, occ = ops.view_pixels(img_cat, occ_cat, crop_off, roi_d, Kvec, picks[it])
+            else:
+                cam, tgt, occ = c["cam"], c["tgt"], c["occ"]
+            if opt_pose:
+                cam2opt, rays_o, viewdir, z = ops.PoseRays.apply(rot_vec, trans_vec, cam, half, jitter[it, 0], S, opt_cam)
+            else:
+                rays_o, viewdir, z = ops.CamRays.apply(fixed, cam, half, jitter[it, 0], S)
+            lat_i = model.latent_terms(shapecode, texturecode)                      # (I, n_lat, 256): one launch for all instances
+            lb_i = model.latent_biases(lat_i)
+            lat = ops.InstanceRows.apply(lat_i, offsets)                            # (V, n_lat, 256): every view reads its instance's row
+            cfg.latent_bias = cfg_l.latent_bias = None if lb_i is None else ops.instance_rows_fwd(lb_i, offsets)
+            if it == 0:         # which arithmetic the loop runs in: "auto" is decided (and range-checked) once, on the first iteration's batch
+                def probe(p_):
+                    c1 = ops.copy.copy(cfg)
+                    c1.latent_bias = None if cfg.latent_bias is None else cfg.latent_bias[:1]
+                    return ops.render_probe(rays_o.detach()[:n], viewdir.detach()[:n], z[:1], c["diag"][:1], None, lat.detach()[:1], packed, c1, p_)
+                prec = model._auto_precision(model.precision, n * S, probe)
+                cfg.precision = prec
+                cfg_l.precision = prec if (prec != "bf16x3" or ops.split_supported(sb, tb, n_l * S)) else "fp32"
+            rgb, depth, acc = ops.FusedRender.apply(rays_o, viewdir, z, c["diag"], None, lat, packed, cfg)
+            loss, lm = ops.LossTail.apply(rgb, acc, tgt, occ, coef, n)
+            torch.autograd.backward(loss, ones)                                     # the sum of the views' losses (:1192, once per view there)
+            with torch.no_grad():
+                if opt_pose:
+                    c2o, lo, lv, lz = ops.PoseRays.apply(rot_vec.detach(), trans_vec.detach(), c["lid"], half, jitter[it, 1], S, opt_cam)
+                else:
+                    c2o = fixed
+                    lo, lv, lz = ops.CamRays.apply(fixed, c["lid"], half, jitter[it, 1], S)
+                d_vec = ops.render_fwd(lo, lv, lz, c["diag"], None, lat.detach(), packed, cfg_l)[1]
+                out4 = torch.cat([loss.detach()[:, None], lm], dim=1)
+                ops.metric_row(out4, d_vec.view(V, n_l), depth0, it == 0 and not measured, c2o, c["gtR"], c["gtT"], opt_cam, metrics[it],
+                               lidar_count=c["lid_cnt"])
+                if info is not None:
+                    loss_log[it] = loss.detach()
+                    if record:
+                        info["code_grads"].append((shapecode.grad.clone(), texturecode.grad.clone()))
+                if it == T - 1:
+                    pose.copy_(c2o)
+            optim.step()
+            optim.zero_grad()
+            if opt_pose:
+                _halve_rates(optim, it, opt)
+    return metrics.permute(1, 0, 2).contiguous(), shapecode.detach(), texturecode.detach(), pose
+
+
+def make_instances(ids: Sequence[int], n_views: int, lidar: bool = False) -> List[Dict]:
+    """Synthetic instances seen in ``n_views`` cameras each (``synthetic.synthetic_instance``): every view carries its native-size crop
+    (``synthetic_crop_targets``, background whitened like src/optimizer_nuscenes.py:1167-1171), so rois differ in size between views.
+    ``lidar``: every view also carries synthetic lidar returns with measured depths."""
+    out = []
+    for i in ids:
+        inst = synthetic.synthetic_instance(i, n_views)
+        for j, view in enumerate(inst["views"]):
+            x0, y0, x1, y1 = [int(t) for t in view["roi"]]
+            img, mask = synthetic.synthetic_crop_targets(1000 * i + j, y1 - y0, x1 - x0)
+            img = img * (mask > 0) + (mask <= 0)
+            view.update(img=img, mask=mask, index=i, view=j)
+            if lidar:
+                xy, depth = synthetic.synthetic_lidar(1000 * i + j, mask, view)
+                view.update(lidar_xy=xy, lidar_depth=depth)
+        out.append(inst)
+    return out
 
 
 def make_objects(ids: Sequence[int], im_sz: int, lidar: bool = False) -> List[Dict]:

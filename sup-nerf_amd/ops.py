@@ -10,7 +10,7 @@ import operator
 import threading
 import warnings
 import weakref
-from typing import Dict, NamedTuple, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -827,6 +827,106 @@ class LatentLayers(torch.autograd.Function):
         with torch.cuda.device(dev):
             check(_lib.lib().snr_latent_bwd(_p(d_z), _p(z), _p(w_lat), B, sb, tb, _p(d_sc), _p(d_tc), _stream(dev)), "snr_latent_bwd")
         return d_sc, d_tc, None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------ several views of one instance (csrc/snr_views.hip)
+def view_pixels(img_cat, occ_cat, crop_offset, roi, Kvec, picks):
+    """One iteration's random pixels of V views' native-resolution rois (``render_rays``, src/utils.py:380-432), one launch, no host read.
+    img_cat (sum h w, 3), occ_cat (sum h w): the views' crops, row-major, concatenated; crop_offset (V+1,) int64 pixel offsets;
+    roi (V,4) int32 x0 y0 x1 y1; Kvec (V,4) fx fy cx cy; picks (V,n) int32 = y w + x into the view's crop, -1 (or anything outside
+    [0, h w)) = a padding ray -> cam_dirs (V,n,3) = [(x-cx)/fx, (y-cy)/fy, 1], rgb_tgt (V,n,3), occ (V,n); padding rays get (0,0,1), 0, 0,
+    and occ = 0 is a zero weight in every sum of ``LossTail``.  All inputs are data: no gradient."""
+    _need_gpu(img_cat, occ_cat, crop_offset, roi, Kvec, picks)
+    for t in (img_cat, occ_cat, Kvec):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise SnrError("view_pixels: img_cat, occ_cat and Kvec must be fp32 contiguous tensors")
+    if crop_offset.dtype != torch.int64 or not crop_offset.is_contiguous() or crop_offset.dim() != 1 or crop_offset.numel() < 1:
+        raise SnrError("view_pixels: crop_offset must be a contiguous int64 (V+1,) tensor")
+    V = crop_offset.numel() - 1
+    for t, name in ((roi, "roi"), (picks, "picks")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise SnrError(f"view_pixels: {name} must be a contiguous int32 tensor")
+    if tuple(roi.shape) != (V, 4) or tuple(Kvec.shape) != (V, 4) or picks.dim() != 2 or picks.shape[0] != V:
+        raise SnrError(f"view_pixels: expected roi (V,4), Kvec (V,4), picks (V,n) for the V = {V} views of crop_offset, got {tuple(roi.shape)}, "
+                       f"{tuple(Kvec.shape)}, {tuple(picks.shape)}")
+    if occ_cat.dim() != 1 or img_cat.numel() != 3 * occ_cat.numel():
+        raise SnrError(f"view_pixels: img_cat {tuple(img_cat.shape)} and occ_cat {tuple(occ_cat.shape)} must be (P,3) and (P,)")
+    dev = picks.device
+    if any(t.device != dev for t in (img_cat, occ_cat, crop_offset, roi, Kvec)):
+        raise SnrError("view_pixels: all tensors on one GPU")
+    n = picks.shape[1]
+    cam_dirs, rgb_tgt, occ = torch.empty(V, n, 3, device=dev), torch.empty(V, n, 3, device=dev), torch.empty(V, n, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_view_pixels(_p(img_cat), _p(occ_cat), _p(crop_offset), _p(roi), _p(Kvec), _p(picks), V, n, _p(cam_dirs), _p(rgb_tgt),
+                                         _p(occ), _stream(dev)), "snr_view_pixels")
+    return cam_dirs, rgb_tgt, occ
+
+
+def view_offset_of(view_counts) -> Tuple[int, ...]:
+    """(I+1,) offsets of I instances' contiguous views from their view counts; an instance without a view raises."""
+    counts = [int(c) for c in view_counts]
+    if not counts or any(c < 1 for c in counts):
+        raise SnrError(f"every instance needs at least one view, got view counts {counts}")
+    off = [0]
+    for c in counts:
+        off.append(off[-1] + c)
+    return tuple(off)
+
+
+@functools.lru_cache(maxsize=32)
+def _view_offset_on(offsets: Tuple[int, ...], dev_str: str) -> torch.Tensor:
+    return torch.tensor(offsets, dtype=torch.int64).to(torch.device(dev_str))
+
+
+def _view_offset_args(view_offset, n_instances, dev):
+    """The relation is host knowledge: checked here, before any launch; its device copy is made once per (offsets, device)."""
+    off = tuple(int(v) for v in (view_offset.tolist() if isinstance(view_offset, torch.Tensor) else view_offset))
+    if len(off) != n_instances + 1 or off[0] != 0:
+        raise SnrError(f"instance_rows: view_offset must hold I + 1 = {n_instances + 1} offsets starting at 0, got {off}")
+    if any(b <= a for a, b in zip(off, off[1:])):
+        raise SnrError(f"instance_rows: an instance without a view (view_offset {off})")
+    return off, _view_offset_on(off, str(dev)), (C.c_int64 * len(off))(*off)
+
+
+def instance_rows_fwd(rows, view_offset):
+    """rows (I,...) -> (V,...): row v is the row of v's instance (``view_offset`` (I+1,): a host sequence or CPU tensor)."""
+    rows = _f32c(rows)
+    _need_gpu(rows)
+    n_inst = rows.shape[0]
+    off, off_d, off_h = _view_offset_args(view_offset, n_inst, rows.device)
+    n_cols = rows.numel() // n_inst if n_inst else 0
+    if n_cols < 1:
+        raise SnrError(f"instance_rows: rows {tuple(rows.shape)} have no column")
+    out = torch.empty(off[-1], *rows.shape[1:], device=rows.device)
+    with torch.cuda.device(rows.device):
+        check(_lib.lib().snr_instance_rows_fwd(_p(rows), _p(off_d), off_h, n_inst, off[-1], n_cols, _p(out),
+                                               _stream(rows.device)), "snr_instance_rows_fwd")
+    return out
+
+
+class InstanceRows(torch.autograd.Function):
+    """The views of an instance share its row: rows (I,...,256), view_offset (I+1,) [host] -> (V,...,256), row v a copy of its instance's.
+    Backward: the gradient of row i is the sum of its views' gradients in ASCENDING view order, plain fp32 adds from the first term, one
+    thread per element -- no atomics (torch's ``index_select`` backward is an atomic ``index_add``), the same bits every run."""
+
+    @staticmethod
+    def forward(ctx, rows, view_offset):
+        ctx.set_materialize_grads(False)
+        ctx.view_offset, ctx.shape = view_offset, tuple(rows.shape)
+        return instance_rows_fwd(rows, view_offset)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        if d_out is None:
+            return None, None
+        d_out = _f32c(d_out)
+        n_inst = ctx.shape[0]
+        off, off_d, off_h = _view_offset_args(ctx.view_offset, n_inst, d_out.device)
+        d_rows = torch.empty(ctx.shape, device=d_out.device)
+        with torch.cuda.device(d_out.device):
+            check(_lib.lib().snr_instance_rows_bwd(_p(d_out), _p(off_d), off_h, n_inst, off[-1],
+                                                   d_rows.numel() // n_inst, _p(d_rows), _stream(d_out.device)), "snr_instance_rows_bwd")
+        return d_rows, None
 
 
 class TableAdamW:

@@ -64,6 +64,35 @@ def synthetic_object(index, im_w=1600, im_h=900, K=NUSC_K):
     return dict(wlh=wlh, obj_diag=diag, cam_pose=cam_pose, K=torch.from_numpy(K.copy()), roi=roi)
 
 
+def synthetic_instance(index, n_views, im_w=1600, im_h=900, K=NUSC_K, roi_margin=5):
+    """Deterministic in ``index``: ONE car (one ``wlh``) seen by ``n_views`` cameras at different yaws and distances, as the annotations of
+    one nuScenes instance are (src/optimizer_nuscenes.py:1050-1095).  dict(wlh, views): every view is a dict(wlh, obj_diag, cam_pose (3,4)
+    camera-in-object, K, roi int32[4]) whose roi is the projected box grown by ``roi_margin`` and clipped to the image
+    (``utils.roi_process``) at NATIVE size, so the rois of one instance differ in size."""
+    from . import utils
+    rs = np.random.RandomState(11000 + index)
+    wlh = (WLH_MEAN + WLH_STD * rs.randn(3)).astype(np.float32)
+    diag = np.linalg.norm(wlh).astype(np.float32)
+    w, l, h = [float(v) for v in wlh]
+    corners = np.array([[sx * l / 2, sy * w / 2, sz * h / 2] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)], dtype=np.float64).T
+    views = []
+    for _ in range(n_views):
+        yaw = rs.uniform(-np.pi, np.pi)
+        depth = rs.uniform(8.0, 35.0)
+        lateral = rs.uniform(-0.25, 0.25) * depth
+        c, s = np.cos(yaw), np.sin(yaw)
+        R_obj = np.array([[c, -s, 0], [0, 0, -1], [s, c, 0]], dtype=np.float32)      # object axes in the camera frame
+        t_obj = np.array([lateral, 1.2, depth], dtype=np.float32)
+        R_c2o = R_obj.T
+        cam_pose = torch.from_numpy(np.concatenate([R_c2o, (-R_c2o @ t_obj)[:, None]], axis=1).astype(np.float32))
+        uvw = K.astype(np.float64) @ (R_obj.astype(np.float64) @ corners + t_obj.astype(np.float64)[:, None])
+        u, v = uvw[0] / uvw[2], uvw[1] / uvw[2]
+        box = torch.tensor([int(np.floor(u.min())), int(np.floor(v.min())), int(np.ceil(u.max())), int(np.ceil(v.max()))], dtype=torch.int32)
+        roi = utils.roi_process(box, im_h, im_w, roi_margin)
+        views.append(dict(wlh=wlh, obj_diag=diag, cam_pose=cam_pose, K=torch.from_numpy(K.copy()), roi=roi))
+    return dict(wlh=wlh, views=views)
+
+
 def synthetic_targets(index, im_sz):
     """Target crop (im_sz,im_sz,3) in [0,1) and occupancy mask (im_sz,im_sz,1) in {-1,0,1} (ellipse, thin unknown rim)."""
     g = torch.Generator().manual_seed(2000 + index)
