@@ -238,14 +238,9 @@ def optimize_object_api(model, device, obj: Dict, hpams: dict, shapecode0, textu
     img, mask = obj["img"], obj["mask"]
     # ground-truth OBJECT pose in the camera frame and a perturbed start
     gt_pose = U.invert_pose(obj["cam_pose"])
-    R_gt, t_gt = gt_pose[:, :3], gt_pose[:, 3:]
-    rot_vec = (matrix_to_axis_angle(R_gt[None]) + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[0]).to(dev)
-    trans_vec = (t_gt.T + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[1]).to(dev)
-    if pose_per_iter is not None:          # the pose head's table: start from its last pose (src/optimizer_nuscenes.py:652,664-666)
+    if pose_per_iter is not None:
         pose_per_iter = torch.as_tensor(pose_per_iter, dtype=torch.float32).reshape(-1, 3, 4).to(dev)
-        rot_vec = matrix_to_axis_angle(pose_per_iter[-1, :3, :3][None]).contiguous()
-        trans_vec = pose_per_iter[-1, :3, 3][None].clone()
-    rot_vec.requires_grad_(); trans_vec.requires_grad_()
+    rot_vec, trans_vec = [t.to(dev).requires_grad_() for t in _start_pose(gt_pose, rs, pose_noise, None if pose_per_iter is None else pose_per_iter[-1])]
     shapecode = shapecode0.detach().clone().to(dev).requires_grad_()
     texturecode = texturecode0.detach().clone().to(dev).requires_grad_()
     lr = {k: opt[k] for k in ("lr_shape", "lr_texture", "lr_pose")}
@@ -302,7 +297,7 @@ def optimize_objects_batched(model, device, objs: List[Dict], hpams: dict, shape
     """The iteration of ``optimize_object`` for B objects at once: ONE fused forward, one backward and one depth render of the lidar pixels
     per iteration for all of them (per-object codes, poses, depth tables and targets; the loss is the sum of the per-object losses, so
     every object sees exactly its own gradient), AdamW over the stacked leaves in one launch, metrics kept on the device until the end --
-    no host round trip inside the loop (``_optimize_fused``: ~24 launches per iteration for any B).  Jitter: ``jitter``
+    no host round trip inside the loop (``_fit_views``: ~24 launches per iteration for any B).  Jitter: ``jitter``
     (num_opts, 2, B, S) or, by default, drawn up front from one CPU generator per object (seeded like the per-object loop seeds its
     RandomState).  ``info`` (optional dict) receives ``lidar_count`` (B,): the number of depth pixels behind every object's depth metric.
     ``pose_per_iter`` (B, reg_iters + 1, 3, 4): every object's pose table for the render-only iterations, see ``optimize_object``.
@@ -316,7 +311,36 @@ def optimize_objects_batched(model, device, objs: List[Dict], hpams: dict, shape
         pose_per_iter = torch.as_tensor(pose_per_iter, dtype=torch.float32)
         if tuple(pose_per_iter.shape) != (len(objs), reg_iters + 1, 3, 4):
             raise U.SnrError(f"pose_per_iter must be (B, reg_iters + 1, 3, 4) = ({len(objs)}, {reg_iters + 1}, 3, 4), got {tuple(pose_per_iter.shape)}")
-    return _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, pose_noise, reg_iters, n_lidar, jitter, info, pose_per_iter)
+    c = _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter)
+    if jitter is None:
+        jitter = _default_jitter(seeds, hpams["optimize"]["num_opts"], hpams["n_samples"])
+    if info is not None:
+        info["lidar_count"] = c["lid_cnt"].clone()
+    opt_cam = int(bool(hpams["optimize"].get("opt_cam_pose", 0)))
+    given = None
+    if pose_per_iter is not None:
+        # the render-only iterations' camera poses, made once: the inverses of the table's object poses unless the camera pose itself is
+        # what is optimised (src/optimizer_nuscenes.py:684-699); (reg_iters + 1, B, 3, 4) on the device
+        P = pose_per_iter.to(dev).permute(1, 0, 2, 3)
+        given = (P if opt_cam else U.invert_pose(P)).contiguous()
+    return _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, reg_iters=reg_iters, given=given)
+
+
+def _start_pose(gt, rs, pose_noise, last=None):
+    """Where the optimiser's pose starts: the rotation and translation vectors (1,3) of the ground-truth object pose ``gt`` (3,4), perturbed by
+    two ``rs.randn(1, 3)`` draws.  The draws are the FIRST the object's ``RandomState`` makes -- its lidar pixels are drawn next -- and they
+    are made also when ``last``, the last pose of a pose table, then replaces the result (src/optimizer_nuscenes.py:652,664-666; on
+    ``last``'s device)."""
+    rot = matrix_to_axis_angle(gt[None, :, :3]) + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[0]
+    tr = gt[:, 3:].T + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[1]
+    if last is not None:
+        rot, tr = matrix_to_axis_angle(last[:3, :3][None]), last[:3, 3][None].clone()
+    return rot, tr
+
+
+def _default_jitter(seeds, T, S):
+    """(T, 2, len(seeds), S) depth jitter, the render's and the depth render's draw of every iteration: one CPU generator per seed."""
+    return torch.stack([torch.rand(T, 2, S, generator=torch.Generator().manual_seed(int(s_))) for s_ in seeds], dim=2)
 
 
 def _lidar_pixels(ob, rs, n_lidar):
@@ -346,13 +370,9 @@ def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=Non
     for ob, seed in zip(objs, seeds):
         rs = np.random.RandomState(seed)
         gt = U.invert_pose(ob["cam_pose"])
-        R_gt, t_gt = gt[:, :3], gt[:, 3:]
-        rot0.append(matrix_to_axis_angle(R_gt[None]) + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[0])
-        tr0.append(t_gt.T + torch.from_numpy(rs.randn(1, 3).astype(np.float32)) * pose_noise[1])
-        if pose_per_iter is not None:      # (the draws above still happen: the lidar pixels below come from the same RandomState)
-            last = pose_per_iter[len(rot0) - 1, -1]
-            rot0[-1], tr0[-1] = matrix_to_axis_angle(last[:3, :3][None]), last[:3, 3][None].clone()
-        gtR.append(R_gt); gtT.append(t_gt.reshape(3))
+        rot, tr = _start_pose(gt, rs, pose_noise, None if pose_per_iter is None else pose_per_iter[len(rot0), -1])
+        rot0.append(rot); tr0.append(tr)
+        gtR.append(gt[:, :3]); gtT.append(gt[:, 3])
         x_vec, y_vec, depth = _lidar_pixels(ob, rs, n_lidar)
         x0, y0, x1, y1 = [int(v) for v in ob["roi"]]
         K = ob["K"]
@@ -400,13 +420,16 @@ def _decoder_frozen(model):
 
 
 def _leaves_and_adamw(shapecodes0, texturecodes0, rot0, tr0, opt, dev):
-    """The four leaves of a fused loop on the device -- clones of the start codes, the start rotation and translation vectors -- and
-    ``ops.DeviceAdamW`` over them with the three learning rates (src/optimizer_nuscenes.py:1762-1769)."""
+    """The leaves of a fused loop on the device -- clones of the start codes and, unless ``rot0`` is None (poses that are not optimised: no
+    pose leaves, two parameter groups), the start rotation and translation vectors -- and ``ops.DeviceAdamW`` over them with the three
+    learning rates (src/optimizer_nuscenes.py:1762-1769)."""
     shapecode, texturecode = [t.detach().clone().to(dev).contiguous().requires_grad_() for t in (shapecodes0, texturecodes0)]
-    rot_vec, trans_vec = [t.to(dev).contiguous().requires_grad_() for t in (rot0, tr0)]
-    lr_shape, lr_texture, lr_pose = [float(opt[k]) for k in ("lr_shape", "lr_texture", "lr_pose")]
-    optim = U.ops.DeviceAdamW([(shapecode, lr_shape), (texturecode, lr_texture), (rot_vec, lr_pose), (trans_vec, lr_pose)])
-    return shapecode, texturecode, rot_vec, trans_vec, optim
+    groups = [(shapecode, float(opt["lr_shape"])), (texturecode, float(opt["lr_texture"]))]
+    rot_vec = trans_vec = None
+    if rot0 is not None:
+        rot_vec, trans_vec = [t.to(dev).contiguous().requires_grad_() for t in (rot0, tr0)]
+        groups += [(rot_vec, float(opt["lr_pose"])), (trans_vec, float(opt["lr_pose"]))]
+    return shapecode, texturecode, rot_vec, trans_vec, U.ops.DeviceAdamW(groups)
 
 
 def _halve_rates(optim, it, opt):
@@ -415,52 +438,61 @@ def _halve_rates(optim, it, opt):
         optim.restart(2.0 ** (-((it + 1) // opt["lr_half_interval"])))
 
 
-def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, pose_noise, reg_iters, n_lidar, jitter, info=None,
-                    pose_per_iter=None):
-    """The iteration as ~30 launches for any number of objects: pose -> rays + depths (one launch), the per-object layers (two GEMMs),
-    fused render, loss tail (one launch), backward = their four backward launches, the 64-pixel depth render, the metric row (one
-    launch), AdamW over the four parameter groups (one launch).  Nothing reads back until the loop has finished."""
+def _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, reg_iters=-1, crops=None, picks=None, given=None,
+               view_offset=None, opt_pose=True, loss_log=None, grad_log=None):
+    """THE fused iteration of ``optimize_objects_batched`` and ``optimize_instances``, ~30 launches for any number V of views ("objects" of
+    the launches): pose -> rays + depths (one launch), the latent layers (two GEMMs), fused render, loss tail (one launch), backward = their
+    four backward launches, the 64-pixel depth render, the metric row (one launch), AdamW over the parameter groups (one launch).  Nothing
+    reads back until the loop has finished.  ``c``: ``_loop_inputs`` of the V views; ``jitter`` (T, 2, V, S).  What the callers choose:
+
+    * the pixels: the fixed resized grid of ``c`` (``cam``, ``tgt``, ``occ``), or with ``crops`` (``_view_crops``) and ``picks`` (T, V, n) on
+      the device every iteration's own native pixels, one ``ops.view_pixels`` launch more;
+    * the camera poses: ``given`` (n_given, V, 3, 4) on the device holds those of iterations ``it < n_given`` (``CamRays``, nothing to
+      differentiate), every other iteration renders at the optimised ``rot_vec`` / ``trans_vec`` (``PoseRays``).  Iterations ``it <= reg_iters``
+      only render (no graph, no step).  ``opt_pose=False``: there are no pose leaves (``given`` covers all T iterations), AdamW has the two
+      code groups and its rates are never halved;
+    * the code rows: ``view_offset`` None = one row per view, (V,256); a tuple of I + 1 offsets = (I,256) codes, ``ops.InstanceRows`` hands
+      every instance's latent row to its views and sums their gradients in view order.
+
+    ``loss_log`` (T,V) on the device and ``grad_log`` (a list), when given, receive every iteration's per-view losses and clones of the code
+    gradients the step reads.  Returns metrics (V,T,4), shape codes, texture codes, the last iteration's camera-in-object poses (V,3,4)."""
     ops = U.ops
     opt = hpams["optimize"]
-    S, im_sz, T = hpams["n_samples"], hpams["render_im_sz"], opt["num_opts"]
-    B, n = len(objs), im_sz * im_sz
-    c = _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter)
-    n_l = c["n_lidar"]
-    shapecode, texturecode, rot_vec, trans_vec, optim = _leaves_and_adamw(shapecodes0, texturecodes0, c["rot0"], c["tr0"], opt, dev)
-    if jitter is None:
-        gens = [torch.Generator().manual_seed(int(s_)) for s_ in seeds]
-        jitter = torch.stack([torch.rand(T, 2, S, generator=g) for g in gens], dim=2)
-    jitter = jitter.to(dev).contiguous()
+    S, T = int(hpams["n_samples"]), int(opt["num_opts"])
+    V, n_l = c["lid"].shape[0], c["n_lidar"]
+    n = c["cam"].shape[1] if crops is None else picks.shape[2]
+    shapecode, texturecode, rot_vec, trans_vec, optim = _leaves_and_adamw(shapecodes0, texturecodes0, c["rot0"] if opt_pose else None, c["tr0"], opt, dev)
+    jitter = jitter.to(dev, torch.float32).contiguous()
     frame = U._frame(False, False, hpams["shapenet_obj_cood"])
     sb, tb = model.shape_blocks, model.texture_blocks
     half = (c["diag"] / 2).contiguous()
-    opt_cam = int(bool(opt.get("opt_cam_pose", 0)))
     coef = float(hpams["loss_occ_coef"])
-    metrics = torch.zeros(T, B, 4, device=dev)
+    metrics = torch.zeros(T, V, 4, device=dev)
     measured = c["lid_depth"] is not None
-    depth0 = c["lid_depth"] if measured else torch.zeros(B, n_l, device=dev)       # measured depths, or the rendered depths of iteration 0
-    if info is not None:
-        info["lidar_count"] = c["lid_cnt"].clone()
-    ones = torch.ones(B, device=dev)
-    pose = torch.zeros(B, 3, 4, device=dev)
+    depth0 = c["lid_depth"] if measured else torch.zeros(V, n_l, device=dev)       # measured depths, or the rendered depths of iteration 0
+    ones = torch.ones(V, device=dev)
+    pose = torch.zeros(V, 3, 4, device=dev)
     cfg = ops.RenderCfg(S, ops.Z_PER_OBJECT, n, sb, tb, frame=frame, precision=model.precision)
     cfg_l = ops.RenderCfg(S, ops.Z_PER_OBJECT, n_l, sb, tb, frame=frame, precision=model.precision)
     packed = model.packed_weights()
-    table = None
-    if pose_per_iter is not None:
-        # the render-only iterations' camera poses, made once: the inverses of the table's object poses unless the camera pose itself is
-        # what is optimised (src/optimizer_nuscenes.py:684-699); (reg_iters + 1, B, 3, 4) on the device
-        P = pose_per_iter.to(dev).permute(1, 0, 2, 3)
-        table = (P if opt_cam else U.invert_pose(P)).contiguous()
     with _decoder_frozen(model):
         for it in range(T):
-            from_table = table is not None and it <= reg_iters
-            if from_table:      # a pre-computed pose per object: rays straight from the (3,4) camera poses (snr_cam_rays_fwd), nothing to differentiate
-                rays_o, viewdir, z = ops.CamRays.apply(table[it], c["cam"], half, jitter[it, 0], S)
+            if crops is None:
+                cam, tgt, occ = c["cam"], c["tgt"], c["occ"]
+            else:               # this iteration's pixels of every view: directions, targets and labels in one launch
+                cam, tgt, occ = ops.view_pixels(*crops, picks[it])
+            from_given = given is not None and it < given.shape[0]
+            if from_given:      # a given camera pose per view: rays straight from the (3,4) poses (snr_cam_rays_fwd), nothing to differentiate
+                c2o = given[it]
+                rays_o, viewdir, z = ops.CamRays.apply(c2o, cam, half, jitter[it, 0], S)
             else:
-                cam2opt, rays_o, viewdir, z = ops.PoseRays.apply(rot_vec, trans_vec, c["cam"], half, jitter[it, 0], S, opt_cam)
-            lat = model.latent_terms(shapecode, texturecode)
-            cfg.latent_bias = cfg_l.latent_bias = model.latent_biases(lat)
+                cam2opt, rays_o, viewdir, z = ops.PoseRays.apply(rot_vec, trans_vec, cam, half, jitter[it, 0], S, opt_cam)
+            lat = model.latent_terms(shapecode, texturecode)                        # one launch for all code rows
+            bias = model.latent_biases(lat)
+            if view_offset is not None:                                             # (I, n_lat, 256) -> (V, n_lat, 256): every view reads its instance's row
+                lat = ops.InstanceRows.apply(lat, view_offset)
+                bias = None if bias is None else ops.instance_rows_fwd(bias, view_offset)
+            cfg.latent_bias = cfg_l.latent_bias = bias
             if it == 0:         # which arithmetic the loop runs in: "auto" is decided (and range-checked) once, on the first iteration's batch
                 def probe(p_):      # (one object of the batch: the decoder is the same for all of them)
                     c1 = ops.copy.copy(cfg)
@@ -469,30 +501,33 @@ def _optimize_fused(model, dev, objs, hpams, shapecodes0, texturecodes0, seeds, 
                 prec = model._auto_precision(model.precision, n * S, probe)
                 cfg.precision = prec
                 cfg_l.precision = prec if (prec != "bf16x3" or ops.split_supported(sb, tb, n_l * S)) else "fp32"
-            if it > reg_iters:
+            # a render-only iteration (it <= reg_iters): its gradients are cleared unread (:676,768-769), so nothing is recorded -- the forward
+            # then does not save ReLU bits either (the launch that saves them is 9 % slower and writes 208 B per point)
+            with contextlib.nullcontext() if it > reg_iters else torch.no_grad():
                 rgb, depth, acc = ops.FusedRender.apply(rays_o, viewdir, z, c["diag"], None, lat, packed, cfg)
-                loss, lm = ops.LossTail.apply(rgb, acc, c["tgt"], c["occ"], coef, n)
-                torch.autograd.backward(loss, ones)
-            else:               # a render-only iteration: its gradients are cleared unread (:676,768-769), so nothing is recorded -- the forward then
-                with torch.no_grad():      # does not save ReLU bits either (the launch that saves them is 9 % slower and writes 208 B per point)
-                    rgb, depth, acc = ops.FusedRender.apply(rays_o, viewdir, z, c["diag"], None, lat, packed, cfg)
-                    loss, lm = ops.LossTail.apply(rgb, acc, c["tgt"], c["occ"], coef, n)
+                loss, lm = ops.LossTail.apply(rgb, acc, tgt, occ, coef, n)
+            if it > reg_iters:
+                torch.autograd.backward(loss, ones)                                 # the sum of the views' losses (:1192, once per view there)
             with torch.no_grad():
-                if from_table:
-                    c2o = table[it]
+                if from_given:
                     lo, lv, lz = ops.CamRays.apply(c2o, c["lid"], half, jitter[it, 1], S)
                 else:
                     c2o, lo, lv, lz = ops.PoseRays.apply(rot_vec.detach(), trans_vec.detach(), c["lid"], half, jitter[it, 1], S, opt_cam)
                 d_vec = ops.render_fwd(lo, lv, lz, c["diag"], None, lat.detach(), packed, cfg_l)[1]
                 out4 = torch.cat([loss.detach()[:, None], lm], dim=1)
-                ops.metric_row(out4, d_vec.view(B, n_l), depth0, it == 0 and not measured, c2o, c["gtR"], c["gtT"], opt_cam, metrics[it],
+                ops.metric_row(out4, d_vec.view(V, n_l), depth0, it == 0 and not measured, c2o, c["gtR"], c["gtT"], opt_cam, metrics[it],
                                lidar_count=c["lid_cnt"])
+                if loss_log is not None:
+                    loss_log[it] = loss.detach()
+                if grad_log is not None:
+                    grad_log.append((shapecode.grad.clone(), texturecode.grad.clone()))
                 if it == T - 1:
                     pose.copy_(c2o)
             if it > reg_iters:
                 optim.step()
             optim.zero_grad()
-            _halve_rates(optim, it, opt)
+            if opt_pose:
+                _halve_rates(optim, it, opt)
     return metrics.permute(1, 0, 2).contiguous(), shapecode.detach(), texturecode.detach(), pose
 
 
@@ -729,6 +764,7 @@ def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapec
         raise U.SnrError(f"optimize_instances: sampling is 'random' or 'grid', got {sampling!r}")
     random_px = sampling == "random"
     c = _loop_inputs(views, seeds, hpams, pose_noise, n_lidar, dev, grid=not random_px)
+    crops = None
     if random_px:
         n = int(n_rays if n_rays is not None else hpams.get("n_rays", 0))
         if n < 1:
@@ -738,7 +774,7 @@ def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapec
         picks = torch.as_tensor(picks)
         if tuple(picks.shape) != (T, V, n):
             raise U.SnrError(f"optimize_instances: picks must be (num_opts, V, n_rays) = ({T}, {V}, {n}), got {tuple(picks.shape)}")
-        img_cat, occ_cat, crop_off, roi_d, Kvec = _view_crops(views, dev)
+        crops = _view_crops(views, dev)
         picks = picks.to(dev, torch.int32).contiguous()
         rays_per_view = torch.tensor([min(n, int((v["roi"][2] - v["roi"][0]) * (v["roi"][3] - v["roi"][1]))) for v in views], dtype=torch.int32)
     else:
@@ -746,87 +782,23 @@ def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapec
             raise U.SnrError("optimize_instances: picks belong to sampling='random'")
         n = int(hpams["render_im_sz"]) ** 2
         rays_per_view = torch.full((V,), n, dtype=torch.int32)
-    n_l = c["n_lidar"]
     if jitter is None:
-        gens = [torch.Generator().manual_seed(int(s_)) for s_ in seeds]
-        jitter = torch.stack([torch.rand(T, 2, S, generator=g) for g in gens], dim=2)
+        jitter = _default_jitter(seeds, T, S)
     if tuple(jitter.shape) != (T, 2, V, S):
         raise U.SnrError(f"optimize_instances: jitter must be (num_opts, 2, V, S) = ({T}, 2, {V}, {S}), got {tuple(jitter.shape)}")
-    jitter = jitter.to(dev, torch.float32).contiguous()
-    shapecode, texturecode = [t.detach().clone().to(dev).contiguous().requires_grad_() for t in (shapecodes0, texturecodes0)]
-    groups = [(shapecode, float(opt["lr_shape"])), (texturecode, float(opt["lr_texture"]))]
-    opt_cam = int(bool(opt.get("opt_cam_pose", 0))) if opt_pose else 0
-    if opt_pose:
-        rot_vec, trans_vec = [t.to(dev).contiguous().requires_grad_() for t in (c["rot0"], c["tr0"])]
-        groups += [(rot_vec, float(opt["lr_pose"])), (trans_vec, float(opt["lr_pose"]))]
-    else:
-        fixed = torch.stack([torch.as_tensor(v["cam_pose"], dtype=torch.float32)[:3, :4] for v in views]).to(dev).contiguous()
-    optim = ops.DeviceAdamW(groups)
-    frame = U._frame(False, False, hpams["shapenet_obj_cood"])
-    sb, tb = model.shape_blocks, model.texture_blocks
-    half = (c["diag"] / 2).contiguous()
-    coef = float(hpams["loss_occ_coef"])
-    metrics = torch.zeros(T, V, 4, device=dev)
-    measured = c["lid_depth"] is not None
-    depth0 = c["lid_depth"] if measured else torch.zeros(V, n_l, device=dev)
-    record = info is not None and bool(info.get("record_grads"))
+    opt_cam, given = int(bool(opt.get("opt_cam_pose", 0))), None
+    if not opt_pose:            # every view's own cam_pose in all T iterations: ONE (V,3,4) tensor, read T times through a stride-0 view
+        opt_cam = 0
+        given = torch.stack([torch.as_tensor(v["cam_pose"], dtype=torch.float32)[:3, :4] for v in views]).to(dev).contiguous().expand(T, V, 3, 4)
+    loss_log = grad_log = None
     if info is not None:
         info["view_offset"] = torch.tensor(offsets, dtype=torch.int64)
         info["lidar_count"], info["rays_per_view"] = c["lid_cnt"].clone(), rays_per_view
         info["loss"] = loss_log = torch.zeros(T, V, device=dev)
-        if record:
-            info["code_grads"] = []
-    ones = torch.ones(V, device=dev)
-    pose = torch.zeros(V, 3, 4, device=dev)
-    cfg = ops.RenderCfg(S, ops.Z_PER_OBJECT, n, sb, tb, frame=frame, precision=model.precision)
-    cfg_l = ops.RenderCfg(S, ops.Z_PER_OBJECT, n_l, sb, tb, frame=frame, precision=model.precision)
-    packed = model.packed_weights()
-    with _decoder_frozen(model):
-        for it in range(T):
-            if random_px:      # this iteration's pixels of every view: directions, targets and labels in one launch
-                cam, tgt, occ = ops.view_pixels(img_cat, occ_cat, crop_off, roi_d, Kvec, picks[it])
-            else:
-                cam, tgt, occ = c["cam"], c["tgt"], c["occ"]
-            if opt_pose:
-                cam2opt, rays_o, viewdir, z = ops.PoseRays.apply(rot_vec, trans_vec, cam, half, jitter[it, 0], S, opt_cam)
-            else:
-                rays_o, viewdir, z = ops.CamRays.apply(fixed, cam, half, jitter[it, 0], S)
-            lat_i = model.latent_terms(shapecode, texturecode)                      # (I, n_lat, 256): one launch for all instances
-            lb_i = model.latent_biases(lat_i)
-            lat = ops.InstanceRows.apply(lat_i, offsets)                            # (V, n_lat, 256): every view reads its instance's row
-            cfg.latent_bias = cfg_l.latent_bias = None if lb_i is None else ops.instance_rows_fwd(lb_i, offsets)
-            if it == 0:         # which arithmetic the loop runs in: "auto" is decided (and range-checked) once, on the first iteration's batch
-                def probe(p_):
-                    c1 = ops.copy.copy(cfg)
-                    c1.latent_bias = None if cfg.latent_bias is None else cfg.latent_bias[:1]
-                    return ops.render_probe(rays_o.detach()[:n], viewdir.detach()[:n], z[:1], c["diag"][:1], None, lat.detach()[:1], packed, c1, p_)
-                prec = model._auto_precision(model.precision, n * S, probe)
-                cfg.precision = prec
-                cfg_l.precision = prec if (prec != "bf16x3" or ops.split_supported(sb, tb, n_l * S)) else "fp32"
-            rgb, depth, acc = ops.FusedRender.apply(rays_o, viewdir, z, c["diag"], None, lat, packed, cfg)
-            loss, lm = ops.LossTail.apply(rgb, acc, tgt, occ, coef, n)
-            torch.autograd.backward(loss, ones)                                     # the sum of the views' losses (:1192, once per view there)
-            with torch.no_grad():
-                if opt_pose:
-                    c2o, lo, lv, lz = ops.PoseRays.apply(rot_vec.detach(), trans_vec.detach(), c["lid"], half, jitter[it, 1], S, opt_cam)
-                else:
-                    c2o = fixed
-                    lo, lv, lz = ops.CamRays.apply(fixed, c["lid"], half, jitter[it, 1], S)
-                d_vec = ops.render_fwd(lo, lv, lz, c["diag"], None, lat.detach(), packed, cfg_l)[1]
-                out4 = torch.cat([loss.detach()[:, None], lm], dim=1)
-                ops.metric_row(out4, d_vec.view(V, n_l), depth0, it == 0 and not measured, c2o, c["gtR"], c["gtT"], opt_cam, metrics[it],
-                               lidar_count=c["lid_cnt"])
-                if info is not None:
-                    loss_log[it] = loss.detach()
-                    if record:
-                        info["code_grads"].append((shapecode.grad.clone(), texturecode.grad.clone()))
-                if it == T - 1:
-                    pose.copy_(c2o)
-            optim.step()
-            optim.zero_grad()
-            if opt_pose:
-                _halve_rates(optim, it, opt)
-    return metrics.permute(1, 0, 2).contiguous(), shapecode.detach(), texturecode.detach(), pose
+        if info.get("record_grads"):
+            info["code_grads"] = grad_log = []
+    return _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, crops=crops, picks=picks, given=given, view_offset=offsets,
+                      opt_pose=opt_pose, loss_log=loss_log, grad_log=grad_log)
 
 
 def make_instances(ids: Sequence[int], n_views: int, lidar: bool = False) -> List[Dict]:

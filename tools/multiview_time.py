@@ -2,8 +2,9 @@
 
   * one iteration of ``driver.optimize_instances`` at ``--instances`` instances x ``--views`` views each, ``--rays`` random native pixels per
     view and iteration, ``--samples`` samples: the difference of a 6- and a 2-iteration run over 4 (picks and jitter made beforehand);
-  * beside it the same views run one at a time: as many separate ``driver.optimize_object`` loops (the single-view fused loop, untouched by
-    the multi-view path; ``render_im_sz``^2 = ``--rays`` grid pixels each), the same difference summed over the views;
+  * beside it the same views run one at a time: as many separate ``driver.optimize_object`` loops (the same loop body,
+    ``driver._fit_views``, at one object on the fixed grid and without the ``view_pixels`` / ``InstanceRows`` launches; ``render_im_sz``^2 =
+    ``--rays`` grid pixels each), the same difference summed over the views;
   * ``--target V T``: only run ``optimize_instances`` on V views (instances of ``--views`` views; one instance of one view at V = 1) for T
     iterations, twice (the first run warms up) -- the profiling target for the launch count per iteration, counted like tools/prof_loop.py:
 
