@@ -489,10 +489,18 @@ def fused_render(params: Dict[str, Tensor], rays_o: Tensor, rays_d: Tensor, t_va
                  rays_per_obj: int, z_scale: Tensor, box_half: Optional[Tensor] = None, shape_code: Optional[Tensor] = None,
                  texture_code: Optional[Tensor] = None, latent: Optional[Tensor] = None,
                  relu_masks: Optional[Sequence[Tensor]] = None, white_bkgd: bool = False, metric_z: bool = False, slab=slab_intersect,
-                 box_detach: bool = False):
-    """What one ``snr_render_fwd`` launch computes (include/supnerf_hip.h) with xyz_div = xyz_mul = 1 and the identity frame: rays_o,
-    rays_d (N,3), ray r of object r // rays_per_obj, z_scale (B,).  Returns rgb (N,3), depth (N), acc_trans (N), differentiable in
-    every tensor argument (tests only).
+                 box_detach: bool = False, xyz_div: Optional[Tensor] = None, xyz_mul: float = 1.0, frame: Optional[Tensor] = None,
+                 obj: Optional[Tensor] = None):
+    """What one ``snr_render_fwd`` launch computes (include/supnerf_hip.h): rays_o, rays_d (N,3) in the sampling frame, ray r of object
+    r // rays_per_obj, z_scale (B,).  Returns rgb (N,3), depth (N), acc_trans (N), differentiable in every tensor argument (tests only).
+
+    The decoder sees p = M (((o + t d) / xyz_div[obj]) * xyz_mul) and dir = M d: ``xyz_div`` (B,) per object (family A's obj_diag; NOT
+    applied in "box" mode, where the origin is already rays_o / z_scale), ``xyz_mul`` a scalar (render_rays_v3's adjust_scale), ``frame`` M
+    a (3,3) tensor, row-major, applied to points and directions after the scale (``object_frame_transforms`` as one matrix).  The depths
+    of the composite are taken in the sampling frame, before any of the three.  Left at their defaults (None, 1.0, None) none of them is
+    applied: the points and directions reach the decoder as sampled.  ``obj`` (N,) long: the object whose xyz_div, z_scale, box_half and
+    per-object depth row each ray takes, when a test wants it to be another than r // rays_per_obj (the codes stay those of
+    r // rays_per_obj).
 
     ``z_mode`` lays out the depths t: "shared" t_vals (S,), "per_object" (B,S), "per_ray" (N,S); "box": t_vals is the (N,S) jitter
     table, and the depths are family B's stratified samples between the bounds of the slab test of o_n = rays_o / z_scale against
@@ -501,7 +509,8 @@ def fused_render(params: Dict[str, Tensor], rays_o: Tensor, rays_d: Tensor, t_va
     ``slab``: the slab test of "box", ``slab_intersect`` or a function of its signature (``guarded_slab_intersect``); ``box_detach``
     (SNR_BOX_DETACH): the bounds are constants of the backward."""
     N, S = rays_o.shape[0], n_samples
-    obj = torch.arange(N, device=rays_o.device) // rays_per_obj
+    if obj is None:
+        obj = torch.arange(N, device=rays_o.device) // rays_per_obj
     zs = z_scale[obj]
     if z_mode == "box":
         o = rays_o / zs[:, None]
@@ -514,8 +523,14 @@ def fused_render(params: Dict[str, Tensor], rays_o: Tensor, rays_d: Tensor, t_va
         t = {"shared": lambda: t_vals[None, :].expand(N, S), "per_object": lambda: t_vals[obj], "per_ray": lambda: t_vals}[z_mode]()
     xyz = o[:, None, :] + rays_d[:, None, :] * t[:, :, None]
     z = torch.norm(xyz - o[:, None, :], dim=-1) * zs[:, None] if metric_z else t
-    sig, rgb = decoder_forward(params, xyz, rays_d[:, None, :].expand(N, S, 3), shape_code, texture_code, relu_masks=relu_masks,
-                               latent=latent)
+    vd = rays_d[:, None, :].expand(N, S, 3)
+    if xyz_div is not None and z_mode != "box":
+        xyz = xyz / xyz_div[obj][:, None, None]
+    if xyz_mul != 1.0:
+        xyz = xyz * xyz_mul
+    if frame is not None:                       # p'[k] = sum_i M[k,i] p[i]
+        xyz, vd = (xyz[..., None, :] * frame).sum(-1), (vd[..., None, :] * frame).sum(-1)
+    sig, rgb = decoder_forward(params, xyz, vd, shape_code, texture_code, relu_masks=relu_masks, latent=latent)
     return composite(sig, rgb, z, white_bkgd=white_bkgd)
 
 

@@ -2011,8 +2011,8 @@ def render_fwd(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg: Re
 
 def pad_render_inputs(rays_o, rays_d, t_vals, z_scale, cfg, B, n, n_pad):
     """Every object's n rays padded to n_pad with dummy rays (whole 32-point wave tiles per object); returns the padded operands and a
-    copy of ``cfg`` for the padded launch.  Box sampling with in-kernel jitter (Z_BOX, no jitter tensor): the kernel's Philox stream is
-    indexed by the LAUNCH's point index, which padding shifts -- so the reference's draw, ``torch.rand_like`` of the caller's (N,S) table
+    copy of ``cfg`` for the padded launch; ``z_scale`` (B,), one per object, comes back unchanged (the ABI has no per-ray scale).
+    Box sampling with in-kernel jitter (Z_BOX, no jitter tensor): the kernel's Philox stream is indexed by the LAUNCH's point index, which padding shifts -- so the reference's draw, ``torch.rand_like`` of the caller's (N,S) table
     (src/renderer.py:40: the same numbers and the same generator consumption), is materialised BEFORE padding and padded like any other
     jitter table; seeded parity with the reference survives ragged ray counts."""
     cfg = copy.copy(cfg)
@@ -2021,9 +2021,7 @@ def pad_render_inputs(rays_o, rays_d, t_vals, z_scale, cfg, B, n, n_pad):
     rays_o, rays_d = _pad_rows(rays_o, B, n, n_pad), _pad_rows(rays_d, B, n, n_pad)
     if cfg.z_mode in (Z_PER_RAY, Z_BOX) and t_vals is not None:
         t_vals = _pad_rows(t_vals, B, n, n_pad)
-    if z_scale is not None and z_scale.numel() == B * n:
-        z_scale = _pad_rows(z_scale, B, n, n_pad)
-    cfg.rays_per_obj = n_pad
+    cfg.rays_per_obj = n_pad            # (z_scale is (B,), one per object like xyz_div: padding rays leaves it as it is)
     if cfg.z_mode == Z_BOX:             # (a dummy ray with direction 0 would divide 0 by 0 in the slab test: give it any unit direction)
         rays_d = rays_d.clone()
         rays_d.view(B, n_pad, 3)[:, n:, 2] = 1.0
