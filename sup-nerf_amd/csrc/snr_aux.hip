@@ -2,6 +2,7 @@
 // analytic backward), standalone sample encoding, and the small reductions used by the backward pass.
 #include "snr_device.hpp"
 #include "snr_host.hpp"
+#include "snr_scene_merge.hpp"
 
 namespace snr {
 
@@ -189,23 +190,7 @@ __device__ __forceinline__ bool scene_merge_fast(const float* zs, int n, int n_r
     return __all(ok);
 }
 
-template <bool UPPER>
-__device__ __forceinline__ int run_bound(const float* zr, int len, float v) {
-    int lo = 0;
-    while (len > 0) {
-        const int half = len >> 1;
-        const float m = zr[lo + half];
-        const bool go = UPPER ? (m <= v) : (m < v);
-        lo = go ? lo + half + 1 : lo;
-        len = go ? len - half - 1 : half;
-    }
-    return lo;
-}
-
-// `run` > 0: the pixel's n samples are n/run lists of `run` samples each, every list ascending in depth (one object's samples along its
-// ray; a list of an object that does not cover the pixel is all -1).  Then a sample's rank is its position in its own list plus, for every
-// other list, the number of smaller depths there -- two binary searches per list, O(n log(run) Nb) LDS reads per pixel instead of the n^2
-// of the generic rank sort below.  The lists are CHECKED to be ascending; a pixel whose lists are not takes the generic path.
+// The merge of verified ascending lists and the check that verifies them: snr_scene_merge.hpp, shared with the backward.
 template <bool MARKED_ONLY>
 __global__ void __launch_bounds__(256) scene_general_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                               const float* __restrict__ zv, long long n_pixels, int n, int run, int flags,
@@ -228,12 +213,7 @@ __global__ void __launch_bounds__(256) scene_general_kernel(const float* __restr
         // memory order wins and the group's other slots keep zero density / zero colour (torch scatter_ on the CPU).  Equal
         // depths are the rule for empty space (-1) and happen for ~1 % of pixels between real samples (fp32 depth grid), so
         // that is reproduced: the sorted depth row is complete, data goes to the group's first slot from its last member.
-        bool merged = false;
-        if (run > 1 && n % run == 0) {
-            bool sorted = true;
-            for (int i = lane; i < n; i += 64) sorted = sorted && ((i % run) == run - 1 || zs[i] <= zs[i + 1]);
-            merged = __all(sorted);
-        }
+        const bool merged = scene_lists_ascend(zs, n, run, lane);
         if (merged) {
             const int n_runs = n / run;
             for (int base = 0; base < n; base += 256) {          // up to four own elements per pass; their payload loads fly under the searches
@@ -250,19 +230,8 @@ __global__ void __launch_bounds__(256) scene_general_kernel(const float* __restr
                 for (int c = 0; c < 4; ++c) {
                     const int i = base + 64 * c + lane;
                     if (i >= n) continue;
-                    const int r = i / run, p = i - r * run;
-                    int lt = 0, eb = 0, ea = 0;
-                    for (int q = 0; q < n_runs; ++q) {
-                        const float* zr = zs + q * run;
-                        const int lb = run_bound<false>(zr, run, zi[c]);
-                        const bool has_eq = lb < run && zr[lb] == zi[c];
-                        const int ub = has_eq ? lb + 1 + run_bound<true>(zr + lb + 1, run - lb - 1, zi[c]) : lb;
-                        lt += lb;
-                        if (q < r) eb += ub - lb;
-                        else if (q > r) ea += ub - lb;
-                        else { eb += p - lb; ea += ub - p - 1; }
-                    }
-                    const int pos = lt + eb;
+                    const SceneRank k = scene_list_rank(zs, n_runs, run, i, zi[c]);
+                    const int lt = k.lt, eb = k.eb, ea = k.ea, pos = lt + eb;
                     s_z[pos] = zi[c];
                     if (eb > 0) { s_sig[pos] = 0.f; s_r[pos] = 0.f; s_g[pos] = 0.f; s_b[pos] = 0.f; }
                     if (ea == 0) { s_sig[lt] = sg[c]; s_r[lt] = cr[c]; s_g[lt] = cg[c]; s_b[lt] = cb[c]; }

@@ -1,27 +1,14 @@
 // Backward of the scene composite (snr_aux.hip: scene_general_kernel) for gfx950: per pixel the depth merge of n = Nb*S samples, the
 // analytic composite backward on the merged rows, and the way back through the merge to the samples.  HBM-bound: 20 B per sample in,
-// 20 B per sample out.  The forward's kernels are not touched; the two rank searches below restate scene_general_kernel's.
+// 20 B per sample out.  The ranks over verified lists are the forward's own: snr_scene_merge.hpp.
 #include "snr_device.hpp"
 #include "snr_host.hpp"
+#include "snr_scene_merge.hpp"
 
 namespace snr {
 
 constexpr int SCENE_BWD_MAX_N = 512;            // 8 objects x 64 samples; 7 n floats of LDS per wave, 56 KiB per workgroup there
 constexpr uint32_t SCENE_NO_SURVIVOR = 0xffffu;
-
-// # entries of the ascending list zr[0..len) that are < v (UPPER: <= v)
-template <bool UPPER>
-__device__ __forceinline__ int scene_bwd_bound(const float* zr, int len, float v) {
-    int lo = 0;
-    while (len > 0) {
-        const int half = len >> 1;
-        const float m = zr[lo + half];
-        const bool go = UPPER ? (m <= v) : (m < v);
-        lo = go ? lo + half + 1 : lo;
-        len = go ? len - half - 1 : half;
-    }
-    return lo;
-}
 
 // One wave per pixel, grid-stride over pixels.  LDS per wave: the depth row in memory order | five sorted rows (sigma, r, g, b, z) that
 // the composite backward reads and then overwrites, slot by slot, with its five gradients | one word per SAMPLE: its own slot pos_i
@@ -54,29 +41,13 @@ __global__ void __launch_bounds__(256) scene_bwd_kernel(const float* __restrict_
             if (ea == 0) { s_sig[lt] = srow[i]; s_r[lt] = crow[3 * i]; s_g[lt] = crow[3 * i + 1]; s_b[lt] = crow[3 * i + 2]; }
             slot[i] = (uint32_t)pos | ((ea == 0 ? (uint32_t)lt : SCENE_NO_SURVIVOR) << 16);
         };
-        bool merged = false;
-        if (run > 1 && n % run == 0) {
-            bool sorted = true;
-            for (int i = lane; i < n; i += 64) sorted = sorted && ((i % run) == run - 1 || zs[i] <= zs[i + 1]);
-            merged = __all(sorted);
-        }
+        const bool merged = scene_lists_ascend(zs, n, run, lane);
         if (merged) {                                          // verified ascending lists: two binary searches per (sample, list)
             const int n_runs = n / run;
             for (int i = lane; i < n; i += 64) {
                 const float zi = zs[i];
-                const int r = i / run, p = i - r * run;
-                int lt = 0, eb = 0, ea = 0;
-                for (int q = 0; q < n_runs; ++q) {
-                    const float* zr = zs + q * run;
-                    const int lb = scene_bwd_bound<false>(zr, run, zi);
-                    const bool has_eq = lb < run && zr[lb] == zi;
-                    const int ub = has_eq ? lb + 1 + scene_bwd_bound<true>(zr + lb + 1, run - lb - 1, zi) : lb;
-                    lt += lb;
-                    if (q < r) eb += ub - lb;
-                    else if (q > r) ea += ub - lb;
-                    else { eb += p - lb; ea += ub - p - 1; }
-                }
-                place(i, zi, lt, eb, ea);
+                const SceneRank k = scene_list_rank(zs, n_runs, run, i, zi);
+                place(i, zi, k.lt, k.eb, k.ea);
             }
         }
         for (int base = 0; base < n && !merged; base += 256) {   // rank sort: up to four own samples per pass against broadcast reads

@@ -8,6 +8,10 @@
 //     the decoder, `capacity` slots per object, a pair's slot its rank among its object's hits (the caller's prefix sum of the flags).
 // All HBM-bound.  One workgroup owns PAIRS consecutive pixels of one object: its threads first set the pairs up (one pair each, in double:
 // a few dozen flops against S samples of traffic), park what the samples need in LDS, then sweep the samples in memory order.
+// The dense and the compact entry points run the same four kernels, scene_samples_fwd / _bwd_kernel and scene_gather_fwd / _bwd_kernel, as
+// template <bool COMPACT> instantiations: the routes differ only in which row of the decoder's layout a pair owns (b * Nr + r | b * C + slot),
+// which flag array is written (hit | kept) and the compact forward's padding tail; scene_pair_hits_kernel and scene_samples_sum_kernel have
+// no twin.
 #include "snr_device.hpp"
 #include "snr_host.hpp"
 
@@ -126,25 +130,47 @@ __device__ __forceinline__ void park_pair(PairLds& q, const PairRay& p) {
     q.u[0] = p.u[0]; q.u[1] = p.u[1]; q.u[2] = p.u[2]; q.near = p.near; q.far = p.far;
 }
 
+// the slot of a hit pair, -1 when it is not kept: scan is only compared, a value outside [1, C] keeps nothing
+__device__ __forceinline__ int slot_of(bool hit, int32_t scan, int C) { return hit && scan >= 1 && scan <= C ? scan - 1 : -1; }
+
+// how many of an object's C slots are taken: its true count, clamped
+__device__ __forceinline__ int slots_taken(const int32_t* __restrict__ scan, long long Nr, int Nb, long long b, int C) {
+    if (Nr <= 0) return 0;
+    const int32_t n = scan[(Nr - 1) * Nb + b];
+    return n < 0 ? 0 : (n > C ? C : n);
+}
+
+// The slot a thread parks for its pair decides everything the two routes differ in.  Dense: 0 on a hit, -1 otherwise; the pair's row of the
+// decoder's layout is b * Nr + r and every row is written, a miss with sample_miss.  COMPACT: slot_of(hit, scan); the row is b * C + slot, only
+// kept pairs have one, and the workgroups of an object share out its padding slots.  `flag` is hit (dense) / kept (compact); only dense
+// fills `valid`, only compact reads `scan` and fills `pair_of_slot`.
+template <bool COMPACT>
 __global__ void __launch_bounds__(PAIRS) scene_samples_fwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
                                                                   const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels, SceneCam cam,
                                                                   const float* __restrict__ jitter, long long Nr, int Nb, int S, float adjust_scale,
-                                                                  int rend_aabb, int shapenet, float* __restrict__ xyz, float* __restrict__ viewdir,
-                                                                  float* __restrict__ z_vals, uint8_t* __restrict__ hit, uint8_t* __restrict__ valid) {
+                                                                  int rend_aabb, int shapenet, const int32_t* __restrict__ scan, int C,
+                                                                  float* __restrict__ xyz, float* __restrict__ viewdir, float* __restrict__ z_vals,
+                                                                  uint8_t* __restrict__ flag, uint8_t* __restrict__ valid,
+                                                                  int32_t* __restrict__ pair_of_slot) {
     __shared__ PairLds prm[PAIRS];
-    __shared__ uint8_t hits[PAIRS];
+    __shared__ int slots[PAIRS];
     const long long b = blockIdx.y;
     const long long r0 = (long long)blockIdx.x * PAIRS;
-    const int np = (int)(Nr - r0 < PAIRS ? Nr - r0 : PAIRS);
+    const long long left = Nr - r0;                              // (<= 0: the compact launch with Nr = 0, padding only)
+    const int np = (int)(left < 0 ? 0 : (left < PAIRS ? left : PAIRS));
+    const long long R = COMPACT ? C : Nr;                        // rows per object of the decoder's layout
     const ObjFrame f = load_object(cam2obj, wlh, rois, b);
     if ((int)threadIdx.x < np) {
         const long long r = r0 + threadIdx.x;
         const int x = pixels[2 * r], y = pixels[2 * r + 1];
         const PairRay p = make_pair(f, x, y, cam, rend_aabb != 0);
-        hits[threadIdx.x] = p.hit;
-        if (p.hit) park_pair(prm[threadIdx.x], p);
-        hit[r * Nb + b] = p.hit ? 1 : 0;
-        if (valid && b == 0) {       // some object is hit: the workgroups of object 0 look at the others too
+        const int slot = COMPACT ? slot_of(p.hit, scan[r * Nb + b], C) : (p.hit ? 0 : -1);
+        slots[threadIdx.x] = slot;
+        flag[r * Nb + b] = slot >= 0 ? 1 : 0;
+        if (slot >= 0) park_pair(prm[threadIdx.x], p);
+        if constexpr (COMPACT) {
+            if (slot >= 0) pair_of_slot[b * C + slot] = (int32_t)r;
+        } else if (valid && b == 0) {       // some object is hit: the workgroups of object 0 look at the others too
             bool any = p.hit;
             for (long long b2 = 1; b2 < Nb && !any; ++b2) any = make_pair(load_object(cam2obj, wlh, rois, b2), x, y, cam, rend_aabb != 0).hit;
             valid[r] = any ? 1 : 0;
@@ -157,14 +183,35 @@ __global__ void __launch_bounds__(PAIRS) scene_samples_fwd_kernel(const float* _
     for (long long e = threadIdx.x; e < n; e += PAIRS) {
         const int q = (int)(e / S), k = (int)(e - (long long)q * S);
         const long long r = r0 + q;
-        const long long io = ((b * Nr + r) * S + k) * 3;        // object-major: the decoder's layout
         const long long ip = (r * Nb + b) * S + k;              // pixel-major: the composite's (and the jitter's)
+        const int slot = slots[q];
         float px[3], dv[3], z;
-        if (hits[q]) sample_fwd(f, o, prm[q], k, jitter, ip, inv_s, scale, shapenet, px, dv, z);
-        else sample_miss(px, dv, z);
+        if (slot >= 0) {
+            sample_fwd(f, o, prm[q], k, jitter, ip, inv_s, scale, shapenet, px, dv, z);
+        } else {
+            sample_miss(px, dv, z);
+            if (COMPACT) { z_vals[ip] = z; continue; }          // no row to write
+        }
+        const long long io = ((b * R + (COMPACT ? slot : r)) * S + k) * 3;            // object-major: the decoder's layout
 #pragma unroll
         for (int c = 0; c < 3; ++c) { xyz[io + c] = px[c]; viewdir[io + c] = dv[c]; }
         z_vals[ip] = z;
+    }
+    if constexpr (COMPACT) {     // padding: slots taken .. C-1 of this object, an equal run of them per workgroup
+        const int taken = slots_taken(scan, Nr, Nb, b, C);
+        const int run = (C + (int)gridDim.x - 1) / (int)gridDim.x;
+        const long long lo0 = (long long)blockIdx.x * run, hi0 = lo0 + run;
+        const int lo = (int)(lo0 < taken ? taken : (lo0 > C ? C : lo0)), hi = (int)(hi0 > C ? C : hi0);
+        if (hi <= lo) return;
+        for (int sl = lo + (int)threadIdx.x; sl < hi; sl += PAIRS) pair_of_slot[b * C + sl] = -1;
+        float px[3], dv[3], z;
+        sample_miss(px, dv, z);
+        const long long m = (long long)(hi - lo) * S;
+        for (long long e = threadIdx.x; e < m; e += PAIRS) {
+            const long long io = ((b * C + lo) * S + e) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { xyz[io + c] = px[c]; viewdir[io + c] = dv[c]; }
+        }
     }
 }
 
@@ -246,25 +293,30 @@ __device__ __forceinline__ void meet_slice(double (&part)[12][PAIRS], double (&p
     }
 }
 
+// scene_samples_fwd_kernel's slot policy on the way back: d_xyz and d_viewdir are read at row b * Nr + r (dense) or b * C + slot (COMPACT);
+// the pairs of a slice, the sweep and the meeting order are one and the same, so the two routes add the same numbers in the same order
+template <bool COMPACT>
 __global__ void __launch_bounds__(PAIRS) scene_samples_bwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
                                                                   const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels, SceneCam cam,
                                                                   const float* __restrict__ jitter, long long Nr, int Nb, int S, float adjust_scale,
-                                                                  int rend_aabb, int shapenet, const float* __restrict__ d_xyz,
-                                                                  const float* __restrict__ d_viewdir, const float* __restrict__ d_z,
-                                                                  double* __restrict__ partial) {
+                                                                  int rend_aabb, int shapenet, const int32_t* __restrict__ scan, int C,
+                                                                  const float* __restrict__ d_xyz, const float* __restrict__ d_viewdir,
+                                                                  const float* __restrict__ d_z, double* __restrict__ partial) {
     __shared__ PairBwd prm[PAIRS];
-    __shared__ uint8_t hits[PAIRS];
+    __shared__ int slots[PAIRS];
     __shared__ double part[12][PAIRS];
     __shared__ double part2[12][16];
     const long long b = blockIdx.y;
     const long long r0 = (long long)blockIdx.x * PAIRS;
     const int np = (int)(Nr - r0 < PAIRS ? Nr - r0 : PAIRS);
+    const long long R = COMPACT ? C : Nr;
     const ObjFrame f = load_object(cam2obj, wlh, rois, b);
     if ((int)threadIdx.x < np) {
         const long long r = r0 + threadIdx.x;
         const PairRay p = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0);
-        hits[threadIdx.x] = p.hit;
-        if (p.hit) park_pair_bwd(prm[threadIdx.x], p);
+        const int slot = COMPACT ? slot_of(p.hit, scan[r * Nb + b], C) : (p.hit ? 0 : -1);
+        slots[threadIdx.x] = slot;
+        if (slot >= 0) park_pair_bwd(prm[threadIdx.x], p);
     }
     __syncthreads();
     const double scale = (double)adjust_scale, inv_s = 1.0 / (double)S;
@@ -274,10 +326,11 @@ __global__ void __launch_bounds__(PAIRS) scene_samples_bwd_kernel(const float* _
     const long long n = (long long)np * S;
     for (long long e = threadIdx.x; e < n; e += PAIRS) {
         const int q = (int)(e / S), k = (int)(e - (long long)q * S);
-        if (!hits[q]) continue;                                  // pairs that are not hit contribute exact zeros
+        const int slot = slots[q];
+        if (slot < 0) continue;                                  // not hit, or dropped: exact zeros
         const long long r = r0 + q;
-        sample_bwd(f, prm[q], k, jitter, ((b * Nr + r) * S + k) * 3, (r * Nb + b) * S + k, inv_s, scale, rend_aabb, shapenet, dist, d_xyz, d_viewdir,
-                   d_z, gR, gt);
+        sample_bwd(f, prm[q], k, jitter, ((b * R + (COMPACT ? slot : r)) * S + k) * 3, (r * Nb + b) * S + k, inv_s, scale, rend_aabb, shapenet, dist,
+                   d_xyz, d_viewdir, d_z, gR, gt);
     }
     meet_slice(part, part2, gR, gt, partial + (b * gridDim.x + blockIdx.x) * 12);
 }
@@ -293,17 +346,20 @@ __global__ void __launch_bounds__(64) scene_samples_sum_kernel(const double* __r
     d_cam2obj[b * 12 + threadIdx.x] = (float)sum;
 }
 
-// pixel-major rows of the decoder's object-major outputs: (0, white) where the pair is not hit
+// pixel-major rows of the decoder's object-major outputs, (0, white) where the pair has no row: dense, row b * Nr + r where `flag` = hit says
+// so; COMPACT, row b * C + slot with the slot from `flag` = kept and scan
+template <bool COMPACT>
 __global__ void __launch_bounds__(256) scene_gather_fwd_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
-                                                               const uint8_t* __restrict__ hit, long long Nr, int Nb, int S,
-                                                               float* __restrict__ sig_out, float* __restrict__ rgb_out) {
+                                                               const int32_t* __restrict__ scan, const uint8_t* __restrict__ flag, long long Nr,
+                                                               int Nb, int S, int C, float* __restrict__ sig_out, float* __restrict__ rgb_out) {
     const long long n = Nr * Nb * S;
     for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         const long long pair = e / S;
         const int k = (int)(e - pair * S);
         const long long r = pair / Nb, b = pair - r * Nb;
-        const long long src = (b * Nr + r) * S + k;
-        const bool h = hit[pair] != 0;
+        const int slot = COMPACT ? slot_of(flag[pair] != 0, scan[pair], C) : (flag[pair] != 0 ? 0 : -1);
+        const bool h = slot >= 0;
+        const long long src = (COMPACT ? b * C + (h ? slot : 0) : b * Nr + r) * S + k;
         if (sig_out) sig_out[e] = h ? sigmas[src] : 0.f;
         if (rgb_out) {
 #pragma unroll
@@ -312,17 +368,24 @@ __global__ void __launch_bounds__(256) scene_gather_fwd_kernel(const float* __re
     }
 }
 
-// the inverse scatter: object-major gradients of pixel-major ones, exact zeros where the pair is not hit
+// the inverse scatter in the destination's order, Nb * R rows: dense (R = Nr), row b * Nr + r takes pixel r where hit says so; COMPACT
+// (R = C), slot (b, s) takes pixel pair_of_slot[b][s], range-checked; exact zeros on every other row
+template <bool COMPACT>
 __global__ void __launch_bounds__(256) scene_gather_bwd_kernel(const float* __restrict__ d_sig_rows, const float* __restrict__ d_rgb_rows,
-                                                               const uint8_t* __restrict__ hit, long long Nr, int Nb, int S,
-                                                               float* __restrict__ d_sigmas, float* __restrict__ d_rgbs) {
-    const long long n = Nr * Nb * S;
+                                                               const uint8_t* __restrict__ hit, const int32_t* __restrict__ pair_of_slot,
+                                                               long long Nr, int Nb, int S, int C, float* __restrict__ d_sigmas,
+                                                               float* __restrict__ d_rgbs) {
+    const long long R = COMPACT ? C : Nr;
+    const long long n = (long long)Nb * R * S;
     for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-        const long long pair = e / S;                 // object-major: pair = b * Nr + r
-        const int k = (int)(e - pair * S);
-        const long long b = pair / Nr, r = pair - b * Nr;
+        const long long row = e / S;
+        const int k = (int)(e - row * S);
+        const long long b = row / R;
+        long long r;
+        bool h;
+        if constexpr (COMPACT) { r = pair_of_slot[row]; h = r >= 0 && r < Nr; if (!h) r = 0; }
+        else { r = row - b * R; h = hit[r * Nb + b] != 0; }
         const long long src = (r * Nb + b) * S + k;
-        const bool h = hit[r * Nb + b] != 0;
         if (d_sigmas) d_sigmas[e] = h ? d_sig_rows[src] : 0.f;
         if (d_rgbs) {
 #pragma unroll
@@ -331,8 +394,7 @@ __global__ void __launch_bounds__(256) scene_gather_bwd_kernel(const float* __re
     }
 }
 
-// ------------------------------------------------------------------------------------------------ compact route
-// the hit flags alone: what scene_samples_fwd_kernel decides, for the caller's prefix sum
+// the hit flags alone: what scene_samples_fwd_kernel decides, for the compact route's prefix sum
 __global__ void __launch_bounds__(PAIRS) scene_pair_hits_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
                                                                 const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels, SceneCam cam,
                                                                 long long Nr, int Nb, int rend_aabb, uint8_t* __restrict__ hit) {
@@ -341,157 +403,6 @@ __global__ void __launch_bounds__(PAIRS) scene_pair_hits_kernel(const float* __r
     if (r >= Nr) return;
     const ObjFrame f = load_object(cam2obj, wlh, rois, b);
     hit[r * Nb + b] = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0).hit ? 1 : 0;
-}
-
-// the slot of a hit pair, -1 when it is not kept: scan is only compared, a value outside [1, C] keeps nothing
-__device__ __forceinline__ int slot_of(bool hit, int32_t scan, int C) { return hit && scan >= 1 && scan <= C ? scan - 1 : -1; }
-
-// how many of an object's C slots are taken: its true count, clamped
-__device__ __forceinline__ int slots_taken(const int32_t* __restrict__ scan, long long Nr, int Nb, long long b, int C) {
-    if (Nr <= 0) return 0;
-    const int32_t n = scan[(Nr - 1) * Nb + b];
-    return n < 0 ? 0 : (n > C ? C : n);
-}
-
-// scene_samples_fwd_kernel with the points and directions of kept pairs at their slots; the workgroups of an object share its padding slots
-__global__ void __launch_bounds__(PAIRS) scene_samples_compact_fwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
-                                                                          const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels,
-                                                                          SceneCam cam, const float* __restrict__ jitter, long long Nr, int Nb, int S,
-                                                                          float adjust_scale, int rend_aabb, int shapenet,
-                                                                          const int32_t* __restrict__ scan, int C, float* __restrict__ xyz,
-                                                                          float* __restrict__ viewdir, float* __restrict__ z_vals,
-                                                                          uint8_t* __restrict__ kept, int32_t* __restrict__ pair_of_slot) {
-    __shared__ PairLds prm[PAIRS];
-    __shared__ int slots[PAIRS];
-    const long long b = blockIdx.y;
-    const long long r0 = (long long)blockIdx.x * PAIRS;
-    const long long left = Nr - r0;
-    const int np = (int)(left < 0 ? 0 : (left < PAIRS ? left : PAIRS));
-    const ObjFrame f = load_object(cam2obj, wlh, rois, b);
-    if ((int)threadIdx.x < np) {
-        const long long r = r0 + threadIdx.x;
-        const PairRay p = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0);
-        const int slot = slot_of(p.hit, scan[r * Nb + b], C);
-        slots[threadIdx.x] = slot;
-        kept[r * Nb + b] = slot >= 0 ? 1 : 0;
-        if (slot >= 0) {
-            park_pair(prm[threadIdx.x], p);
-            pair_of_slot[b * C + slot] = (int32_t)r;
-        }
-    }
-    __syncthreads();
-    const double o[3] = {f.t[0] / f.hd, f.t[1] / f.hd, f.t[2] / f.hd};
-    const double scale = (double)adjust_scale, inv_s = 1.0 / (double)S;
-    const long long n = (long long)np * S;
-    for (long long e = threadIdx.x; e < n; e += PAIRS) {
-        const int q = (int)(e / S), k = (int)(e - (long long)q * S);
-        const long long ip = ((r0 + q) * Nb + b) * S + k;
-        const int slot = slots[q];
-        float px[3], dv[3], z;
-        if (slot >= 0) {
-            sample_fwd(f, o, prm[q], k, jitter, ip, inv_s, scale, shapenet, px, dv, z);
-            const long long io = ((b * C + slot) * S + k) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { xyz[io + c] = px[c]; viewdir[io + c] = dv[c]; }
-        } else {
-            sample_miss(px, dv, z);
-        }
-        z_vals[ip] = z;
-    }
-    // padding: slots taken .. C-1 of this object, an equal run of them per workgroup
-    const int taken = slots_taken(scan, Nr, Nb, b, C);
-    const int run = (C + (int)gridDim.x - 1) / (int)gridDim.x;
-    const long long lo0 = (long long)blockIdx.x * run, hi0 = lo0 + run;
-    const int lo = (int)(lo0 < taken ? taken : (lo0 > C ? C : lo0)), hi = (int)(hi0 > C ? C : hi0);
-    if (hi <= lo) return;
-    for (int sl = lo + (int)threadIdx.x; sl < hi; sl += PAIRS) pair_of_slot[b * C + sl] = -1;
-    float px[3], dv[3], z;
-    sample_miss(px, dv, z);
-    const long long m = (long long)(hi - lo) * S;
-    for (long long e = threadIdx.x; e < m; e += PAIRS) {
-        const long long io = ((b * C + lo) * S + e) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { xyz[io + c] = px[c]; viewdir[io + c] = dv[c]; }
-    }
-}
-
-// scene_samples_bwd_kernel reading d_xyz and d_viewdir at the slot: the same pairs per slice, the same sweep, the same meeting order
-__global__ void __launch_bounds__(PAIRS) scene_samples_compact_bwd_kernel(const float* __restrict__ cam2obj, const float* __restrict__ wlh,
-                                                                          const int32_t* __restrict__ rois, const int32_t* __restrict__ pixels,
-                                                                          SceneCam cam, const float* __restrict__ jitter, long long Nr, int Nb, int S,
-                                                                          float adjust_scale, int rend_aabb, int shapenet,
-                                                                          const int32_t* __restrict__ scan, int C, const float* __restrict__ d_xyz,
-                                                                          const float* __restrict__ d_viewdir, const float* __restrict__ d_z,
-                                                                          double* __restrict__ partial) {
-    __shared__ PairBwd prm[PAIRS];
-    __shared__ int slots[PAIRS];
-    __shared__ double part[12][PAIRS];
-    __shared__ double part2[12][16];
-    const long long b = blockIdx.y;
-    const long long r0 = (long long)blockIdx.x * PAIRS;
-    const int np = (int)(Nr - r0 < PAIRS ? Nr - r0 : PAIRS);
-    const ObjFrame f = load_object(cam2obj, wlh, rois, b);
-    if ((int)threadIdx.x < np) {
-        const long long r = r0 + threadIdx.x;
-        const PairRay p = make_pair(f, pixels[2 * r], pixels[2 * r + 1], cam, rend_aabb != 0);
-        const int slot = slot_of(p.hit, scan[r * Nb + b], C);
-        slots[threadIdx.x] = slot;
-        if (slot >= 0) park_pair_bwd(prm[threadIdx.x], p);
-    }
-    __syncthreads();
-    const double scale = (double)adjust_scale, inv_s = 1.0 / (double)S;
-    double dist = 1.0;
-    if (!rend_aabb) dist = sqrt(f.t[0] * f.t[0] + f.t[1] * f.t[1] + f.t[2] * f.t[2]);
-    double gR[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.}, gt[3] = {0., 0., 0.};
-    const long long n = (long long)np * S;
-    for (long long e = threadIdx.x; e < n; e += PAIRS) {
-        const int q = (int)(e / S), k = (int)(e - (long long)q * S);
-        const int slot = slots[q];
-        if (slot < 0) continue;                                  // not hit, or dropped: exact zeros
-        sample_bwd(f, prm[q], k, jitter, ((b * C + slot) * S + k) * 3, ((r0 + q) * Nb + b) * S + k, inv_s, scale, rend_aabb, shapenet, dist, d_xyz,
-                   d_viewdir, d_z, gR, gt);
-    }
-    meet_slice(part, part2, gR, gt, partial + (b * gridDim.x + blockIdx.x) * 12);
-}
-
-// pixel-major rows of the decoder's compact outputs: a kept pair's rows from its slot, (0, white) on every other pair
-__global__ void __launch_bounds__(256) scene_gather_compact_fwd_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
-                                                                       const int32_t* __restrict__ scan, const uint8_t* __restrict__ kept,
-                                                                       long long Nr, int Nb, int S, int C, float* __restrict__ sig_out,
-                                                                       float* __restrict__ rgb_out) {
-    const long long n = Nr * Nb * S;
-    for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-        const long long pair = e / S;
-        const int k = (int)(e - pair * S);
-        const long long b = pair % Nb;
-        const int slot = slot_of(kept[pair] != 0, scan[pair], C);
-        const long long src = ((b * C + (slot < 0 ? 0 : slot)) * S + k);
-        if (sig_out) sig_out[e] = slot >= 0 ? sigmas[src] : 0.f;
-        if (rgb_out) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) rgb_out[3 * e + c] = slot >= 0 ? rgbs[3 * src + c] : 1.f;
-        }
-    }
-}
-
-// the inverse scatter in the destination's order: slot (b, s) takes the gradients of pixel pair_of_slot[b][s], padding exact zeros
-__global__ void __launch_bounds__(256) scene_gather_compact_bwd_kernel(const float* __restrict__ d_sig_rows, const float* __restrict__ d_rgb_rows,
-                                                                       const int32_t* __restrict__ pair_of_slot, long long Nr, int Nb, int S, int C,
-                                                                       float* __restrict__ d_sigmas, float* __restrict__ d_rgbs) {
-    const long long n = (long long)Nb * C * S;
-    for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-        const long long row = e / S;                 // row = b * C + slot
-        const int k = (int)(e - row * S);
-        const long long b = row / C;
-        const long long r = pair_of_slot[row];
-        const bool h = r >= 0 && r < Nr;
-        const long long src = ((h ? r : 0) * Nb + b) * S + k;
-        if (d_sigmas) d_sigmas[e] = h ? d_sig_rows[src] : 0.f;
-        if (d_rgbs) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) d_rgbs[3 * e + c] = h ? d_rgb_rows[3 * src + c] : 0.f;
-        }
-    }
 }
 
 inline long long scene_slices(long long Nr) { return (Nr + PAIRS - 1) / PAIRS; }
@@ -506,6 +417,25 @@ inline bool scene_capacity_ok(long long C, long long Nb, int S) { return C >= 1 
 
 using namespace snr;
 
+// The backward's two launches, after an entry point's own argument checks: the workspace, every slice's 12 sums, then every object's slices
+// added in slice order.
+template <bool COMPACT>
+static int scene_samples_bwd_run(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, SceneCam cam, const float* jitter,
+                                 int64_t n_pixels, int64_t n_objects, int n_samples, float adjust_scale, int rend_aabb, int shapenet,
+                                 const int32_t* scan, int C, const float* d_xyz, const float* d_viewdir, const float* d_z, float* d_cam2obj, void* ws,
+                                 size_t ws_bytes, hipStream_t stream) {
+    if (((uintptr_t)ws & 7) != 0) return SNR_E_ARG;
+    if (ws_bytes < snr_scene_samples_bwd_ws_bytes(n_pixels, n_objects)) return SNR_E_WORKSPACE;
+    const long long slices = scene_slices(n_pixels);
+    scene_samples_bwd_kernel<COMPACT><<<dim3((unsigned)slices, (unsigned)n_objects), PAIRS, 0, stream>>>(
+        cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet, scan, C, d_xyz, d_viewdir, d_z,
+        (double*)ws);
+    const int rc = snr_check_launch_();
+    if (rc != SNR_OK) return rc;
+    scene_samples_sum_kernel<<<(unsigned)n_objects, 64, 0, stream>>>((const double*)ws, slices, d_cam2obj);
+    return snr_check_launch_();
+}
+
 extern "C" {
 
 int snr_scene_samples_fwd(const float* cam2obj, const float* wlh, const int32_t* rois, const int32_t* pixels, float fx, float fy, float cx, float cy,
@@ -515,9 +445,9 @@ int snr_scene_samples_fwd(const float* cam2obj, const float* wlh, const int32_t*
     if (!scene_sizes_ok(n_pixels, n_objects, n_samples)) return SNR_E_ARG;
     if (!cam2obj || !wlh || !rois || !pixels || !xyz || !viewdir || !z_vals || !hit) return SNR_E_ARG;
     const SceneCam cam = {fx, fy, cx, cy};
-    scene_samples_fwd_kernel<<<dim3((unsigned)scene_slices(n_pixels), (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
-        cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, xyz, viewdir, z_vals,
-        hit, valid);
+    scene_samples_fwd_kernel<false><<<dim3((unsigned)scene_slices(n_pixels), (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
+        cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, nullptr, 0, xyz,
+        viewdir, z_vals, hit, valid, nullptr);
     return snr_check_launch_();
 }
 
@@ -533,17 +463,8 @@ int snr_scene_samples_bwd(const float* cam2obj, const float* wlh, const int32_t*
     if (n_pixels == 0) return SNR_OK;
     if (!scene_sizes_ok(n_pixels, n_objects, n_samples)) return SNR_E_ARG;
     if (!cam2obj || !wlh || !rois || !pixels || !d_cam2obj || !ws) return SNR_E_ARG;
-    if (((uintptr_t)ws & 7) != 0) return SNR_E_ARG;
-    if (ws_bytes < snr_scene_samples_bwd_ws_bytes(n_pixels, n_objects)) return SNR_E_WORKSPACE;
-    const SceneCam cam = {fx, fy, cx, cy};
-    const long long slices = scene_slices(n_pixels);
-    scene_samples_bwd_kernel<<<dim3((unsigned)slices, (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
-        cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, d_xyz, d_viewdir, d_z,
-        (double*)ws);
-    const int rc = snr_check_launch_();
-    if (rc != SNR_OK) return rc;
-    scene_samples_sum_kernel<<<(unsigned)n_objects, 64, 0, (hipStream_t)stream>>>((const double*)ws, slices, d_cam2obj);
-    return snr_check_launch_();
+    return scene_samples_bwd_run<false>(cam2obj, wlh, rois, pixels, {fx, fy, cx, cy}, jitter, n_pixels, n_objects, n_samples, adjust_scale, rend_aabb,
+                                        shapenet_obj_cood, nullptr, 0, d_xyz, d_viewdir, d_z, d_cam2obj, ws, ws_bytes, (hipStream_t)stream);
 }
 
 static unsigned gather_grid(long long n) {
@@ -556,8 +477,8 @@ int snr_scene_gather_fwd(const float* sigmas, const float* rgbs, const uint8_t* 
     if (n_pixels == 0) return SNR_OK;
     if (!scene_sizes_ok(n_pixels, n_objects, n_samples)) return SNR_E_ARG;
     if (!hit || (sigma_rows && !sigmas) || (rgb_rows && !rgbs) || (!sigma_rows && !rgb_rows)) return SNR_E_ARG;
-    scene_gather_fwd_kernel<<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(sigmas, rgbs, hit, n_pixels, (int)n_objects,
-                                                                                                          n_samples, sigma_rows, rgb_rows);
+    scene_gather_fwd_kernel<false><<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(
+        sigmas, rgbs, nullptr, hit, n_pixels, (int)n_objects, n_samples, 0, sigma_rows, rgb_rows);
     return snr_check_launch_();
 }
 
@@ -566,8 +487,8 @@ int snr_scene_gather_bwd(const float* d_sigma_rows, const float* d_rgb_rows, con
     if (n_pixels == 0) return SNR_OK;
     if (!scene_sizes_ok(n_pixels, n_objects, n_samples)) return SNR_E_ARG;
     if (!hit || (d_sigmas && !d_sigma_rows) || (d_rgbs && !d_rgb_rows) || (!d_sigmas && !d_rgbs)) return SNR_E_ARG;
-    scene_gather_bwd_kernel<<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(d_sigma_rows, d_rgb_rows, hit, n_pixels,
-                                                                                                          (int)n_objects, n_samples, d_sigmas, d_rgbs);
+    scene_gather_bwd_kernel<false><<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(
+        d_sigma_rows, d_rgb_rows, hit, nullptr, n_pixels, (int)n_objects, n_samples, 0, d_sigmas, d_rgbs);
     return snr_check_launch_();
 }
 
@@ -591,9 +512,9 @@ int snr_scene_samples_compact_fwd(const float* cam2obj, const float* wlh, const 
     if (n_pixels > 0 && (!pixels || !hit_scan || !z_vals || !kept)) return SNR_E_ARG;
     const SceneCam cam = {fx, fy, cx, cy};
     const long long slices = scene_slices(n_pixels);
-    scene_samples_compact_fwd_kernel<<<dim3((unsigned)(slices < 1 ? 1 : slices), (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
+    scene_samples_fwd_kernel<true><<<dim3((unsigned)(slices < 1 ? 1 : slices), (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
         cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, hit_scan,
-        (int)capacity, xyz, viewdir, z_vals, kept, pair_of_slot);
+        (int)capacity, xyz, viewdir, z_vals, kept, nullptr, pair_of_slot);
     return snr_check_launch_();
 }
 
@@ -604,17 +525,8 @@ int snr_scene_samples_compact_bwd(const float* cam2obj, const float* wlh, const 
     if (!scene_sizes_ok(n_pixels, n_objects, n_samples) || !scene_capacity_ok(capacity, n_objects, n_samples)) return SNR_E_ARG;
     if (n_pixels == 0) return SNR_OK;
     if (!cam2obj || !wlh || !rois || !pixels || !hit_scan || !d_cam2obj || !ws) return SNR_E_ARG;
-    if (((uintptr_t)ws & 7) != 0) return SNR_E_ARG;
-    if (ws_bytes < snr_scene_samples_bwd_ws_bytes(n_pixels, n_objects)) return SNR_E_WORKSPACE;
-    const SceneCam cam = {fx, fy, cx, cy};
-    const long long slices = scene_slices(n_pixels);
-    scene_samples_compact_bwd_kernel<<<dim3((unsigned)slices, (unsigned)n_objects), PAIRS, 0, (hipStream_t)stream>>>(
-        cam2obj, wlh, rois, pixels, cam, jitter, n_pixels, (int)n_objects, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood, hit_scan,
-        (int)capacity, d_xyz, d_viewdir, d_z, (double*)ws);
-    const int rc = snr_check_launch_();
-    if (rc != SNR_OK) return rc;
-    scene_samples_sum_kernel<<<(unsigned)n_objects, 64, 0, (hipStream_t)stream>>>((const double*)ws, slices, d_cam2obj);
-    return snr_check_launch_();
+    return scene_samples_bwd_run<true>(cam2obj, wlh, rois, pixels, {fx, fy, cx, cy}, jitter, n_pixels, n_objects, n_samples, adjust_scale, rend_aabb,
+                                       shapenet_obj_cood, hit_scan, (int)capacity, d_xyz, d_viewdir, d_z, d_cam2obj, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int snr_scene_gather_compact_fwd(const float* sigmas, const float* rgbs, const int32_t* hit_scan, const uint8_t* kept, int64_t n_pixels,
@@ -622,7 +534,7 @@ int snr_scene_gather_compact_fwd(const float* sigmas, const float* rgbs, const i
     if (!scene_sizes_ok(n_pixels, n_objects, n_samples) || !scene_capacity_ok(capacity, n_objects, n_samples)) return SNR_E_ARG;
     if (n_pixels == 0) return SNR_OK;
     if (!hit_scan || !kept || (sigma_rows && !sigmas) || (rgb_rows && !rgbs) || (!sigma_rows && !rgb_rows)) return SNR_E_ARG;
-    scene_gather_compact_fwd_kernel<<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(
+    scene_gather_fwd_kernel<true><<<gather_grid(n_pixels * n_objects * n_samples), 256, 0, (hipStream_t)stream>>>(
         sigmas, rgbs, hit_scan, kept, n_pixels, (int)n_objects, n_samples, (int)capacity, sigma_rows, rgb_rows);
     return snr_check_launch_();
 }
@@ -632,8 +544,8 @@ int snr_scene_gather_compact_bwd(const float* d_sigma_rows, const float* d_rgb_r
     if (!scene_sizes_ok(n_pixels, n_objects, n_samples) || !scene_capacity_ok(capacity, n_objects, n_samples)) return SNR_E_ARG;
     if (!pair_of_slot || (!d_sigmas && !d_rgbs)) return SNR_E_ARG;
     if (n_pixels > 0 && ((d_sigmas && !d_sigma_rows) || (d_rgbs && !d_rgb_rows))) return SNR_E_ARG;
-    scene_gather_compact_bwd_kernel<<<gather_grid(n_objects * capacity * n_samples), 256, 0, (hipStream_t)stream>>>(
-        d_sigma_rows, d_rgb_rows, pair_of_slot, n_pixels, (int)n_objects, n_samples, (int)capacity, d_sigmas, d_rgbs);
+    scene_gather_bwd_kernel<true><<<gather_grid(n_objects * capacity * n_samples), 256, 0, (hipStream_t)stream>>>(
+        d_sigma_rows, d_rgb_rows, nullptr, pair_of_slot, n_pixels, (int)n_objects, n_samples, (int)capacity, d_sigmas, d_rgbs);
     return snr_check_launch_();
 }
 

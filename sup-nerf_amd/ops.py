@@ -221,9 +221,7 @@ def scene_composite(sigmas, rgbs, z_vals, white_bkgd=True, run_length=0):
     every object's S samples are contiguous and ascending, so it merges the lists instead of rank-sorting (verified per pixel, see the header)."""
     sigmas, rgbs, z_vals = _f32c(sigmas), _f32c(rgbs), _f32c(z_vals)
     _need_gpu(sigmas, rgbs, z_vals)
-    if sigmas.dim() != 2 or rgbs.shape != (*sigmas.shape, 3) or z_vals.shape != sigmas.shape:
-        raise SnrError(f"scene_composite: expected sigmas/z (P,n) and rgbs (P,n,3), got {tuple(sigmas.shape)}, {tuple(z_vals.shape)}, {tuple(rgbs.shape)}")
-    P, n = sigmas.shape
+    P, n = _scene_shapes("scene_composite", sigmas, rgbs, z_vals)
     dev = sigmas.device
     rgb = torch.empty(P, 3, device=dev); depth = torch.empty(P, device=dev); acc = torch.empty(P, device=dev)
     with torch.cuda.device(dev):
@@ -305,6 +303,67 @@ def _scene_lists(name, cam2obj, wlh, rois, pixels, jitter, S):
     return Nr, Nb
 
 
+def _scene_samples_fwd(ctx, name, cam2obj, wlh, rois, pixels, Kvec, jitter, S, adjust_scale, rend_aabb, shapenet_obj_cood, hit_scan=None, capacity=None):
+    """Forward of ``SceneSamples`` and, with ``hit_scan`` and ``capacity``, of ``SceneSamplesCompact``: R = Nr or capacity rows per object
+    -> xyz, viewdir (Nb*R,S,3), z_vals (Nr,Nb*S), the pair flags (Nr,Nb) uint8, and valid (Nr) uint8 or pair_of_slot (Nb,capacity) int32."""
+    compact = hit_scan is not None
+    cam2obj, wlh, jitter = _f32c(cam2obj), _f32c(wlh), _f32c(jitter)
+    Nr, Nb = _scene_lists(name, cam2obj, wlh, rois, pixels, jitter, S)
+    if len(Kvec) != 4:
+        raise SnrError(f"{name}: Kvec is (fx, fy, cx, cy)")
+    if compact:
+        cap = _scene_capacity_arg(name, capacity)
+        hit_scan = _scene_scan(name, hit_scan, Nr, Nb)
+    _need_gpu(cam2obj, wlh, rois, pixels, jitter, hit_scan)
+    rois, pixels = rois.contiguous(), pixels.contiguous()
+    cfg = (*[float(v) for v in Kvec], int(S), float(adjust_scale), int(bool(rend_aabb)), int(bool(shapenet_obj_cood)))
+    S = cfg[4]
+    dev = cam2obj.device
+    ctx.set_materialize_grads(False)        # (the kernel takes null for the gradients of outputs that were not used)
+    R = cap if compact else Nr
+    xyz, viewdir = torch.empty(Nb * R, S, 3, device=dev), torch.empty(Nb * R, S, 3, device=dev)
+    z = torch.empty(Nr, Nb * S, device=dev)
+    flag = torch.empty(Nr, Nb, dtype=torch.uint8, device=dev)
+    last = torch.empty(Nb, cap, dtype=torch.int32, device=dev) if compact else torch.empty(Nr, dtype=torch.uint8, device=dev)
+    lists = (_p(cam2obj), _p(wlh), _p(rois), _p(pixels), *cfg[:4], _p(jitter), Nr, Nb, *cfg[4:])
+    outs = (_p(xyz), _p(viewdir), _p(z), _p(flag), _p(last))
+    with torch.cuda.device(dev):
+        if compact:
+            check(_lib.lib().snr_scene_samples_compact_fwd(*lists, _p(hit_scan), cap, *outs, _stream(dev)), "snr_scene_samples_compact_fwd")
+        else:
+            check(_lib.lib().snr_scene_samples_fwd(*lists, *outs, _stream(dev)), "snr_scene_samples_fwd")
+    ctx.save_for_backward(cam2obj, wlh, rois, pixels, jitter, *((hit_scan,) if compact else ()))
+    ctx.cfg = cfg + ((cap,) if compact else ())
+    ctx.mark_non_differentiable(flag, last)
+    return xyz, viewdir, z, flag, last
+
+
+def _scene_samples_bwd(ctx, name, n_inputs, d_xyz, d_viewdir, d_z):
+    """Backward of both sample classes to cam2obj, one gradient slot per forward input; the compact one saved ``hit_scan`` and the capacity."""
+    cam2obj, wlh, rois, pixels, jitter, *hit_scan = ctx.saved_tensors
+    if ctx.needs_input_grad[1] or ctx.needs_input_grad[5]:
+        raise SnrError(f"{name}: the box sizes and the jitter are data, no gradient is provided")
+    if not ctx.needs_input_grad[0] or (d_xyz is None and d_viewdir is None and d_z is None):
+        return (None,) * n_inputs
+    *cfg, cap = ctx.cfg if hit_scan else (*ctx.cfg, None)
+    Nr, Nb = pixels.shape[0], cam2obj.shape[0]
+    dev = cam2obj.device
+    d_xyz, d_viewdir, d_z = _f32c(d_xyz), _f32c(d_viewdir), _f32c(d_z)       # NAMED: they live until the launch is enqueued (see composite_bwd)
+    if Nr == 0:
+        return (torch.zeros_like(cam2obj),) + (None,) * (n_inputs - 1)
+    d_cam2obj = torch.empty_like(cam2obj)
+    n_ws = int(_lib.lib().snr_scene_samples_bwd_ws_bytes(Nr, Nb))
+    ws = torch.empty(n_ws // 8, dtype=torch.float64, device=dev)
+    lists = (_p(cam2obj), _p(wlh), _p(rois), _p(pixels), *cfg[:4], _p(jitter), Nr, Nb, *cfg[4:])
+    grads = (_p(d_xyz), _p(d_viewdir), _p(d_z), _p(d_cam2obj), _p(ws), n_ws)
+    with torch.cuda.device(dev):
+        if hit_scan:
+            check(_lib.lib().snr_scene_samples_compact_bwd(*lists, _p(hit_scan[0]), cap, *grads, _stream(dev)), "snr_scene_samples_compact_bwd")
+        else:
+            check(_lib.lib().snr_scene_samples_bwd(*lists, *grads, _stream(dev)), "snr_scene_samples_bwd")
+    return (d_cam2obj,) + (None,) * (n_inputs - 1)
+
+
 class SceneSamples(torch.autograd.Function):
     """Rays, bounds and samples of every (pixel, object) pair of a scene in one launch (snr_scene_samples_fwd; rules: include/supnerf_hip.h):
     cam2obj (Nb,3,4) [differentiable], wlh (Nb,3), rois (Nb,4) int32, pixels (Nr,2) int32, Kvec = (fx, fy, cx, cy) host numbers, jitter
@@ -313,49 +372,71 @@ class SceneSamples(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cam2obj, wlh, rois, pixels, Kvec, jitter, S, adjust_scale, rend_aabb, shapenet_obj_cood):
-        cam2obj, wlh, jitter = _f32c(cam2obj), _f32c(wlh), _f32c(jitter)
-        Nr, Nb = _scene_lists("scene_samples", cam2obj, wlh, rois, pixels, jitter, S)
-        if len(Kvec) != 4:
-            raise SnrError("scene_samples: Kvec is (fx, fy, cx, cy)")
-        _need_gpu(cam2obj, wlh, rois, pixels, jitter)
-        rois, pixels = rois.contiguous(), pixels.contiguous()
-        cfg = (*[float(v) for v in Kvec], int(S), float(adjust_scale), int(bool(rend_aabb)), int(bool(shapenet_obj_cood)))
-        fx, fy, cx, cy, S = cfg[:5]
-        dev = cam2obj.device
-        ctx.set_materialize_grads(False)        # (the kernel takes null for the gradients of outputs that were not used)
-        xyz, viewdir = torch.empty(Nb * Nr, S, 3, device=dev), torch.empty(Nb * Nr, S, 3, device=dev)
-        z = torch.empty(Nr, Nb * S, device=dev)
-        hit = torch.empty(Nr, Nb, dtype=torch.uint8, device=dev)
-        valid = torch.empty(Nr, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().snr_scene_samples_fwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, cfg[5], cfg[6],
-                                                   cfg[7], _p(xyz), _p(viewdir), _p(z), _p(hit), _p(valid), _stream(dev)), "snr_scene_samples_fwd")
-        ctx.save_for_backward(cam2obj, wlh, rois, pixels, jitter)
-        ctx.cfg = cfg
-        ctx.mark_non_differentiable(hit, valid)
-        return xyz, viewdir, z, hit, valid
+        return _scene_samples_fwd(ctx, "scene_samples", cam2obj, wlh, rois, pixels, Kvec, jitter, S, adjust_scale, rend_aabb, shapenet_obj_cood)
 
     @staticmethod
     def backward(ctx, d_xyz, d_viewdir, d_z, _d_hit, _d_valid):
-        cam2obj, wlh, rois, pixels, jitter = ctx.saved_tensors
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[5]:
-            raise SnrError("scene_samples: the box sizes and the jitter are data, no gradient is provided")
-        if not ctx.needs_input_grad[0] or (d_xyz is None and d_viewdir is None and d_z is None):
-            return (None,) * 10
-        fx, fy, cx, cy, S, scale, aabb, shapenet = ctx.cfg
-        Nr, Nb = pixels.shape[0], cam2obj.shape[0]
-        dev = cam2obj.device
-        d_xyz, d_viewdir, d_z = _f32c(d_xyz), _f32c(d_viewdir), _f32c(d_z)
-        if Nr == 0:
-            return (torch.zeros_like(cam2obj),) + (None,) * 9
-        d_cam2obj = torch.empty_like(cam2obj)
-        n_ws = int(_lib.lib().snr_scene_samples_bwd_ws_bytes(Nr, Nb))
-        ws = torch.empty(n_ws // 8, dtype=torch.float64, device=dev)
+        return _scene_samples_bwd(ctx, "scene_samples", 10, d_xyz, d_viewdir, d_z)
+
+
+def _scene_gather_fwd(ctx, sigmas, rgbs, flag, S, hit_scan=None, pair_of_slot=None):
+    """Forward of ``SceneGather`` (``flag`` = hit) and, with ``hit_scan`` and ``pair_of_slot``, of ``SceneGatherCompact`` (``flag`` = kept): the
+    decoder's Nb*R*S values, R = Nr or C -> rows (Nr,Nb*S) / (Nr,Nb*S,3)."""
+    compact = pair_of_slot is not None
+    sigmas, rgbs = _f32c(sigmas), _f32c(rgbs)
+    S = int(S)
+    ok = flag.dim() == 2 and flag.dtype == torch.uint8 and S >= 1 and (not compact or (pair_of_slot.dim() == 2 and pair_of_slot.dtype == torch.int32))
+    if ok:
+        Nr, Nb = flag.shape
+        R = pair_of_slot.shape[1] if compact else Nr
+        ok = (not compact or (pair_of_slot.shape[0] == Nb and Nb >= 1)) and sigmas.numel() == Nb * R * S and rgbs.numel() == 3 * sigmas.numel()
+    if not ok and compact:
+        raise SnrError(f"scene_gather_compact: expected sigmas (Nb*C*S), rgbs (Nb*C*S,3), kept (Nr,Nb) uint8 and pair_of_slot (Nb,C) int32, got "
+                       f"{tuple(sigmas.shape)}, {tuple(rgbs.shape)}, {tuple(flag.shape)} {flag.dtype}, {tuple(pair_of_slot.shape)} "
+                       f"{pair_of_slot.dtype}, S = {S}")
+    if not ok:
+        raise SnrError(f"scene_gather: expected sigmas (Nb*Nr*S), rgbs (Nb*Nr*S,3) and hit (Nr,Nb) uint8, got {tuple(sigmas.shape)}, "
+                       f"{tuple(rgbs.shape)}, {tuple(flag.shape)} {flag.dtype}, S = {S}")
+    if compact:
+        cap = _scene_capacity_arg("scene_gather_compact", R)
+        hit_scan = _scene_scan("scene_gather_compact", hit_scan, Nr, Nb)
+        pair_of_slot = pair_of_slot.contiguous()
+    _need_gpu(sigmas, rgbs, hit_scan, flag, pair_of_slot)
+    flag = flag.contiguous()
+    dev = sigmas.device
+    ctx.set_materialize_grads(False)
+    sig_rows, rgb_rows = torch.empty(Nr, Nb * S, device=dev), torch.empty(Nr, Nb * S, 3, device=dev)
+    with torch.cuda.device(dev):
+        if compact:
+            check(_lib.lib().snr_scene_gather_compact_fwd(_p(sigmas), _p(rgbs), _p(hit_scan), _p(flag), Nr, Nb, S, cap, _p(sig_rows), _p(rgb_rows),
+                                                          _stream(dev)), "snr_scene_gather_compact_fwd")
+        else:
+            check(_lib.lib().snr_scene_gather_fwd(_p(sigmas), _p(rgbs), _p(flag), Nr, Nb, S, _p(sig_rows), _p(rgb_rows), _stream(dev)),
+                  "snr_scene_gather_fwd")
+    ctx.save_for_backward(pair_of_slot if compact else flag)
+    ctx.cfg = (S, Nr, sigmas.shape, rgbs.shape)
+    return sig_rows, rgb_rows
+
+
+def _scene_gather_bwd(ctx, d_sig_rows, d_rgb_rows, compact):
+    """Backward of both gather classes: the inverse scatter through the saved hit (Nr,Nb) or, ``compact``, pair_of_slot (Nb,C)."""
+    saved, = ctx.saved_tensors
+    S, Nr, sig_shape, rgb_shape = ctx.cfg
+    Nb = saved.shape[0 if compact else 1]
+    dev = saved.device
+    d_sig_rows = _f32c(d_sig_rows) if ctx.needs_input_grad[0] else None          # NAMED, as in composite_bwd
+    d_rgb_rows = _f32c(d_rgb_rows) if ctx.needs_input_grad[1] else None
+    d_sig = torch.empty(sig_shape, device=dev) if d_sig_rows is not None else None
+    d_rgb = torch.empty(rgb_shape, device=dev) if d_rgb_rows is not None else None
+    if d_sig is not None or d_rgb is not None:
         with torch.cuda.device(dev):
-            check(_lib.lib().snr_scene_samples_bwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, scale, aabb,
-                                                   shapenet, _p(d_xyz), _p(d_viewdir), _p(d_z), _p(d_cam2obj), _p(ws), n_ws, _stream(dev)),
-                  "snr_scene_samples_bwd")
-        return (d_cam2obj,) + (None,) * 9
+            if compact:
+                check(_lib.lib().snr_scene_gather_compact_bwd(_p(d_sig_rows), _p(d_rgb_rows), _p(saved), Nr, Nb, S, saved.shape[1], _p(d_sig),
+                                                              _p(d_rgb), _stream(dev)), "snr_scene_gather_compact_bwd")
+            else:
+                check(_lib.lib().snr_scene_gather_bwd(_p(d_sig_rows), _p(d_rgb_rows), _p(saved), Nr, Nb, S, _p(d_sig), _p(d_rgb), _stream(dev)),
+                      "snr_scene_gather_bwd")
+    return d_sig, d_rgb
 
 
 class SceneGather(torch.autograd.Function):
@@ -365,39 +446,11 @@ class SceneGather(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigmas, rgbs, hit, S):
-        sigmas, rgbs = _f32c(sigmas), _f32c(rgbs)
-        S = int(S)
-        if hit.dim() != 2 or hit.dtype != torch.uint8 or S < 1 or sigmas.numel() != hit.numel() * S or rgbs.numel() != 3 * sigmas.numel():
-            raise SnrError(f"scene_gather: expected sigmas (Nb*Nr*S), rgbs (Nb*Nr*S,3) and hit (Nr,Nb) uint8, got {tuple(sigmas.shape)}, "
-                           f"{tuple(rgbs.shape)}, {tuple(hit.shape)} {hit.dtype}, S = {S}")
-        _need_gpu(sigmas, rgbs, hit)
-        hit = hit.contiguous()
-        Nr, Nb = hit.shape
-        dev = sigmas.device
-        ctx.set_materialize_grads(False)
-        sig_rows, rgb_rows = torch.empty(Nr, Nb * S, device=dev), torch.empty(Nr, Nb * S, 3, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().snr_scene_gather_fwd(_p(sigmas), _p(rgbs), _p(hit), Nr, Nb, S, _p(sig_rows), _p(rgb_rows), _stream(dev)),
-                  "snr_scene_gather_fwd")
-        ctx.save_for_backward(hit)
-        ctx.cfg = (S, sigmas.shape, rgbs.shape)
-        return sig_rows, rgb_rows
+        return _scene_gather_fwd(ctx, sigmas, rgbs, hit, S)
 
     @staticmethod
     def backward(ctx, d_sig_rows, d_rgb_rows):
-        hit, = ctx.saved_tensors
-        S, sig_shape, rgb_shape = ctx.cfg
-        Nr, Nb = hit.shape
-        dev = hit.device
-        d_sig_rows = _f32c(d_sig_rows) if ctx.needs_input_grad[0] else None
-        d_rgb_rows = _f32c(d_rgb_rows) if ctx.needs_input_grad[1] else None
-        d_sig = torch.empty(sig_shape, device=dev) if d_sig_rows is not None else None
-        d_rgb = torch.empty(rgb_shape, device=dev) if d_rgb_rows is not None else None
-        if d_sig is not None or d_rgb is not None:
-            with torch.cuda.device(dev):
-                check(_lib.lib().snr_scene_gather_bwd(_p(d_sig_rows), _p(d_rgb_rows), _p(hit), Nr, Nb, S, _p(d_sig), _p(d_rgb), _stream(dev)),
-                      "snr_scene_gather_bwd")
-        return d_sig, d_rgb, None, None
+        return (*_scene_gather_bwd(ctx, d_sig_rows, d_rgb_rows, False), None, None)
 
 
 def scene_capacity(n) -> int:
@@ -448,52 +501,12 @@ class SceneSamplesCompact(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cam2obj, wlh, rois, pixels, Kvec, jitter, S, adjust_scale, rend_aabb, shapenet_obj_cood, hit_scan, capacity):
-        cam2obj, wlh, jitter = _f32c(cam2obj), _f32c(wlh), _f32c(jitter)
-        Nr, Nb = _scene_lists("scene_samples_compact", cam2obj, wlh, rois, pixels, jitter, S)
-        if len(Kvec) != 4:
-            raise SnrError("scene_samples_compact: Kvec is (fx, fy, cx, cy)")
-        cap = _scene_capacity_arg("scene_samples_compact", capacity)
-        hit_scan = _scene_scan("scene_samples_compact", hit_scan, Nr, Nb)
-        _need_gpu(cam2obj, wlh, rois, pixels, jitter, hit_scan)
-        rois, pixels = rois.contiguous(), pixels.contiguous()
-        cfg = (*[float(v) for v in Kvec], int(S), float(adjust_scale), int(bool(rend_aabb)), int(bool(shapenet_obj_cood)), cap)
-        fx, fy, cx, cy, S = cfg[:5]
-        dev = cam2obj.device
-        ctx.set_materialize_grads(False)
-        xyz, viewdir = torch.empty(Nb * cap, S, 3, device=dev), torch.empty(Nb * cap, S, 3, device=dev)
-        z = torch.empty(Nr, Nb * S, device=dev)
-        kept = torch.empty(Nr, Nb, dtype=torch.uint8, device=dev)
-        pair_of_slot = torch.empty(Nb, cap, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().snr_scene_samples_compact_fwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, cfg[5],
-                                                           cfg[6], cfg[7], _p(hit_scan), cap, _p(xyz), _p(viewdir), _p(z), _p(kept),
-                                                           _p(pair_of_slot), _stream(dev)), "snr_scene_samples_compact_fwd")
-        ctx.save_for_backward(cam2obj, wlh, rois, pixels, jitter, hit_scan)
-        ctx.cfg = cfg
-        ctx.mark_non_differentiable(kept, pair_of_slot)
-        return xyz, viewdir, z, kept, pair_of_slot
+        return _scene_samples_fwd(ctx, "scene_samples_compact", cam2obj, wlh, rois, pixels, Kvec, jitter, S, adjust_scale, rend_aabb, shapenet_obj_cood,
+                                  hit_scan, capacity)
 
     @staticmethod
     def backward(ctx, d_xyz, d_viewdir, d_z, _d_kept, _d_slots):
-        cam2obj, wlh, rois, pixels, jitter, hit_scan = ctx.saved_tensors
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[5]:
-            raise SnrError("scene_samples_compact: the box sizes and the jitter are data, no gradient is provided")
-        if not ctx.needs_input_grad[0] or (d_xyz is None and d_viewdir is None and d_z is None):
-            return (None,) * 12
-        fx, fy, cx, cy, S, scale, aabb, shapenet, cap = ctx.cfg
-        Nr, Nb = pixels.shape[0], cam2obj.shape[0]
-        dev = cam2obj.device
-        d_xyz, d_viewdir, d_z = _f32c(d_xyz), _f32c(d_viewdir), _f32c(d_z)
-        if Nr == 0:
-            return (torch.zeros_like(cam2obj),) + (None,) * 11
-        d_cam2obj = torch.empty_like(cam2obj)
-        n_ws = int(_lib.lib().snr_scene_samples_bwd_ws_bytes(Nr, Nb))
-        ws = torch.empty(n_ws // 8, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().snr_scene_samples_compact_bwd(_p(cam2obj), _p(wlh), _p(rois), _p(pixels), fx, fy, cx, cy, _p(jitter), Nr, Nb, S, scale,
-                                                           aabb, shapenet, _p(hit_scan), cap, _p(d_xyz), _p(d_viewdir), _p(d_z), _p(d_cam2obj),
-                                                           _p(ws), n_ws, _stream(dev)), "snr_scene_samples_compact_bwd")
-        return (d_cam2obj,) + (None,) * 11
+        return _scene_samples_bwd(ctx, "scene_samples_compact", 12, d_xyz, d_viewdir, d_z)
 
 
 class SceneGatherCompact(torch.autograd.Function):
@@ -503,45 +516,11 @@ class SceneGatherCompact(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigmas, rgbs, hit_scan, kept, pair_of_slot, S):
-        sigmas, rgbs = _f32c(sigmas), _f32c(rgbs)
-        S = int(S)
-        ok = kept.dim() == 2 and kept.dtype == torch.uint8 and pair_of_slot.dim() == 2 and pair_of_slot.dtype == torch.int32 and S >= 1
-        if ok:
-            (Nr, Nb), cap = kept.shape, pair_of_slot.shape[1]
-            ok = pair_of_slot.shape[0] == Nb and Nb >= 1 and sigmas.numel() == Nb * cap * S and rgbs.numel() == 3 * sigmas.numel()
-        if not ok:
-            raise SnrError(f"scene_gather_compact: expected sigmas (Nb*C*S), rgbs (Nb*C*S,3), kept (Nr,Nb) uint8 and pair_of_slot (Nb,C) int32, got "
-                           f"{tuple(sigmas.shape)}, {tuple(rgbs.shape)}, {tuple(kept.shape)} {kept.dtype}, {tuple(pair_of_slot.shape)} "
-                           f"{pair_of_slot.dtype}, S = {S}")
-        cap = _scene_capacity_arg("scene_gather_compact", cap)
-        hit_scan = _scene_scan("scene_gather_compact", hit_scan, Nr, Nb)
-        _need_gpu(sigmas, rgbs, hit_scan, kept, pair_of_slot)
-        kept, pair_of_slot = kept.contiguous(), pair_of_slot.contiguous()
-        dev = sigmas.device
-        ctx.set_materialize_grads(False)
-        sig_rows, rgb_rows = torch.empty(Nr, Nb * S, device=dev), torch.empty(Nr, Nb * S, 3, device=dev)
-        with torch.cuda.device(dev):
-            check(_lib.lib().snr_scene_gather_compact_fwd(_p(sigmas), _p(rgbs), _p(hit_scan), _p(kept), Nr, Nb, S, cap, _p(sig_rows), _p(rgb_rows),
-                                                          _stream(dev)), "snr_scene_gather_compact_fwd")
-        ctx.save_for_backward(pair_of_slot)
-        ctx.cfg = (S, Nr, sigmas.shape, rgbs.shape)
-        return sig_rows, rgb_rows
+        return _scene_gather_fwd(ctx, sigmas, rgbs, kept, S, hit_scan, pair_of_slot)
 
     @staticmethod
     def backward(ctx, d_sig_rows, d_rgb_rows):
-        pair_of_slot, = ctx.saved_tensors
-        S, Nr, sig_shape, rgb_shape = ctx.cfg
-        Nb, cap = pair_of_slot.shape
-        dev = pair_of_slot.device
-        d_sig_rows = _f32c(d_sig_rows) if ctx.needs_input_grad[0] else None
-        d_rgb_rows = _f32c(d_rgb_rows) if ctx.needs_input_grad[1] else None
-        d_sig = torch.empty(sig_shape, device=dev) if d_sig_rows is not None else None
-        d_rgb = torch.empty(rgb_shape, device=dev) if d_rgb_rows is not None else None
-        if d_sig is not None or d_rgb is not None:
-            with torch.cuda.device(dev):
-                check(_lib.lib().snr_scene_gather_compact_bwd(_p(d_sig_rows), _p(d_rgb_rows), _p(pair_of_slot), Nr, Nb, S, cap, _p(d_sig), _p(d_rgb),
-                                                              _stream(dev)), "snr_scene_gather_compact_bwd")
-        return d_sig, d_rgb, None, None, None, None
+        return (*_scene_gather_bwd(ctx, d_sig_rows, d_rgb_rows, True), None, None, None, None)
 
 
 def composite_bwd(sigmas, rgbs, z_vals, z_mode, white_bkgd, rays_per_obj, d_rgb, d_depth, d_acc, need_dz):

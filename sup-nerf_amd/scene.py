@@ -269,19 +269,17 @@ def render_pairs(decode, cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, ad
     ``ops.SceneSamplesCompact``, ``decode`` on Nb * capacity * S points, ``ops.SceneGatherCompact``, the same composite; no host read.  -> rgb,
     depth, acc_trans, kept (Nr,Nb) uint8, count (Nb,) int32: an object's hit pairs beyond ``capacity`` (count - capacity of them) render as
     misses."""
-    if capacity is None:
-        xyz, viewdir, z_vals, hit, _ = ops.SceneSamples.apply(cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood)
-        sig, rgb = decode(xyz, viewdir)                                                              # object-major, Nb codes
-        sig, rgb = ops.SceneGather.apply(sig, rgb, hit, n_samples)
-        return (*_composite(sig, rgb, z_vals, n_samples), hit)
-    hit = ops.scene_pair_hits(cam2obj, wlh, rois, pixels, Kvec, rend_aabb)
-    scan = torch.cumsum(hit.to(torch.int32), 0, dtype=torch.int32)
-    count = scan[-1] if scan.shape[0] else scan.new_zeros(scan.shape[1])
-    xyz, viewdir, z_vals, kept, pair_of_slot = ops.SceneSamplesCompact.apply(cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale,
-                                                                              rend_aabb, shapenet_obj_cood, scan, capacity)
-    sig, rgb = decode(xyz, viewdir)                                                                  # object-major, Nb codes, capacity rows each
-    sig, rgb = ops.SceneGatherCompact.apply(sig, rgb, scan, kept, pair_of_slot, n_samples)
-    return (*_composite(sig, rgb, z_vals, n_samples), kept, count)
+    compact = capacity is not None
+    lists = (cam2obj, wlh, rois, pixels, Kvec, jitter, n_samples, adjust_scale, rend_aabb, shapenet_obj_cood)
+    if compact:
+        scan = torch.cumsum(ops.scene_pair_hits(cam2obj, wlh, rois, pixels, Kvec, rend_aabb).to(torch.int32), 0, dtype=torch.int32)
+        count = scan[-1] if scan.shape[0] else scan.new_zeros(scan.shape[1])
+    # flag: hit | kept; last: valid (unused) | pair_of_slot
+    xyz, viewdir, z_vals, flag, last = ops.SceneSamplesCompact.apply(*lists, scan, capacity) if compact else ops.SceneSamples.apply(*lists)
+    sig, rgb = decode(xyz, viewdir)                                                                  # object-major, Nb codes, Nr | capacity rows each
+    sig, rgb = ops.SceneGatherCompact.apply(sig, rgb, scan, flag, last, n_samples) if compact else ops.SceneGather.apply(sig, rgb, flag, n_samples)
+    out = _composite(sig, rgb, z_vals, n_samples)
+    return (*out, flag, count) if compact else (*out, flag)
 
 
 def vis_scene(model, device, obj_poses, obj_wlh, shapecodes, texturecodes, K, H, W, n_samples, manipulation=(0.0, 0.0, 0.0),
