@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 19
+#define SNR_ABI_VERSION 20
 
 enum {
     SNR_OK = 0,
@@ -738,6 +738,27 @@ int snr_instance_rows_fwd(const float* src, const int64_t* view_offset, const in
                           int64_t n_cols, float* dst, void* stream);
 int snr_instance_rows_bwd(const float* d_dst, const int64_t* view_offset, const int64_t* view_offset_host, int64_t n_instances, int64_t n_views,
                           int64_t n_cols, float* d_src, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Cross-view evaluation (OptimizerNuScenes.eval_cross_view, src/optimizer_nuscenes.py:1279-1410): the codes fitted to view ii of an instance,
+ * rendered from the camera of view num and scored against view num's whitened crop and lidar returns.
+ *
+ * snr_cross_metrics: the rendered outputs of P (code row, target view) pairs -> out (P,3) = [mse_fg, depth_err, sum |occ|], one launch.
+ *   rgb (P,n,3) and depth_pred (P,n_l): pair p's renders of the target view's n grid pixels and n_l (padded) lidar pixels;
+ *   tgt (V,n,3), occ (V,n), lid_depth (V,n_l), lid_cnt (V) int32: the V views' resized targets, labels, measured depths and lidar
+ *   counts; pairs (P,2) int32 in DEVICE memory = [code row, target view].  Pair p reads tgt / occ / lid_depth / lid_cnt THROUGH
+ *   v = pairs[p][1]: nothing per-view is copied per pair (the code row is the caller's bookkeeping; the kernel does not read it).
+ *     mse_fg    = sum_i ((rgb - tgt)^2 summed over the 3 channels) |occ_i| / (sum_i |occ_i| + 1e-9)              (:1359-1360)
+ *     depth_err = sum_{k < lid_cnt[v]} |depth_pred[p,k] - lid_depth[v,k]| / (lid_cnt[v] + 1e-8)                   (:1378-1379)
+ *   in fp32; lid_cnt is clamped to [0, n_l]; n_l == 0 (depth_pred, lid_depth, lid_cnt may be null): depth_err = 0.  A view whose occ is
+ *   all zero gives mse_fg = 0 exactly.  One workgroup of 256 threads per pair, thread t owns the rays t + 256 k, fixed-order wave
+ *   reduction, the 4 wave partials added in wave order through LDS, plain stores: no atomics, the same bits every run.
+ *   pairs_host [nullable]: the same 2 P numbers in HOST memory, checked before the launch against n_codes and V.
+ * SNR_E_ARG without a launch: a null pointer, P < 1, V < 1, n_codes < 1, n < 1, n_l < 0, or a host pair outside [0, n_codes) x [0, V).
+ * ---------------------------------------------------------------------------------- */
+int snr_cross_metrics(const float* rgb, const float* depth_pred, const float* tgt, const float* occ, const float* lid_depth,
+                      const int32_t* lid_cnt, const int32_t* pairs, const int32_t* pairs_host, int64_t n_pairs, int64_t n_views, int64_t n_codes,
+                      int64_t n, int64_t n_l, float* out, void* stream);
 
 #ifdef __cplusplus
 }

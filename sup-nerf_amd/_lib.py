@@ -124,6 +124,7 @@ _SIGS = {
     "snr_view_pixels": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "snr_instance_rows_fwd": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "snr_instance_rows_bwd": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "snr_cross_metrics": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
 }
 
 

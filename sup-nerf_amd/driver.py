@@ -19,6 +19,10 @@ launches.  ``ops.InstanceRows`` copies an instance's latent row to its views and
 order with plain fp32 adds (no atomics: the same bits every run).  With random sampling every iteration picks ``n_rays`` pixels of each
 view's native roi (``ops.view_pixels``); a view with fewer pixels is padded with rays of occupancy 0, which weigh exactly 0 in its loss.
 
+Cross-view evaluation (``eval_cross_view``; ``OptimizerNuScenes.eval_cross_view`` :1279-1410): the codes fitted to every view and saved at
+``code_save_iters`` by the loops above are rendered in every other view of their instance; every (snapshot, code view, rendered view) pair
+is one "object" of the fused forward launches and ``ops.cross_metrics`` reduces a chunk of pairs to PSNR inputs and depth errors at once.
+
 No dataset is available offline: objects come from ``synthetic.py``.  The rotation parametrisation
 (pytorch3d ``axis_angle_to_matrix`` / ``matrix_to_axis_angle`` in the reference, un-pinned and not installed) is
 restated here via Rodrigues' formula; parity for it is pinned only by self-consistency tests.
@@ -293,7 +297,8 @@ def optimize_object_api(model, device, obj: Dict, hpams: dict, shapecode0, textu
 
 # ------------------------------------------------------------------ many objects per launch (BASELINE config 3)
 def optimize_objects_batched(model, device, objs: List[Dict], hpams: dict, shapecodes0, texturecodes0, seeds: Sequence[int],
-                             pose_noise=(0.05, 0.3), reg_iters=3, n_lidar=64, jitter=None, info: Optional[dict] = None, pose_per_iter=None):
+                             pose_noise=(0.05, 0.3), reg_iters=3, n_lidar=64, jitter=None, info: Optional[dict] = None, pose_per_iter=None,
+                             code_save_iters=None):
     """The iteration of ``optimize_object`` for B objects at once: ONE fused forward, one backward and one depth render of the lidar pixels
     per iteration for all of them (per-object codes, poses, depth tables and targets; the loss is the sum of the per-object losses, so
     every object sees exactly its own gradient), AdamW over the stacked leaves in one launch, metrics kept on the device until the end --
@@ -301,12 +306,14 @@ def optimize_objects_batched(model, device, objs: List[Dict], hpams: dict, shape
     (num_opts, 2, B, S) or, by default, drawn up front from one CPU generator per object (seeded like the per-object loop seeds its
     RandomState).  ``info`` (optional dict) receives ``lidar_count`` (B,): the number of depth pixels behind every object's depth metric.
     ``pose_per_iter`` (B, reg_iters + 1, 3, 4): every object's pose table for the render-only iterations, see ``optimize_object``.
+    ``code_save_iters``: ``info`` also receives ``shape_snapshots`` / ``texture_snapshots`` (C,B,256), see ``_fit_views``.
     Returns metrics (B, num_opts, 4), shape codes, texture codes, poses (B,3,4).
     (Round 2 also carried a HIP-graph replay of the torch-op iteration; it lost to this eager fused loop, 2.3 vs 1.3 ms per iteration, and
     is gone.)"""
     dev = torch.device(device)
     if hpams.get("sym_aug", 0):
         raise U.SnrError("optimize_objects_batched: sym_aug draws one python coin per object and iteration; use optimize_object")
+    _save_iters(code_save_iters)
     if pose_per_iter is not None:
         pose_per_iter = torch.as_tensor(pose_per_iter, dtype=torch.float32)
         if tuple(pose_per_iter.shape) != (len(objs), reg_iters + 1, 3, 4):
@@ -323,7 +330,8 @@ def optimize_objects_batched(model, device, objs: List[Dict], hpams: dict, shape
         # what is optimised (src/optimizer_nuscenes.py:684-699); (reg_iters + 1, B, 3, 4) on the device
         P = pose_per_iter.to(dev).permute(1, 0, 2, 3)
         given = (P if opt_cam else U.invert_pose(P)).contiguous()
-    return _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, reg_iters=reg_iters, given=given)
+    return _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, reg_iters=reg_iters, given=given,
+                      code_save_iters=code_save_iters, info=info)
 
 
 def _start_pose(gt, rs, pose_noise, last=None):
@@ -359,12 +367,13 @@ def _lidar_pixels(ob, rs, n_lidar):
     return xs[pick], ys[pick], None
 
 
-def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=None, grid=True):
+def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=None, grid=True, need_depth=True):
     """Per-object constants of the loop, built once on the host and moved to the device: perturbed start pose, ground truth, the pixel
     direction tables [(px-cx)/fx, (py-cy)/fy, 1] of the render grid and of the lidar pixels (every object keeps ITS OWN count: the tables
     are padded to the largest, the metric kernel averages each object's first ``lid_cnt`` entries), measured depths when the objects
     carry them, resized targets (the reference resizes the same crop again in every iteration, src/utils.py:447-456).  ``grid=False``
-    (a loop that samples native pixels anew every iteration, ``optimize_instances``): no render grid and no resized targets."""
+    (a loop that samples native pixels anew every iteration, ``optimize_instances``): no render grid and no resized targets.
+    ``need_depth=False`` (``eval_cross_view``): a batch without a single depth pixel is not an error (tables of width 0)."""
     im_sz = hpams["render_im_sz"]
     rot0, tr0, gtR, gtT, cam, lid, lid_d, tgt, occ = [], [], [], [], [], [], [], [], []
     for ob, seed in zip(objs, seeds):
@@ -392,7 +401,7 @@ def _loop_inputs(objs, seeds, hpams, pose_noise, n_lidar, dev, pose_per_iter=Non
         raise U.SnrError("optimize_objects_batched: either every object of a batch carries lidar_xy / lidar_depth or none does")
     cnt = [v.shape[0] for v in lid]
     n_l = max(cnt) if cnt else 0
-    if n_l == 0:
+    if n_l == 0 and need_depth:
         raise U.SnrError("optimize_objects_batched: no object has a depth pixel (empty foreground / no lidar return)")
     one_ray = torch.tensor([[0.0, 0.0, 1.0]])
 
@@ -439,7 +448,7 @@ def _halve_rates(optim, it, opt):
 
 
 def _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, reg_iters=-1, crops=None, picks=None, given=None,
-               view_offset=None, opt_pose=True, loss_log=None, grad_log=None):
+               view_offset=None, opt_pose=True, loss_log=None, grad_log=None, code_save_iters=None, info=None):
     """THE fused iteration of ``optimize_objects_batched`` and ``optimize_instances``, ~30 launches for any number V of views ("objects" of
     the launches): pose -> rays + depths (one launch), the latent layers (two GEMMs), fused render, loss tail (one launch), backward = their
     four backward launches, the 64-pixel depth render, the metric row (one launch), AdamW over the parameter groups (one launch).  Nothing
@@ -455,7 +464,11 @@ def _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam
       every instance's latent row to its views and sums their gradients in view order.
 
     ``loss_log`` (T,V) on the device and ``grad_log`` (a list), when given, receive every iteration's per-view losses and clones of the code
-    gradients the step reads.  Returns metrics (V,T,4), shape codes, texture codes, the last iteration's camera-in-object poses (V,3,4)."""
+    gradients the step reads.  ``code_save_iters`` (ascending iterations; None adds no operation): ``info["shape_snapshots"]`` /
+    ``info["texture_snapshots"]`` (C, rows, 256), row c = the codes ENTERING iteration ``code_save_iters[c]`` (the reference saves at the top
+    of the iteration, src/optimizer_nuscenes.py:675-678), an iteration at or past ``num_opts`` = the returned codes (its ``[-1]`` row,
+    :789-790); device clones inside the loop, stacked once after it.
+    Returns metrics (V,T,4), shape codes, texture codes, the last iteration's camera-in-object poses (V,3,4)."""
     ops = U.ops
     opt = hpams["optimize"]
     S, T = int(hpams["n_samples"]), int(opt["num_opts"])
@@ -475,8 +488,12 @@ def _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam
     cfg = ops.RenderCfg(S, ops.Z_PER_OBJECT, n, sb, tb, frame=frame, precision=model.precision)
     cfg_l = ops.RenderCfg(S, ops.Z_PER_OBJECT, n_l, sb, tb, frame=frame, precision=model.precision)
     packed = model.packed_weights()
+    save_at = _save_iters(code_save_iters)
+    snaps = []
     with _decoder_frozen(model):
         for it in range(T):
+            if save_at is not None and it in save_at:
+                snaps.append((shapecode.detach().clone(), texturecode.detach().clone()))
             if crops is None:
                 cam, tgt, occ = c["cam"], c["tgt"], c["occ"]
             else:               # this iteration's pixels of every view: directions, targets and labels in one launch
@@ -528,7 +545,21 @@ def _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam
             optim.zero_grad()
             if opt_pose:
                 _halve_rates(optim, it, opt)
+    if save_at is not None and info is not None:
+        snaps += [(shapecode.detach(), texturecode.detach())] * (len(save_at) - len(snaps))        # iterations at or past num_opts
+        info["shape_snapshots"] = torch.stack([s_[0] for s_ in snaps]) if snaps else shapecode.detach().new_zeros(0, *shapecode.shape)
+        info["texture_snapshots"] = torch.stack([s_[1] for s_ in snaps]) if snaps else texturecode.detach().new_zeros(0, *texturecode.shape)
     return metrics.permute(1, 0, 2).contiguous(), shapecode.detach(), texturecode.detach(), pose
+
+
+def _save_iters(code_save_iters):
+    """``code_save_iters`` as a list of ascending non-negative iterations (the reference's ``CODE_SAVE_ITERS_``), or None."""
+    if code_save_iters is None:
+        return None
+    its = [int(i) for i in code_save_iters]
+    if any(i < 0 for i in its) or any(b <= a for a, b in zip(its, its[1:])):
+        raise U.SnrError(f"code_save_iters must be ascending non-negative iterations, got {its}")
+    return its
 
 
 # ------------------------------------------------------------------ all objects of a frame, jointly against the frame
@@ -711,7 +742,8 @@ def _view_crops(views, dev):
 
 
 def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapecodes0, texturecodes0, seeds: Sequence[int], opt_pose=True,
-                       sampling=None, n_rays=None, pose_noise=(0.05, 0.3), n_lidar=64, picks=None, jitter=None, info: Optional[dict] = None):
+                       sampling=None, n_rays=None, pose_noise=(0.05, 0.3), n_lidar=64, picks=None, jitter=None, info: Optional[dict] = None,
+                       code_save_iters=None):
     """Fit I instances, each seen in one or more views, with ONE shape code and ONE texture code per instance -- the reference's
     ``optimize_objs_multi_anns_w_pose`` (``opt_pose=True``, src/optimizer_nuscenes.py:1050-1277: also one object pose per VIEW) and
     ``optimize_objs_multi_anns`` (``opt_pose=False``, :796-1048: poses fixed at every view's ``cam_pose``) -- as the fused iteration of
@@ -734,7 +766,9 @@ def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapec
     Learning rates are halved every ``lr_half_interval`` with ``opt_pose`` (:1266-1270) and never without (:1039-1040 is commented out).
     ``jitter`` (num_opts, 2, V, S), default one seeded generator per view.  ``info`` receives ``view_offset`` (I+1,), ``lidar_count`` (V,),
     ``rays_per_view`` (V,), ``loss`` (num_opts, V); with ``info["record_grads"]`` set also ``code_grads``: per iteration the
-    (shape, texture) code gradients as the optimiser step reads them.
+    (shape, texture) code gradients as the optimiser step reads them.  ``code_save_iters`` (ascending iterations): ``info`` also receives
+    ``shape_snapshots`` / ``texture_snapshots`` (C,I,256), the codes entering those iterations (``_fit_views``) -- what ``eval_cross_view``
+    scores, after ``ops.instance_rows_fwd`` has handed every instance's row to its views.
 
     Returns metrics (V, num_opts, 4) = [psnr, depth_err, rot_err, trans_err] per view, shape codes (I,256), texture codes (I,256), and the
     camera-in-object poses (V,3,4) of the last iteration.  Not provided: ``sym_aug``, per-view texture residuals (``slack_tex``),
@@ -749,6 +783,7 @@ def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapec
             raise U.SnrError(f"optimize_instances: the reference's {key} is not provided (codes and poses only, one texture code per instance)")
     if not U._is_native(model):
         raise U.SnrError("optimize_instances needs the package's own decoder")
+    _save_iters(code_save_iters)
     views, offsets = _flatten_instances(instances)
     I, V = len(instances), len(views)
     S, T = int(hpams["n_samples"]), int(opt["num_opts"])
@@ -798,7 +833,142 @@ def optimize_instances(model, device, instances: List[Dict], hpams: dict, shapec
         if info.get("record_grads"):
             info["code_grads"] = grad_log = []
     return _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, crops=crops, picks=picks, given=given, view_offset=offsets,
-                      opt_pose=opt_pose, loss_log=loss_log, grad_log=grad_log)
+                      opt_pose=opt_pose, loss_log=loss_log, grad_log=grad_log, code_save_iters=code_save_iters, info=info)
+
+
+# ------------------------------------------------------------------ cross-view evaluation: every code of an instance in every one of its views
+CROSS_POINTS_PER_LAUNCH = 1 << 24      # eval_cross_view's default chunk: pairs whose grid + lidar points stay below this
+
+
+def eval_cross_view(model, device, instances: List[Dict], hpams: dict, shapecodes, texturecodes, *, jitter=None, seeds=None, pair_chunk=None,
+                    info: Optional[dict] = None):
+    """``OptimizerNuScenes.eval_cross_view`` (src/optimizer_nuscenes.py:1279-1410) for all instances, snapshots and view pairs in a handful of
+    launches: the codes fitted to view ``ii`` of an instance are rendered from the ground-truth camera of every view ``num`` of that instance
+    (``render_rays_v2`` on the ``render_im_sz``^2 grid, :1351-1356), PSNR against that view's whitened crop (:1359-1362), depth L1 against
+    its lidar returns (``render_rays_specified``, :1366-1380).
+
+    ``instances`` as for ``optimize_instances`` (views instance-major); every view carries img (already whitened), mask, cam_pose, K, roi,
+    obj_diag, lidar_xy (n,2) crop pixels and lidar_depth (n,) -- both may be empty: that view's depth column is 0, the reference's
+    0 / (0 + 1e-8).  ``shapecodes`` / ``texturecodes``: (V,256) or (C,V,256), one code per view and snapshot (per-instance codes: expand
+    them with ``ops.instance_rows_fwd``).  Instances with fewer than 2 views are skipped (:1318-1319) and listed in ``info["skipped"]``.
+
+    Layout: every (snapshot, ii, num) triple is one PAIR = one "object" of the launches (``ops.cross_pairs``: instance-major, then
+    snapshot, ii, num).  One ``latent_terms`` launch covers all C V code rows; per chunk of pairs the rows, camera poses, direction
+    tables and half diagonals are gathered with plain indexing, then ``CamRays`` + ``ops.render_fwd`` on the grid, the same on the padded
+    lidar tables, and ONE ``ops.cross_metrics`` launch that reads targets, labels and measured depths through the pair's target view.
+    ``jitter`` (P,2,S): every pair's grid and depth draw (the reference draws ``torch.rand`` twice per pair); default one CPU generator
+    per pair, seeded with ``seeds[p]`` (``seeds``: P integers, or one integer base -> base + p; default base 0).  ``pair_chunk``: pairs
+    per launch, default ``CROSS_POINTS_PER_LAUNCH`` points.  Precision as ``_fit_views`` decides it.  One host read at the end; PSNR on
+    the host in float64, ``-10 log(mse) / log(10)`` from the fp32 loss (:1362): a view whose mask is all zero gives mse 0, PSNR +inf.
+
+    Returns {instance index: (psnr (C,V_i,V_i), depth (C,V_i,V_i))} float64 numpy, row = the view the codes come from, column = the view
+    rendered.  ``info`` also receives ``pairs`` (P,2), ``pair_offset``, ``kept_views``, ``pair_chunk`` and ``metrics`` (P,3) = [mse_fg,
+    depth_err, sum |occ|] as the kernel wrote them."""
+    ops = U.ops
+    dev = torch.device(device)
+    if hpams.get("sym_aug", 0):
+        raise U.SnrError("eval_cross_view: sym_aug draws one python coin per render call; it is not provided here")
+    if not U._is_native(model):
+        raise U.SnrError("eval_cross_view needs the package's own decoder")
+    views_all, offsets_all = _flatten_instances(instances)
+    V_all = len(views_all)
+    shapecodes, texturecodes = torch.as_tensor(shapecodes), torch.as_tensor(texturecodes)
+    if shapecodes.dim() == 2:
+        shapecodes = shapecodes[None]
+    if texturecodes.dim() == 2:
+        texturecodes = texturecodes[None]
+    if shapecodes.dim() != 3 or tuple(shapecodes.shape[1:]) != (V_all, 256) or shapecodes.shape[0] < 1 or texturecodes.shape != shapecodes.shape:
+        raise U.SnrError(f"eval_cross_view: shapecodes / texturecodes must both be (V,256) or (C,V,256) with V = {V_all} views, got "
+                         f"{tuple(shapecodes.shape)} and {tuple(texturecodes.shape)}")
+    C_ = shapecodes.shape[0]
+    S = int(hpams["n_samples"])
+    if not ops.fused_supported(S):
+        raise U.SnrError(f"eval_cross_view: n_samples = {S} is not a divisor of 128 (the fused render)")
+    if dev.type != "cuda":
+        raise U.SnrError("eval_cross_view runs on the GPU (no CPU fallback)")
+    kept = [i for i in range(len(instances)) if offsets_all[i + 1] - offsets_all[i] >= 2]
+    if info is not None:
+        info["skipped"] = [i for i in range(len(instances)) if i not in kept]
+    if not kept:
+        return {}
+    kept_views = [v for i in kept for v in range(offsets_all[i], offsets_all[i + 1])]
+    views = [views_all[v] for v in kept_views]
+    for v, view in zip(kept_views, views):
+        if view.get("lidar_xy") is None or view.get("lidar_depth") is None:
+            raise U.SnrError(f"eval_cross_view: view {v} carries no lidar_xy / lidar_depth (empty arrays are fine: depth error 0)")
+    V = len(views)
+    offsets = ops.view_offset_of([offsets_all[i + 1] - offsets_all[i] for i in kept])
+    pairs, pair_off = ops.cross_pairs(offsets, C_)
+    P = pairs.shape[0]
+    if jitter is None:
+        base = 0 if seeds is None else seeds
+        seeds = [int(base) + p for p in range(P)] if isinstance(base, int) else [int(s_) for s_ in base]
+        if len(seeds) != P:
+            raise U.SnrError(f"eval_cross_view: one seed per pair expected ({P}), got {len(seeds)}")
+        jitter = torch.stack([torch.rand(2, S, generator=torch.Generator().manual_seed(s_)) for s_ in seeds])
+    jitter = torch.as_tensor(jitter)
+    if tuple(jitter.shape) != (P, 2, S):
+        raise U.SnrError(f"eval_cross_view: jitter must be (P, 2, S) = ({P}, 2, {S}), got {tuple(jitter.shape)}")
+    c = _loop_inputs(views, [0] * V, hpams, (0.0, 0.0), 0, dev, grid=True, need_depth=False)
+    n, n_l = c["cam"].shape[1], c["n_lidar"]
+    if pair_chunk is None:
+        pair_chunk = max(1, CROSS_POINTS_PER_LAUNCH // ((n + n_l) * S))
+    pair_chunk = int(pair_chunk)
+    if pair_chunk < 1:
+        raise U.SnrError(f"eval_cross_view: pair_chunk must be at least 1, got {pair_chunk}")
+    jitter = jitter.to(dev, torch.float32).contiguous()
+    pairs_d = pairs.to(dev)
+    code_row, tgt_view = pairs_d[:, 0].long(), pairs_d[:, 1].long()
+    cam_pose = torch.stack([torch.as_tensor(v["cam_pose"], dtype=torch.float32)[:3, :4] for v in views]).to(dev).contiguous()
+    half = (c["diag"] / 2).contiguous()
+    lid_depth = c["lid_depth"] if c["lid_depth"] is not None else torch.zeros(V, n_l, device=dev)
+    frame = U._frame(False, False, hpams["shapenet_obj_cood"])
+    sb, tb = model.shape_blocks, model.texture_blocks
+    cfg = ops.RenderCfg(S, ops.Z_PER_OBJECT, n, sb, tb, frame=frame, precision=model.precision)
+    cfg_l = ops.RenderCfg(S, ops.Z_PER_OBJECT, n_l, sb, tb, frame=frame, precision=model.precision)
+    packed = model.packed_weights()
+    keep_idx = torch.tensor(kept_views, device=dev)
+    out = torch.empty(P, 3, device=dev)
+    with torch.no_grad():
+        sc = shapecodes.to(dev, torch.float32).index_select(1, keep_idx).reshape(C_ * V, 256).contiguous()
+        tc = texturecodes.to(dev, torch.float32).index_select(1, keep_idx).reshape(C_ * V, 256).contiguous()
+        lat = model.latent_terms(sc, tc)                                            # one launch for all C V code rows
+        bias = model.latent_biases(lat)
+        for p0 in range(0, P, pair_chunk):
+            p1 = min(P, p0 + pair_chunk)
+            rows, tv = code_row[p0:p1], tgt_view[p0:p1]
+            lat_p = lat.index_select(0, rows)
+            cfg.latent_bias = cfg_l.latent_bias = None if bias is None else bias.index_select(0, rows)
+            c2w, half_p, diag_p = cam_pose.index_select(0, tv), half.index_select(0, tv), c["diag"].index_select(0, tv)
+            rays_o, viewdir, z = ops.CamRays.apply(c2w, c["cam"].index_select(0, tv), half_p, jitter[p0:p1, 0].contiguous(), S)
+            if p0 == 0:         # which arithmetic the evaluation runs in: decided once, on the first pair, as _fit_views does
+                def probe(p_):
+                    c1 = ops.copy.copy(cfg)
+                    c1.latent_bias = None if cfg.latent_bias is None else cfg.latent_bias[:1]
+                    return ops.render_probe(rays_o[:n], viewdir[:n], z[:1], diag_p[:1], None, lat_p[:1], packed, c1, p_)
+                prec = model._auto_precision(model.precision, n * S, probe)
+                cfg.precision = prec
+                cfg_l.precision = prec if (prec != "bf16x3" or ops.split_supported(sb, tb, n_l * S)) else "fp32"
+            rgb = ops.render_fwd(rays_o, viewdir, z, diag_p, None, lat_p, packed, cfg)[0]
+            if n_l:
+                lo, lv, lz = ops.CamRays.apply(c2w, c["lid"].index_select(0, tv), half_p, jitter[p0:p1, 1].contiguous(), S)
+                d_vec = ops.render_fwd(lo, lv, lz, diag_p, None, lat_p, packed, cfg_l)[1].view(p1 - p0, n_l)
+            else:
+                d_vec = torch.zeros(p1 - p0, 0, device=dev)
+            out[p0:p1] = ops.cross_metrics(rgb.view(p1 - p0, n, 3), d_vec, c["tgt"], c["occ"], lid_depth, c["lid_cnt"], pairs[p0:p1], n_codes=C_ * V)
+    rows_h = out.cpu()                                                              # the one host read
+    mse = rows_h[:, 0].numpy().astype(np.float64)
+    with np.errstate(divide="ignore"):
+        psnr = -10 * np.log(mse) / np.log(10)                                       # (:1362, from the fp32 loss)
+    depth = rows_h[:, 1].numpy().astype(np.float64)
+    result = {}
+    for k, i in enumerate(kept):
+        Vi = offsets[k + 1] - offsets[k]
+        a, b = int(pair_off[k]), int(pair_off[k + 1])
+        result[i] = (psnr[a:b].reshape(C_, Vi, Vi).copy(), depth[a:b].reshape(C_, Vi, Vi).copy())
+    if info is not None:
+        info.update(pairs=pairs, pair_offset=pair_off, kept_views=kept_views, pair_chunk=pair_chunk, metrics=rows_h)
+    return result
 
 
 def make_instances(ids: Sequence[int], n_views: int, lidar: bool = False) -> List[Dict]:

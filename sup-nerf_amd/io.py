@@ -5,7 +5,9 @@
   (src/trainer_unified_nuscenes.py:476-490): ``model_params`` (state-dict), ``shape_code_params`` /
   ``texture_code_params`` (nn.Embedding state-dicts), ``niter``, ``nepoch``, ``instoken2idx``, ``optimized_idx``;
 * optimisation results ``codes+poses.pth`` -- dict written by ``save_opts_w_pose`` (src/optimizer_nuscenes.py:1463-1476),
-  consumed by ``scripts/eval_saved_result.py`` / ``collect_eval_results`` (src/utils.py:786).
+  consumed by ``scripts/eval_saved_result.py`` / ``collect_eval_results`` (src/utils.py:786);
+* cross-view evaluation results ``cross_eval.pth`` -- dict written by ``eval_cross_view`` (src/optimizer_nuscenes.py:1405-1409), the
+  ``cross_eval_file`` of ``collect_eval_results`` (src/utils.py:926-986).
 Pure host code (torch.save / torch.load)."""
 import os
 from typing import Dict, Optional
@@ -84,3 +86,52 @@ def save_driver_results(save_dir: str, metrics: torch.Tensor, ids, shapecodes=No
     ids = list(ids)                          # (a generator would be empty after the first pass)
     psnr, depth, R, T, cnt = metric_rows_to_eval_dicts(metrics, ids, cam_id, n_lidar)
     return save_opts_w_pose(save_dir, len(ids), shapecodes or {}, texturecodes or {}, poses or {}, psnr, depth, R, T, lidar_pts_cnt=cnt)
+
+
+def save_cross_eval(save_dir: str, results: dict, code_save_iters, ids=None) -> str:
+    """``driver.eval_cross_view`` output -> ``cross_eval.pth`` with the reference's keys (src/optimizer_nuscenes.py:1405-1409), which
+    ``collect_eval_results`` reads as ``cross_eval_file`` (src/utils.py:926-986).  ``results``: {instance: (psnr (C,V,V), depth (C,V,V))};
+    ``ids``: {instance: key to save under} or a sequence indexed by instance (the reference keys by instance token; default the instance
+    index).  ``psnr_eval_mat_per_ins`` / ``depth_eval_mat_per_ins``: {key: list of C float64 (V,V) numpy matrices};
+    ``cnt_lidar_pts_per_ins`` stays the empty dict the reference writes."""
+    import numpy as np
+    iters = [int(i) for i in code_save_iters]
+    psnr_d, depth_d = {}, {}
+    for i, (psnr, depth) in results.items():
+        psnr, depth = np.asarray(psnr, dtype=np.float64), np.asarray(depth, dtype=np.float64)
+        if psnr.ndim != 3 or psnr.shape != depth.shape or psnr.shape[1] != psnr.shape[2] or psnr.shape[0] != len(iters):
+            raise ValueError(f"save_cross_eval: instance {i}: expected (C,V,V) = ({len(iters)},V,V) matrices, got {psnr.shape} and {depth.shape}")
+        key = i if ids is None else ids[i]
+        psnr_d[key] = [np.array(m) for m in psnr]
+        depth_d[key] = [np.array(m) for m in depth]
+    d = {"psnr_eval_mat_per_ins": psnr_d, "depth_eval_mat_per_ins": depth_d, "cnt_lidar_pts_per_ins": {}, "CODE_SAVE_ITERS_": iters}
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, "cross_eval.pth")
+    torch.save(d, path)
+    return path
+
+
+def cross_view_means(results: dict):
+    """Per-snapshot means of the off-diagonal entries of all instances' matrices, as ``collect_eval_results`` computes them
+    (src/utils.py:949-973: the diagonal -- a code rendered in its own view -- is discarded, instances with fewer than 2 views skipped,
+    every remaining entry weighs the same).  ``results``: ``eval_cross_view``'s dict, or a loaded ``cross_eval.pth``.
+    Returns (psnr_mean (C,), depth_mean (C,)) float64 numpy."""
+    import numpy as np
+    if "psnr_eval_mat_per_ins" in results:
+        results = {k: (np.stack(results["psnr_eval_mat_per_ins"][k]), np.stack(results["depth_eval_mat_per_ins"][k]))
+                   for k in results["psnr_eval_mat_per_ins"]}
+    psnr_all, depth_all = None, None
+    for psnr, depth in results.values():
+        psnr, depth = np.asarray(psnr, dtype=np.float64), np.asarray(depth, dtype=np.float64)
+        V = psnr.shape[1]
+        if V < 2:
+            continue
+        r_vec, c_vec = np.where(~np.eye(V, dtype=bool))
+        if psnr_all is None:
+            psnr_all, depth_all = [[] for _ in range(psnr.shape[0])], [[] for _ in range(psnr.shape[0])]
+        for c in range(psnr.shape[0]):
+            psnr_all[c] += psnr[c][r_vec, c_vec].tolist()
+            depth_all[c] += depth[c][r_vec, c_vec].tolist()
+    if psnr_all is None:
+        return np.zeros(0), np.zeros(0)
+    return np.array([np.array(x).mean() for x in psnr_all]), np.array([np.mean(np.array(x)) for x in depth_all])

@@ -908,6 +908,65 @@ class InstanceRows(torch.autograd.Function):
         return d_rows, None
 
 
+# ------------------------------------------------------------------------------------ cross-view evaluation (csrc/snr_cross.hip)
+def cross_pairs(view_offset, n_snapshots):
+    """The (code row, target view) pairs of ``eval_cross_view`` (src/optimizer_nuscenes.py:1322-1335), built on the host: for every
+    instance, every snapshot c, every view ii whose codes are rendered and every view num that is rendered -- in that order -- the row
+    ``[c V + ii, num]``: the code row indexes the flattened (C V) code rows, views instance-major.  Returns pairs (P,2) int32 and the
+    (I+1,) int64 offsets of every instance's pairs (instance i owns C V_i^2 of them)."""
+    off = [int(v) for v in (view_offset.tolist() if isinstance(view_offset, torch.Tensor) else view_offset)]
+    n_snap = int(n_snapshots)
+    if len(off) < 2 or off[0] != 0 or any(b <= a for a, b in zip(off, off[1:])) or n_snap < 1:
+        raise SnrError(f"cross_pairs: view_offset must hold I + 1 strictly ascending offsets starting at 0 and n_snapshots >= 1, got {off}, {n_snap}")
+    V = off[-1]
+    rows, pair_off = [], [0]
+    for v0, v1 in zip(off, off[1:]):
+        views = torch.arange(v0, v1, dtype=torch.int32)
+        code = (torch.arange(n_snap, dtype=torch.int32)[:, None, None] * V + views[None, :, None]).expand(n_snap, v1 - v0, v1 - v0)
+        rows.append(torch.stack([code, views[None, None, :].expand_as(code)], dim=-1).reshape(-1, 2))
+        pair_off.append(pair_off[-1] + rows[-1].shape[0])
+    return torch.cat(rows).contiguous(), torch.tensor(pair_off, dtype=torch.int64)
+
+
+def cross_metrics(rgb, depth_pred, tgt, occ, lid_depth, lid_cnt, pairs, n_codes=None):
+    """(P,3) = [mse_fg, depth_err, sum |occ|] of P rendered (code row, target view) pairs, one launch (``snr_cross_metrics``).
+    rgb (P,n,3), depth_pred (P,n_l): the pairs' renders; tgt (V,n,3), occ (V,n), lid_depth (V,n_l), lid_cnt (V,) int32: the V views'
+    targets, labels, measured depths and lidar counts, read through the pair's target view; pairs (P,2) int32 (a CPU tensor is uploaded;
+    a GPU tensor is read back once for the host check); ``n_codes``: the number of code rows the pairs index, checked on the host
+    (default: whatever the table spans).  n_l = 0: depth_err = 0."""
+    _need_gpu(rgb, depth_pred, tgt, occ, lid_depth, lid_cnt)
+    for t in (rgb, depth_pred, tgt, occ, lid_depth):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise SnrError("cross_metrics: rgb, depth_pred, tgt, occ and lid_depth must be fp32 contiguous tensors")
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+        raise SnrError(f"cross_metrics: pairs must be an int32 (P,2) tensor with P >= 1, got {pairs.dtype} {tuple(pairs.shape)}")
+    P = pairs.shape[0]
+    if rgb.dim() != 3 or rgb.shape[0] != P or rgb.shape[2] != 3 or rgb.shape[1] < 1 or depth_pred.dim() != 2 or depth_pred.shape[0] != P:
+        raise SnrError(f"cross_metrics: expected rgb (P,n,3) and depth_pred (P,n_l) for the P = {P} pairs, got {tuple(rgb.shape)}, {tuple(depth_pred.shape)}")
+    n, n_l = rgb.shape[1], depth_pred.shape[1]
+    V = occ.shape[0] if occ.dim() == 2 else 0
+    if V < 1 or tuple(tgt.shape) != (V, n, 3) or tuple(occ.shape) != (V, n) or tuple(lid_depth.shape) != (V, n_l):
+        raise SnrError(f"cross_metrics: expected tgt (V,{n},3), occ (V,{n}), lid_depth (V,{n_l}), got {tuple(tgt.shape)}, {tuple(occ.shape)}, "
+                       f"{tuple(lid_depth.shape)}")
+    if lid_cnt.dtype != torch.int32 or not lid_cnt.is_contiguous() or tuple(lid_cnt.shape) != (V,):
+        raise SnrError(f"cross_metrics: lid_cnt must be a contiguous int32 (V,) = ({V},) tensor")
+    dev = rgb.device
+    if any(t.device != dev for t in (depth_pred, tgt, occ, lid_depth, lid_cnt)):
+        raise SnrError("cross_metrics: all tensors on one GPU")
+    pairs_h = pairs.cpu().contiguous()
+    pairs_d = pairs.contiguous() if pairs.is_cuda else pairs_h.to(dev)
+    if pairs_d.device != dev:
+        raise SnrError("cross_metrics: all tensors on one GPU")
+    if n_codes is None:     # (the code row is the caller's bookkeeping: without a count its range is whatever the table itself spans)
+        n_codes = max(int(pairs_h[:, 0].max()) + 1, 1)
+    out = torch.empty(P, 3, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_cross_metrics(_p(rgb), _p(depth_pred), _p(tgt), _p(occ), _p(lid_depth), _p(lid_cnt), _p(pairs_d),
+                                           C.cast(pairs_h.data_ptr(), C.POINTER(C.c_int32)), P, V, int(n_codes), n, n_l, _p(out), _stream(dev)),
+              "snr_cross_metrics")
+    return out
+
+
 class TableAdamW:
     """torch.optim.AdamW's update (amsgrad off, same defaults) for ANY number of tensors as ONE launch per step: the training step's
     optimiser (src/trainer_unified_nuscenes.py:414-422; torch's foreach form is ~18 launches over the 36 tensors, its ``fused=True`` form
