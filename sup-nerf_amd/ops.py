@@ -202,9 +202,8 @@ def pack_weights(params: Dict[str, torch.Tensor], shape_blocks: int, texture_blo
 # ------------------------------------------------------------------------------------ composite
 def composite_fwd(sigmas, rgbs, z_vals, z_mode, white_bkgd, rays_per_obj=0):
     sigmas, rgbs, z_vals = _f32c(sigmas), _f32c(rgbs), _f32c(z_vals)
+    n_rays, S = _composite_shapes("composite_fwd", sigmas, rgbs, z_vals, z_mode, rays_per_obj)
     _need_gpu(sigmas, rgbs, z_vals)
-    S = rgbs.shape[-2]
-    n_rays = rgbs.numel() // (3 * S) if rgbs.numel() else 0
     dev = rgbs.device
     rgb = torch.empty(n_rays, 3, device=dev)
     depth = torch.empty(n_rays, device=dev)
@@ -237,6 +236,31 @@ def _scene_shapes(name, sigmas, rgbs, z_vals):
     if sigmas.dim() != 2 or rgbs.shape != (*sigmas.shape, 3) or z_vals.shape != sigmas.shape:
         raise SnrError(f"{name}: expected sigmas/z (P,n) and rgbs (P,n,3), got {tuple(sigmas.shape)}, {tuple(z_vals.shape)}, {tuple(rgbs.shape)}")
     return sigmas.shape
+
+
+def _composite_shapes(name, sigmas, rgbs, z_vals, z_mode, rays_per_obj, grads=None):
+    """Sizes the stand-alone composite kernels index with -> (n_rays, S): rgbs (..., S, 3), sigmas n_rays * S values, z_vals S (shared),
+    B * S with B * rays_per_obj == n_rays (per object) or n_rays * S (per ray) values; ``grads`` = (d_rgb, d_depth, d_acc), each None or
+    3 n_rays / n_rays / n_rays values.  Elements are counted, not dimensions: callers pass (B, n, S) as well as (N, S).  The C ABI sees
+    pointers only, so a short operand here is an out-of-bounds read on the device.  An empty packet (n_rays == 0) launches nothing."""
+    if rgbs.dim() < 2 or rgbs.shape[-1] != 3:
+        raise SnrError(f"{name}: expected rgbs (..., S, 3), got {tuple(rgbs.shape)}")
+    S = rgbs.shape[-2]
+    n_rays = rgbs.numel() // (3 * S) if rgbs.numel() else 0
+    if sigmas.numel() != n_rays * S:
+        raise SnrError(f"{name}: sigmas {tuple(sigmas.shape)} do not hold one value per sample of rgbs {tuple(rgbs.shape)} ({n_rays} rays x {S} samples)")
+    if n_rays:
+        rpo = int(rays_per_obj)
+        if z_mode == Z_PER_OBJECT and (rpo < 1 or n_rays % rpo):
+            raise SnrError(f"{name}: per-object depths need rays_per_obj >= 1 that divides the ray count, got rays_per_obj {rpo} for {n_rays} rays")
+        want = {Z_SHARED: S, Z_PER_OBJECT: n_rays // max(rpo, 1) * S, Z_PER_RAY: n_rays * S}.get(z_mode)
+        if want is not None and z_vals.numel() != want:
+            raise SnrError(f"{name}: z_vals {tuple(z_vals.shape)} hold {z_vals.numel()} depths, z_mode {z_mode} needs {want} for {n_rays} rays x {S} samples"
+                           + (f" in {n_rays // rpo} objects of {rpo} rays" if z_mode == Z_PER_OBJECT else ""))
+    for g, per_ray, gname in zip(grads or (), (3, 1, 1), ("d_rgb", "d_depth", "d_acc")):
+        if g is not None and g.numel() != per_ray * n_rays:
+            raise SnrError(f"{name}: {gname} {tuple(g.shape)} holds {g.numel()} values, {n_rays} rays need {per_ray * n_rays}")
+    return n_rays, S
 
 
 def scene_composite_bwd(sigmas, rgbs, z_vals, white_bkgd, run_length, d_rgb, d_depth=None, d_acc=None, need_dz=True):
@@ -528,9 +552,8 @@ def composite_bwd(sigmas, rgbs, z_vals, z_mode, white_bkgd, rays_per_obj, d_rgb,
     # dense copies are NAMED so that they live until the launch is enqueued: `_p(_f32c(t))` inside the argument list frees the temporary before
     # the next argument is evaluated, and the allocator hands the same block to the next temporary (found by tests/test_strided_operands.py)
     d_rgb, d_depth, d_acc = _f32c(d_rgb), _f32c(d_depth), _f32c(d_acc)
+    n_rays, S = _composite_shapes("composite_bwd", sigmas, rgbs, z_vals, z_mode, rays_per_obj, grads=(d_rgb, d_depth, d_acc))
     _need_gpu(sigmas, rgbs, z_vals, d_rgb, d_depth, d_acc)
-    S = rgbs.shape[-2]
-    n_rays = rgbs.numel() // (3 * S) if rgbs.numel() else 0
     dev = rgbs.device
     d_sig = torch.empty(n_rays, S, device=dev)
     d_rgbs = torch.empty(n_rays, S, 3, device=dev)
