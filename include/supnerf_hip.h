@@ -129,7 +129,7 @@ size_t snr_mask_bytes(int64_t n_points, int shape_blocks, int texture_blocks);
 int snr_decoder_fwd(const float* xyz, const float* viewdir, const float* latent, const float* packed,
                     int64_t n_points, int64_t points_per_obj, int shape_blocks, int texture_blocks,
                     float* sigmas, float* rgbs, void* relu_masks, float* activations, int precision, void* stream);
-/* gradients wrt latent (B,NLAT,256), xyz (P,3), viewdir (P,3) [each nullable] given d_sigmas (P) and d_rgbs (P,3).
+/* gradients wrt latent (B,NLAT,256), xyz (P,3), viewdir (P,3) [each nullable] given d_sigmas (P) and d_rgbs (P,3) [each nullable = zero].
  * layer_grads: NULL, or (shape_blocks+texture_blocks+4, P, 256) floats receiving the gradient wrt the pre-activation of
  * every MFMA layer (slot l = layer l; rgb.0 uses 128 columns), both precisions.  workspace: snr_decoder_bwd_ws_bytes(). */
 size_t snr_decoder_bwd_ws_bytes(int64_t n_points, int64_t points_per_obj, int shape_blocks, int texture_blocks);
