@@ -447,6 +447,21 @@ def _halve_rates(optim, it, opt):
         optim.restart(2.0 ** (-((it + 1) // opt["lr_half_interval"])))
 
 
+def _decide_precision(model, cfg, cfg_l, packed, rays_o, viewdir, z, diag, lat):
+    """Which arithmetic a fused loop runs in, set on its two launches' cfgs: "auto" is decided (and range-checked) once, on the first
+    batch (``model._auto_precision``); the probe renders one object of it, the decoder being the same for all.  The lidar launch
+    ``cfg_l`` follows ``cfg`` except where the split kernels do not take its shape."""
+    ops = U.ops
+    n, S = cfg.rays_per_obj, cfg.n_samples
+
+    def probe(p_):
+        c1 = cfg.replace(latent_bias=None if cfg.latent_bias is None else cfg.latent_bias[:1])
+        return ops.render_probe(rays_o.detach()[:n], viewdir.detach()[:n], z.detach()[:1], diag[:1], None, lat.detach()[:1], packed, c1, p_)
+    prec = model._auto_precision(model.precision, n * S, probe)
+    cfg.precision = prec
+    cfg_l.precision = prec if (prec != "bf16x3" or ops.split_supported(cfg.shape_blocks, cfg.texture_blocks, cfg_l.rays_per_obj * S)) else "fp32"
+
+
 def _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam, reg_iters=-1, crops=None, picks=None, given=None,
                view_offset=None, opt_pose=True, loss_log=None, grad_log=None, code_save_iters=None, info=None):
     """THE fused iteration of ``optimize_objects_batched`` and ``optimize_instances``, ~30 launches for any number V of views ("objects" of
@@ -510,16 +525,11 @@ def _fit_views(model, dev, hpams, c, shapecodes0, texturecodes0, jitter, opt_cam
                 lat = ops.InstanceRows.apply(lat, view_offset)
                 bias = None if bias is None else ops.instance_rows_fwd(bias, view_offset)
             cfg.latent_bias = cfg_l.latent_bias = bias
-            if it == 0:         # which arithmetic the loop runs in: "auto" is decided (and range-checked) once, on the first iteration's batch
-                def probe(p_):      # (one object of the batch: the decoder is the same for all of them)
-                    c1 = ops.copy.copy(cfg)
-                    c1.latent_bias = None if cfg.latent_bias is None else cfg.latent_bias[:1]
-                    return ops.render_probe(rays_o.detach()[:n], viewdir.detach()[:n], z[:1], c["diag"][:1], None, lat.detach()[:1], packed, c1, p_)
-                prec = model._auto_precision(model.precision, n * S, probe)
-                cfg.precision = prec
-                cfg_l.precision = prec if (prec != "bf16x3" or ops.split_supported(sb, tb, n_l * S)) else "fp32"
-            # a render-only iteration (it <= reg_iters): its gradients are cleared unread (:676,768-769), so nothing is recorded -- the forward
-            # then does not save ReLU bits either (the launch that saves them is 9 % slower and writes 208 B per point)
+            if it == 0:         # which arithmetic the loop runs in: decided once, on the first iteration's batch
+                _decide_precision(model, cfg, cfg_l, packed, rays_o, viewdir, z, c["diag"], lat)
+            # a render-only iteration (it <= reg_iters): its gradients are cleared unread (:676,768-769), so no_grad keeps autograd from
+            # recording it.  FusedRender still pads and saves ReLU bits whenever an input requires grad (needs_input_grad does not see grad
+            # mode; the launch that saves them is 9 % slower and writes 208 B per point): avoiding that is left to a later change
             with contextlib.nullcontext() if it > reg_iters else torch.no_grad():
                 rgb, depth, acc = ops.FusedRender.apply(rays_o, viewdir, z, c["diag"], None, lat, packed, cfg)
                 loss, lm = ops.LossTail.apply(rgb, acc, tgt, occ, coef, n)
@@ -941,14 +951,8 @@ def eval_cross_view(model, device, instances: List[Dict], hpams: dict, shapecode
             cfg.latent_bias = cfg_l.latent_bias = None if bias is None else bias.index_select(0, rows)
             c2w, half_p, diag_p = cam_pose.index_select(0, tv), half.index_select(0, tv), c["diag"].index_select(0, tv)
             rays_o, viewdir, z = ops.CamRays.apply(c2w, c["cam"].index_select(0, tv), half_p, jitter[p0:p1, 0].contiguous(), S)
-            if p0 == 0:         # which arithmetic the evaluation runs in: decided once, on the first pair, as _fit_views does
-                def probe(p_):
-                    c1 = ops.copy.copy(cfg)
-                    c1.latent_bias = None if cfg.latent_bias is None else cfg.latent_bias[:1]
-                    return ops.render_probe(rays_o[:n], viewdir[:n], z[:1], diag_p[:1], None, lat_p[:1], packed, c1, p_)
-                prec = model._auto_precision(model.precision, n * S, probe)
-                cfg.precision = prec
-                cfg_l.precision = prec if (prec != "bf16x3" or ops.split_supported(sb, tb, n_l * S)) else "fp32"
+            if p0 == 0:         # which arithmetic the evaluation runs in: decided once, on the first chunk, as _fit_views does
+                _decide_precision(model, cfg, cfg_l, packed, rays_o, viewdir, z, diag_p, lat_p)
             rgb = ops.render_fwd(rays_o, viewdir, z, diag_p, None, lat_p, packed, cfg)[0]
             if n_l:
                 lo, lv, lz = ops.CamRays.apply(c2w, c["lid"].index_select(0, tv), half_p, jitter[p0:p1, 1].contiguous(), S)

@@ -368,15 +368,12 @@ class _DecoderBase(nn.Module):
 
     @staticmethod
     def _points_shape(x3, d3, lat, pad):
-        """(points per object as the operators will launch them -- they pad ragged objects to whole 32-point tiles when latent gradients
-        are wanted --, a thunk giving the point tensors in that shape for the range guard's probe launches)."""
+        """(points per object as the operators will launch them -- they pad ragged objects to whole wave tiles when latent gradients
+        are wanted, ``ops._tile_pad`` --, a thunk giving the point tensors in that shape for the range guard's probe launches)."""
         B = max(lat.shape[0], 1)
         P = x3.shape[0]
-        per_obj = P // B
-        n_pad = ops._tile_pad(per_obj) if (pad and P % B == 0 and P > 0) else 0
-        if not n_pad:
-            return per_obj, lambda: (x3.detach(), d3.detach())
-        return n_pad, lambda: (ops._pad_rows(x3.detach(), B, per_obj, n_pad), ops._pad_rows(d3.detach(), B, per_obj, n_pad))
+        launch = ops.ObjectPad(B, P // B, ops._tile_pad(P // B) if (pad and P % B == 0 and P > 0) else 0)
+        return launch.n_pad or launch.n, lambda: (launch.pad(x3.detach()), launch.pad(d3.detach()))
 
     def fused_render(self, rays_o, rays_d, t_vals, xyz_div, z_scale, shape_latent, texture_latent, cfg: "ops.RenderCfg"):
         """rays -> (rgb (N,3), depth (N,), acc_trans (N,)) in one launch (see ops.FusedRender)."""
@@ -397,12 +394,9 @@ class _DecoderBase(nn.Module):
             tv = None if t_vals is None else (t_vals.detach() if cfg.z_mode == ops.Z_SHARED else first(t_vals, 1 if cfg.z_mode == ops.Z_PER_OBJECT else k))
             per_obj = lambda t: None if t is None else (first(t, 1) if t.shape[0] == B else first(t, k))
             div1, zs, lat1 = per_obj(xyz_div), per_obj(z_scale), lat.detach()[:1] if B > 1 else lat.detach()
-            c = ops.copy.copy(cfg)
-            if c.latent_bias is not None and B > 1:
-                c.latent_bias = c.latent_bias[:1]
-            if c.box_half is not None and B > 1:
-                c.box_half = c.box_half[:1]
-            if n_launch != n:               # ragged objects: padded with dummy rays exactly like FusedRender will (their outputs are compared too)
+            one = lambda t: t[:1] if (t is not None and B > 1) else t
+            c = cfg.replace(latent_bias=one(cfg.latent_bias), box_half=one(cfg.box_half))
+            if n_launch != n:               # ragged objects: padded by what FusedRender pads with (the dummy rays' outputs are compared too)
                 if tv is None and c.z_mode == ops.Z_BOX and c.rng is None:
                     tv = torch.zeros(ro.shape[0], S, device=ro.device)          # (any jitter serves a range check; the generator is not touched)
                 ro, rd, tv, zs, c = ops.pad_render_inputs(ops._f32c(ro), ops._f32c(rd), ops._f32c(tv), ops._f32c(zs), c, 1, n, n_launch)

@@ -2,7 +2,6 @@
 
 Everything here requires fp32 tensors on an AMD GPU (``tensor.is_cuda`` under PyTorch-ROCm).
 There is no CPU/eager fallback -- a CPU tensor raises."""
-import copy
 import ctypes as C
 import functools
 import math
@@ -38,7 +37,7 @@ def resolve_precision(precision, shape_blocks, texture_blocks, points_per_obj, b
     if precision is None or precision == "auto":
         ok = _lib.lib().snr_precision_supported(BF16X3, shape_blocks, texture_blocks, int(points_per_obj))
         if not ok:
-            key = (shape_blocks, texture_blocks, int(points_per_obj) % 32 == 0)
+            key = (shape_blocks, texture_blocks, int(points_per_obj) % WAVE_TILE == 0)
             if key not in _AUTO_DOWNGRADES:          # say it once per configuration: 'auto' is several times slower here
                 _AUTO_DOWNGRADES.add(key)
                 warnings.warn(f"supnerf_amd: precision 'auto' runs the exact fp32 kernels for shape_blocks={shape_blocks}, texture_blocks={texture_blocks}, "
@@ -480,7 +479,7 @@ class SceneGather(torch.autograd.Function):
 def scene_capacity(n) -> int:
     """Slots per object of the compact scene route that hold ``n`` pairs: ``n`` rounded up to a multiple of 32 (whole decoder tiles for every
     sample count), at least 32."""
-    return max(32, 32 * ((int(n) + 31) // 32))
+    return max(WAVE_TILE, _tile_pad(int(n)) or int(n))
 
 
 def _scene_capacity_arg(name, capacity):
@@ -488,7 +487,7 @@ def _scene_capacity_arg(name, capacity):
         cap = None if isinstance(capacity, bool) else operator.index(capacity)
     except TypeError:
         cap = None
-    if cap is None or cap < 1 or cap % 32 != 0:
+    if cap is None or cap < 1 or cap % WAVE_TILE != 0:
         raise SnrError(f"{name}: capacity is a positive multiple of 32 (ops.scene_capacity), got {capacity!r}")
     return cap
 
@@ -1085,7 +1084,7 @@ def decoder_bwd(xyz, viewdir, latent, packed, masks, sigmas, d_sig, d_rgb, shape
     masks, d_sig, d_rgb = masks.contiguous(), _f32c(d_sig), _f32c(d_rgb)
     P, B = xyz.shape[0], latent.shape[0]
     dev = xyz.device
-    if need_latent and shape_blocks + texture_blocks > 0 and (P // B) % 32:
+    if need_latent and shape_blocks + texture_blocks > 0 and _tile_pad(P // B):
         raise SnrError(f"gradient wrt the latent codes needs whole 32-point wave tiles per object, got {P // B} points per object "
                        f"({P} points / {B} codes): pad the ray batch of every object to a multiple of 32 / n_samples rays, or detach the codes")
     d_latent = torch.empty_like(latent) if need_latent else None
@@ -1101,11 +1100,20 @@ def decoder_bwd(xyz, viewdir, latent, packed, masks, sigmas, d_sig, d_rgb, shape
     return d_latent, d_xyz, d_dir
 
 
-def _tile_pad(per_obj: int, unit: int = 1) -> int:
-    """Items per object after padding so that items x unit is a multiple of the 32-point wave tile (0 = no padding needed)."""
-    if (per_obj * unit) % 32 == 0:
+# The latent-gradient partials are reduced per object over whole tiles of points (csrc/snr_host.hpp):
+WAVE_TILE = 32          # "partial rows of 32 points": the decoder / render backward, split and exact fp32 with one wave per SIMD
+DENSITY_TILE = 64       # "partial rows of 64 points": the density backward (mode 2), always the exact-fp32 backward with two waves per SIMD
+
+
+def _tile_pad(per_obj: int, unit: int = 1, tile: int = WAVE_TILE) -> int:
+    """Items per object after padding so that items x unit is a multiple of ``tile`` points (0 = no padding needed).  THE statement
+    of the per-object tile rule: the Functions pad with it, the raw backwards check their operands with it, ``model`` sizes its probe
+    launches with it.  Whether a latent gradient is wanted -- the only reason to pad -- is asked in two ways that differ under
+    ``torch.no_grad()``: the Functions read ``ctx.needs_input_grad``, which does not see grad mode; ``model`` and ``driver`` read
+    ``torch.is_grad_enabled() and lat.requires_grad``."""
+    if (per_obj * unit) % tile == 0:
         return 0
-    step = 32 // math.gcd(32, unit)
+    step = tile // math.gcd(tile, unit)
     return -(-per_obj // step) * step
 
 
@@ -1125,6 +1133,20 @@ def _unpad_rows(t, B, n, n_pad):
     return t.reshape(B, n_pad, *t.shape[1:])[:, :n].reshape(B * n, *t.shape[1:])
 
 
+class ObjectPad(NamedTuple):
+    """What a Function's ``ctx.pad`` carries from forward to backward: B objects of n rows each, launched as n_pad rows each
+    (``_tile_pad``'s count; 0 = launched as they are).  ``pad`` / ``strip`` hand back their argument itself when nothing was padded."""
+    B: int
+    n: int
+    n_pad: int
+
+    def pad(self, t):
+        return _pad_rows(t, *self) if self.n_pad and t is not None else t
+
+    def strip(self, t):
+        return _unpad_rows(t, *self) if self.n_pad and t is not None else t
+
+
 class DecoderPoints(torch.autograd.Function):
     """SUPNeRF.forward on explicit points.  Differentiable wrt latent terms, xyz and viewdir (weights are
     treated as constants on this path)."""
@@ -1137,30 +1159,23 @@ class DecoderPoints(torch.autograd.Function):
         # the latent-gradient reduction works on whole 32-point wave tiles per object: other point counts (the reference takes any) are padded
         # per object with dummy points whose upstream gradients are zero
         n_pad = _tile_pad(P // B) if (ctx.needs_input_grad[2] and shape_blocks + texture_blocks > 0 and P % B == 0 and P > 0) else 0
-        ctx.pad = (B, P // B, n_pad)
-        if n_pad:
-            xyz, viewdir = _pad_rows(xyz, B, P // B, n_pad), _pad_rows(viewdir, B, P // B, n_pad)
+        ctx.pad = pad = ObjectPad(B, P // B, n_pad)
+        xyz, viewdir = pad.pad(xyz), pad.pad(viewdir)
         prec = resolve_precision(precision, shape_blocks, texture_blocks, xyz.shape[0] // B)
         sig, rgb, masks = decoder_fwd(xyz, viewdir, latent, packed, shape_blocks, texture_blocks, save_masks=need, precision=prec)
         if need:
             ctx.save_for_backward(xyz, viewdir, latent, packed, masks, sig)
             ctx.cfg = (shape_blocks, texture_blocks, resolve_precision(precision, shape_blocks, texture_blocks, xyz.shape[0] // B, backward=True))
-        if n_pad:
-            return _unpad_rows(sig, B, P // B, n_pad), _unpad_rows(rgb, B, P // B, n_pad)
-        return sig, rgb
+        return pad.strip(sig), pad.strip(rgb)
 
     @staticmethod
     def backward(ctx, d_sig, d_rgb):
         xyz, viewdir, latent, packed, masks, sig = ctx.saved_tensors
         sb, tb, prec = ctx.cfg
-        B, n, n_pad = ctx.pad
-        if n_pad:
-            d_sig, d_rgb = _pad_rows(_f32c(d_sig), B, n, n_pad), _pad_rows(_f32c(d_rgb), B, n, n_pad)
-        d_lat, d_xyz, d_dir = decoder_bwd(xyz, viewdir, latent, packed, masks, sig, d_sig, d_rgb, sb, tb,
+        pad = ctx.pad
+        d_lat, d_xyz, d_dir = decoder_bwd(xyz, viewdir, latent, packed, masks, sig, pad.pad(_f32c(d_sig)), pad.pad(_f32c(d_rgb)), sb, tb,
                                           ctx.needs_input_grad[2], ctx.needs_input_grad[0], ctx.needs_input_grad[1], precision=prec)
-        if n_pad:
-            d_xyz, d_dir = _unpad_rows(d_xyz, B, n, n_pad), _unpad_rows(d_dir, B, n, n_pad)
-        return d_xyz, d_dir, d_lat, None, None, None, None
+        return pad.strip(d_xyz), pad.strip(d_dir), d_lat, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------ density-only decoder on points
@@ -1214,7 +1229,7 @@ def density_bwd(xyz, latent, packed, masks, sigmas, d_sig, shape_blocks, texture
     if masks.dtype != torch.uint8 or masks.numel() < _lib.lib().snr_mask_bytes(P, shape_blocks, texture_blocks):
         raise SnrError("density_bwd: masks must be the uint8 buffer density_fwd(..., save_masks=True) returned for these points")
     lat_rows = shape_blocks + texture_blocks > 0
-    if need_latent and lat_rows and (P // B) % 64:
+    if need_latent and lat_rows and _tile_pad(P // B, 1, DENSITY_TILE):
         raise SnrError(f"the latent gradient of the density path needs a multiple of 64 points per object, got {P // B} "
                        "(DensityPoints pads them)")
     dev = xyz.device
@@ -1240,29 +1255,22 @@ class DensityPoints(torch.autograd.Function):
         P, B = _density_shapes(xyz, latent, shape_blocks, texture_blocks)
         xyz, latent = _f32c(xyz), _f32c(latent)
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        n = P // B
-        n_pad = -(-n // 64) * 64 if (ctx.needs_input_grad[1] and shape_blocks + texture_blocks > 0 and n % 64) else 0
-        ctx.pad = (B, n, n_pad)
-        if n_pad:
-            xyz = _pad_rows(xyz, B, n, n_pad)
+        n_pad = _tile_pad(P // B, 1, DENSITY_TILE) if (ctx.needs_input_grad[1] and shape_blocks + texture_blocks > 0) else 0
+        ctx.pad = pad = ObjectPad(B, P // B, n_pad)
+        xyz = pad.pad(xyz)
         sig, masks = density_fwd(xyz, latent, packed, shape_blocks, texture_blocks, save_masks=need)
         if need:
             ctx.save_for_backward(xyz, latent, packed, masks, sig)
             ctx.cfg = (shape_blocks, texture_blocks)
-        return _unpad_rows(sig, B, n, n_pad) if n_pad else sig
+        return pad.strip(sig)
 
     @staticmethod
     def backward(ctx, d_sig):
         xyz, latent, packed, masks, sig = ctx.saved_tensors
         sb, tb = ctx.cfg
-        B, n, n_pad = ctx.pad
-        d_sig = _f32c(d_sig)
-        if n_pad:
-            d_sig = _pad_rows(d_sig, B, n, n_pad)
-        d_lat, d_xyz = density_bwd(xyz, latent, packed, masks, sig, d_sig, sb, tb, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
-        if n_pad and d_xyz is not None:
-            d_xyz = _unpad_rows(d_xyz, B, n, n_pad)
-        return d_xyz, d_lat, None, None, None
+        pad = ctx.pad
+        d_lat, d_xyz = density_bwd(xyz, latent, packed, masks, sig, pad.pad(_f32c(d_sig)), sb, tb, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
+        return pad.strip(d_xyz), d_lat, None, None, None
 
 
 # ------------------------------------------------------------------------------------ density on lattices, and the narrow band's passes
@@ -1384,7 +1392,8 @@ def iso_surface_points(on_surface, d_grid, lat):
     dev = on_surface.device
     scan = torch.cumsum(on_surface, dim=1, dtype=torch.int32)
     counts = scan[:, -1].long() if B else torch.zeros(0, dtype=torch.int64, device=dev)
-    n = -(-int(counts.max()) // 64) * 64 if B else 0
+    n = int(counts.max()) if B else 0
+    n = _tile_pad(n, 1, DENSITY_TILE) or n
     xyz = torch.empty(B * n, 3, device=dev)
     d_sig = torch.empty(B * n, device=dev)
     if B:
@@ -1744,14 +1753,10 @@ class RaySurface(torch.autograd.Function):
         br = ray_brackets(o, d, _f32c(near.detach()), _f32c(far.detach()), latent, packed, level, n_samples, levels, refine_samples, sb, tb)
         state = br[4]
         t, width, x = ray_hit_points(o, d, *br, level)
-        n = R // B
-        n_pad = -(-n // 64) * 64 if (ctx.needs_input_grad[4] and sb + tb > 0 and n % 64) else 0
-        if n_pad:
-            x = _pad_rows(x, B, n, n_pad)
+        ctx.pad = pad = ObjectPad(B, R // B, _tile_pad(R // B, 1, DENSITY_TILE) if (ctx.needs_input_grad[4] and sb + tb > 0) else 0)
+        x = pad.pad(x)
         sig, masks = density_fwd(x, latent, packed, sb, tb, save_masks=True)
-        _, g = density_bwd(x, latent, packed, masks, sig, torch.ones_like(sig), sb, tb, need_latent=False)
-        if n_pad:
-            g = _unpad_rows(g, B, n, n_pad)
+        g = pad.strip(density_bwd(x, latent, packed, masks, sig, torch.ones_like(sig), sb, tb, need_latent=False)[1])
         hit = state == 1
         norm = g.norm(dim=1, keepdim=True)
         good = hit[:, None] & torch.isfinite(norm) & (norm > 0)
@@ -1759,21 +1764,20 @@ class RaySurface(torch.autograd.Function):
         if any(ctx.needs_input_grad[i] for i in (0, 1, 4)):
             slope = g[:, 0] * d[:, 0] + g[:, 1] * d[:, 1] + g[:, 2] * d[:, 2]
             ctx.save_for_backward(d, t, g, slope, hit, x, latent, packed, masks, sig)
-            ctx.cfg = (sb, tb, B, n, n_pad)
+            ctx.cfg = (sb, tb)
         ctx.mark_non_differentiable(state, normal, width)
         return t, state, normal, width
 
     @staticmethod
     def backward(ctx, d_t, _d_state, _d_normal, _d_width):
         d, t, g, slope, hit, x, latent, packed, masks, sig = ctx.saved_tensors
-        sb, tb, B, n, n_pad = ctx.cfg
+        sb, tb = ctx.cfg
         c = torch.where(hit, -_f32c(d_t) / slope, torch.zeros_like(t))
         d_o = c[:, None] * g if ctx.needs_input_grad[0] else None
         d_d = (t * c)[:, None] * g if ctx.needs_input_grad[1] else None
         d_lat = None
         if ctx.needs_input_grad[4]:
-            d_lat, _ = density_bwd(x, latent, packed, masks, sig, _pad_rows(c, B, n, n_pad) if n_pad else c, sb, tb,
-                                   need_latent=True, need_xyz=False)
+            d_lat, _ = density_bwd(x, latent, packed, masks, sig, ctx.pad.pad(c), sb, tb, need_latent=True, need_xyz=False)
         return d_o, d_d, None, None, d_lat, None, None, None, None, None, None, None
 
 
@@ -1865,9 +1869,8 @@ class DecoderPointsTrain(torch.autograd.Function):
         # nothing to any weight gradient either)
         B, P0 = max(latent.shape[0], 1), xyz.shape[0]
         n_pad = _tile_pad(P0 // B) if (shape_blocks + texture_blocks > 0 and P0 % B == 0 and P0 > 0) else 0
-        ctx.pad = (B, P0 // B, n_pad)
-        if n_pad:
-            xyz, viewdir = _pad_rows(xyz, B, P0 // B, n_pad), _pad_rows(viewdir, B, P0 // B, n_pad)
+        ctx.pad = pad = ObjectPad(B, P0 // B, n_pad)
+        xyz, viewdir = pad.pad(xyz), pad.pad(viewdir)
         # one arithmetic for the whole step: the forward / backward layer chains and the weight-gradient products
         # ``precision``: one name for the whole step, (forward chain, backward chain) -- the products follow the backward chain -- or (forward
         # chain, backward chain, products); ("fp32", "auto", "bf16x3") is what "auto" trains in (model.forward): the forward chain decides
@@ -1888,9 +1891,7 @@ class DecoderPointsTrain(torch.autograd.Function):
                                       activations=act)
         ctx.save_for_backward(xyz, viewdir, latent, packed, masks, sig, act, *weights)
         ctx.cfg = (shape_blocks, texture_blocks, wgrad_precision, prec_bwd)
-        if n_pad:
-            return _unpad_rows(sig, B, P0 // B, n_pad), _unpad_rows(rgb, B, P0 // B, n_pad)
-        return sig, rgb
+        return pad.strip(sig), pad.strip(rgb)
 
     @staticmethod
     def backward(ctx, d_sig, d_rgb):
@@ -1900,10 +1901,8 @@ class DecoderPointsTrain(torch.autograd.Function):
         layers = decoder_layers(sb, tb)
         n_slots = sum(l.slot is not None for l in layers)
         G = torch.empty(n_slots, P, 256, device=dev)
-        d_sig, d_rgb = _f32c(d_sig), _f32c(d_rgb)
-        B_, n_, n_pad = ctx.pad
-        if n_pad:
-            d_sig, d_rgb = _pad_rows(d_sig, B_, n_, n_pad), _pad_rows(d_rgb, B_, n_, n_pad)
+        pad = ctx.pad
+        d_sig, d_rgb = pad.pad(_f32c(d_sig)), pad.pad(_f32c(d_rgb))
         d_lat, d_xyz, d_dir = decoder_bwd(xyz, viewdir, latent, packed, masks, sig, d_sig, d_rgb, sb, tb,
                                           ctx.needs_input_grad[2], ctx.needs_input_grad[0], ctx.needs_input_grad[1], precision=prec,
                                           layer_grads=G)
@@ -1934,9 +1933,7 @@ class DecoderPointsTrain(torch.autograd.Function):
             if l.slot is None:
                 grads[l.stem] = weight_grad(upstream[l.stem], l.n_out, act[before.slot], l.n_in, ws=ws)
         out = [g for l in layers for g in grads[l.stem]]
-        if n_pad:
-            d_xyz, d_dir = _unpad_rows(d_xyz, B_, n_, n_pad), _unpad_rows(d_dir, B_, n_, n_pad)
-        return (d_xyz, d_dir, d_lat, None, None, None, *out)
+        return (pad.strip(d_xyz), pad.strip(d_dir), d_lat, None, None, None, *out)
 
 
 # ------------------------------------------------------------------------------------ fused render
@@ -1993,8 +1990,7 @@ def reserve_rand_like(dev, numel):
 def render_probe(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg, precision):
     """The fused forward once more, without autograd and WITHOUT consuming the device generator (box sampling with in-kernel jitter draws
     from the state the real launch is about to reserve): (rgb, depth, acc_trans) in ``precision``.  Used by the range guard of ``auto``."""
-    c = copy.copy(cfg)
-    c.precision = precision
+    c = cfg.replace(precision=precision)
     with torch.no_grad():
         if c.z_mode == Z_BOX and t_vals is None and c.rng is None:
             dev = torch.device(rays_o.device)
@@ -2031,6 +2027,12 @@ class RenderCfg:
         self.box_half = box_half
         self.rng = None
 
+    def replace(self, **changes):
+        """A shallow copy with the named attributes set: THE per-launch copy (a launch records its generator state in its own)."""
+        c = object.__new__(type(self))
+        c.__dict__.update(self.__dict__, **changes)
+        return c
+
 
 def _box_rng(cfg, t_vals, dev, n_points):
     """Box sampling without a caller-supplied jitter: fix the generator state the kernels will draw from (once per forward; the
@@ -2055,7 +2057,7 @@ def render_fwd(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg: Re
         rgbs = torch.empty(N * S, 3, device=dev)
         masks = torch.empty(_lib.lib().snr_mask_bytes(N * S, cfg.shape_blocks, cfg.texture_blocks), dtype=torch.uint8, device=dev)
     prec = resolve_precision(cfg.precision, cfg.shape_blocks, cfg.texture_blocks, cfg.rays_per_obj * S)
-    lb = getattr(cfg, "latent_bias", None)
+    lb = cfg.latent_bias
     if lb is not None:
         lb = _f32c(lb.detach())
         if lb.shape != latent.shape or lb.device != dev:
@@ -2076,13 +2078,12 @@ def pad_render_inputs(rays_o, rays_d, t_vals, z_scale, cfg, B, n, n_pad):
     Box sampling with in-kernel jitter (Z_BOX, no jitter tensor): the kernel's Philox stream is indexed by the LAUNCH's point index, which padding shifts -- so the reference's draw, ``torch.rand_like`` of the caller's (N,S) table
     (src/renderer.py:40: the same numbers and the same generator consumption), is materialised BEFORE padding and padded like any other
     jitter table; seeded parity with the reference survives ragged ray counts."""
-    cfg = copy.copy(cfg)
+    cfg = cfg.replace(rays_per_obj=n_pad)       # (z_scale is (B,), one per object like xyz_div: padding rays leaves it as it is)
     if cfg.z_mode == Z_BOX and t_vals is None and cfg.rng is None:
         t_vals = torch.rand(B * n, cfg.n_samples, device=rays_o.device)
     rays_o, rays_d = _pad_rows(rays_o, B, n, n_pad), _pad_rows(rays_d, B, n, n_pad)
     if cfg.z_mode in (Z_PER_RAY, Z_BOX) and t_vals is not None:
         t_vals = _pad_rows(t_vals, B, n, n_pad)
-    cfg.rays_per_obj = n_pad            # (z_scale is (B,), one per object like xyz_div: padding rays leaves it as it is)
     if cfg.z_mode == Z_BOX:             # (a dummy ray with direction 0 would divide 0 by 0 in the slab test: give it any unit direction)
         rays_d = rays_d.clone()
         rays_d.view(B, n_pad, 3)[:, n:, 2] = 1.0
@@ -2104,17 +2105,16 @@ class FusedRender(torch.autograd.Function):
         n = cfg.rays_per_obj
         B = rays_o.shape[0] // n if n else 0
         n_pad = _tile_pad(n, cfg.n_samples) if (ctx.needs_input_grad[5] and cfg.shape_blocks + cfg.texture_blocks > 0 and B > 0) else 0
-        ctx.pad = (B, n, n_pad)
-        cfg = copy.copy(cfg)                    # (the launch's generator state is recorded in it: one copy per call)
+        ctx.pad = pad = ObjectPad(B, n, n_pad)
         if n_pad:
-            rays_o, rays_d, t_vals, z_scale, cfg = pad_render_inputs(rays_o, rays_d, t_vals, z_scale, cfg, B, n, n_pad)
+            rays_o, rays_d, t_vals, z_scale, cfg = pad_render_inputs(rays_o, rays_d, t_vals, z_scale, cfg, *pad)
+        else:
+            cfg = cfg.replace()                 # (the launch's generator state is recorded in it: one copy per call)
         rgb, depth, acc, sig, rgbs, masks = render_fwd(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg, save_for_bwd=need)
         if need:
             ctx.save_for_backward(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, sig, rgbs, masks)
             ctx.cfg = cfg
-        if n_pad:
-            return _unpad_rows(rgb, B, n, n_pad), _unpad_rows(depth, B, n, n_pad), _unpad_rows(acc, B, n, n_pad)
-        return rgb, depth, acc
+        return pad.strip(rgb), pad.strip(depth), pad.strip(acc)
 
     @staticmethod
     def backward(ctx, d_rgb, d_depth, d_acc):
@@ -2125,17 +2125,14 @@ class FusedRender(torch.autograd.Function):
         need_t = ctx.needs_input_grad[2]
         if need_t and cfg.z_mode != Z_PER_RAY:
             raise SnrError("gradient wrt shared / per-object depths or the box jitter is not provided (the reference detaches them)")
-        B, n, n_pad = ctx.pad
         if d_rgb is None and d_depth is None and d_acc is None:
             return None, None, None, None, None, None, None, None
-        if n_pad:
-            d_rgb, d_depth, d_acc = [_pad_rows(_f32c(t), B, n, n_pad) for t in (d_rgb, d_depth, d_acc)]
-        d_o, d_d, d_t, d_lat = render_bwd(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg, sig, rgbs, masks, d_rgb, d_depth, d_acc,
+        pad = ctx.pad
+        d_o, d_d, d_t, d_lat = render_bwd(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg, sig, rgbs, masks,
+                                          pad.pad(d_rgb), pad.pad(d_depth), pad.pad(d_acc),
                                           need_o=ctx.needs_input_grad[0], need_d=ctx.needs_input_grad[1], need_t=need_t,
                                           need_latent=ctx.needs_input_grad[5])
-        if n_pad:
-            d_o, d_d, d_t = _unpad_rows(d_o, B, n, n_pad), _unpad_rows(d_d, B, n, n_pad), _unpad_rows(d_t, B, n, n_pad)
-        return d_o, d_d, d_t, None, None, d_lat, None, None
+        return pad.strip(d_o), pad.strip(d_d), pad.strip(d_t), None, None, d_lat, None, None
 
 
 def render_bwd(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg: RenderCfg, sig, rgbs, masks, d_rgb, d_depth, d_acc,
@@ -2158,7 +2155,7 @@ def render_bwd(rays_o, rays_d, t_vals, xyz_div, z_scale, latent, packed, cfg: Re
     for t, k, name in ((d_rgb, 3 * N, "d_rgb"), (d_depth, N, "d_depth"), (d_acc, N, "d_acc")):
         if t is not None and t.numel() != k:
             raise SnrError(f"render_bwd: {name} holds {t.numel()} values, expected {k}")
-    if need_latent and cfg.shape_blocks + cfg.texture_blocks > 0 and (cfg.rays_per_obj * cfg.n_samples) % 32:
+    if need_latent and cfg.shape_blocks + cfg.texture_blocks > 0 and _tile_pad(cfg.rays_per_obj, cfg.n_samples):
         raise SnrError(f"gradient wrt the latent codes needs whole 32-point wave tiles per object, got {cfg.rays_per_obj} rays x {cfg.n_samples} "
                        "samples per object: pad the ray batch of every object so that rays x samples is a multiple of 32, or detach the codes")
     if need_t and cfg.z_mode != Z_PER_RAY:
