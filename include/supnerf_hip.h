@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 20
+#define SNR_ABI_VERSION 21
 
 enum {
     SNR_OK = 0,
@@ -659,6 +659,69 @@ int snr_mesh_face_terms(const float* verts, const int32_t* faces, const int32_t*
 int64_t snr_mesh_slab_bound(int64_t n_comps, int64_t n_faces);
 int snr_mesh_segment_sum(const double* area_terms, const double* volume_terms, const int64_t* seg_start, const int64_t* slab_offset,
                          int64_t n_comps, int64_t n_faces, double* partial, int64_t n_slabs, double* area, double* volume, void* stream);
+
+/* Mesh simplification: quadric vertex clustering (Lindstrom 2000) of a packed mesh -- the form of "Mesh components" above (verts, object-
+ * local int32 faces, vert_offset and face_offset DEVICE arrays).  Every object b has a cell edge cell[b] > 0 and an origin origin[b] (3),
+ * both fp32 DEVICE arrays ((n_objects) and (n_objects, 3)).  tests/simplify_restatement.py restates every rule step by step.
+ *   1. Cell of a vertex: q_a = (int32) floorf((x_a - origin_a) / cell), the subtraction and the division each one correctly rounded fp32
+ *      operation.  A coordinate exactly on a cell face belongs to the upper cell; -0 counts as 0.  Two vertices of an object fall into one
+ *      cluster iff their (qx, qy, qz) are equal.  Connectivity plays no part: two sheets that pass through one cell merge there.  A
+ *      non-finite coordinate or a |q_a| >= 2^20 sets *bad (snr_simplify_keys); a face index outside [0, V) sets *bad (snr_simplify_faces).
+ *   2. Numbering: the clusters of an object are numbered in ascending lexicographic (qx, qy, qz) order; new vertex k is cluster k.
+ *      vert_map (sum V) int32 = the new local index of every old vertex; members (sum V') int32 = the size of each cluster.  The order
+ *      comes from the caller's stable sort of the packed keys ((qx + 2^20) << 42 | (qy + 2^20) << 21 | (qz + 2^20), int64) within each
+ *      object, head flags and an inclusive scan; it is fully determined by the mesh.
+ *   3. Position, mean placement: m = (sum of the members' coordinates widened to float64) / count, rounded to fp32.
+ *   4. Position, quadric placement: with c0 = origin + (q + 1/2) cell in float64, over every (face, corner) pair of the ORIGINAL faces
+ *      whose corner vertex lies in the cluster (faces that will degenerate included), with a', b', c' the face's vertices minus c0 in
+ *      float64:  n = (b' - a') x (c' - a'),  d = -n . a',  A += n n^T (six unique sums),  v += d n (three sums).
+ *      tr = A00 + A11 + A22.  If tr <= (1e-12 cell^2)^2 (a cluster touched only by faces without area): x = m.  Otherwise lambda =
+ *      SNR_SIMPLIFY_EPS tr, (A + lambda I) y = lambda (m - c0) - v solved in float64 by a 3x3 Cholesky factorisation (m not rounded),
+ *      x = c0 + y: the minimum of sum (n . y + d)^2 + lambda |y - (m - c0)|^2, continuous in its inputs, no rank test, condition number
+ *      at most (1 + eps) / eps.  Then x is clamped, component by component in float64, to the cell's closed box
+ *      [origin + q cell, origin + (q + 1) cell] and rounded to fp32 (which may leave it one ulp outside).
+ *   5. Order of every sum: the float64 sums of rules 3, 4 and 7 run over lists sorted by (cluster, original index) -- the members of a
+ *      cluster by packed vertex index, its corners by packed corner index 3 f + k -- cut into slabs of 4096: within a slab, thread t of 256
+ *      adds the entries t, t + 256, ... then a binary tree over the threads; per cluster, lane l of 64 adds its slab sums l, l + 64, ...
+ *      then a butterfly over the lanes (snr_mesh_segment_sum's scheme).  The ten quadric terms per corner are never stored: the corner
+ *      pass reads the sorted corner list and forms n and d on the fly.  No floating-point atomics anywhere: two runs give the same bits.
+ *   6. Faces: new face = (vert_map[v0], vert_map[v1], vert_map[v2]), same winding, kept iff its three new indices differ; kept faces stay
+ *      in their original order; face_index (sum F') int64 points into the old packed face array.  Faces that come out equal are all kept.
+ *   7. Attributes (sum V, C) fp32, 1 <= C <= 16: per cluster the mean of the members' rows, by the sums of rule 5, rounded to fp32.
+ *
+ * snr_simplify_keys: key (sum V) int64 of rule 2, 0 where rule 1 fails, and then *bad = 1 (device int32, zeroed by the caller).
+ * snr_simplify_faces: new_faces (sum F, 3) int32 and keep (sum F) uint8 of rule 6 from vert_map; a face with an index outside its object
+ *   reads nothing, gets (-1, -1, -1), keep 0, and *bad = 1.
+ * snr_simplify_compact: out_faces (n_kept, 3), face_index (n_kept) from new_faces, keep and keep_scan (sum F) int64, the INCLUSIVE scan of
+ *   keep along the packed faces; face f goes to slot keep_scan[f] - 1.
+ * snr_simplify_positions: out_verts (n_clusters, 3) by rule 3 (quadric = 0) or rule 4 (quadric = 1).  vert_order (sum V) int64: the packed
+ *   vertex indices sorted by (object, key), stable; vert_seg_start (n_clusters + 1) int64: cluster k's members at vert_order[vert_seg_start
+ *   [k] .. vert_seg_start[k+1]), clusters of all objects packed object after object; vert_slab_offset (n_clusters + 1) int64: the EXCLUSIVE
+ *   scan of ceil(members / 4096).  corner_order (3 sum F) int64: the corners 3 f + k sorted by the cluster of their vertex, stable, with
+ *   corner_seg_start and corner_slab_offset alike (read only when quadric = 1 and sum F > 0).  vert_partial (n_vert_slabs, 3) and
+ *   corner_partial (n_corner_slabs, 9) float64 scratch, n_vert_slabs >= snr_simplify_slab_bound(n_clusters, sum V), n_corner_slabs >=
+ *   snr_simplify_slab_bound(n_clusters, 3 sum F) (= n_clusters + items / 4096), else SNR_E_WORKSPACE.  The cell of a cluster is rule 1
+ *   applied to its first member.  Every index read from a list is range-checked before use; an entry out of range adds nothing.
+ * snr_simplify_attributes: out (n_clusters, C) of rule 7 on the same vertex segments; partial (n_slabs, C) float64 scratch.
+ * A null pointer, a negative size, n_clusters > sum V or C outside [1, 16]: SNR_E_ARG; more than 2^38 vertices or faces, or 2^31 clusters
+ * or slabs, in a launch: SNR_E_UNSUPPORTED. */
+#define SNR_SIMPLIFY_EPS 1e-3 /* rule 4's ridge weight: a design constant, not a tolerance */
+int snr_simplify_keys(const float* verts, const int64_t* vert_offset, const float* cell, const float* origin, int64_t n_objects,
+                      int64_t n_verts, int64_t* key, int32_t* bad, void* stream);
+int snr_simplify_faces(const int32_t* faces, const int32_t* vert_map, const int64_t* vert_offset, const int64_t* face_offset,
+                       int64_t n_objects, int64_t n_verts, int64_t n_faces, int32_t* new_faces, uint8_t* keep, int32_t* bad, void* stream);
+int snr_simplify_compact(const int32_t* new_faces, const uint8_t* keep, const int64_t* keep_scan, int64_t n_faces, int64_t n_kept,
+                         int32_t* out_faces, int64_t* face_index, void* stream);
+int64_t snr_simplify_slab_bound(int64_t n_clusters, int64_t n_items);
+int snr_simplify_positions(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset,
+                           const float* cell, const float* origin, int64_t n_objects, int64_t n_verts, int64_t n_faces,
+                           const int64_t* vert_order, const int64_t* vert_seg_start, const int64_t* vert_slab_offset,
+                           const int64_t* corner_order, const int64_t* corner_seg_start, const int64_t* corner_slab_offset,
+                           int64_t n_clusters, int quadric, double* vert_partial, int64_t n_vert_slabs, double* corner_partial,
+                           int64_t n_corner_slabs, float* out_verts, void* stream);
+int snr_simplify_attributes(const float* attributes, int n_channels, int64_t n_verts, const int64_t* vert_order,
+                            const int64_t* vert_seg_start, const int64_t* vert_slab_offset, int64_t n_clusters, double* partial,
+                            int64_t n_slabs, float* out, void* stream);
 
 /* Mesh rasteriser: which face of a packed triangle mesh each pixel of a pinhole camera sees, at which depth and with which barycentric
  * weights.  The mesh is the packed form of "Mesh components" above (verts, object-local int32 faces, vert_offset and face_offset DEVICE

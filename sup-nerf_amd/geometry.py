@@ -25,6 +25,8 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     ``select_components(mesh, components, keep)``: the sub-mesh of some components, with the index maps back to the full mesh;
     ``largest_component(meshes, by=..., drop_cavities=...)``: the object without its floaters (and, by default, without the closed pockets
     inside it); ``extract_mesh(..., keep="largest")`` does it in one call;
+  * ``simplify_mesh(meshes, cell)``: each mesh with a fraction of its faces, by quadric vertex clustering -- one new vertex per occupied cell
+    of a grid, placed so that edges and corners stay, per-vertex attributes averaged (``ops.mesh_simplify``: ``snr_simplify_*``);
   * ``rasterize(meshes, obj_to_cam, K, size)``: the meshes as a pinhole camera sees them -- per pixel the nearest face, the object it belongs
     to, its depth and barycentric weights, all objects in one scene image or one image each (``ops.rasterize``: ``snr_raster_*``);
     ``interpolate(raster, attributes)``: per-vertex normals, colours or any data of up to 16 channels at the pixels;
@@ -525,6 +527,82 @@ def largest_component(meshes, by="area", drop_cavities=True):
         return []
     comps = mesh_components(ms)
     out = [select_components(m, c, largest_keep(c, by, drop_cavities)) for m, c in zip(ms, comps)]
+    return out[0] if single else out
+
+
+class Simplified(NamedTuple):
+    verts: torch.Tensor          # (V', 3) fp32, no grad_fn
+    faces: torch.Tensor          # (F', 3) int32
+    vert_map: torch.Tensor       # (V,) int32: the new index of every old vertex; -1 where its cluster was dropped
+    face_index: torch.Tensor     # (F',) int64: the kept faces, as indices into the old faces
+    members: torch.Tensor        # (V',) int32: how many old vertices each new one stands for
+    attributes: object           # (V', C) fp32 or None
+
+
+def _drop_unreferenced(s):
+    """``s`` without the vertices no face names, renumbered; ``vert_map`` is -1 for the old vertices whose cluster went."""
+    used = torch.zeros(s.verts.shape[0], dtype=torch.bool, device=s.verts.device)
+    used[s.faces.view(-1).long()] = True
+    renumber = torch.where(used, torch.cumsum(used, 0, dtype=torch.int32) - 1, torch.full_like(used, -1, dtype=torch.int32))
+    index = torch.nonzero(used).view(-1)
+    return Simplified(s.verts[index], renumber[s.faces.long()].view(-1, 3), renumber[s.vert_map.long()], s.face_index, s.members[index],
+                      None if s.attributes is None else s.attributes[index])
+
+
+def simplify_mesh(meshes, cell, *, origin=None, placement="quadric", attributes=None, drop_unreferenced=True):
+    """Each mesh of ``meshes`` -- the list ``extract_mesh`` returns, or one (verts, faces) pair -- with fewer faces, by quadric vertex
+    clustering (Lindstrom 2000; include/supnerf_hip.h, "Mesh simplification").  A grid of cubic cells of edge ``cell`` (a float, or one
+    per object), anchored at ``origin`` (3,) or (B, 3), zeros by default, is laid over each object; all vertices in one cell become one
+    vertex and a face survives iff its corners land in three different cells.  Cells of two grid steps of the extraction lattice leave
+    about a twelfth of the faces, four steps a fiftieth.  Returns one ``Simplified`` per object, or a single one for a single pair.
+
+    * Clusters go by position alone.  Connectivity plays no part: two sheets that pass through one cell merge there, so choose ``cell``
+      below the thinnest wall worth keeping.  The map is simplicial: a closed surface stays closed (every directed edge a->b keeps as
+      many b->a), though faces that come out equal (or as opposite flaps) are all kept and ``mesh_components`` counts them as often.
+    * ``placement="quadric"`` puts each new vertex where the planes of the original faces around its cluster meet, least squares with a
+      small pull to the members' mean, clamped to the cell: edges and corners stay where they are.  ``"mean"`` takes the mean, which
+      shrinks them.
+    * ``attributes``: a (V, C) tensor (C <= 16) or a list of them, one per object (normals, colours): each new vertex gets the mean of its
+      members' rows.  Normals want renormalising afterwards.
+    * ``drop_unreferenced`` removes the new vertices no kept face names; ``vert_map`` is then -1 for the old vertices whose cluster
+      went.  A floater that lies inside one cell disappears entirely instead of surviving as a vertex without faces.
+    * New vertices are numbered by cell, ascending (qx, qy, qz); kept faces keep their order and winding.  The result is fully determined
+      by the mesh and has the same bits from run to run.
+
+    Vertices with a ``grad_fn`` are read by value and the output carries none: simplification is not differentiable.  All objects go
+    through the same launches with one host read (``drop_unreferenced`` adds one per object: how many vertices stay).
+    CPU tensors, faces that are not int32, a non-positive ``cell``, an unknown ``placement``, a non-finite vertex, a vertex 2^20 cells or
+    more from ``origin`` and a face index outside its mesh raise ``SnrError``."""
+    if placement not in ops.SIMPLIFY_PLACEMENTS:
+        raise SnrError(f"placement is 'mean' or 'quadric', got {placement!r}")
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    B = len(ms)
+    for v, f in ms:
+        if f.dtype != torch.int32:
+            raise SnrError(f"faces are int32, got {f.dtype}")
+    if attributes is not None:
+        attributes = [attributes] if torch.is_tensor(attributes) else list(attributes)
+        if len(attributes) != B:
+            raise SnrError(f"{B} meshes but {len(attributes)} attribute tensors")
+        for a, (v, _) in zip(attributes, ms):
+            _gpu(a, "attributes")
+            if a.dim() != 2 or a.shape[0] != v.shape[0] or a.shape[1] != attributes[0].shape[1]:
+                raise SnrError(f"attributes are (V, C) per object with one C, got {tuple(a.shape)} for {v.shape[0]} vertices")
+        attributes = torch.cat([a.detach().float() for a in attributes])
+    if origin is None:
+        origin = torch.zeros(B, 3)
+    nvs, nfs = [v.shape[0] for v, _ in ms], [f.shape[0] for _, f in ms]
+    verts, faces = torch.cat([v.detach().float() for v, _ in ms]), torch.cat([f for _, f in ms])
+    s = ops.mesh_simplify(verts, faces, nvs, nfs, cell, origin, placement, attributes)
+    out, v0, f0, c0, k0 = [], 0, 0, 0, 0
+    for b in range(B):
+        c1, k1 = c0 + s.n_verts[b], k0 + s.n_faces[b]
+        one = Simplified(s.verts[c0:c1], s.faces[k0:k1], s.vert_map[v0:v0 + nvs[b]], s.face_index[k0:k1] - f0, s.members[c0:c1],
+                         None if s.attributes is None else s.attributes[c0:c1])
+        out.append(_drop_unreferenced(one) if drop_unreferenced else one)
+        v0, f0, c0, k0 = v0 + nvs[b], f0 + nfs[b], c1, k1
     return out[0] if single else out
 
 

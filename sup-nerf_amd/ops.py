@@ -1575,6 +1575,160 @@ def mesh_components(verts, faces, n_verts, n_faces):
     return MeshComponents(vert_label, face_label, n_comps, coff_h, comp_verts, comp_faces, area, volume, bbox_lo, bbox_hi)
 
 
+# ------------------------------------------------------------------------------------ mesh simplification
+SIMPLIFY_PLACEMENTS = ("mean", "quadric")
+
+
+class SimplifiedMesh(NamedTuple):
+    verts: torch.Tensor        # (sum V', 3) fp32: one vertex per cluster, object after object
+    faces: torch.Tensor        # (sum F', 3) int32, indices local to each object
+    n_verts: list              # V' per object
+    n_faces: list              # F' per object
+    vert_map: torch.Tensor     # (sum V,) int32: the new local index of every old vertex
+    members: torch.Tensor      # (sum V',) int32: how many old vertices each new one stands for
+    face_index: torch.Tensor   # (sum F',) int64: the kept faces, as indices into the old packed face array
+    attributes: Optional[torch.Tensor]     # (sum V', C) fp32 or None
+
+
+def _per_object_f32(x, B, width, dev, what):
+    t = torch.as_tensor(x, dtype=torch.float32) if not torch.is_tensor(x) else x.detach().float()
+    shape = (B,) if width == 1 else (B, width)
+    if t.dim() == 0 or (width > 1 and t.dim() == 1 and t.shape[0] == width):
+        t = t.expand(shape)
+    if tuple(t.shape) != shape:
+        raise SnrError(f"mesh_simplify: {what} is one value or one per object {shape}, got {tuple(t.shape)}")
+    return t.to(dev).contiguous()
+
+
+def _segments(sorted_ids, n_segments, dev):
+    """(seg_start, slab_offset), both (n_segments + 1) int64, of a list sorted by segment id (include/supnerf_hip.h: rule 5)."""
+    seg_start = torch.searchsorted(sorted_ids, torch.arange(n_segments + 1, dtype=sorted_ids.dtype, device=dev))
+    slab_off = torch.zeros(n_segments + 1, dtype=torch.int64, device=dev)
+    torch.cumsum((seg_start[1:] - seg_start[:-1] + (MESH_SLAB - 1)) // MESH_SLAB, 0, out=slab_off[1:])
+    return seg_start, slab_off
+
+
+def mesh_simplify(verts, faces, n_verts, n_faces, cell, origin, placement="quadric", attributes=None) -> SimplifiedMesh:
+    """Quadric vertex clustering of a packed mesh (include/supnerf_hip.h, "Mesh simplification"): ``verts`` (sum V, 3) fp32 and ``faces``
+    (sum F, 3) int32 with indices local to each object, ``n_verts`` / ``n_faces`` the V and F per object (host lists); ``cell`` (B,) > 0
+    and ``origin`` (B, 3) the grid of cubic cells each object lays over its vertices (one value serves every object).  All vertices of an
+    object that fall into one cell become one new vertex -- whether or not faces connect them: two sheets that pass through one cell merge
+    there -- placed at their mean (``placement="mean"``) or where the planes of the original faces around them meet, inside the cell
+    (``"quadric"``, which keeps edges and corners).  A face survives iff its corners land in three different cells; survivors keep their
+    order and winding, and faces that come out equal are all kept.  ``attributes`` (sum V, C) fp32, C <= 16, are averaged per cluster.
+
+    ``snr_simplify_keys`` -> a stable ``torch.sort`` (a second one by object when B > 1), head flags and ``torch.cumsum`` ->
+    ``snr_simplify_faces`` -> ``torch.cumsum`` of the keep flags -> the one host read (both flags, the cluster counts and the kept-face
+    counts) -> ``snr_simplify_compact``; a stable sort of the face corners by cluster (quadric only) -> ``snr_simplify_positions`` and
+    ``snr_simplify_attributes`` (float64 sums in a fixed order: the same bits from run to run).  A non-finite coordinate, a cell index of
+    2^20 or beyond and a face index outside its object raise.  Nothing here is differentiable."""
+    if placement not in SIMPLIFY_PLACEMENTS:
+        raise SnrError(f"mesh_simplify: placement is 'mean' or 'quadric', got {placement!r}")
+    if not torch.is_tensor(cell) or not cell.is_cuda:               # (a cell on the device is checked there: it rides the one host read)
+        cell_h = torch.as_tensor(cell, dtype=torch.float32).reshape(-1)
+        if not bool(((cell_h > 0) & torch.isfinite(cell_h)).all()):
+            raise SnrError(f"mesh_simplify: cell must be positive and finite, got {cell_h.tolist()}")
+    if faces.dtype != torch.int32:
+        raise SnrError(f"mesh_simplify: faces are int32, got {faces.dtype}")
+    mesh = pack_mesh(verts, faces, n_verts, n_faces)
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    B, dev = len(n_verts), verts.device
+    nV, nF = verts.shape[0], faces.shape[0]
+    cell = _per_object_f32(cell, B, 1, dev, "cell")
+    origin = _per_object_f32(origin, B, 3, dev, "origin")
+    if attributes is not None:
+        _need_gpu(attributes)
+        if attributes.dim() != 2 or attributes.shape[0] != nV or not 1 <= attributes.shape[1] <= RASTER_MAX_CHANNELS:
+            raise SnrError(f"mesh_simplify: attributes are ({nV}, C) with 1 <= C <= {RASTER_MAX_CHANNELS}, got {tuple(attributes.shape)}")
+        attributes = _f32c(attributes.detach())
+    lib, st = _lib.lib(), _stream(dev)
+    i32, i64, f64, u8 = torch.int32, torch.int64, torch.float64, torch.uint8
+    with torch.cuda.device(dev):
+        bad = torch.zeros(3, dtype=i32, device=dev)                 # a vertex without a cell, a face index out of range, a bad cell edge
+        bad[2:] = (~((cell > 0) & torch.isfinite(cell))).any().to(i32)
+        key = torch.empty(nV, dtype=i64, device=dev)
+        check(lib.snr_simplify_keys(_ptr(verts), _ptr(voff, i64), _ptr(cell), _ptr(origin), B, nV, _ptr(key, i64), _ptr(bad[0:1], i32), st),
+              "snr_simplify_keys")
+        # rule 2: the vertices by (object, key, index); a cluster starts where the key or the object changes
+        key, vert_order = torch.sort(key, stable=True)
+        counts_v = torch.tensor(n_verts, dtype=i64).to(dev)
+        obj = torch.repeat_interleave(torch.arange(B, dtype=i32, device=dev), counts_v, output_size=nV)
+        if B > 1:
+            obj_sorted, by_obj = torch.sort(obj[vert_order], stable=True)
+            key, vert_order = key[by_obj], vert_order[by_obj]
+        else:
+            obj_sorted = obj
+        head = torch.ones(nV, dtype=torch.bool, device=dev)
+        if nV > 1:
+            head[1:] = (key[1:] != key[:-1]) | (obj_sorted[1:] != obj_sorted[:-1])
+        cluster_sorted = torch.cumsum(head, 0, dtype=i64) - 1       # the cluster of the whole call, per sorted vertex
+        cluster_of = torch.empty(nV, dtype=i64, device=dev)
+        cluster_of[vert_order] = cluster_sorted
+        full = [b for b in range(B) if n_verts[b]]
+        voff_h = [sum(n_verts[:b]) for b in range(B + 1)]
+        foff_h = [sum(n_faces[:b]) for b in range(B + 1)]
+        first_cluster = torch.zeros(B, dtype=i64, device=dev)       # (object b's vertices hold the sorted slots voff[b] .. voff[b + 1])
+        if full:
+            first_cluster[torch.tensor(full, dtype=i64).to(dev)] = cluster_sorted[torch.tensor([voff_h[b] for b in full], dtype=i64).to(dev)]
+        vert_map = (cluster_of - first_cluster[obj.long()]).to(i32)
+        # rule 6
+        new_faces = torch.empty(nF, 3, dtype=i32, device=dev)
+        keep = torch.empty(nF, dtype=u8, device=dev)
+        check(lib.snr_simplify_faces(_ptr(faces, i32), _ptr(vert_map, i32), _ptr(voff, i64), _ptr(foff, i64), B, nV, nF,
+                                     _ptr(new_faces, i32), _ptr(keep, u8), _ptr(bad[1:2], i32), st), "snr_simplify_faces")
+        keep_scan = torch.cumsum(keep, 0, dtype=i64)
+        last_v = torch.tensor([voff_h[b + 1] - 1 for b in full], dtype=i64).to(dev)
+        with_faces = [b for b in range(B) if n_faces[b]]
+        last_f = torch.tensor([foff_h[b + 1] - 1 for b in with_faces], dtype=i64).to(dev)
+        host = torch.cat([bad.long(), cluster_sorted[last_v] + 1, keep_scan[last_f]]).cpu().tolist()      # the one host read
+        if host[2]:
+            raise SnrError("mesh_simplify: cell must be positive and finite")
+        if host[0]:
+            raise SnrError("mesh_simplify: a vertex is not finite or lies 2^20 cells or more from the origin")
+        if host[1]:
+            raise SnrError("mesh_simplify: a face index lies outside its object's vertices")
+        ends_v, ends_f = host[3:3 + len(full)], host[3 + len(full):]
+        new_n_verts, new_n_faces, prev = [0] * B, [0] * B, 0
+        for b, e in zip(full, ends_v):
+            new_n_verts[b], prev = e - prev, e
+        prev = 0
+        for b, e in zip(with_faces, ends_f):
+            new_n_faces[b], prev = e - prev, e
+        nC, nK = sum(new_n_verts), sum(new_n_faces)
+        out_faces = torch.empty(nK, 3, dtype=i32, device=dev)
+        face_index = torch.empty(nK, dtype=i64, device=dev)
+        check(lib.snr_simplify_compact(_ptr(new_faces, i32), _ptr(keep, u8), _ptr(keep_scan, i64), nF, nK, _ptr(out_faces, i32),
+                                       _ptr(face_index, i64), st), "snr_simplify_compact")
+        # rules 3 to 5 and 7: the sorted member and corner lists, cut into slabs
+        vseg, vslab = _segments(cluster_sorted, nC, dev)
+        members = (vseg[1:] - vseg[:-1]).to(i32)
+        out_verts = torch.empty(nC, 3, device=dev)
+        quadric = placement == "quadric" and nF > 0
+        corder = cseg = cslab = cpartial = None
+        n_cslabs = 0
+        if quadric and nC:
+            counts_f = torch.tensor(n_faces, dtype=i64).to(dev)
+            face_v0 = torch.repeat_interleave(voff[:-1], counts_f, output_size=nF)
+            corner_cluster, corder = torch.sort(cluster_of[(faces.long() + face_v0[:, None]).view(-1)], stable=True)
+            cseg, cslab = _segments(corner_cluster, nC, dev)
+            n_cslabs = int(lib.snr_simplify_slab_bound(nC, nF * 3))
+            cpartial = torch.empty(n_cslabs, 9, dtype=f64, device=dev)
+        n_vslabs = int(lib.snr_simplify_slab_bound(nC, nV))
+        vpartial = torch.empty(n_vslabs, 3, dtype=f64, device=dev)
+        check(lib.snr_simplify_positions(_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), _ptr(cell), _ptr(origin), B, nV, nF,
+                                         _ptr(vert_order, i64), _ptr(vseg, i64), _ptr(vslab, i64), _ptr(corder, i64), _ptr(cseg, i64),
+                                         _ptr(cslab, i64), nC, int(quadric), _ptr(vpartial, f64), n_vslabs, _ptr(cpartial, f64), n_cslabs,
+                                         _ptr(out_verts), st), "snr_simplify_positions")
+        out_attr = None
+        if attributes is not None:
+            nCh = attributes.shape[1]
+            out_attr = torch.empty(nC, nCh, device=dev)
+            apartial = torch.empty(n_vslabs, nCh, dtype=f64, device=dev)
+            check(lib.snr_simplify_attributes(_ptr(attributes), nCh, nV, _ptr(vert_order, i64), _ptr(vseg, i64), _ptr(vslab, i64), nC,
+                                              _ptr(apartial, f64), n_vslabs, _ptr(out_attr), st), "snr_simplify_attributes")
+    return SimplifiedMesh(out_verts, out_faces, new_n_verts, new_n_faces, vert_map, members, face_index, out_attr)
+
+
 # ------------------------------------------------------------------------------------ mesh rasteriser
 RASTER_MAX_CHANNELS = 16
 
