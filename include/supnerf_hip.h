@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 21
+#define SNR_ABI_VERSION 22
 
 enum {
     SNR_OK = 0,
@@ -599,6 +599,19 @@ int snr_ray_first_crossing(const float* sigmas, int64_t n_rays, int n_samples, f
 int snr_ray_hit_points(const float* rays_o, const float* rays_d, const float* ta, const float* tb, const float* va, const float* vb,
                        const uint8_t* state, int64_t n_rays, float level, float* depth, float* width, float* xyz, void* stream);
 
+/* Fixed-order segmented sums: how every float64 sum of the packed-mesh entry points below (snr_mesh_segment_sum, snr_simplify_positions,
+ * snr_simplify_attributes) runs.  The terms form a list sorted by segment: seg_start (n_segments + 1) int64, ascending, segment k's terms at
+ * [seg_start[k], seg_start[k+1]).  A segment's terms are cut into slabs of 4096, the last one short; slab_offset (n_segments + 1) int64 =
+ * the EXCLUSIVE prefix sum of ceil(terms / 4096) per segment, so slab s of segment k holds the terms [seg_start[k] + 4096 j, + 4096), j =
+ * s - slab_offset[k], and an empty segment has no slab.  Order of every sum: within a slab, thread t of 256 starts from 0.0 and adds the
+ * terms t, t + 256, ... in that order, then a binary tree over the threads (k = 128, 64, ..., 1: t += t + k for t < k); per segment, lane l
+ * of 64 starts from 0.0 and adds the segment's slab sums l, l + 64, ... in that order, then a butterfly over the lanes (l += l xor 32, 16,
+ * ..., 1).  Several channels are summed side by side, each in this order.  The library is built without fused multiply-adds and nothing
+ * is added atomically: the bits are those of the order (tests/segment_sum_restatement.py restates it; tests/test_segment_sum_gpu.py holds
+ * the kernels to it), the same from run to run.  The slab sums go through a float64 scratch of n_slabs rows, n_slabs >=
+ * snr_segment_slab_bound(n_segments, n_items) = n_segments + n_items / 4096 (0 for a negative argument), else SNR_E_WORKSPACE. */
+int64_t snr_segment_slab_bound(int64_t n_segments, int64_t n_items);
+
 /* Mesh components: which vertices and faces of a triangle mesh hang together, and what each piece measures.  The mesh is the packed form
  * snr_iso_emit writes, or any caller's of the same form: verts (sum V, 3) fp32 and faces (sum F, 3) int32 of n_objects objects, object
  * after object, face indices local to their object; vert_offset, face_offset (n_objects + 1) int64 DEVICE arrays, ascending, from 0 to
@@ -617,8 +630,8 @@ int snr_ray_hit_points(const float* rays_o, const float* rays_d, const float* ta
  *          area term = |(b - a) x (c - a)| / 2,      volume term = (a - p0) . ((b - p0) x (c - p0)) / 6,
  *      each summed over the component's faces.  The volume is signed: the iso rules wind faces counter-clockwise seen from the low side,
  *      so a closed dense blob is positive and a closed cavity negative.  For a closed component the value does not depend on p0; for one
- *      cut open (by the border of the grid) it is this rule's value and no more.  The sums run in a fixed order (below): two runs give
- *      the same bits.  No floating-point atomics anywhere.
+ *      cut open (by the border of the grid) it is this rule's value and no more.  The sums run in a fixed order ("Fixed-order segmented
+ *      sums" above): two runs give the same bits.  No floating-point atomics anywhere.
  *   4. Selection: a subset of components gives a sub-mesh -- the kept vertices in their original order, the kept faces in their original
  *      order, indices renumbered.  (Host policy over the labels; no kernel.)
  *
@@ -638,11 +651,8 @@ int snr_ray_hit_points(const float* rays_o, const float* rays_d, const float* ta
  *   packed face indices -- the faces sorted by component -- or NULL = as stored).  p0 = the vertex root[v0].  A face with a bad index
  *   gives 0, 0.
  * snr_mesh_segment_sum: area, volume (sum C) float64 from terms sorted by component: seg_start (sum C + 1) int64, component k's terms at
- *   [seg_start[k], seg_start[k+1]).  A component's terms are cut into slabs of 4096; slab_offset (sum C + 1) int64 = the EXCLUSIVE prefix
- *   sum of ceil(faces / 4096) per component.  Order of every sum: within a slab, thread t of 256 adds the terms t, t + 256, ... then a
- *   binary tree over the threads (t += t + 128, t + 64, ...); per component, lane l of 64 adds its slab sums l, l + 64, ... then a
- *   butterfly over the lanes.  partial: (n_slabs, 2) float64 scratch, n_slabs >= snr_mesh_slab_bound (= sum C + sum F / 4096), else
- *   SNR_E_WORKSPACE.
+ *   [seg_start[k], seg_start[k+1]), with slab_offset (sum C + 1) int64, both as "Fixed-order segmented sums" above defines them, which
+ *   is also the order of the two sums.  partial: (n_slabs, 2) float64 scratch, n_slabs >= snr_segment_slab_bound(sum C, sum F).
  * A null pointer or a negative size: SNR_E_ARG; more than 2^38 vertices, faces or components in a launch: SNR_E_UNSUPPORTED. */
 int snr_mesh_hook(const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, int64_t n_objects, int64_t n_verts,
                   int64_t n_faces, int32_t* parent, int32_t* bad, void* stream);
@@ -656,7 +666,6 @@ int snr_mesh_boxes(const float* verts, const int32_t* vert_label, const int64_t*
 int snr_mesh_face_terms(const float* verts, const int32_t* faces, const int32_t* root, const int64_t* order, const int64_t* vert_offset,
                         const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, double* area_terms,
                         double* volume_terms, void* stream);
-int64_t snr_mesh_slab_bound(int64_t n_comps, int64_t n_faces);
 int snr_mesh_segment_sum(const double* area_terms, const double* volume_terms, const int64_t* seg_start, const int64_t* slab_offset,
                          int64_t n_comps, int64_t n_faces, double* partial, int64_t n_slabs, double* area, double* volume, void* stream);
 
@@ -681,10 +690,9 @@ int snr_mesh_segment_sum(const double* area_terms, const double* volume_terms, c
  *      at most (1 + eps) / eps.  Then x is clamped, component by component in float64, to the cell's closed box
  *      [origin + q cell, origin + (q + 1) cell] and rounded to fp32 (which may leave it one ulp outside).
  *   5. Order of every sum: the float64 sums of rules 3, 4 and 7 run over lists sorted by (cluster, original index) -- the members of a
- *      cluster by packed vertex index, its corners by packed corner index 3 f + k -- cut into slabs of 4096: within a slab, thread t of 256
- *      adds the entries t, t + 256, ... then a binary tree over the threads; per cluster, lane l of 64 adds its slab sums l, l + 64, ...
- *      then a butterfly over the lanes (snr_mesh_segment_sum's scheme).  The ten quadric terms per corner are never stored: the corner
- *      pass reads the sorted corner list and forms n and d on the fly.  No floating-point atomics anywhere: two runs give the same bits.
+ *      cluster by packed vertex index, its corners by packed corner index 3 f + k -- in the order of "Fixed-order segmented sums" above,
+ *      a cluster being a segment.  The ten quadric terms per corner are never stored: the corner pass reads the sorted corner list and
+ *      forms n and d on the fly.  No floating-point atomics anywhere: two runs give the same bits.
  *   6. Faces: new face = (vert_map[v0], vert_map[v1], vert_map[v2]), same winding, kept iff its three new indices differ; kept faces stay
  *      in their original order; face_index (sum F') int64 points into the old packed face array.  Faces that come out equal are all kept.
  *   7. Attributes (sum V, C) fp32, 1 <= C <= 16: per cluster the mean of the members' rows, by the sums of rule 5, rounded to fp32.
@@ -696,11 +704,11 @@ int snr_mesh_segment_sum(const double* area_terms, const double* volume_terms, c
  *   keep along the packed faces; face f goes to slot keep_scan[f] - 1.
  * snr_simplify_positions: out_verts (n_clusters, 3) by rule 3 (quadric = 0) or rule 4 (quadric = 1).  vert_order (sum V) int64: the packed
  *   vertex indices sorted by (object, key), stable; vert_seg_start (n_clusters + 1) int64: cluster k's members at vert_order[vert_seg_start
- *   [k] .. vert_seg_start[k+1]), clusters of all objects packed object after object; vert_slab_offset (n_clusters + 1) int64: the EXCLUSIVE
- *   scan of ceil(members / 4096).  corner_order (3 sum F) int64: the corners 3 f + k sorted by the cluster of their vertex, stable, with
+ *   [k] .. vert_seg_start[k+1]), clusters of all objects packed object after object; vert_slab_offset (n_clusters + 1) int64: its slab
+ *   offsets.  corner_order (3 sum F) int64: the corners 3 f + k sorted by the cluster of their vertex, stable, with
  *   corner_seg_start and corner_slab_offset alike (read only when quadric = 1 and sum F > 0).  vert_partial (n_vert_slabs, 3) and
- *   corner_partial (n_corner_slabs, 9) float64 scratch, n_vert_slabs >= snr_simplify_slab_bound(n_clusters, sum V), n_corner_slabs >=
- *   snr_simplify_slab_bound(n_clusters, 3 sum F) (= n_clusters + items / 4096), else SNR_E_WORKSPACE.  The cell of a cluster is rule 1
+ *   corner_partial (n_corner_slabs, 9) float64 scratch, n_vert_slabs >= snr_segment_slab_bound(n_clusters, sum V), n_corner_slabs >=
+ *   snr_segment_slab_bound(n_clusters, 3 sum F), else SNR_E_WORKSPACE.  The cell of a cluster is rule 1
  *   applied to its first member.  Every index read from a list is range-checked before use; an entry out of range adds nothing.
  * snr_simplify_attributes: out (n_clusters, C) of rule 7 on the same vertex segments; partial (n_slabs, C) float64 scratch.
  * A null pointer, a negative size, n_clusters > sum V or C outside [1, 16]: SNR_E_ARG; more than 2^38 vertices or faces, or 2^31 clusters
@@ -712,7 +720,6 @@ int snr_simplify_faces(const int32_t* faces, const int32_t* vert_map, const int6
                        int64_t n_objects, int64_t n_verts, int64_t n_faces, int32_t* new_faces, uint8_t* keep, int32_t* bad, void* stream);
 int snr_simplify_compact(const int32_t* new_faces, const uint8_t* keep, const int64_t* keep_scan, int64_t n_faces, int64_t n_kept,
                          int32_t* out_faces, int64_t* face_index, void* stream);
-int64_t snr_simplify_slab_bound(int64_t n_clusters, int64_t n_items);
 int snr_simplify_positions(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset,
                            const float* cell, const float* origin, int64_t n_objects, int64_t n_verts, int64_t n_faces,
                            const int64_t* vert_order, const int64_t* vert_seg_start, const int64_t* vert_slab_offset,

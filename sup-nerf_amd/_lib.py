@@ -115,12 +115,11 @@ _SIGS = {
     "snr_mesh_label": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "snr_mesh_boxes": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "snr_mesh_face_terms": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
-    "snr_mesh_slab_bound": (C.c_int64, [C.c_int64, C.c_int64]),
+    "snr_segment_slab_bound": (C.c_int64, [C.c_int64, C.c_int64]),
     "snr_mesh_segment_sum": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     "snr_simplify_keys": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "snr_simplify_faces": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "snr_simplify_compact": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
-    "snr_simplify_slab_bound": (C.c_int64, [C.c_int64, C.c_int64]),
     "snr_simplify_positions": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int,
                                          _P, C.c_int64, _P, C.c_int64, _P, _P]),
     "snr_simplify_attributes": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),

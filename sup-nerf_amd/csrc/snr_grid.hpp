@@ -1,6 +1,7 @@
 // The lattice and Kuhn-edge rules of the geometry kernels (snr_iso.hip, snr_iso_grad.hip, snr_band.hip; the density entry points of
-// snr_decoder.hip use the host part) and the offset search of the packed-mesh kernels (snr_mesh.hip, snr_raster.hip), stated once.  The specification is include/supnerf_hip.h ("Geometry", "Narrow band", "Iso-surface
-// backward").  Functions only, no __constant__ object: a table here would be copied into every code object that includes the header.
+// snr_decoder.hip use the host part), stated once; the packed-mesh kernels (snr_packed_mesh.hpp) take the launch shape from here.  The
+// specification is include/supnerf_hip.h ("Geometry", "Narrow band", "Iso-surface backward").  Functions only, no __constant__ object: a
+// table here would be copied into every code object that includes the header.
 //
 //   * a grid of n0 x n1 x n2 points per object, x-major (z fastest): point (i, j, k) has the linear index v = (i n1 + j) n2 + k;
 //   * corner bits: bit a = +1 on axis a.  Every tetrahedron edge of the Kuhn (Freudenthal) split is a grid edge from its lower corner u in
@@ -89,31 +90,5 @@ __device__ __forceinline__ unsigned cell_inside_bits(const float* __restrict__ f
     for (int c = 0; c < 8; ++c) in |= (unsigned)(f[v + corner_off(c, n1, n2)] > level) << c;
     return in;
 }
-
-// ---- packed meshes (snr_mesh.hip, snr_raster.hip): verts (sum V, 3) and object-local faces (sum F, 3) of several objects, object after
-// object, with (n + 1) ascending int64 offsets that say where each object's vertices / faces start
-//
-// entry b of the (n + 1) ascending offsets `off` that holds item i: the largest b < n with off[b] <= i (empty entries are skipped)
-__device__ __forceinline__ long long mesh_entry_of(const long long* __restrict__ off, long long n, long long i) {
-    long long lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const long long mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct MeshObject {
-    long long v0;                // where the object's vertices start
-    long long V;                 // how many it has; 0 when the offsets are not usable
-};
-__device__ __forceinline__ MeshObject mesh_object(const long long* __restrict__ voff, long long b, long long nV) {
-    MeshObject o;
-    o.v0 = voff[b];
-    o.V = voff[b + 1] - o.v0;
-    if (o.v0 < 0 || o.V < 0 || o.V > 0x7fffffffll || o.v0 + o.V > nV) o.V = 0;
-    return o;
-}
-__device__ __forceinline__ bool mesh_index_ok(int i, long long V) { return i >= 0 && (long long)i < V; }
 
 }  // namespace snr

@@ -11,14 +11,11 @@
 // loads of it happen only in later launches (mesh_flatten_kernel), plain stores only in the launch before (mesh_identity_kernel).  A stale
 // parent is still an ancestor, and a compare-and-swap that fails retries on the value it returned: no thread ever waits for another one.
 // Nothing here adds floating-point numbers atomically: counts and boxes use integer atomics (exact, whatever the order), the float64 sums
-// walk the faces sorted by component in fixed slabs and fixed trees, so every output has the same bits from run to run.
-#include "snr_grid.hpp"
+// walk the faces sorted by component in the fixed order of snr_packed_mesh.hpp, so every output has the same bits from run to run.
+#include "snr_packed_mesh.hpp"
 #include "snr_host.hpp"
 
 namespace snr {
-
-constexpr long long MESH_MAX_ITEMS = 1ll << 38;      // vertices, faces or components of one launch (blocks of 256 threads fit a 1-D grid)
-constexpr int MESH_SLAB = 4096;                      // faces of one component summed by one workgroup, in a fixed order
 
 #define SNR_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -60,15 +57,11 @@ __global__ void mesh_hook_kernel(const int* __restrict__ faces, const long long*
                                  long long B, long long nV, long long nF, int* parent, int* bad) {
     const long long f = grid_thread();
     if (f >= nF) return;
-    const MeshObject o = mesh_object(voff, mesh_entry_of(foff, B, f), nV);
-    const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-    if (!mesh_index_ok(i0, o.V) || !mesh_index_ok(i1, o.V) || !mesh_index_ok(i2, o.V)) {
-        __hip_atomic_store(bad, 1, SNR_RLX_AGENT);            // checked before anything is dereferenced with it
-        return;
-    }
-    int* par = parent + o.v0;
-    mesh_unite(par, i0, i1);
-    mesh_unite(par, i0, i2);
+    const MeshFace m = mesh_face(faces, voff, foff, B, nV, f);
+    if (!m.ok) { __hip_atomic_store(bad, 1, SNR_RLX_AGENT); return; }
+    int* par = parent + m.v0;
+    mesh_unite(par, m.idx[0], m.idx[1]);
+    mesh_unite(par, m.idx[0], m.idx[2]);
 }
 
 // ---- later launches: the parent array is final and read with plain loads
@@ -216,13 +209,12 @@ __global__ void mesh_face_terms_kernel(const float* __restrict__ verts, const in
     const long long f = order ? order[i] : i;
     double area = 0.0, vol = 0.0;
     if (f >= 0 && f < nF) {
-        const MeshObject o = mesh_object(voff, mesh_entry_of(foff, B, f), nV);
-        const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-        if (mesh_index_ok(i0, o.V) && mesh_index_ok(i1, o.V) && mesh_index_ok(i2, o.V)) {
-            const float* pa = verts + (o.v0 + i0) * 3;
-            const float* pb = verts + (o.v0 + i1) * 3;
-            const float* pc = verts + (o.v0 + i2) * 3;
-            const float* p0 = verts + (o.v0 + root[o.v0 + i0]) * 3;       // the component's vertex of smallest index is its root
+        const MeshFace m = mesh_face(faces, voff, foff, B, nV, f);
+        if (m.ok) {
+            const float* pa = verts + (m.v0 + m.idx[0]) * 3;
+            const float* pb = verts + (m.v0 + m.idx[1]) * 3;
+            const float* pc = verts + (m.v0 + m.idx[2]) * 3;
+            const float* p0 = verts + (m.v0 + root[m.v0 + m.idx[0]]) * 3;    // the component's vertex of smallest index is its root
             double a[3], b[3], c[3], p[3];
             for (int k = 0; k < 3; ++k) { a[k] = (double)pa[k]; b[k] = (double)pb[k]; c[k] = (double)pc[k]; p[k] = (double)p0[k]; }
             double e1[3], e2[3];
@@ -238,52 +230,29 @@ __global__ void mesh_face_terms_kernel(const float* __restrict__ verts, const in
     vol_t[i] = vol;
 }
 
-// ---- the two float64 sums per component, in a fixed order: slab s of component c is its sorted faces [seg_start[c] + 4096 j, + 4096)
-// (j = s - slab_off[c]); thread t adds the slab's terms t, t + 256, ... in that order, then a binary tree over the 256 threads in LDS.
+// ---- the two float64 sums per component: the fixed-order segmented sum of snr_packed_mesh.hpp with N = 2 (area, volume)
 __global__ void __launch_bounds__(GRID_THREADS) mesh_slab_sum_kernel(const double* __restrict__ area_t, const double* __restrict__ vol_t,
                                                                      const long long* __restrict__ seg_start,
                                                                      const long long* __restrict__ slab_off, long long nC, long long nF,
                                                                      double* __restrict__ partial) {
-    __shared__ double s_a[GRID_THREADS], s_v[GRID_THREADS];
-    const long long s = blockIdx.x;
-    if (s >= slab_off[nC]) return;                                          // (the grid is an upper bound of the slab count)
-    const long long c = mesh_entry_of(slab_off, nC, s);
-    long long begin = seg_start[c] + (s - slab_off[c]) * MESH_SLAB, end = begin + MESH_SLAB;
-    if (end > seg_start[c + 1]) end = seg_start[c + 1];
-    if (begin < 0) begin = 0;
-    if (end > nF) end = nF;
-    const int t = threadIdx.x;
-    double a = 0.0, v = 0.0;
-    for (long long i = begin + t; i < end; i += GRID_THREADS) { a += area_t[i]; v += vol_t[i]; }
-    s_a[t] = a;
-    s_v[t] = v;
-    for (int k = GRID_THREADS / 2; k; k >>= 1) {
-        __syncthreads();
-        if (t < k) { s_a[t] += s_a[t + k]; s_v[t] += s_v[t + k]; }
-    }
-    if (t == 0) { partial[s * 2] = s_a[0]; partial[s * 2 + 1] = s_v[0]; }
+    __shared__ double s_sum[2 * GRID_THREADS];
+    const SegmentSlab sl = segment_slab(seg_start, slab_off, nC, nF);
+    if (sl.c < 0) return;                                                   // (uniform over the block)
+    double acc[2] = {0.0, 0.0};
+    for (long long i = sl.begin + threadIdx.x; i < sl.end; i += GRID_THREADS) { acc[0] += area_t[i]; acc[1] += vol_t[i]; }
+    block_tree<2>(acc, s_sum, partial + (long long)blockIdx.x * 2);
 }
 
-// a wave per component: lane l adds the component's slab sums l, l + 64, ... in that order, then a butterfly over the 64 lanes
+// a wave per component
 __global__ void mesh_comp_sum_kernel(const double* __restrict__ partial, const long long* __restrict__ slab_off, long long nC,
                                      long long n_slabs, double* __restrict__ area, double* __restrict__ volume) {
     const long long gid = grid_thread();
     const long long c = gid >> 6;
     const int lane = (int)(gid & 63);
     if (c >= nC) return;                                                    // (whole waves: 256 threads per block, 64 per component)
-    long long begin = slab_off[c], end = slab_off[c + 1];
-    if (begin < 0) begin = 0;
-    if (end > n_slabs) end = n_slabs;
-    double a = 0.0, v = 0.0;
-    for (long long s = begin + lane; s < end; s += 64) { a += partial[s * 2]; v += partial[s * 2 + 1]; }
-    for (int k = 32; k; k >>= 1) { a += __shfl_xor(a, k); v += __shfl_xor(v, k); }
-    if (lane == 0) { area[c] = a; volume[c] = v; }
-}
-
-static int mesh_sizes(int64_t n_objects, int64_t a, int64_t b) {
-    if (n_objects < 0 || a < 0 || b < 0) return SNR_E_ARG;
-    if (n_objects > 0x7fffffffll || a > MESH_MAX_ITEMS || b > MESH_MAX_ITEMS) return SNR_E_UNSUPPORTED;
-    return SNR_OK;
+    double acc[2];
+    wave_sum<2>(partial, 2, slab_off[c], slab_off[c + 1], n_slabs, lane, acc);
+    if (lane == 0) { area[c] = acc[0]; volume[c] = acc[1]; }
 }
 
 }  // namespace snr
@@ -294,7 +263,7 @@ extern "C" {
 
 int snr_mesh_hook(const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, int64_t n_objects, int64_t n_verts,
                   int64_t n_faces, int32_t* parent, int32_t* bad, void* stream) {
-    const int rc = mesh_sizes(n_objects, n_verts, n_faces);
+    const int rc = packed_sizes(n_objects, n_verts, n_faces);
     if (rc != SNR_OK) return rc;
     if (!bad) return SNR_E_ARG;
     if (n_verts == 0 && n_faces == 0) return SNR_OK;
@@ -310,7 +279,7 @@ int snr_mesh_hook(const int32_t* faces, const int64_t* vert_offset, const int64_
 
 int snr_mesh_flatten(const int32_t* parent, const int64_t* vert_offset, int64_t n_objects, int64_t n_verts, int32_t* root, uint8_t* is_root,
                      void* stream) {
-    const int rc = mesh_sizes(n_objects, n_verts, 0);
+    const int rc = packed_sizes(n_objects, n_verts, 0);
     if (rc != SNR_OK) return rc;
     if (n_verts == 0) return SNR_OK;
     if (n_objects == 0 || !parent || !vert_offset || !root || !is_root) return SNR_E_ARG;
@@ -322,7 +291,7 @@ int snr_mesh_flatten(const int32_t* parent, const int64_t* vert_offset, int64_t 
 int snr_mesh_label(const int32_t* root, const int32_t* root_scan, const int32_t* faces, const int64_t* vert_offset,
                    const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, int32_t* vert_label, int32_t* face_label,
                    void* stream) {
-    const int rc = mesh_sizes(n_objects, n_verts, n_faces);
+    const int rc = packed_sizes(n_objects, n_verts, n_faces);
     if (rc != SNR_OK) return rc;
     if (n_verts == 0 && n_faces == 0) return SNR_OK;
     if (n_objects == 0 || !vert_offset || !face_offset || (n_verts && (!root || !root_scan || !vert_label)) ||
@@ -341,7 +310,7 @@ int snr_mesh_label(const int32_t* root, const int32_t* root_scan, const int32_t*
 
 int snr_mesh_boxes(const float* verts, const int32_t* vert_label, const int64_t* vert_offset, const int64_t* comp_offset, int64_t n_objects,
                    int64_t n_verts, int64_t n_comps, int64_t* comp_verts, float* bbox_lo, float* bbox_hi, void* stream) {
-    const int rc = mesh_sizes(n_objects, n_verts, n_comps);
+    const int rc = packed_sizes(n_objects, n_verts, n_comps);
     if (rc != SNR_OK) return rc;
     if (n_comps == 0) return SNR_OK;
     if (n_objects == 0 || !vert_offset || !comp_offset || !comp_verts || !bbox_lo || !bbox_hi || (n_verts && (!verts || !vert_label)))
@@ -361,7 +330,7 @@ int snr_mesh_boxes(const float* verts, const int32_t* vert_label, const int64_t*
 int snr_mesh_face_terms(const float* verts, const int32_t* faces, const int32_t* root, const int64_t* order, const int64_t* vert_offset,
                         const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, double* area_terms,
                         double* volume_terms, void* stream) {
-    const int rc = mesh_sizes(n_objects, n_verts, n_faces);
+    const int rc = packed_sizes(n_objects, n_verts, n_faces);
     if (rc != SNR_OK) return rc;
     if (n_faces == 0) return SNR_OK;
     if (n_objects == 0 || !verts || !faces || !root || !vert_offset || !face_offset || !area_terms || !volume_terms) return SNR_E_ARG;
@@ -371,18 +340,18 @@ int snr_mesh_face_terms(const float* verts, const int32_t* faces, const int32_t*
     return snr_check_launch_();
 }
 
-int64_t snr_mesh_slab_bound(int64_t n_comps, int64_t n_faces) {
-    if (n_comps < 0 || n_faces < 0) return 0;
-    return n_comps + n_faces / MESH_SLAB;
+int64_t snr_segment_slab_bound(int64_t n_segments, int64_t n_items) {
+    if (n_segments < 0 || n_items < 0) return 0;
+    return n_segments + n_items / SEGMENT_SLAB;
 }
 
 int snr_mesh_segment_sum(const double* area_terms, const double* volume_terms, const int64_t* seg_start, const int64_t* slab_offset,
                          int64_t n_comps, int64_t n_faces, double* partial, int64_t n_slabs, double* area, double* volume, void* stream) {
-    const int rc = mesh_sizes(0, n_comps, n_faces);
+    const int rc = packed_sizes(0, n_comps, n_faces);
     if (rc != SNR_OK) return rc;
     if (n_slabs < 0) return SNR_E_ARG;
     if (n_comps == 0) return SNR_OK;
-    if (n_slabs < snr_mesh_slab_bound(n_comps, n_faces)) return SNR_E_WORKSPACE;
+    if (n_slabs < snr_segment_slab_bound(n_comps, n_faces)) return SNR_E_WORKSPACE;
     if (n_slabs > 0x7fffffffll) return SNR_E_UNSUPPORTED;
     if (!seg_start || !slab_offset || !partial || !area || !volume || (n_faces && (!area_terms || !volume_terms))) return SNR_E_ARG;
     hipStream_t st = (hipStream_t)stream;

@@ -12,7 +12,7 @@
 // One thread per face walks the face's box of candidate pixels: iso-surface triangles seen from a camera cover a few pixels or none.  A
 // face whose box holds RASTER_BIG_BOX candidates or more would serialise one lane over all of them, so it is handed to its whole wave
 // instead: a ballot finds such faces, each one's snapped vertices are broadcast by shuffles, and the 64 lanes stride its box.
-#include "snr_grid.hpp"
+#include "snr_packed_mesh.hpp"
 #include "snr_host.hpp"
 
 namespace snr {
@@ -23,7 +23,6 @@ namespace snr {
 constexpr int RASTER_BIG_BOX = SNR_RASTER_BIG_BOX;           // candidate pixels from which a face's box is walked by the whole wave
 constexpr unsigned long long RASTER_EMPTY = ~0ull;           // the key of a pixel no face covers
 constexpr float RASTER_MAX_PIXEL = 4194304.0f;               // 2^22: a vertex this far from the origin of the image drops its face
-constexpr int RASTER_MAX_CHANNELS = 16;
 
 struct RasterTri {               // a snapped face: everything coverage, depth and weights are computed from
     int xs[3], ys[3];            // screen position with 8 sub-pixel bits
@@ -138,15 +137,13 @@ __global__ void __launch_bounds__(GRID_THREADS) raster_faces_kernel(const float*
     long long A = 0, image = 0;
     int count = 0;                                       // candidate pixels; 0 for a dropped face and past the end of the list
     if (f < nF) {
-        const long long b = mesh_entry_of(foff, B, f);
-        const MeshObject o = mesh_object(voff, b, nV);
-        const int idx[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
-        image = image_of[b];
-        bool ok = mesh_index_ok(idx[0], o.V) && mesh_index_ok(idx[1], o.V) && mesh_index_ok(idx[2], o.V) && image >= 0 && image < n_images;
-        if (ok) ok = raster_snap(screen, o.v0, idx, z_near, t);
+        const MeshFace m = mesh_face(faces, voff, foff, B, nV, f);
+        image = image_of[m.b];
+        bool ok = m.ok && image >= 0 && image < n_images;
+        if (ok) ok = raster_snap(screen, m.v0, m.idx, z_near, t);
         if (ok) {
             A = raster_area(t);
-            const int front = cull_sign ? cull_sign[b] : 0;
+            const int front = cull_sign ? cull_sign[m.b] : 0;
             ok = A != 0 && !((A > 0 && front > 0) || (A < 0 && front < 0));
         }
         if (ok) count = raster_box(t, W, H, box);
@@ -187,16 +184,6 @@ __global__ void __launch_bounds__(GRID_THREADS) raster_faces_kernel(const float*
     }
 }
 
-// the face's vertex indices and object, range-checked; false = not a face of this mesh
-__device__ __forceinline__ bool raster_face_of(const int* __restrict__ faces, const long long* __restrict__ voff,
-                                               const long long* __restrict__ foff, long long B, long long nV, long long f, int idx[3],
-                                               long long& v0) {
-    const MeshObject o = mesh_object(voff, mesh_entry_of(foff, B, f), nV);
-    idx[0] = faces[f * 3]; idx[1] = faces[f * 3 + 1]; idx[2] = faces[f * 3 + 2];
-    v0 = o.v0;
-    return mesh_index_ok(idx[0], o.V) && mesh_index_ok(idx[1], o.V) && mesh_index_ok(idx[2], o.V);
-}
-
 // a later launch: the keys are final and read with plain loads
 __global__ void raster_resolve_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ screen,
                                       const int* __restrict__ faces, const long long* __restrict__ voff, const long long* __restrict__ foff,
@@ -208,14 +195,13 @@ __global__ void raster_resolve_kernel(const unsigned long long* __restrict__ key
     const long long f = (long long)(key & 0xffffffffull);
     int face = -1;
     float depth = 0.0f, w[3] = {0.0f, 0.0f, 0.0f};
-    int idx[3];
-    long long v0;
-    if (key != RASTER_EMPTY && f < nF && raster_face_of(faces, voff, foff, B, nV, f, idx, v0)) {
+    MeshFace m;
+    if (key != RASTER_EMPTY && f < nF && (m = mesh_face(faces, voff, foff, B, nV, f)).ok) {
         const long long rest = p % ((long long)H * W);
         RasterTri t;
         RasterEdges e;
         long long E[3];
-        raster_snap(screen, v0, idx, 0.0f, t);
+        raster_snap(screen, m.v0, m.idx, 0.0f, t);
         raster_edges(t, raster_area(t), e);
         raster_cover(t, e, (int)(rest % W), (int)(rest / W), E);
         const float q = raster_q(t, E);
@@ -241,11 +227,11 @@ __global__ void raster_interpolate_kernel(const int* __restrict__ face, const fl
     const int c = (int)(g - p * C);
     const long long f = face[p];
     float v = background;
-    int idx[3];
-    long long v0;
-    if (f >= 0 && f < nF && raster_face_of(faces, voff, foff, B, nV, f, idx, v0)) {
+    MeshFace m;
+    if (f >= 0 && f < nF && (m = mesh_face(faces, voff, foff, B, nV, f)).ok) {
         const float* w = weights + p * 3;
-        v = (w[0] * attributes[(v0 + idx[0]) * C + c] + w[1] * attributes[(v0 + idx[1]) * C + c]) + w[2] * attributes[(v0 + idx[2]) * C + c];
+        v = (w[0] * attributes[(m.v0 + m.idx[0]) * C + c] + w[1] * attributes[(m.v0 + m.idx[1]) * C + c]) +
+            w[2] * attributes[(m.v0 + m.idx[2]) * C + c];
     }
     out[g] = v;
 }
@@ -316,7 +302,7 @@ int snr_raster_interpolate(const int32_t* face, const float* weights, const int3
     long long none;
     const int rc = raster_sizes(n_objects, n_verts, n_faces, 0, 0, 0, none);
     if (rc != SNR_OK) return rc;
-    if (n_pixels < 0 || n_channels < 1 || n_channels > RASTER_MAX_CHANNELS) return SNR_E_ARG;
+    if (n_pixels < 0 || n_channels < 1 || n_channels > PACKED_MAX_CHANNELS) return SNR_E_ARG;
     if (n_pixels > 0x7fffffffll) return SNR_E_UNSUPPORTED;
     if (n_pixels == 0) return SNR_OK;
     if (!face || !weights || !out || (n_faces && (n_objects == 0 || !faces || !vert_offset || !face_offset || !attributes))) return SNR_E_ARG;

@@ -8,18 +8,15 @@
 //
 // One pass over vertices (keys), one over faces (remap), one over the member and corner lists (sums).  The caller sorts: the vertices by
 // (object, cell), the face corners by (cluster, corner index).  Every float64 sum walks its sorted list in slabs of 4096 and fixed trees,
-// the scheme of snr_mesh_segment_sum, so the output has the same bits from run to run; there is no floating-point atomic anywhere, and no
-// launch reads what another thread of the same launch wrote.
-#include "snr_grid.hpp"
+// the segmented sum of snr_packed_mesh.hpp, so the output has the same bits from run to run; there is no floating-point atomic anywhere,
+// and no launch reads what another thread of the same launch wrote.
+#include "snr_packed_mesh.hpp"
 #include "snr_host.hpp"
 
 namespace snr {
 
-constexpr long long SIMPLIFY_MAX_ITEMS = 1ll << 38;    // vertices, faces, corners or clusters of one launch
-constexpr int SIMPLIFY_SLAB = 4096;                    // list entries one workgroup sums in a fixed order (MESH_SLAB of snr_mesh.hip)
 constexpr int SIMPLIFY_Q_BITS = 21;                    // bits per axis of the packed key
 constexpr int SIMPLIFY_Q_BIAS = 1 << 20;               // |q| < 2^20, so q + bias fits 21 bits
-constexpr int SIMPLIFY_MAX_CHANNELS = 16;              // (RASTER_MAX_CHANNELS)
 
 // ---- rule 1: the cell of a vertex.  (x - origin) and the division each round once; false where the cell index is not usable.
 __device__ __forceinline__ bool simplify_cell_of(const float* __restrict__ p, const float* __restrict__ org, float cell, int q[3]) {
@@ -55,21 +52,16 @@ __global__ void simplify_faces_kernel(const int* __restrict__ faces, const int* 
                                       int* __restrict__ new_faces, unsigned char* __restrict__ keep, int* bad) {
     const long long f = grid_thread();
     if (f >= nF) return;
-    const MeshObject o = mesh_object(voff, mesh_entry_of(foff, B, f), nV);
-    const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-    int n0 = -1, n1 = -1, n2 = -1;
+    const MeshFace m = mesh_face(faces, voff, foff, B, nV, f);
+    int n[3] = {-1, -1, -1};
     bool k = false;
-    if (mesh_index_ok(i0, o.V) && mesh_index_ok(i1, o.V) && mesh_index_ok(i2, o.V)) {      // checked before anything is read with them
-        n0 = vert_map[o.v0 + i0];
-        n1 = vert_map[o.v0 + i1];
-        n2 = vert_map[o.v0 + i2];
-        k = n0 != n1 && n1 != n2 && n0 != n2;
+    if (m.ok) {
+        for (int a = 0; a < 3; ++a) n[a] = vert_map[m.v0 + m.idx[a]];
+        k = n[0] != n[1] && n[1] != n[2] && n[0] != n[2];
     } else {
         __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    new_faces[f * 3] = n0;
-    new_faces[f * 3 + 1] = n1;
-    new_faces[f * 3 + 2] = n2;
+    for (int a = 0; a < 3; ++a) new_faces[f * 3 + a] = n[a];
     keep[f] = k;
 }
 
@@ -85,51 +77,7 @@ __global__ void simplify_compact_kernel(const int* __restrict__ new_faces, const
     face_index[s] = f;
 }
 
-// ---- rule 5: the fixed order of every sum.  Slab s of segment c is the sorted entries [seg_start[c] + 4096 j, + 4096), j = s -
-// slab_off[c]; thread t adds the slab's entries t, t + 256, ... in that order, then a binary tree over the 256 threads in LDS.
-struct SimplifySlab {
-    long long c, begin, end;          // segment, entries [begin, end) of the sorted list; c < 0: no such slab
-};
-__device__ __forceinline__ SimplifySlab simplify_slab(const long long* __restrict__ seg_start, const long long* __restrict__ slab_off,
-                                                      long long nC, long long n_items) {
-    SimplifySlab r;
-    const long long s = blockIdx.x;
-    r.c = -1; r.begin = r.end = 0;
-    if (s >= slab_off[nC]) return r;                                         // (the grid is an upper bound of the slab count)
-    r.c = mesh_entry_of(slab_off, nC, s);
-    r.begin = seg_start[r.c] + (s - slab_off[r.c]) * SIMPLIFY_SLAB;
-    r.end = r.begin + SIMPLIFY_SLAB;
-    if (r.end > seg_start[r.c + 1]) r.end = seg_start[r.c + 1];
-    if (r.begin < 0) r.begin = 0;
-    if (r.end > n_items) r.end = n_items;
-    return r;
-}
-
-template <int N>
-__device__ __forceinline__ void simplify_block_tree(double (&acc)[N], double* __restrict__ s_sum, double* __restrict__ out) {
-    const int t = threadIdx.x;
-    for (int j = 0; j < N; ++j) s_sum[j * GRID_THREADS + t] = acc[j];
-    for (int k = GRID_THREADS / 2; k; k >>= 1) {
-        __syncthreads();
-        if (t < k)
-            for (int j = 0; j < N; ++j) s_sum[j * GRID_THREADS + t] += s_sum[j * GRID_THREADS + t + k];
-    }
-    if (t == 0)
-        for (int j = 0; j < N; ++j) out[j] = s_sum[j * GRID_THREADS];
-}
-
-// per segment, lane l of a wave adds the slab sums l, l + 64, ... in that order, then a butterfly over the 64 lanes
-template <int N>
-__device__ __forceinline__ void simplify_wave_sum(const double* __restrict__ partial, long long begin, long long end, long long n_slabs,
-                                                  int lane, double (&acc)[N]) {
-    if (begin < 0) begin = 0;
-    if (end > n_slabs) end = n_slabs;
-    for (int j = 0; j < N; ++j) acc[j] = 0.0;
-    for (long long s = begin + lane; s < end; s += 64)
-        for (int j = 0; j < N; ++j) acc[j] += partial[s * N + j];
-    for (int k = 32; k; k >>= 1)
-        for (int j = 0; j < N; ++j) acc[j] += __shfl_xor(acc[j], k);
-}
+// ---- rule 5: every sum below is the fixed-order segmented sum of snr_packed_mesh.hpp (segment_slab, block_tree, wave_sum)
 
 // the members' coordinates, widened: partial (n_slabs, 3)
 __global__ void __launch_bounds__(GRID_THREADS) simplify_vert_slab_kernel(const float* __restrict__ verts,
@@ -138,7 +86,7 @@ __global__ void __launch_bounds__(GRID_THREADS) simplify_vert_slab_kernel(const 
                                                                           const long long* __restrict__ slab_off, long long nC, long long nV,
                                                                           double* __restrict__ partial) {
     __shared__ double s_sum[3 * GRID_THREADS];
-    const SimplifySlab sl = simplify_slab(seg_start, slab_off, nC, nV);
+    const SegmentSlab sl = segment_slab(seg_start, slab_off, nC, nV);
     if (sl.c < 0) return;                                                    // (uniform over the block)
     double acc[3] = {0.0, 0.0, 0.0};
     for (long long i = sl.begin + threadIdx.x; i < sl.end; i += GRID_THREADS) {
@@ -146,7 +94,7 @@ __global__ void __launch_bounds__(GRID_THREADS) simplify_vert_slab_kernel(const 
         if (g < 0 || g >= nV) continue;
         for (int a = 0; a < 3; ++a) acc[a] += (double)verts[g * 3 + a];
     }
-    simplify_block_tree<3>(acc, s_sum, partial + (long long)blockIdx.x * 3);
+    block_tree<3>(acc, s_sum, partial + (long long)blockIdx.x * 3);
 }
 
 // the object and the cell of cluster k, from its first member in the sorted order (rule 1 again: the same operations, the same bits)
@@ -185,7 +133,7 @@ __global__ void __launch_bounds__(GRID_THREADS) simplify_corner_slab_kernel(
     const long long* __restrict__ vert_order, const long long* __restrict__ vseg_start, const long long* __restrict__ corner_order,
     const long long* __restrict__ cseg_start, const long long* __restrict__ cslab_off, long long nC, double* __restrict__ partial) {
     __shared__ double s_sum[9 * GRID_THREADS];
-    const SimplifySlab sl = simplify_slab(cseg_start, cslab_off, nC, nF * 3);
+    const SegmentSlab sl = segment_slab(cseg_start, cslab_off, nC, nF * 3);
     if (sl.c < 0) return;
     const SimplifyCell cc = simplify_cluster_cell(verts, vert_order, vseg_start, voff, cell, origin, B, nV, sl.c);
     double c0[3];
@@ -195,15 +143,13 @@ __global__ void __launch_bounds__(GRID_THREADS) simplify_corner_slab_kernel(
     for (long long i = sl.begin + threadIdx.x; i < sl.end && cc.ok; i += GRID_THREADS) {
         const long long corner = corner_order[i];
         if (corner < 0 || corner >= nF * 3) continue;
-        const long long f = corner / 3;
-        const MeshObject o = mesh_object(voff, mesh_entry_of(foff, B, f), nV);
-        const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-        if (!mesh_index_ok(i0, o.V) || !mesh_index_ok(i1, o.V) || !mesh_index_ok(i2, o.V)) continue;
+        const MeshFace m = mesh_face(faces, voff, foff, B, nV, corner / 3);
+        if (!m.ok) continue;
         double pa[3], e1[3], e2[3];
         for (int a = 0; a < 3; ++a) {
-            pa[a] = (double)verts[(o.v0 + i0) * 3 + a] - c0[a];
-            e1[a] = ((double)verts[(o.v0 + i1) * 3 + a] - c0[a]) - pa[a];
-            e2[a] = ((double)verts[(o.v0 + i2) * 3 + a] - c0[a]) - pa[a];
+            pa[a] = (double)verts[(m.v0 + m.idx[0]) * 3 + a] - c0[a];
+            e1[a] = ((double)verts[(m.v0 + m.idx[1]) * 3 + a] - c0[a]) - pa[a];
+            e2[a] = ((double)verts[(m.v0 + m.idx[2]) * 3 + a] - c0[a]) - pa[a];
         }
         double n[3];
         n[0] = e1[1] * e2[2] - e1[2] * e2[1];
@@ -214,7 +160,7 @@ __global__ void __launch_bounds__(GRID_THREADS) simplify_corner_slab_kernel(
         acc[3] += n[1] * n[1]; acc[4] += n[1] * n[2]; acc[5] += n[2] * n[2];
         acc[6] += d * n[0]; acc[7] += d * n[1]; acc[8] += d * n[2];
     }
-    simplify_block_tree<9>(acc, s_sum, partial + (long long)blockIdx.x * 9);
+    block_tree<9>(acc, s_sum, partial + (long long)blockIdx.x * 9);
 }
 
 // (A + lambda I) y = r for a symmetric positive definite A + lambda I, by Cholesky; a = A00 A01 A02 A11 A12 A22
@@ -244,9 +190,9 @@ __global__ void simplify_cluster_kernel(const float* __restrict__ verts, const l
     const int lane = (int)(gid & 63);
     if (k >= nC) return;                                                     // (whole waves: 256 threads per block, 64 per cluster)
     double sv[3], sq[9];
-    simplify_wave_sum<3>(vpartial, vslab_off[k], vslab_off[k + 1], n_vslabs, lane, sv);
+    wave_sum<3>(vpartial, 3, vslab_off[k], vslab_off[k + 1], n_vslabs, lane, sv);
     for (int j = 0; j < 9; ++j) sq[j] = 0.0;
-    if (quadric) simplify_wave_sum<9>(cpartial, cslab_off[k], cslab_off[k + 1], n_cslabs, lane, sq);
+    if (quadric) wave_sum<9>(cpartial, 9, cslab_off[k], cslab_off[k + 1], n_cslabs, lane, sq);
     if (lane != 0) return;
     const long long count = vseg_start[k + 1] - vseg_start[k];
     double m[3], x[3];
@@ -278,7 +224,7 @@ __global__ void __launch_bounds__(GRID_THREADS) simplify_attr_slab_kernel(const 
                                                                           const long long* __restrict__ slab_off, long long nC, long long nV,
                                                                           double* __restrict__ partial) {
     __shared__ double s_sum[GRID_THREADS];
-    const SimplifySlab sl = simplify_slab(seg_start, slab_off, nC, nV);
+    const SegmentSlab sl = segment_slab(seg_start, slab_off, nC, nV);
     if (sl.c < 0) return;
     const int ch = blockIdx.y;
     double acc[1] = {0.0};
@@ -287,7 +233,7 @@ __global__ void __launch_bounds__(GRID_THREADS) simplify_attr_slab_kernel(const 
         if (g < 0 || g >= nV) continue;
         acc[0] += (double)attr[g * C + ch];
     }
-    simplify_block_tree<1>(acc, s_sum, partial + (long long)blockIdx.x * C + ch);
+    block_tree<1>(acc, s_sum, partial + (long long)blockIdx.x * C + ch);
 }
 
 // a wave per (cluster, channel)
@@ -300,20 +246,10 @@ __global__ void simplify_attr_cluster_kernel(const double* __restrict__ partial,
     if (w >= nC * C) return;
     const long long k = w / C;
     const int ch = (int)(w - k * C);
-    long long begin = slab_off[k], end = slab_off[k + 1];
-    if (begin < 0) begin = 0;
-    if (end > n_slabs) end = n_slabs;
-    double a = 0.0;
-    for (long long s = begin + lane; s < end; s += 64) a += partial[s * C + ch];
-    for (int j = 32; j; j >>= 1) a += __shfl_xor(a, j);
+    double a[1];
+    wave_sum<1>(partial + ch, C, slab_off[k], slab_off[k + 1], n_slabs, lane, a);
     const long long count = seg_start[k + 1] - seg_start[k];
-    if (lane == 0) out[k * C + ch] = (float)(a / (double)(count > 0 ? count : 1));
-}
-
-static int simplify_sizes(int64_t n_objects, int64_t a, int64_t b) {
-    if (n_objects < 0 || a < 0 || b < 0) return SNR_E_ARG;
-    if (n_objects > 0x7fffffffll || a > SIMPLIFY_MAX_ITEMS || b > SIMPLIFY_MAX_ITEMS) return SNR_E_UNSUPPORTED;
-    return SNR_OK;
+    if (lane == 0) out[k * C + ch] = (float)(a[0] / (double)(count > 0 ? count : 1));
 }
 
 }  // namespace snr
@@ -324,7 +260,7 @@ extern "C" {
 
 int snr_simplify_keys(const float* verts, const int64_t* vert_offset, const float* cell, const float* origin, int64_t n_objects,
                       int64_t n_verts, int64_t* key, int32_t* bad, void* stream) {
-    const int rc = simplify_sizes(n_objects, n_verts, 0);
+    const int rc = packed_sizes(n_objects, n_verts, 0);
     if (rc != SNR_OK) return rc;
     if (!bad) return SNR_E_ARG;
     if (n_verts == 0) return SNR_OK;
@@ -336,7 +272,7 @@ int snr_simplify_keys(const float* verts, const int64_t* vert_offset, const floa
 
 int snr_simplify_faces(const int32_t* faces, const int32_t* vert_map, const int64_t* vert_offset, const int64_t* face_offset,
                        int64_t n_objects, int64_t n_verts, int64_t n_faces, int32_t* new_faces, uint8_t* keep, int32_t* bad, void* stream) {
-    const int rc = simplify_sizes(n_objects, n_verts, n_faces);
+    const int rc = packed_sizes(n_objects, n_verts, n_faces);
     if (rc != SNR_OK) return rc;
     if (!bad) return SNR_E_ARG;
     if (n_faces == 0) return SNR_OK;
@@ -348,7 +284,7 @@ int snr_simplify_faces(const int32_t* faces, const int32_t* vert_map, const int6
 
 int snr_simplify_compact(const int32_t* new_faces, const uint8_t* keep, const int64_t* keep_scan, int64_t n_faces, int64_t n_kept,
                          int32_t* out_faces, int64_t* face_index, void* stream) {
-    const int rc = simplify_sizes(0, n_faces, n_kept);
+    const int rc = packed_sizes(0, n_faces, n_kept);
     if (rc != SNR_OK) return rc;
     if (n_kept > n_faces) return SNR_E_ARG;
     if (n_faces == 0 || n_kept == 0) return SNR_OK;
@@ -358,26 +294,21 @@ int snr_simplify_compact(const int32_t* new_faces, const uint8_t* keep, const in
     return snr_check_launch_();
 }
 
-int64_t snr_simplify_slab_bound(int64_t n_clusters, int64_t n_items) {
-    if (n_clusters < 0 || n_items < 0) return 0;
-    return n_clusters + n_items / SIMPLIFY_SLAB;
-}
-
 int snr_simplify_positions(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset,
                            const float* cell, const float* origin, int64_t n_objects, int64_t n_verts, int64_t n_faces,
                            const int64_t* vert_order, const int64_t* vert_seg_start, const int64_t* vert_slab_offset,
                            const int64_t* corner_order, const int64_t* corner_seg_start, const int64_t* corner_slab_offset,
                            int64_t n_clusters, int quadric, double* vert_partial, int64_t n_vert_slabs, double* corner_partial,
                            int64_t n_corner_slabs, float* out_verts, void* stream) {
-    int rc = simplify_sizes(n_objects, n_verts, n_faces);
+    int rc = packed_sizes(n_objects, n_verts, n_faces);
     if (rc != SNR_OK) return rc;
-    rc = simplify_sizes(0, n_clusters, 0);
+    rc = packed_sizes(0, n_clusters, 0);
     if (rc != SNR_OK) return rc;
     if (n_vert_slabs < 0 || n_corner_slabs < 0 || (quadric != 0 && quadric != 1) || n_clusters > n_verts) return SNR_E_ARG;
     if (n_clusters == 0) return SNR_OK;
     const bool corners = quadric && n_faces > 0;
-    if (n_vert_slabs < snr_simplify_slab_bound(n_clusters, n_verts)) return SNR_E_WORKSPACE;
-    if (corners && n_corner_slabs < snr_simplify_slab_bound(n_clusters, n_faces * 3)) return SNR_E_WORKSPACE;
+    if (n_vert_slabs < snr_segment_slab_bound(n_clusters, n_verts)) return SNR_E_WORKSPACE;
+    if (corners && n_corner_slabs < snr_segment_slab_bound(n_clusters, n_faces * 3)) return SNR_E_WORKSPACE;
     if (n_vert_slabs > 0x7fffffffll || n_corner_slabs > 0x7fffffffll || n_clusters > 0x7fffffffll) return SNR_E_UNSUPPORTED;
     if (n_objects == 0 || !verts || !vert_offset || !cell || !origin || !vert_order || !vert_seg_start || !vert_slab_offset ||
         !vert_partial || !out_verts)
@@ -403,11 +334,11 @@ int snr_simplify_positions(const float* verts, const int32_t* faces, const int64
 int snr_simplify_attributes(const float* attributes, int n_channels, int64_t n_verts, const int64_t* vert_order,
                             const int64_t* vert_seg_start, const int64_t* vert_slab_offset, int64_t n_clusters, double* partial,
                             int64_t n_slabs, float* out, void* stream) {
-    const int rc = simplify_sizes(0, n_verts, n_clusters);
+    const int rc = packed_sizes(0, n_verts, n_clusters);
     if (rc != SNR_OK) return rc;
-    if (n_channels < 1 || n_channels > SIMPLIFY_MAX_CHANNELS || n_slabs < 0 || n_clusters > n_verts) return SNR_E_ARG;
+    if (n_channels < 1 || n_channels > PACKED_MAX_CHANNELS || n_slabs < 0 || n_clusters > n_verts) return SNR_E_ARG;
     if (n_clusters == 0) return SNR_OK;
-    if (n_slabs < snr_simplify_slab_bound(n_clusters, n_verts)) return SNR_E_WORKSPACE;
+    if (n_slabs < snr_segment_slab_bound(n_clusters, n_verts)) return SNR_E_WORKSPACE;
     if (n_slabs > 0x7fffffffll || n_clusters * n_channels > (0x7fffffffll >> 2)) return SNR_E_UNSUPPORTED;
     if (!attributes || !vert_order || !vert_seg_start || !vert_slab_offset || !partial || !out) return SNR_E_ARG;
     hipStream_t st = (hipStream_t)stream;

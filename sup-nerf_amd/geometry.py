@@ -429,6 +429,25 @@ def _one_or_many(meshes):
     return _meshes([tuple(meshes)] if single else meshes), single
 
 
+def _packed(ms):
+    """(verts, faces, n_verts, n_faces) of a list of (verts, faces) pairs that is not empty: the packed form ``ops`` takes."""
+    for _, f in ms:
+        if f.dtype != torch.int32:
+            raise SnrError(f"faces are int32, got {f.dtype}")
+    nvs, nfs = [v.shape[0] for v, _ in ms], [f.shape[0] for _, f in ms]
+    if len(ms) == 1:
+        return ms[0][0].detach(), ms[0][1], nvs, nfs
+    return torch.cat([v.detach().float() for v, _ in ms]), torch.cat([f for _, f in ms]), nvs, nfs
+
+
+def _object_slices(*sizes):
+    """Per object one slice per list of ``sizes``: where the object's items lie in the packed array those sizes add up to."""
+    starts = [0] * len(sizes)
+    for ns in zip(*sizes):
+        yield tuple(slice(s, s + n) for s, n in zip(starts, ns))
+        starts = [s + n for s, n in zip(starts, ns)]
+
+
 def mesh_components(meshes):
     """The connected components of each mesh of ``meshes`` -- the list ``extract_mesh`` returns (vertices with a ``grad_fn`` are fine: the
     analysis reads their values), or one (verts, faces) pair.  Returns one ``Components`` per object (a single one for a single pair).
@@ -446,22 +465,10 @@ def mesh_components(meshes):
     ms, single = _one_or_many(meshes)
     if not ms:
         return []
-    for v, f in ms:
-        if f.dtype != torch.int32:
-            raise SnrError(f"faces are int32, got {f.dtype}")
-    nvs, nfs = [v.shape[0] for v, _ in ms], [f.shape[0] for _, f in ms]
-    if len(ms) == 1:
-        verts, faces = ms[0][0].detach(), ms[0][1]
-    else:
-        verts, faces = torch.cat([v.detach().float() for v, _ in ms]), torch.cat([f for _, f in ms])
+    verts, faces, nvs, nfs = _packed(ms)
     m = ops.mesh_components(verts, faces, nvs, nfs)
-    out, v0, f0 = [], 0, 0
-    for b in range(len(ms)):
-        c0, c1 = m.comp_offset[b], m.comp_offset[b + 1]
-        out.append(Components(m.vert_label[v0:v0 + nvs[b]], m.face_label[f0:f0 + nfs[b]], m.n_verts[c0:c1], m.n_faces[c0:c1], m.area[c0:c1],
-                              m.volume[c0:c1], m.bbox_lo[c0:c1], m.bbox_hi[c0:c1]))
-        v0 += nvs[b]
-        f0 += nfs[b]
+    out = [Components(m.vert_label[v], m.face_label[f], m.n_verts[c], m.n_faces[c], m.area[c], m.volume[c], m.bbox_lo[c], m.bbox_hi[c])
+           for v, f, c in _object_slices(nvs, nfs, m.n_comps)]
     return out[0] if single else out
 
 
@@ -579,9 +586,7 @@ def simplify_mesh(meshes, cell, *, origin=None, placement="quadric", attributes=
     if not ms:
         return []
     B = len(ms)
-    for v, f in ms:
-        if f.dtype != torch.int32:
-            raise SnrError(f"faces are int32, got {f.dtype}")
+    verts, faces, nvs, nfs = _packed(ms)
     if attributes is not None:
         attributes = [attributes] if torch.is_tensor(attributes) else list(attributes)
         if len(attributes) != B:
@@ -593,16 +598,12 @@ def simplify_mesh(meshes, cell, *, origin=None, placement="quadric", attributes=
         attributes = torch.cat([a.detach().float() for a in attributes])
     if origin is None:
         origin = torch.zeros(B, 3)
-    nvs, nfs = [v.shape[0] for v, _ in ms], [f.shape[0] for _, f in ms]
-    verts, faces = torch.cat([v.detach().float() for v, _ in ms]), torch.cat([f for _, f in ms])
     s = ops.mesh_simplify(verts, faces, nvs, nfs, cell, origin, placement, attributes)
-    out, v0, f0, c0, k0 = [], 0, 0, 0, 0
-    for b in range(B):
-        c1, k1 = c0 + s.n_verts[b], k0 + s.n_faces[b]
-        one = Simplified(s.verts[c0:c1], s.faces[k0:k1], s.vert_map[v0:v0 + nvs[b]], s.face_index[k0:k1] - f0, s.members[c0:c1],
-                         None if s.attributes is None else s.attributes[c0:c1])
+    out = []
+    for v, f, c, k in _object_slices(nvs, nfs, s.n_verts, s.n_faces):
+        one = Simplified(s.verts[c], s.faces[k], s.vert_map[v], s.face_index[k] - f.start, s.members[c],
+                         None if s.attributes is None else s.attributes[c])
         out.append(_drop_unreferenced(one) if drop_unreferenced else one)
-        v0, f0, c0, k0 = v0 + nvs[b], f0 + nfs[b], c1, k1
     return out[0] if single else out
 
 
@@ -670,17 +671,10 @@ def _det3(m):
 
 
 def _pack(meshes):
-    ms, single = _one_or_many(meshes)
-    for _, f in ms:
-        if f.dtype != torch.int32:
-            raise SnrError(f"faces are int32, got {f.dtype}")
+    ms, _ = _one_or_many(meshes)
     if not ms:
         raise SnrError("no mesh to draw")
-    if len(ms) == 1:
-        verts, faces = ms[0][0].detach(), ms[0][1]
-    else:
-        verts, faces = torch.cat([v.detach().float() for v, _ in ms]), torch.cat([f for _, f in ms])
-    return ops.pack_mesh(verts, faces, [v.shape[0] for v, _ in ms], [f.shape[0] for _, f in ms])
+    return ops.pack_mesh(*_packed(ms))
 
 
 def rasterize(meshes, obj_to_cam, K, size, *, cull=None, z_near=1e-3, per_object=False):

@@ -1457,7 +1457,7 @@ class IsoVerticesLatent(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------ mesh components
-MESH_SLAB = 4096         # faces per slab of the fixed-order float64 sums (include/supnerf_hip.h: snr_mesh_segment_sum)
+MESH_SLAB = 4096         # list entries per slab of the fixed-order float64 sums (include/supnerf_hip.h, "Fixed-order segmented sums")
 
 
 class MeshComponents(NamedTuple):
@@ -1473,11 +1473,32 @@ class MeshComponents(NamedTuple):
     bbox_hi: torch.Tensor      # (sum C, 3) fp32
 
 
-def _offsets(sizes, dev):
+def _host_offsets(sizes):
+    """[0, s0, s0 + s1, ...]: where each object's items start in a packed array, and the total."""
     off = [0]
     for s in sizes:
         off.append(off[-1] + int(s))
+    return off
+
+
+def _offsets(sizes, dev):
+    off = _host_offsets(sizes)
     return off, torch.tensor(off, dtype=torch.int64).to(dev)
+
+
+def _last_slots(off_h, dev):
+    """(the objects that are not empty, the last packed slot of each as an int64 index tensor on ``dev``): what a host read gathers."""
+    full = [b for b in range(len(off_h) - 1) if off_h[b + 1] > off_h[b]]
+    return full, torch.tensor([off_h[b + 1] - 1 for b in full], dtype=torch.int64).to(dev)
+
+
+def _segments(sorted_ids, n_segments, dev):
+    """(seg_start, slab_offset), both (n_segments + 1) int64, of a list sorted by segment id (include/supnerf_hip.h, "Fixed-order
+    segmented sums")."""
+    seg_start = torch.searchsorted(sorted_ids, torch.arange(n_segments + 1, dtype=sorted_ids.dtype, device=dev))
+    slab_off = torch.zeros(n_segments + 1, dtype=torch.int64, device=dev)
+    torch.cumsum((seg_start[1:] - seg_start[:-1] + (MESH_SLAB - 1)) // MESH_SLAB, 0, out=slab_off[1:])
+    return seg_start, slab_off
 
 
 class PackedMesh(NamedTuple):
@@ -1520,7 +1541,7 @@ def mesh_components(verts, faces, n_verts, n_faces):
     nV, nF = verts.shape[0], faces.shape[0]
     lib, st = _lib.lib(), _stream(dev)
     i32, i64, f64 = torch.int32, torch.int64, torch.float64
-    voff_h = [sum(n_verts[:b]) for b in range(B + 1)]
+    voff_h = _host_offsets(n_verts)
     with torch.cuda.device(dev):
         parent = torch.empty(nV, dtype=i32, device=dev)
         root = torch.empty(nV, dtype=i32, device=dev)
@@ -1534,8 +1555,7 @@ def mesh_components(verts, faces, n_verts, n_faces):
         for b in range(B):
             if n_verts[b]:
                 torch.cumsum(is_root[voff_h[b]:voff_h[b + 1]], 0, dtype=i32, out=root_scan[voff_h[b]:voff_h[b + 1]])
-        full = [b for b in range(B) if n_verts[b]]
-        last = torch.tensor([voff_h[b + 1] - 1 for b in full], dtype=i64).to(dev)
+        full, last = _last_slots(voff_h, dev)
         host = torch.cat([bad.long(), root_scan[last].long()]).cpu().tolist()          # the one host read
         if host[0]:
             raise SnrError("mesh_components: a face index lies outside its object's vertices")
@@ -1561,14 +1581,12 @@ def mesh_components(verts, faces, n_verts, n_faces):
             if B > 1:       # component ids of the whole call: the object's first id added to every face of the object
                 key = face_label + torch.repeat_interleave(coff[:-1].to(i32), torch.tensor(n_faces, dtype=i64).to(dev), output_size=nF)
             key, order = torch.sort(key, stable=True)
-            seg_start = torch.searchsorted(key, torch.arange(nC + 1, dtype=i32, device=dev))
+            seg_start, slab_off = _segments(key, nC, dev)
             comp_faces = seg_start[1:] - seg_start[:-1]
-            slab_off = torch.zeros(nC + 1, dtype=i64, device=dev)
-            torch.cumsum((comp_faces + (MESH_SLAB - 1)) // MESH_SLAB, 0, out=slab_off[1:])
             area_t, vol_t = torch.empty(nF, dtype=f64, device=dev), torch.empty(nF, dtype=f64, device=dev)
             check(lib.snr_mesh_face_terms(_ptr(verts), _ptr(faces, i32), _ptr(root, i32), _ptr(order, i64), _ptr(voff, i64), _ptr(foff, i64),
                                           B, nV, nF, _ptr(area_t, f64), _ptr(vol_t, f64), st), "snr_mesh_face_terms")
-            n_slabs = int(lib.snr_mesh_slab_bound(nC, nF))
+            n_slabs = int(lib.snr_segment_slab_bound(nC, nF))
             partial = torch.empty(n_slabs, 2, dtype=f64, device=dev)
             check(lib.snr_mesh_segment_sum(_ptr(area_t, f64), _ptr(vol_t, f64), _ptr(seg_start, i64), _ptr(slab_off, i64), nC, nF,
                                            _ptr(partial, f64), n_slabs, _ptr(area, f64), _ptr(volume, f64), st), "snr_mesh_segment_sum")
@@ -1598,14 +1616,6 @@ def _per_object_f32(x, B, width, dev, what):
     if tuple(t.shape) != shape:
         raise SnrError(f"mesh_simplify: {what} is one value or one per object {shape}, got {tuple(t.shape)}")
     return t.to(dev).contiguous()
-
-
-def _segments(sorted_ids, n_segments, dev):
-    """(seg_start, slab_offset), both (n_segments + 1) int64, of a list sorted by segment id (include/supnerf_hip.h: rule 5)."""
-    seg_start = torch.searchsorted(sorted_ids, torch.arange(n_segments + 1, dtype=sorted_ids.dtype, device=dev))
-    slab_off = torch.zeros(n_segments + 1, dtype=torch.int64, device=dev)
-    torch.cumsum((seg_start[1:] - seg_start[:-1] + (MESH_SLAB - 1)) // MESH_SLAB, 0, out=slab_off[1:])
-    return seg_start, slab_off
 
 
 def mesh_simplify(verts, faces, n_verts, n_faces, cell, origin, placement="quadric", attributes=None) -> SimplifiedMesh:
@@ -1664,9 +1674,8 @@ def mesh_simplify(verts, faces, n_verts, n_faces, cell, origin, placement="quadr
         cluster_sorted = torch.cumsum(head, 0, dtype=i64) - 1       # the cluster of the whole call, per sorted vertex
         cluster_of = torch.empty(nV, dtype=i64, device=dev)
         cluster_of[vert_order] = cluster_sorted
-        full = [b for b in range(B) if n_verts[b]]
-        voff_h = [sum(n_verts[:b]) for b in range(B + 1)]
-        foff_h = [sum(n_faces[:b]) for b in range(B + 1)]
+        voff_h, foff_h = _host_offsets(n_verts), _host_offsets(n_faces)
+        (full, last_v), (with_faces, last_f) = _last_slots(voff_h, dev), _last_slots(foff_h, dev)
         first_cluster = torch.zeros(B, dtype=i64, device=dev)       # (object b's vertices hold the sorted slots voff[b] .. voff[b + 1])
         if full:
             first_cluster[torch.tensor(full, dtype=i64).to(dev)] = cluster_sorted[torch.tensor([voff_h[b] for b in full], dtype=i64).to(dev)]
@@ -1677,9 +1686,6 @@ def mesh_simplify(verts, faces, n_verts, n_faces, cell, origin, placement="quadr
         check(lib.snr_simplify_faces(_ptr(faces, i32), _ptr(vert_map, i32), _ptr(voff, i64), _ptr(foff, i64), B, nV, nF,
                                      _ptr(new_faces, i32), _ptr(keep, u8), _ptr(bad[1:2], i32), st), "snr_simplify_faces")
         keep_scan = torch.cumsum(keep, 0, dtype=i64)
-        last_v = torch.tensor([voff_h[b + 1] - 1 for b in full], dtype=i64).to(dev)
-        with_faces = [b for b in range(B) if n_faces[b]]
-        last_f = torch.tensor([foff_h[b + 1] - 1 for b in with_faces], dtype=i64).to(dev)
         host = torch.cat([bad.long(), cluster_sorted[last_v] + 1, keep_scan[last_f]]).cpu().tolist()      # the one host read
         if host[2]:
             raise SnrError("mesh_simplify: cell must be positive and finite")
@@ -1711,9 +1717,9 @@ def mesh_simplify(verts, faces, n_verts, n_faces, cell, origin, placement="quadr
             face_v0 = torch.repeat_interleave(voff[:-1], counts_f, output_size=nF)
             corner_cluster, corder = torch.sort(cluster_of[(faces.long() + face_v0[:, None]).view(-1)], stable=True)
             cseg, cslab = _segments(corner_cluster, nC, dev)
-            n_cslabs = int(lib.snr_simplify_slab_bound(nC, nF * 3))
+            n_cslabs = int(lib.snr_segment_slab_bound(nC, nF * 3))
             cpartial = torch.empty(n_cslabs, 9, dtype=f64, device=dev)
-        n_vslabs = int(lib.snr_simplify_slab_bound(nC, nV))
+        n_vslabs = int(lib.snr_segment_slab_bound(nC, nV))
         vpartial = torch.empty(n_vslabs, 3, dtype=f64, device=dev)
         check(lib.snr_simplify_positions(_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), _ptr(cell), _ptr(origin), B, nV, nF,
                                          _ptr(vert_order, i64), _ptr(vseg, i64), _ptr(vslab, i64), _ptr(corder, i64), _ptr(cseg, i64),

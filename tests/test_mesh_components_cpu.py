@@ -124,7 +124,7 @@ def test_selection_restated(planted):
 
 
 # ------------------------------------------------------------------ the API without a GPU
-MESH_SYMBOLS = ("snr_mesh_hook", "snr_mesh_flatten", "snr_mesh_label", "snr_mesh_boxes", "snr_mesh_face_terms", "snr_mesh_slab_bound",
+MESH_SYMBOLS = ("snr_mesh_hook", "snr_mesh_flatten", "snr_mesh_label", "snr_mesh_boxes", "snr_mesh_face_terms", "snr_segment_slab_bound",
                 "snr_mesh_segment_sum")
 
 
@@ -166,7 +166,7 @@ def test_symbols_and_signatures():
     assert lib.snr_mesh_face_terms(None, None, None, None, None, None, 1, 4, 4, None, None, None) == -1
     assert lib.snr_mesh_face_terms(None, None, None, None, None, None, 1, 4, 0, None, None, None) == 0
     assert lib.snr_mesh_face_terms(None, None, None, None, None, None, 1, 4, big, None, None, None) == -5
-    assert lib.snr_mesh_slab_bound(5, 10000) == 5 + 10000 // ops.MESH_SLAB and lib.snr_mesh_slab_bound(-1, 4) == 0
+    assert lib.snr_segment_slab_bound(5, 10000) == 5 + 10000 // ops.MESH_SLAB and lib.snr_segment_slab_bound(-1, 4) == 0
     assert lib.snr_mesh_segment_sum(None, None, None, None, 2, 100, None, 2, None, None, None) == -1
     assert lib.snr_mesh_segment_sum(None, None, None, None, 2, 10000, None, 3, None, None, None) == -3     # workspace: 4 slabs needed
     assert lib.snr_mesh_segment_sum(None, None, None, None, 0, 0, None, 0, None, None, None) == 0

@@ -130,7 +130,7 @@ def test_rule_one_ties_and_limits():
 
 
 # ------------------------------------------------------------------ the API without a GPU
-SIMPLIFY_SYMBOLS = ("snr_simplify_keys", "snr_simplify_faces", "snr_simplify_compact", "snr_simplify_slab_bound", "snr_simplify_positions",
+SIMPLIFY_SYMBOLS = ("snr_simplify_keys", "snr_simplify_faces", "snr_simplify_compact", "snr_segment_slab_bound", "snr_simplify_positions",
                     "snr_simplify_attributes")
 
 
@@ -172,7 +172,7 @@ def test_symbols_and_signatures():
     assert lib.snr_simplify_compact(None, None, None, 4, 5, None, None, None) == -1                          # more kept than there are
     assert lib.snr_simplify_compact(None, None, None, 4, 0, None, None, None) == 0
     assert lib.snr_simplify_compact(None, None, None, big, 1, None, None, None) == -5
-    assert lib.snr_simplify_slab_bound(5, 10000) == 5 + 10000 // ops.MESH_SLAB and lib.snr_simplify_slab_bound(-1, 4) == 0
+    assert lib.snr_segment_slab_bound(5, 10000) == 5 + 10000 // ops.MESH_SLAB and lib.snr_segment_slab_bound(-1, 4) == 0
     pos = lambda nV, nF, nC, quadric, vs, cs: lib.snr_simplify_positions(None, None, None, None, None, None, 1, nV, nF, None, None, None,  # noqa: E731
                                                                          None, None, None, nC, quadric, None, vs, None, cs, None, None)
     assert pos(100, 50, 10, 1, 10, 10) == -1

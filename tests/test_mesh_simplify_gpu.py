@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import simplify_restatement as SR
+from segment_sum_restatement import banded as _banded, bands_intact as _bands_intact, segments as slab_segments
 from oracle_bands import amd, dev  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -196,17 +197,6 @@ def test_extracted_sphere(amd, dev):  # noqa: F811
     assert abs(float(comps.volume[0]) - full) < 0.05 * full                       # (a ball has no edges to keep: a loose sanity bound)
 
 
-def _banded(n, dtype, dev, fill, band=64):  # noqa: F811
-    full = torch.full((n + 2 * band,), fill, dtype=dtype, device=dev)
-    return full, full[band:band + n]
-
-
-def _bands_intact(full, n, fill, band=64):
-    lo, hi = full[:band], full[band + n:]
-    ok = (lambda t: bool(torch.isnan(t).all())) if fill != fill else (lambda t: bool((t == fill).all()))
-    return ok(lo) and ok(hi)
-
-
 def test_canaries_through_the_c_abi(amd, dev, box):  # noqa: F811
     """Every output buffer of every entry point between NaN- or -1-filled guard bands, the sorted lists fed from the restatement: the
     outputs are the restatement's and the bands are intact."""
@@ -249,15 +239,9 @@ def test_canaries_through_the_c_abi(amd, dev, box):  # noqa: F811
     checks += [(of_full, nK * 3, -1), (fi_full, nK, -1)]
     assert np.array_equal(_np(out_faces).reshape(-1, 3), ref["faces"]) and np.array_equal(_np(face_index), ref["face_index"])
 
-    def segments(ids, n):
-        order = np.argsort(ids, kind="stable")
-        start = np.searchsorted(ids[order], np.arange(n + 1))
-        slabs = np.concatenate([[0], np.cumsum((np.diff(start) + 4095) // 4096)])
-        return up(order, i64), up(start, i64), up(slabs, i64)
-
-    vorder, vseg, vslab = segments(ref["vert_map"].astype(np.int64), nC)
-    corder, cseg, cslab = segments(ref["vert_map"].astype(np.int64)[_np(faces)].reshape(-1), nC)
-    n_vs, n_cs = int(lib.snr_simplify_slab_bound(nC, nV)), int(lib.snr_simplify_slab_bound(nC, nF * 3))
+    vorder, vseg, vslab = (up(a, i64) for a in slab_segments(ref["vert_map"].astype(np.int64), nC))
+    corder, cseg, cslab = (up(a, i64) for a in slab_segments(ref["vert_map"].astype(np.int64)[_np(faces)].reshape(-1), nC))
+    n_vs, n_cs = int(lib.snr_segment_slab_bound(nC, nV)), int(lib.snr_segment_slab_bound(nC, nF * 3))
     assert n_vs == nC + nV // 4096 and n_cs == nC + 3 * nF // 4096
     for quadric in (1, 0):
         vp_full, vpart = _banded(n_vs * 3, f64, dev, nan)
