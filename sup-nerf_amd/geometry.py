@@ -303,43 +303,62 @@ def narrow_band_grid(model, shapecode, resolution, *, level, band=0.0, bound=(-0
     dev, B = sc.device, sc.shape[0]
     clat = coarse_lattice(lat)
     nb = tuple(clat.n[a] - 1 for a in range(3))
-    grid = torch.empty(B, lat.n[0], lat.n[1], lat.n[2], device=dev)
-    state = torch.zeros(B, *nb, dtype=torch.int32, device=dev)
+    ib = None
     if initial_bricks is not None:
         ib = torch.as_tensor(initial_bricks)
         if tuple(ib.shape) != (B,) + nb:
             raise SnrError(f"initial_bricks must be a {(B,) + nb} mask, got {tuple(ib.shape)}")
         ib = ib.to(dev) != 0
     if B == 0:
-        return NarrowBand(grid, state != 0, 0, 0)
+        return NarrowBand(torch.empty(0, *lat.n, device=dev), torch.zeros(0, *nb, dtype=torch.bool, device=dev), 0, 0)
     _, latent, packed = _decoder_inputs(model, sc)
     sb, tb = model.shape_blocks, model.texture_blocks
+    with torch.cuda.device(dev):
+        coarse = ops.density_grid(clat, latent, packed, sb, tb)
+
+    def evaluate(bricks, n, grid):
+        ops.density_bricks(lat, bricks, n, latent, packed, sb, tb, grid)
+
+    grid, state, _, rounds, evaluated = _band_rounds(lat, B, coarse, evaluate, level, band, ib)
+    points = B * clat.n[0] * clat.n[1] * clat.n[2] + BRICK ** 3 * evaluated
+    return NarrowBand(grid, state != 0, rounds, points)
+
+
+def _band_rounds(lat, B, coarse, evaluate, level, band, initial_bricks):
+    """The narrow band's loop on the coarse grids ``coarse`` (B, nb0+1, nb1+1, nb2+1) of any field, B >= 1: classify, compact, fill, the
+    first evaluation and the seam rounds.  ``evaluate(bricks, n, grid)`` writes the field's values at the points of the first ``n`` bricks
+    (object, I, J, K) of the int32 list ``bricks`` into ``grid``, as ``ops.density_bricks`` does; nothing else fills a brick.
+    ``initial_bricks``: None or a (B, nb0, nb1, nb2) bool mask on the device that replaces the classification.  Returns (grid, state,
+    fill, rounds, evaluated bricks): ``state`` (B, nb0, nb1, nb2) int32 with its stamps (0: filled, 1: the first evaluation, s: growth
+    round s - 1), ``fill`` the fill value of every brick."""
+    dev = coarse.device
+    nb = tuple((lat.n[a] + BRICK - 1) // BRICK for a in range(3))
+    grid = torch.empty(B, lat.n[0], lat.n[1], lat.n[2], device=dev)
+    state = torch.zeros(B, *nb, dtype=torch.int32, device=dev)
     fill = torch.empty(B, *nb, device=dev)
     bricks = torch.empty(B * nb[0] * nb[1] * nb[2], 4, dtype=torch.int32, device=dev)
     n_new = torch.zeros(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        coarse = ops.density_grid(clat, latent, packed, sb, tb)
         ops.band_classify(coarse, lat, level, band, state, fill)
         if initial_bricks is not None:
-            state.copy_(ib.to(torch.int32))
+            state.copy_(initial_bricks.to(torch.int32))
         scan = torch.cumsum((state == 1).view(-1), 0, dtype=torch.int32)
         ops.band_compact(state, scan, lat, bricks)
         ops.band_fill(grid, lat, state, fill)
         evaluated = int(scan[-1])                      # host read: the size of the first brick list
         if evaluated:
-            ops.density_bricks(lat, bricks, evaluated, latent, packed, sb, tb, grid)
+            evaluate(bricks, evaluated, grid)
         rounds, stamp = 0, 2
         while True:
             ops.band_seam(grid, lat, level, stamp, state, bricks, n_new)
             k = int(n_new.item())                      # host read: the bricks this round added
             if k == 0:
                 break
-            ops.density_bricks(lat, bricks, k, latent, packed, sb, tb, grid)
+            evaluate(bricks, k, grid)
             evaluated += k
             rounds += 1
             stamp += 1
-    points = B * clat.n[0] * clat.n[1] * clat.n[2] + BRICK ** 3 * evaluated
-    return NarrowBand(grid, state != 0, rounds, points)
+    return grid, state, fill, rounds, evaluated
 
 
 def extract_mesh(model_or_grid, shapecode=None, *, level, resolution=128, bound=(-0.5, 0.5), narrow_band=False, band=0.0,

@@ -9,16 +9,7 @@ import torch
 
 import band_restatement as NB
 import iso_restatement as I
-
-FIELDS = {
-    "sphere": (NB.sphere(), 64),
-    "torus": (NB.torus(), 48),
-    "two_spheres": (NB.two_spheres(), (61, 40, 23)),
-    "sphere_17": (NB.sphere(r=0.3), 17),
-    "torus_45": (NB.torus(0.28, 0.15), (45, 50, 39)),
-    "sphere_30": (NB.sphere(r=0.3), (30, 33, 26)),
-    "plane_between_bricks": (NB.plane(-0.5 + 15.5 / 47), 48),     # between fine points 15 and 16: growth across a brick face
-}
+from band_cases import FIELDS
 
 
 def _evaluated(active, shape):

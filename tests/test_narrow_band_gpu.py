@@ -1,6 +1,7 @@
 """Narrow-band grids on the MI355X: the brick mode of the density decoder against the lattice kernel (bit for bit), the coarse pass against
-the fine grid, the band kernels against tests/band_restatement.py, and narrow-band meshes against dense ones (planted box, growth from one
-brick, the fog decoder cut at its median)."""
+the fine grid, the band kernels against tests/band_restatement.py, and narrow-band meshes against dense ones (planted box on cubic lattices and
+on (61, 40, 23) with and without a band, growth from one brick, the fog decoder cut at its median).  The band kernels alone, on analytic
+fields: tests/test_band_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -107,6 +108,32 @@ def test_planted_box_narrow_band_mesh_is_the_dense_mesh(amd, dev, sb, far):  # n
         assert nbg.points < 3 * R ** 3                                      # the work the dense grid does
         if R >= 129:
             assert nbg.points < 3 * R ** 3 // 2
+
+
+def test_planted_box_off_the_cube_and_with_a_band(amd, dev):  # noqa: F811
+    """The decoder path on a lattice whose brick counts differ per axis (8, 5, 3), at band 0 and at a band read from the coarse grid itself:
+    the median |corner - level|, so that half the corners lie within it and one lies exactly on it."""
+    from supnerf_amd import geometry as G
+    sb, R = 3, (61, 40, 23)
+    model = box(amd, dev, sb, 1, seed=sb, wobble=WOBBLE)
+    sc = _codes(3, 43, dev)
+    dense = G.extract_mesh(model, sc, level=LEVEL_BOX, resolution=R, bound=BOUND_BOX)
+    assert all(f.shape[0] > 0 for _, f in dense)
+    coarse = _on_lattice(amd, model, sc, G.coarse_lattice(G.lattice(R, BOUND_BOX)))
+    band = float((coarse - np.float32(LEVEL_BOX)).abs().median())
+    assert band > 0
+    actives = []
+    for b in (0.0, band):
+        nbg = G.narrow_band_grid(model, sc, R, level=LEVEL_BOX, band=b, bound=BOUND_BOX)
+        assert tuple(nbg.grid.shape) == (3,) + R and tuple(nbg.active.shape) == (3,) + NB.n_bricks(R)
+        assert _same_meshes(G.extract_mesh(nbg.grid, level=LEVEL_BOX, bound=BOUND_BOX), dense), b
+        g, active, rounds, points = _restated(amd, model, sc, R, BOUND_BOX, LEVEL_BOX, band=b)
+        assert np.array_equal(nbg.active.cpu().numpy(), active), b
+        assert nbg.rounds == rounds and nbg.points == points, (b, nbg.rounds, rounds, nbg.points, points)
+        assert np.array_equal(nbg.grid.cpu().numpy().view(np.uint32), g.view(np.uint32)), b
+        actives.append(active)
+    assert (actives[1] & ~actives[0]).any()                                               # the band adds bricks
+    assert _same_meshes(G.extract_mesh(model, sc, level=LEVEL_BOX, resolution=R, bound=BOUND_BOX, narrow_band=True, band=band), dense)
 
 
 def test_growth_from_one_brick_reaches_the_whole_box(amd, dev):  # noqa: F811
