@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 22
+#define SNR_ABI_VERSION 23
 
 enum {
     SNR_OK = 0,
@@ -729,6 +729,51 @@ int snr_simplify_positions(const float* verts, const int32_t* faces, const int64
 int snr_simplify_attributes(const float* attributes, int n_channels, int64_t n_verts, const int64_t* vert_order,
                             const int64_t* vert_seg_start, const int64_t* vert_slab_offset, int64_t n_clusters, double* partial,
                             int64_t n_slabs, float* out, void* stream);
+
+/* Mesh smoothing: which vertices of a packed mesh are neighbours, and Jacobi smoothing steps over that adjacency (Taubin 1995).  The mesh is
+ * the packed form of "Mesh components" above (verts (sum V, 3) fp32, object-local int32 faces, vert_offset and face_offset DEVICE arrays).
+ * tests/smooth_restatement.py restates every rule in numpy, one function each.
+ *   1. Neighbours: in one object, j is a neighbour of i iff i != j and some face whose three indices all lie in [0, V) names both.
+ *      Connectivity is by INDEX, not by position.  A face with a repeated index gives the pairs of its distinct indices; a face with an
+ *      index outside [0, V) gives nothing and sets *bad.  Each neighbour counts once, however many faces name the pair; a vertex no face
+ *      names has degree 0.
+ *   2. Adjacency: a CSR over all vertices of the call -- nbr_start (sum V + 1) int64; nbr (E2) int32, LOCAL indices, ascending within each
+ *      vertex; edge_faces (E2) int32 = how many faces name the undirected edge {i, j} (a face names an edge at most once; both directions
+ *      of an edge carry the same count).  d_i = nbr_start[i + 1] - nbr_start[i] is the degree.  It comes from the caller's sort of the
+ *      keys of snr_smooth_edge_keys: six per face, (global source index) * 2^31 + (local target index) for both directions of each of the
+ *      face's distinct edges, INT64_MAX for a discarded pair; a neighbour is a run of equal keys, edge_faces the run's length.
+ *   3. Classes: an edge with edge_faces == 1 is a boundary edge, one with edge_faces > 2 is non-manifold; a vertex is a boundary
+ *      (non-manifold) vertex iff one of its edges is.  Two identical faces make their edges count 2.
+ *   4. Umbrella operator on C <= 16 channels x (sum V, C) fp32 (positions: C = 3), per channel in float64:
+ *          s = 0.0;  for j over N(i) ASCENDING: s += (double) x_j;   U_i = s / (double) d_i - (double) x_i;   U_i = 0 where d_i = 0.
+ *      The library is built without fused multiply-adds and nothing is added atomically: every operation is one correctly rounded IEEE
+ *      operation and the order is part of the contract (one thread per vertex walks its list; no wave-level reduction).
+ *   5. Step: x'_i = (float)((double) x_i + f * U_i), f a double.  A pinned vertex (pinned[i] != 0) and a vertex of degree 0 keep their
+ *      bits; a pinned vertex still serves as a neighbour.  A Jacobi step: x_out must not overlap x_in, else SNR_E_ARG.  Non-finite values
+ *      are not tested for: a NaN vertex poisons exactly its 1-ring per step.
+ *   6. Taubin lambda|mu: one iteration = a step with f = lambda, then a step with f = mu on the RESULT of the first (U computed anew).
+ *      lambda = 0.5, mu = -0.53 (pass-band 0.1) neither shrink nor grow a closed shape much; without the mu step it is plain Laplacian
+ *      smoothing, which shrinks.  (Host policy: two buffers, one launch per half-step, nothing read back.)
+ *   7. Operator and transpose: transpose = 0 writes (float) U_i.  transpose = 1, of a gradient g (sum V, C):
+ *          t = 0.0;  for j over N(i) ASCENDING: t += (double) g_j / (double) d_j;   out_i = (float)(d_i > 0 ? t - (double) g_i : t).
+ *      The adjacency is symmetric, so both are gathers over the same CSR: no scatter, no atomics.
+ *
+ * snr_smooth_edge_keys: key (6 sum F) int64 of rule 2, face f's at key[6 f .. 6 f + 6); *bad (device int32, zeroed by the caller) = 1 if a
+ *   face index lies outside its object.  Takes sum V < 2^32 (the key keeps 32 bits of source), else SNR_E_UNSUPPORTED.
+ * snr_smooth_vertex_flags: boundary, nonmanifold (sum V) uint8 of rule 3 from nbr_start and edge_faces.
+ * snr_smooth_step: x_out (sum V, C) of rule 5 from x_in; pinned (sum V) uint8 or NULL (nothing pinned).
+ * snr_smooth_laplacian: out (sum V, C) of rule 7 from x; out must not overlap x.
+ * Every neighbour index and every nbr_start pair is range-checked before use (an entry out of range adds nothing; a vertex whose pair is
+ * not usable has degree 0).  A null pointer, a negative size, C outside [1, 16], transpose other than 0 / 1 or overlapping buffers:
+ * SNR_E_ARG; more than 2^38 vertices, faces, keys or CSR entries in a launch: SNR_E_UNSUPPORTED. */
+int snr_smooth_edge_keys(const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, int64_t n_objects, int64_t n_verts,
+                         int64_t n_faces, int64_t* key, int32_t* bad, void* stream);
+int snr_smooth_vertex_flags(const int64_t* nbr_start, const int32_t* edge_faces, int64_t n_verts, int64_t n_edges, uint8_t* boundary,
+                            uint8_t* nonmanifold, void* stream);
+int snr_smooth_step(const float* x_in, int n_channels, const int64_t* nbr_start, const int32_t* nbr, const int64_t* vert_offset,
+                    int64_t n_objects, int64_t n_verts, int64_t n_edges, const uint8_t* pinned, double factor, float* x_out, void* stream);
+int snr_smooth_laplacian(const float* x, int n_channels, const int64_t* nbr_start, const int32_t* nbr, const int64_t* vert_offset,
+                         int64_t n_objects, int64_t n_verts, int64_t n_edges, int transpose, float* out, void* stream);
 
 /* Mesh rasteriser: which face of a packed triangle mesh each pixel of a pinhole camera sees, at which depth and with which barycentric
  * weights.  The mesh is the packed form of "Mesh components" above (verts, object-local int32 faces, vert_offset and face_offset DEVICE

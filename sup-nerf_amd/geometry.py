@@ -27,6 +27,12 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     inside it); ``extract_mesh(..., keep="largest")`` does it in one call;
   * ``simplify_mesh(meshes, cell)``: each mesh with a fraction of its faces, by quadric vertex clustering -- one new vertex per occupied cell
     of a grid, placed so that edges and corners stay, per-vertex attributes averaged (``ops.mesh_simplify``: ``snr_simplify_*``);
+  * ``mesh_adjacency(meshes)``: which vertices are neighbours -- a CSR with the number of faces on every edge, vertex degrees, the rim
+    (boundary) and non-manifold vertices and edge counts, whether the mesh is closed (``ops.mesh_adjacency``: ``snr_smooth_edge_keys``,
+    one sort); ``smooth_mesh(meshes, iterations)``: Taubin lambda|mu smoothing of vertices and per-vertex attributes over it, the rim
+    pinned by default (``ops.mesh_smooth``: one ``snr_smooth_step`` launch per half-step); ``mesh_laplacian(meshes)`` and
+    ``laplacian_energy(meshes)``: the umbrella vectors and their mean square per object, with autograd to the vertices (``ops.MeshLaplacian``)
+    and so, through ``extract_mesh(..., differentiable=True)``, to the grid or the shape codes -- a smoothness regulariser;
   * ``rasterize(meshes, obj_to_cam, K, size)``: the meshes as a pinhole camera sees them -- per pixel the nearest face, the object it belongs
     to, its depth and barycentric weights, all objects in one scene image or one image each (``ops.rasterize``: ``snr_raster_*``);
     ``interpolate(raster, attributes)``: per-vertex normals, colours or any data of up to 16 channels at the pixels;
@@ -45,8 +51,9 @@ first crossing, refinement, depth, implicit gradient) are the header's too, rest
 back to the host.  The component rules (connectivity by vertex index, ids in the order of the smallest vertex index, float64 measures
 summed in a fixed order) are the header's as well, restated in tests/mesh_restatement.py; so are the rasteriser's (projection, snapping
 to 1/256 pixel, exact integer coverage with a tie rule, perspective-correct depth, the nearest face by an integer atomic min), restated in
-tests/raster_restatement.py: no host read, no autograd, the same bits from run to run.  There is no CPU path: CPU tensors raise
-``SnrError``."""
+tests/raster_restatement.py: no host read, no autograd, the same bits from run to run.  The smoothing rules (neighbours by index, each
+once and in ascending order, float64 sums in that order, Jacobi steps between two buffers) are the header's too, restated in
+tests/smooth_restatement.py, which the kernels match bit for bit.  There is no CPU path: CPU tensors raise ``SnrError``."""
 from typing import NamedTuple
 
 import numpy as np
@@ -624,6 +631,175 @@ def simplify_mesh(meshes, cell, *, origin=None, placement="quadric", attributes=
                          None if s.attributes is None else s.attributes[c])
         out.append(_drop_unreferenced(one) if drop_unreferenced else one)
     return out[0] if single else out
+
+
+class Adjacency(NamedTuple):
+    nbr_start: torch.Tensor      # (V + 1,) int64: vertex i's neighbours at nbr[nbr_start[i] : nbr_start[i + 1]]
+    nbr: torch.Tensor            # (E2,) int32, ascending within each vertex
+    edge_faces: torch.Tensor     # (E2,) int32: how many faces name the undirected edge; the same in both directions
+    degree: torch.Tensor         # (V,) int32
+    boundary: torch.Tensor       # (V,) bool: the vertex lies on an edge with exactly one face (a rim)
+    nonmanifold: torch.Tensor    # (V,) bool: the vertex lies on an edge with more than two faces
+    boundary_edges: int          # undirected edges with one face
+    nonmanifold_edges: int       # undirected edges with more than two faces
+    closed: bool                 # faces > 0 and both counts are 0
+
+
+class Smoothed(NamedTuple):
+    verts: torch.Tensor          # (V, 3) fp32, no grad_fn
+    attributes: object           # (V, C) fp32 or None
+
+
+def _unpack_adjacency(a, nvs, nfs):
+    """One ``Adjacency`` per object from the packed ``ops.MeshAdjacency`` of the whole call."""
+    out = []
+    for b, (v,) in enumerate(_object_slices(nvs)):
+        e0, e1 = a.edge_offset[b], a.edge_offset[b + 1]
+        be, ne = a.boundary_edges[b], a.nonmanifold_edges[b]
+        out.append(Adjacency(a.nbr_start[v.start:v.stop + 1] - e0, a.nbr[e0:e1], a.edge_faces[e0:e1], a.degree[v], a.boundary[v],
+                             a.nonmanifold[v], be, ne, nfs[b] > 0 and be == 0 and ne == 0))
+    return out
+
+
+def _pack_adjacency(adjs, nvs, dev):
+    """The packed ``ops.MeshAdjacency`` of per-object ``Adjacency`` values (what ``mesh_adjacency`` returned for these meshes): torch
+    concatenations, nothing read back."""
+    for a, n in zip(adjs, nvs):
+        if not isinstance(a, Adjacency) or a.degree.shape[0] != n or a.nbr_start.shape[0] != n + 1:
+            raise SnrError(f"adjacency is what mesh_adjacency returns for these meshes: one Adjacency per object, here of {n} vertices")
+        _gpu(a.nbr_start, "adjacency")
+    if len(adjs) != len(nvs):
+        raise SnrError(f"{len(nvs)} meshes but {len(adjs)} adjacencies")
+    e_off = ops._host_offsets([a.nbr.shape[0] for a in adjs])
+    if len(adjs) == 1:
+        nbr_start = adjs[0].nbr_start.contiguous()
+    else:
+        nbr_start = torch.cat([a.nbr_start[:-1] + e for a, e in zip(adjs, e_off)] + [torch.tensor(e_off[-1:], dtype=torch.int64).to(dev)])
+    cat = (lambda name: getattr(adjs[0], name).contiguous()) if len(adjs) == 1 else (lambda name: torch.cat([getattr(a, name) for a in adjs]))
+    return ops.MeshAdjacency(nbr_start, cat("nbr"), cat("edge_faces"), cat("degree"), cat("boundary"), cat("nonmanifold"),
+                             [a.boundary_edges for a in adjs], [a.nonmanifold_edges for a in adjs], list(nvs),
+                             ops._offsets(nvs, dev)[1], e_off)
+
+
+def _adjacency(ms, adjacency):
+    """(the packed vertices with their graph, the packed ``ops.MeshAdjacency``, n_verts) of a list of meshes that is not empty; the
+    adjacency is built unless the caller brings it."""
+    verts, faces, nvs, nfs = _packed(ms)
+    if adjacency is None:
+        packed = ops.mesh_adjacency(verts, faces, nvs, nfs)
+    else:
+        packed = _pack_adjacency([adjacency] if isinstance(adjacency, Adjacency) else list(adjacency), nvs, verts.device)
+    live = ms[0][0].float() if len(ms) == 1 else torch.cat([v.float() for v, _ in ms])
+    return live, packed, nvs
+
+
+def mesh_adjacency(meshes):
+    """Which vertices of each mesh of ``meshes`` -- the list ``extract_mesh`` returns, or one (verts, faces) pair -- are neighbours
+    (include/supnerf_hip.h, "Mesh smoothing", rules 1 to 3; ``ops.mesh_adjacency``).  One ``Adjacency`` per object, or a single one for a
+    single pair: a CSR (``nbr_start``, ``nbr`` ascending within each vertex, ``edge_faces`` = the faces on each edge), the ``degree`` of
+    every vertex, which vertices lie on the rim (``boundary``: an edge with one face -- where an iso-surface meets the border of its grid)
+    or on a non-manifold edge (more than two faces -- where ``simplify_mesh`` merged two sheets), how many such edges there are, and
+    ``closed`` = the mesh has faces and neither kind of edge.  Connectivity is by index: coincident vertices are not neighbours unless a
+    face joins them.  All objects go through the same launches with one host read.  Integers only: exact, the same from run to run.
+    CPU tensors, faces that are not int32 and a face index outside its mesh raise ``SnrError``."""
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    verts, faces, nvs, nfs = _packed(ms)
+    out = _unpack_adjacency(ops.mesh_adjacency(verts, faces, nvs, nfs), nvs, nfs)
+    return out[0] if single else out
+
+
+def _per_object_rows(values, ms, what, dtype=None):
+    """``values`` -- one (V, ...) tensor or a list of them, one per object -- checked against the meshes; a list."""
+    values = [values] if torch.is_tensor(values) else list(values)
+    if len(values) != len(ms):
+        raise SnrError(f"{len(ms)} meshes but {len(values)} {what} tensors")
+    for a, (v, _) in zip(values, ms):
+        _gpu(a, what)
+        if a.dim() < 1 or a.shape[0] != v.shape[0] or (dtype is not None and a.dtype != dtype):
+            raise SnrError(f"{what} are one tensor of V rows per object{'' if dtype is None else f' ({dtype})'}, got {tuple(a.shape)} "
+                           f"{a.dtype} for {v.shape[0]} vertices")
+    return values
+
+
+def smooth_mesh(meshes, iterations=10, *, lam=0.5, mu=-0.53, pin="boundary", attributes=None, adjacency=None):
+    """Each mesh of ``meshes`` -- the list ``extract_mesh`` returns, or one (verts, faces) pair -- with its vertices smoothed by
+    ``iterations`` Taubin lambda|mu iterations (Taubin 1995; include/supnerf_hip.h, "Mesh smoothing"): every vertex moves by ``lam`` times
+    the umbrella vector U = (mean of its neighbours) - itself, then by ``mu`` times the U of the result.  The defaults (pass-band 0.1)
+    take out the lattice print of marching tetrahedra and the facets of ``simplify_mesh`` while a closed shape keeps its volume within a
+    few percent; ``mu=None`` is plain Laplacian smoothing, which shrinks.  Faces are untouched.  Returns one ``Smoothed(verts,
+    attributes)`` per object, or a single one for a single pair.
+
+    * ``pin``: the vertices that do not move (they still pull their neighbours).  ``"boundary"``: those on an edge with one face -- the
+      rim where the surface meets the border of its grid, which would otherwise shrink inwards; ``None``: nothing; a bool mask (V,), or a
+      list of them, one per object: exactly those.
+    * ``attributes``: a (V, C) tensor (C <= 16) or a list of them, one per object: they go through the same steps with the same pins.
+    * ``adjacency``: what ``mesh_adjacency`` returned for these meshes, to save building it again (and its host read).
+    * A Jacobi iteration: every vertex reads the previous positions.  One launch per half-step for all objects, float64 sums over the
+      neighbours in ascending order, no atomics: the same bits from run to run.  ``iterations=0`` returns a copy.
+
+    Vertices with a ``grad_fn`` are read by value and the output carries none (``mesh_laplacian`` / ``laplacian_energy`` are the
+    differentiable route).  A ``lam`` or ``mu`` that is not finite, ``iterations < 0``, CPU tensors, faces that are not int32 and a face
+    index outside its mesh raise ``SnrError``."""
+    factors = [float(lam)] + ([] if mu is None else [float(mu)])
+    if not all(np.isfinite(f) for f in factors):
+        raise SnrError(f"lam and mu must be finite, got {lam} and {mu}")
+    if int(iterations) < 0:
+        raise SnrError(f"iterations must not be negative, got {iterations}")
+    if not (pin is None or torch.is_tensor(pin) or isinstance(pin, (list, tuple)) or pin == "boundary"):
+        raise SnrError(f"pin is None, 'boundary' or a bool mask per object, got {pin!r}")
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    live, adj, nvs = _adjacency(ms, adjacency)
+    if pin is None:
+        pinned = None
+    elif isinstance(pin, str):
+        pinned = adj.boundary
+    else:
+        masks = _per_object_rows(pin, ms, "pin masks", torch.bool)
+        pinned = masks[0] if len(masks) == 1 else torch.cat(masks)
+    verts = ops.mesh_smooth(live.detach(), adj, iterations, lam, mu, pinned)
+    att = None
+    if attributes is not None:
+        rows = _per_object_rows(attributes, ms, "attributes")
+        if any(a.dim() != 2 or a.shape[1] != rows[0].shape[1] for a in rows):
+            raise SnrError(f"attributes are (V, C) per object with one C, got {[tuple(a.shape) for a in rows]}")
+        att = ops.mesh_smooth(torch.cat([a.detach().float() for a in rows]), adj, iterations, lam, mu, pinned)
+    out = [Smoothed(verts[v], None if att is None else att[v]) for (v,) in _object_slices(nvs)]
+    return out[0] if single else out
+
+
+def mesh_laplacian(meshes, adjacency=None):
+    """The umbrella vectors U_i = (mean of the neighbours of vertex i) - x_i of each mesh of ``meshes``, (V, 3) per object (one tensor for
+    a single pair), zero at a vertex without neighbours (include/supnerf_hip.h, "Mesh smoothing", rules 4 and 7).  Differentiable wrt the
+    vertices (``ops.MeshLaplacian``: the backward is the transposed operator, a gather over the same adjacency), and so, through
+    ``extract_mesh(..., differentiable=True)``, wrt the grid or the shape codes; the adjacency is a constant."""
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    live, adj, nvs = _adjacency(ms, adjacency)
+    u = ops.MeshLaplacian.apply(live, adj)
+    out = [u[v] for (v,) in _object_slices(nvs)]
+    return out[0] if single else out
+
+
+def laplacian_energy(meshes, adjacency=None):
+    """(B,) fp32: per mesh the mean of |U_i|^2 over its vertices that have neighbours (0 for none), U = ``mesh_laplacian``: the standard
+    first smoothness regulariser of a mesh, differentiable like ``mesh_laplacian`` -- ``laplacian_energy(extract_mesh(model, codes, ...,
+    differentiable=True)).sum().backward()`` fills ``codes.grad``.  Per-object slices and ``sum()``: no atomics, the same bits from run to
+    run."""
+    ms, _ = _one_or_many(meshes)
+    if not ms:
+        return torch.zeros(0)
+    live, adj, nvs = _adjacency(ms, adjacency)
+    u = ops.MeshLaplacian.apply(live, adj)
+    out = []
+    for (v,) in _object_slices(nvs):
+        count = (adj.degree[v] > 0).sum().clamp(min=1)
+        out.append((u[v] ** 2).sum() / count)
+    return torch.stack(out)
 
 
 def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False, direction=False):
