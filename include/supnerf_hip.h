@@ -649,7 +649,7 @@ int64_t snr_segment_slab_bound(int64_t n_segments, int64_t n_items);
  *   keys of the coordinates (exact in any order).  A vertex whose label is not one of its object's components is not counted.
  * snr_mesh_face_terms: the two float64 terms of rule 3 per face; slot i holds face order[i] (order: (sum F) int64, a permutation of the
  *   packed face indices -- the faces sorted by component -- or NULL = as stored).  p0 = the vertex root[v0].  A face with a bad index
- *   gives 0, 0.
+ *   gives 0, 0.  An order entry outside [0, sum F) gives its slot 0, 0 too, and nothing is read with it.
  * snr_mesh_segment_sum: area, volume (sum C) float64 from terms sorted by component: seg_start (sum C + 1) int64, component k's terms at
  *   [seg_start[k], seg_start[k+1]), with slab_offset (sum C + 1) int64, both as "Fixed-order segmented sums" above defines them, which
  *   is also the order of the two sums.  partial: (n_slabs, 2) float64 scratch, n_slabs >= snr_segment_slab_bound(sum C, sum F).

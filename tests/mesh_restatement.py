@@ -11,13 +11,19 @@ Rules:
      face_label (F,) int32 = the label of the face's first vertex;
   3. per component: n_verts, n_faces (int64); bbox_lo, bbox_hi (C, 3) float32 = min / max of its vertex coordinates; area and volume in
      float64: with a, b, c the face's vertices widened to float64 and p0 the component's vertex of smallest index,
-     area term = |(b - a) x (c - a)| / 2, volume term = (a - p0) . ((b - p0) x (c - p0)) / 6, summed over the component's faces (here: in
-     face order -- the order is the implementer's choice, so area and volume are compared within ``sum_bounds``, not bit for bit);
+     area term = |(b - a) x (c - a)| / 2, volume term = (a - p0) . ((b - p0) x (c - p0)) / 6, summed over the component's faces.  The
+     order is fixed: the terms as ``face_terms_exact`` writes them out, the faces sorted by component with a stable sort, then the header's
+     "Fixed-order segmented sums" -- ``components_fixed_order`` restates it and is compared bit for bit.  ``components`` sums in face order
+     with numpy's own term order; the two, and the device, lie within ``sum_bounds`` of each other, which is still asserted;
   4. a subset of components gives a sub-mesh: the kept vertices and faces in their original order, indices renumbered, with the index
      maps into the original arrays.
 
-Also here: the policy of ``geometry.largest_component`` restated on these arrays, and the analytic grids the tests share."""
+Also here: one step function per kernel of snr_mesh.hip (``roots_of``, ``labels_from``, ``boxes_from``, ``face_terms_exact``) for the
+tests that drive the kernels alone, the policy of ``geometry.largest_component`` restated on these arrays, and the analytic grids the tests
+share."""
 import numpy as np
+
+import segment_sum_restatement as SS
 
 
 def reach_smallest(n_verts, faces):
@@ -86,6 +92,83 @@ def components(verts, faces):
     return dict(vert_label=vert_label, face_label=face_label, first=first,
                 n_verts=np.bincount(vert_label, minlength=C).astype(np.int64), n_faces=np.bincount(face_label, minlength=C).astype(np.int64),
                 area=area, volume=volume, bbox_lo=lo, bbox_hi=hi, S_area=float(np.abs(area_t).sum()), S_volume=float(mag.sum()))
+
+
+def face_terms_exact(verts, faces, p0):
+    """Rule 3's two float64 terms per face in exactly the kernel's operation order (``mesh_face_terms_kernel``), every operation one IEEE
+    float64 operation, written out elementwise: with e1 = b - a, e2 = c - a,
+        n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),     area = sqrt((nx nx + ny ny) + nz nz) / 2,
+    and with a' = a - p0, b' = b - p0, c' = c - p0 and c = b' x c' formed the same way,
+        volume = ((a'x cx + a'y cy) + a'z cz) / 6.
+    ``p0`` (F, 3): the reference vertex of each face's component.  Returns (area (F,), volume (F,)) float64."""
+    v = np.asarray(verts, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    p = np.asarray(p0, dtype=np.float64).reshape(-1, 3)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    e1x, e1y, e1z = b[:, 0] - a[:, 0], b[:, 1] - a[:, 1], b[:, 2] - a[:, 2]
+    e2x, e2y, e2z = c[:, 0] - a[:, 0], c[:, 1] - a[:, 1], c[:, 2] - a[:, 2]
+    nx, ny, nz = e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x
+    area = np.sqrt((nx * nx + ny * ny) + nz * nz) / 2.0
+    ax, ay, az = a[:, 0] - p[:, 0], a[:, 1] - p[:, 1], a[:, 2] - p[:, 2]
+    bx, by, bz = b[:, 0] - p[:, 0], b[:, 1] - p[:, 1], b[:, 2] - p[:, 2]
+    cx, cy, cz = c[:, 0] - p[:, 0], c[:, 1] - p[:, 1], c[:, 2] - p[:, 2]
+    ux, uy, uz = by * cz - bz * cy, bz * cx - bx * cz, bx * cy - by * cx
+    return area, ((ax * ux + ay * uy) + az * uz) / 6.0
+
+
+def components_fixed_order(verts, faces, comp=None):
+    """``components`` with ``area`` and ``volume`` summed as the device sums them, bit for bit: the exact terms, sorted by ``face_label``
+    with the stable argsort (ascending face order within a component), summed by ``segment_sum_restatement.segment_sum`` over
+    ``segments(...)``.  ``comp``: what ``components`` gave for this mesh, to save computing it again."""
+    verts = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    out = dict(components(verts, f) if comp is None else comp)
+    C = out["first"].shape[0]
+    p0 = verts.astype(np.float64)[out["first"][out["face_label"]]] if f.size else np.zeros((0, 3))
+    area_t, vol_t = face_terms_exact(verts, f, p0)
+    order, start, _ = SS.segments(out["face_label"], C)
+    both = SS.segment_sum(np.stack([area_t, vol_t], axis=1)[order], start) if f.size else np.zeros((C, 2))
+    out["area"], out["volume"] = both[:, 0].copy(), both[:, 1].copy()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- one step per kernel
+def roots_of(parent):
+    """(V,) the root above every vertex of a forest ``parent`` (V,) with parent[i] <= i: follow the pointers until one points at itself.
+    What ``snr_mesh_flatten`` must give for any such forest of one object (indices local to it)."""
+    parent = np.asarray(parent, dtype=np.int64)
+    root = np.arange(parent.shape[0], dtype=np.int64)
+    while True:
+        up = parent[root]
+        if np.array_equal(up, root):
+            return root.astype(np.int32)
+        root = up
+
+
+def labels_from(root, root_scan, faces, n_verts):
+    """``snr_mesh_label`` for one object: vert_label[v] = root_scan[root[v]] - 1; face_label = the label of the face's first vertex, -1
+    where that index lies outside [0, V) -- the other two indices play no part (rule 2)."""
+    root, root_scan = np.asarray(root, dtype=np.int64), np.asarray(root_scan, dtype=np.int64)
+    vert_label = (root_scan[root] - 1).astype(np.int32)
+    i0 = np.asarray(faces, dtype=np.int64).reshape(-1, 3)[:, 0]
+    ok = (i0 >= 0) & (i0 < n_verts)
+    face_label = np.full(i0.shape[0], -1, np.int32)
+    face_label[ok] = vert_label[i0[ok]]
+    return vert_label, face_label
+
+
+def boxes_from(verts, vert_label, n_comps):
+    """``snr_mesh_boxes`` for one object: (comp_verts (C,) int64, bbox_lo, bbox_hi (C, 3) float32) over the vertices whose label lies in
+    [0, n_comps); the others are not counted.  A component no vertex counts for keeps +inf / -inf here: its box is unspecified."""
+    verts = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    lab = np.asarray(vert_label, dtype=np.int64)
+    ok = (lab >= 0) & (lab < n_comps)
+    lo = np.full((n_comps, 3), np.inf, np.float32)
+    hi = np.full((n_comps, 3), -np.inf, np.float32)
+    for k in range(3):
+        np.minimum.at(lo[:, k], lab[ok], verts[ok, k])
+        np.maximum.at(hi[:, k], lab[ok], verts[ok, k])
+    return np.bincount(lab[ok], minlength=n_comps).astype(np.int64), lo, hi
 
 
 def sum_bounds(comp):

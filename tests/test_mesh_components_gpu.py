@@ -1,13 +1,17 @@
 """Mesh components on the MI355X: ``geometry.mesh_components`` (the ``snr_mesh_*`` kernels) against tests/mesh_restatement.py, object by
-object -- labels, counts and bounding boxes bit for bit, area and volume within the bound any float64 summation order keeps
-(``mesh_restatement.sum_bounds``: (F + 16) 2^-52 S, derived, not measured), two runs bit for bit -- on the planted five-piece grid, the fog
-decoder cut at its median density, renumbered and shuffled meshes, and a long thin helix; the selection functions against the restated
-sub-meshes; the gradient pass-through of a differentiable mesh; and the bad-index flag."""
+object -- labels, counts and bounding boxes bit for bit, area and volume bit for bit the fixed order restated
+(``mesh_restatement.components_fixed_order``: the terms, the stable sort by component and the two sums all have one order) and, beside
+that, within the bound any float64 summation order keeps of the plain restatement (``mesh_restatement.sum_bounds``: (F + 16) 2^-52 S,
+derived, not measured), two runs bit for bit -- on the planted five-piece grid, the fog decoder cut at its median density, renumbered and
+shuffled meshes, a long thin helix, the small hard meshes of tests/mesh_cases.py and its B = 67 objects in one call; the selection
+functions against the restated sub-meshes; the gradient pass-through of a differentiable mesh; and the bad-index flag."""
 import numpy as np
 import pytest
 import torch
 
+import mesh_cases as MC
 import mesh_restatement as MR
+from segment_sum_restatement import same_bits
 from geometry_cases import codes as _codes, model as _model
 from oracle_bands import amd, dev  # noqa: F401  (fixtures)
 
@@ -45,6 +49,10 @@ def _check(G, meshes, tag):
         assert c.area.dtype == torch.float64 and c.volume.dtype == torch.float64
         assert c.area.shape == ref["area"].shape and c.volume.shape == ref["volume"].shape
         assert ea <= ba and ev <= bv, (tag, b, ea, ba, ev, bv)
+        fixed = MR.components_fixed_order(_np(v), _np(f), comp=ref)               # the order is fixed end to end: the same bits
+        for name in ("area", "volume"):
+            differ = ~same_bits(_np(getattr(c, name)), fixed[name])
+            assert not differ.any(), (tag, b, name, int(differ.sum()), "of", differ.shape[0])
         for x, y in zip(c, c2):                                                    # two runs: the same bits, the float64 sums included
             assert torch.equal(x, y), (tag, b, "run to run")
     return got, refs
@@ -60,6 +68,7 @@ def _check_selection(G, meshes, comps, refs, tag):
                 assert sub[1].dtype == torch.int32 and sub[2].dtype == torch.int64 and sub[3].dtype == torch.int64
                 for g, w in zip(sub, want):
                     assert g.shape == w.shape and np.array_equal(_np(g), w), (tag, b, by, drop)
+    all_at_once = G.largest_component(meshes)
     for b, ((v, f), c, ref) in enumerate(zip(meshes, comps, refs)):
         C = ref["n_verts"].shape[0]
         ids = list(range(0, C, 2))[:50]
@@ -71,7 +80,7 @@ def _check_selection(G, meshes, comps, refs, tag):
             sub = G.select_components((v, f), c, keep)
             assert all(g.shape == w.shape and np.array_equal(_np(g), w) for g, w in zip(sub, want)), (tag, b)
         one = G.largest_component((v, f))                                          # one pair in, one tuple out
-        assert torch.equal(one[0], G.largest_component(meshes)[b][0])
+        assert torch.equal(one[0], all_at_once[b][0])
 
 
 @pytest.fixture(scope="module")
@@ -167,6 +176,30 @@ def test_helix(amd, dev):  # noqa: F811
     comps, refs = _check(G, meshes, "helix")
     assert comps[0].n_verts.tolist() == [meshes[0][0].shape[0]] and meshes[0][0].shape[0] > 15000
     assert float(comps[0].volume[0]) > 0
+
+
+@pytest.mark.parametrize("numbering", MC.NUMBERINGS)
+def test_small_hard_meshes(amd, dev, numbering):  # noqa: F811
+    """The corpus of tests/mesh_cases.py -- chains, stars, interleaved combs, repeated faces and indices, singletons beside a fan, a
+    binary-tree merge order -- nine meshes of one numbering in one packed call."""
+    from supnerf_amd import geometry as G
+    cases = [c for c in MC.corpus() if c[0].endswith(", " + numbering)]
+    assert len(cases) == len(MC.SHAPES)
+    comps, _ = _check(G, [_to_gpu((v, f), dev) for _, v, f, _ in cases], f"small hard meshes, {numbering}")
+    assert [c.n_verts.shape[0] for c in comps] == [n for _, _, _, n in cases]
+
+
+def test_many_objects_in_one_call(amd, dev):  # noqa: F811
+    """B = 67 in one packed call (``mesh_cases.many_objects``): runs of empty objects at the start, in the middle and at the end, lone
+    points, small closed and open pieces, a fan and an edge path whose borders fall inside waves and blocks."""
+    from supnerf_amd import geometry as G
+    objects = MC.many_objects()
+    meshes = [_to_gpu((v, f), dev) for _, v, f, _ in objects]
+    comps, refs = _check(G, meshes, "B = 67")
+    assert [c.n_verts.shape[0] for c in comps] == [n for _, _, _, n in objects]
+    tetra = [b for b, (kind, _, _, _) in enumerate(objects) if kind == "tetrahedron"]
+    assert len(tetra) >= 10 and all(comps[b].n_faces.tolist() == [4] for b in tetra)
+    _check_selection(G, meshes, comps, refs, "B = 67")
 
 
 def test_gradients_pass_through_the_selection(amd, dev, planted):  # noqa: F811
