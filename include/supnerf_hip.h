@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 23
+#define SNR_ABI_VERSION 24
 
 enum {
     SNR_OK = 0,
@@ -825,6 +825,52 @@ int snr_raster_resolve(const uint64_t* keys, const float* screen, const int32_t*
 int snr_raster_interpolate(const int32_t* face, const float* weights, const int32_t* faces, const int64_t* vert_offset,
                            const int64_t* face_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces, const float* attributes,
                            int n_channels, int64_t n_pixels, float background, float* out, void* stream);
+
+/* Mesh painting: per-vertex colours of a packed mesh from the photographs of its views.  Each vertex takes its colour from the views that
+ * really see it, weighed by how squarely they face it; what no view sees is filled from its neighbours.  One view per launch: `screen`
+ * (sum V, 3) is snr_raster_project's (u, v, camera z) for that view (rule 1 of "Mesh rasteriser": pixel centres at INTEGER (u, v)),
+ * `depth` (H, W) snr_raster_resolve's for the same view (0 where empty), `image` (H, W, 3) fp32 the photograph on the same pixel grid,
+ * `mask` (H, W) fp32 or NULL its occupancy (> 0: the object; 0 background, -1 another object in front).  All fp32 steps round once per
+ * written operation (no fma), in the written order; tests/paint_restatement.py restates every rule step by step.
+ *   P1. Footprint.  A vertex is skipped when u, v or z is not finite, z < z_near, u < 0, v < 0, u > float(W - 1) or v > float(H - 1).
+ *       Otherwise x0 = min(int(floor(u)), W - 2) and a = u - float(x0) (exact); with W = 1, x0 = 0 and a = 0; y0 and b likewise from v and
+ *       H.  The four taps, in this order, and their weights: (x0, y0) (1 - a)(1 - b); (x0 + 1, y0) a (1 - b); (x0, y0 + 1) (1 - a) b;
+ *       (x0 + 1, y0 + 1) a b -- one subtraction and one product each.  With W = 1 (H = 1) the taps at x0 + 1 (y0 + 1) would repeat
+ *       their neighbour: they are not read and are never valid.  So u = W - 1 exactly has x0 = W - 2 and a = 1.
+ *   P2. Valid taps.  A tap is valid iff depth there > 0, and mask there > 0 when a mask is given, and z <= depth + tol (one fp32 add, one
+ *       compare; false on a NaN).  s = the sum of the valid taps' weights in tap order, STARTING FROM the first valid term (not from 0);
+ *       the view's colour per channel c = (sum over the valid taps of w_t I_t, same order, same start) / s, one division.  Only valid taps
+ *       enter: the whitened background and occluders stay out of silhouette vertices, and the rest is renormalised.  The vertex is seen
+ *       by the view only if s > 0.
+ *   P3. Facing.  Without normals g = 1.  With normals n (sum V, 3) and the stored vertex x: d = centre - x (the camera centre in the
+ *       frame of the stored vertices); dot = (n0 d0 + n1 d1) + n2 d2; nn and dd likewise of n with n and d with d; g = (dot dot) / (nn dd)
+ *       when dot > 0 and nn dd is finite and > 0, else 0: cos^2 of the angle, no square root.  A view with g = 0 (or a g that is not > 0)
+ *       does not see the vertex.
+ *   P4. Accumulate, for a vertex the view sees (P1, s > 0, g > 0), plain in-place fp32 operations: sum_rgb_j = sum_rgb_j + g c_j (one
+ *       product, one add); sum_w = sum_w + g; seen = seen + 1; if g > best_w (strict: ties keep the earlier view): best_w = g, best =
+ *       view, best_rgb = c.  The caller presets sum_rgb, sum_w, best_w, best_rgb to 0, seen to 0 and best to -1 and launches the views in
+ *       ascending order on one stream: that order is the order of the sums.  A vertex the view does not see has nothing written.
+ *   P5. Finish.  Where seen > 0: colors_j = sum_rgb_j / sum_w (blend 0, "weighted": one division) or best_rgb_j (blend 1, "best"), and
+ *       filled = 0.  Elsewhere colors = background and filled = -1.
+ *   P6. Fill, one Jacobi round r >= 1 between two buffers over the adjacency of "Mesh smoothing" (nbr_start, nbr; neighbours ascending):
+ *       a vertex with filled < 0 that has at least one neighbour with filled >= 0 IN THE INPUT takes, per channel, in float64:
+ *           s = 0.0;  for j over N(i) ASCENDING with filled_j >= 0: s += (double) c_j;   c_i = (float)(s / (double) count)
+ *       and filled = r.  Every other vertex copies its colour (the same bits) and its filled.  After R rounds filled is the graph distance
+ *       to the nearest seen vertex where that is <= R, and still -1 beyond.  The outputs must not overlap the inputs, else SNR_E_ARG.
+ *
+ * snr_paint_view: P1 - P4 for view `view` (>= 0), a thread per vertex, grid-stride; verts and normals (sum V, 3) or normals NULL (g = 1).
+ * snr_paint_finish: colors (sum V, 3) and filled (sum V) int32 of P5; blend 0 reads sum_rgb and sum_w, blend 1 best_rgb.
+ * snr_paint_fill: colors_out, filled_out of P6 from colors_in, filled_in; neighbour entries and nbr_start pairs are range-checked as in
+ *   "Mesh smoothing".  No atomics, no LDS: the same bits from run to run.
+ * A null pointer (but mask and normals), a negative size or view, z_near <= 0, a tol that is negative or not finite, blend outside {0, 1},
+ * round < 1 or overlapping fill buffers: SNR_E_ARG; more than 2^38 vertices or CSR entries, or H W >= 2^31: SNR_E_UNSUPPORTED. */
+int snr_paint_view(const float* screen, const float* verts, const float* normals, int64_t n_verts, const float* image, const float* mask,
+                   const float* depth, int height, int width, float centre_x, float centre_y, float centre_z, float tol, float z_near,
+                   int view, float* sum_rgb, float* sum_w, int32_t* seen, float* best_w, int32_t* best, float* best_rgb, void* stream);
+int snr_paint_finish(const float* sum_rgb, const float* sum_w, const int32_t* seen, const float* best_rgb, int64_t n_verts, int blend,
+                     float background, float* colors, int32_t* filled, void* stream);
+int snr_paint_fill(const float* colors_in, const int32_t* filled_in, const int64_t* nbr_start, const int32_t* nbr, const int64_t* vert_offset,
+                   int64_t n_objects, int64_t n_verts, int64_t n_edges, int round, float* colors_out, int32_t* filled_out, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Several views of one instance share one shape and one texture code (src/optimizer_nuscenes.py:796-1277): V rendered views, I <= V code

@@ -131,6 +131,10 @@ _SIGS = {
     "snr_raster_faces": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, _P, _P]),
     "snr_raster_resolve": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     "snr_raster_interpolate": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int, C.c_int64, C.c_float, _P, _P]),
+    "snr_paint_view": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                 _P, _P, _P, _P, _P, _P, _P]),
+    "snr_paint_finish": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_float, _P, _P, _P]),
+    "snr_paint_fill": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "snr_view_pixels": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "snr_instance_rows_fwd": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "snr_instance_rows_bwd": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, _P, _P]),

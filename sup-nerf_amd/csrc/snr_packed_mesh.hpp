@@ -1,5 +1,5 @@
-// What the packed-mesh kernels (snr_mesh.hip, snr_simplify.hip, snr_raster.hip) share, stated once: the offset search, the face loader, the
-// size limits and the fixed-order float64 segmented sum.  The specification is include/supnerf_hip.h ("Mesh components": the packed form;
+// What the packed-mesh kernels (snr_mesh.hip, snr_simplify.hip, snr_smooth.hip, snr_raster.hip, snr_paint.hip) share, stated once: the offset
+// search, the face loader, the neighbour-list reader, the size limits and the fixed-order float64 segmented sum.  The specification is include/supnerf_hip.h ("Mesh components": the packed form;
 // "Fixed-order segmented sums": the order, which tests/test_segment_sum_gpu.py holds the kernels to).  Functions only (see snr_grid.hpp).
 #pragma once
 #include "snr_grid.hpp"
@@ -47,6 +47,20 @@ __device__ __forceinline__ MeshFace mesh_face(const int* __restrict__ faces, con
     m.idx[0] = faces[f * 3]; m.idx[1] = faces[f * 3 + 1]; m.idx[2] = faces[f * 3 + 2];
     m.ok = mesh_index_ok(m.idx[0], o.V) && mesh_index_ok(m.idx[1], o.V) && mesh_index_ok(m.idx[2], o.V);
     return m;
+}
+
+// ---- the vertex adjacency of "Mesh smoothing" (a CSR over all vertices of the call), read by snr_smooth.hip and snr_paint.hip
+// the neighbour list of packed vertex g, range-checked: entries [begin, end) of nbr; empty where nbr_start is not usable
+struct SmoothRing {
+    long long begin, end;
+    __device__ __forceinline__ long long degree() const { return end - begin; }
+};
+__device__ __forceinline__ SmoothRing smooth_ring(const long long* __restrict__ nbr_start, long long g, long long nE) {
+    SmoothRing r;
+    r.begin = nbr_start[g];
+    r.end = nbr_start[g + 1];
+    if (r.begin < 0 || r.end < r.begin || r.end > nE) r.begin = r.end = 0;
+    return r;
 }
 
 constexpr long long PACKED_MAX_ITEMS = 1ll << 38;    // items (vertices, faces, corners, ...) of one launch: blocks of 256 threads fit a 1-D grid

@@ -36,19 +36,6 @@ __global__ void smooth_edge_keys_kernel(const int* __restrict__ faces, const lon
     }
 }
 
-// the neighbour list of packed vertex g, range-checked: entries [begin, end) of nbr; empty where nbr_start is not usable
-struct SmoothRing {
-    long long begin, end;
-    __device__ __forceinline__ long long degree() const { return end - begin; }
-};
-__device__ __forceinline__ SmoothRing smooth_ring(const long long* __restrict__ nbr_start, long long g, long long nE) {
-    SmoothRing r;
-    r.begin = nbr_start[g];
-    r.end = nbr_start[g + 1];
-    if (r.begin < 0 || r.end < r.begin || r.end > nE) r.begin = r.end = 0;
-    return r;
-}
-
 // ---- rule 3: a vertex is a boundary (non-manifold) vertex iff one of its edges has one face (more than two)
 __global__ void smooth_vertex_flags_kernel(const long long* __restrict__ nbr_start, const int* __restrict__ edge_faces, long long nV,
                                            long long nE, unsigned char* __restrict__ boundary, unsigned char* __restrict__ nonmanifold) {

@@ -38,6 +38,9 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     ``interpolate(raster, attributes)``: per-vertex normals, colours or any data of up to 16 channels at the pixels;
     ``mesh_view(mesh, cam_pose, obj_diag, K, roi)``: one object on the pixel grid of ``utils.get_rays``, metric depth comparable with
     ``surface_depth``; ``scene_view(meshes, obj_poses, obj_diags, K, H, W)``: a whole scene with depth and instance ids;
+  * ``paint_mesh(mesh, views, normals=...)``: vertex colours from the photographs of an instance's views -- bilinear samples through the
+    rasteriser's depth buffer and the occupancy mask, weighed by how squarely each view faces the vertex, the unseen rest filled from its
+    neighbours (``ops.paint_view`` / ``paint_finish`` / ``paint_fill``: ``snr_paint_*``; rules restated in tests/paint_restatement.py);
   * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
     ``to_decoder_frame``: its inverse;
   * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
@@ -948,6 +951,25 @@ def _inverse3(r):
     return c / (r[0] * torch.linalg.cross(r[1], r[2])).sum()
 
 
+def _view_camera(cam_pose, obj_diag, K, roi, im_sz, family, shapenet_obj_cood, kitti2nusc):
+    """What ``mesh_view`` and ``paint_mesh`` draw a decoder-frame mesh with: (the (3, 4) float64 decoder -> camera matrix on ``cam_pose``'s
+    device, the effective (fx, fy, cx, cy) of the pixel grid over ``roi``, its size (ny, nx)).  The decoder -> object map of
+    ``to_object_frame`` (frame matrix and scale), the inverse of ``cam_pose`` and the affine pixel grid (offset x0, y0 and the step of
+    ``im_sz``) are composed in float64."""
+    scale = _frame_scale(obj_diag, family)
+    pose = torch.as_tensor(cam_pose).detach().double()[:3]
+    if tuple(pose.shape) != (3, 4):
+        raise SnrError(f"cam_pose is (3, 4) or (4, 4), got {tuple(torch.as_tensor(cam_pose).shape)}")
+    r_inv = _inverse3(pose[:, :3])
+    m = torch.cat([r_inv @ _frame_matrix(shapenet_obj_cood, kitti2nusc, pose) * scale, -(r_inv @ pose[:, 3:4])], dim=1)
+    fx, fy, cx, cy = _camera(K)
+    x0, y0, x1, y1 = [int(v) for v in roi]
+    nx, ny = (int(im_sz), int(im_sz)) if im_sz is not None else (x1 - x0, y1 - y0)
+    sx = (x1 - 1 - x0) / (nx - 1) if nx > 1 else 1.0
+    sy = (y1 - 1 - y0) / (ny - 1) if ny > 1 else 1.0
+    return m, (fx / sx, fy / sy, (cx - x0) / sx, (cy - y0) / sy), (ny, nx)
+
+
 def mesh_view(meshes, cam_pose, obj_diag, K, roi, *, im_sz=None, cull="back", family="a", shapenet_obj_cood=False, kitti2nusc=False,
               normals=None, colors=None, z_near=1e-3):
     """One object's decoder-frame mesh (a (verts, faces) pair, or a list of pieces that share the pose) on the pixel grid of
@@ -962,18 +984,7 @@ def mesh_view(meshes, cam_pose, obj_diag, K, roi, *, im_sz=None, cull="back", fa
     (per-vertex, as ``vertex_normals`` / ``vertex_colors`` return them) the interpolated normals, renormalised and mapped to the object's
     frame with ``to_object_frame(direction=True)``, and colours.  ``obj_diag``, ``K``, ``roi`` and ``im_sz`` are host values; ``cam_pose``
     stays on its device.  No autograd."""
-    scale = _frame_scale(obj_diag, family)
-    pose = torch.as_tensor(cam_pose).detach().double()[:3]
-    if tuple(pose.shape) != (3, 4):
-        raise SnrError(f"cam_pose is (3, 4) or (4, 4), got {tuple(torch.as_tensor(cam_pose).shape)}")
-    r_inv = _inverse3(pose[:, :3])
-    m = torch.cat([r_inv @ _frame_matrix(shapenet_obj_cood, kitti2nusc, pose) * scale, -(r_inv @ pose[:, 3:4])], dim=1)
-    fx, fy, cx, cy = _camera(K)
-    x0, y0, x1, y1 = [int(v) for v in roi]
-    nx, ny = (int(im_sz), int(im_sz)) if im_sz is not None else (x1 - x0, y1 - y0)
-    sx = (x1 - 1 - x0) / (nx - 1) if nx > 1 else 1.0
-    sy = (y1 - 1 - y0) / (ny - 1) if ny > 1 else 1.0
-    cam = (fx / sx, fy / sy, (cx - x0) / sx, (cy - y0) / sy)
+    m, cam, (ny, nx) = _view_camera(cam_pose, obj_diag, K, roi, im_sz, family, shapenet_obj_cood, kitti2nusc)
     ms, single = _one_or_many(meshes)
     r = rasterize(ms, m.unsqueeze(0).expand(len(ms), 3, 4), cam, (ny, nx), cull=cull, z_near=z_near)
     dev = r.depth.device
@@ -987,6 +998,117 @@ def mesh_view(meshes, cam_pose, obj_diag, K, roi, *, im_sz=None, cull="back", fa
     if colors is not None:
         color = interpolate(r, [colors] if single else list(colors))[0]
     return MeshView(r.depth[0] * length, r.face[0] >= 0, r.face[0], normal, color)
+
+
+class Painted(NamedTuple):
+    colors: torch.Tensor     # (V, 3) fp32: the painted colour; fallback / background where nothing reached the vertex
+    weight: torch.Tensor     # (V,) fp32: the sum of the views' weights ("weighted") or the best view's weight ("best"); 0 where unseen
+    seen: torch.Tensor       # (V,) int32: how many views see the vertex
+    best: torch.Tensor       # (V,) int32: the view that faces it most squarely (ties: the lowest index); -1 where unseen
+    filled: torch.Tensor     # (V,) int32: 0 seen by a view; r >= 1 filled from neighbours in round r; -1 neither
+
+
+def _paint_views(views):
+    """The views of ``paint_mesh``, checked as far as the host can: [(img, mask or None, (h, w))]."""
+    if isinstance(views, dict) or not isinstance(views, (list, tuple)) or not views:
+        raise SnrError("views is a non-empty list of the dicts an instance of optimize_instances carries (img, mask, cam_pose, obj_diag, "
+                       "K, roi)")
+    out = []
+    for v, view in enumerate(views):
+        missing = [k for k in ("img", "cam_pose", "obj_diag", "K", "roi") if k not in view]
+        if missing:
+            raise SnrError(f"paint_mesh: view {v} has no {missing}")
+        x0, y0, x1, y1 = [int(t) for t in view["roi"]]
+        h, w = y1 - y0, x1 - x0
+        img, mask = torch.as_tensor(view["img"]), view.get("mask")
+        mask = None if mask is None else torch.as_tensor(mask)
+        if h < 1 or w < 1 or tuple(img.shape) != (h, w, 3) or (mask is not None and mask.numel() != h * w):
+            raise SnrError(f"paint_mesh: view {v}: img {tuple(img.shape)} / mask {None if mask is None else tuple(mask.shape)} are not the "
+                           f"native {h} x {w} crop of its roi")
+        out.append((img, mask, (h, w)))
+    return out
+
+
+def paint_mesh(meshes, views, *, normals=None, blend="weighted", facing=True, tol=None, fill=0, adjacency=None, fallback=None,
+               background=0.0, cull="back", family="a", shapenet_obj_cood=False, kitti2nusc=False, z_near=1e-3):
+    """Vertex colours from the photographs: one object's decoder-frame mesh (a (verts, faces) pair, or a list of pieces that share the
+    pose, as in ``mesh_view``) painted from ``views``, the list an instance of ``optimize_instances`` carries -- per view ``img`` (h, w, 3),
+    the native crop of its ``roi``; optionally ``mask`` (h w values: > 0 the object, 0 background, -1 another object in front);
+    ``cam_pose``, ``obj_diag``, ``K``, ``roi`` as ``mesh_view`` takes them (include/supnerf_hip.h, "Mesh painting"; ``snr_paint_*``).
+
+    Per view the mesh is drawn on the crop's pixel grid exactly as ``mesh_view`` draws it (one composition in float64, then
+    ``ops.rasterize``); its depth buffer decides which vertices the view sees.  A vertex samples the image bilinearly at its projection
+    (pixel centres at integers) over those of its four taps that show the mesh no nearer than the vertex (within ``tol``) and lie inside
+    the mask, renormalised by their weights: the whitened background and an occluder never bleed in.  A view weighs cos^2 of the angle
+    between the vertex normal and the direction to its camera (``facing=True``, which needs ``normals`` as ``vertex_normals`` returns them;
+    a view that faces away does not see the vertex), or 1 (``facing=False``: ``normals`` are ignored).
+
+    * ``blend``: ``"weighted"`` = the weighted mean over the views that see the vertex; ``"best"`` = the colour of the view with the
+      largest weight, ties to the lowest view index.
+    * ``tol``: how far behind the depth buffer (metres of camera z) a vertex may lie and still be seen.  Default ``0.01 * obj_diag`` of the
+      view: a stated choice, not a measured optimum -- at 20 m with fx ~ 1266 one pixel spans about 1.6 cm, so for a 4.7 m car it is
+      about the depth a 45-degree surface gains over three pixels.  Smaller values drop grazing vertices, larger ones let vertices
+      just behind a rim take the rim's colour.
+    * ``fill=R``: R rounds in which every uncoloured vertex with coloured neighbours takes their mean (``adjacency``: what
+      ``mesh_adjacency`` returned for these meshes, else it is built here, with its one host read).
+    * A vertex still uncoloured takes its row of ``fallback`` ((V, 3), or a list of them per piece; for example ``vertex_colors``), else
+      ``background``; its ``filled`` stays -1.
+
+    Returns a ``Painted`` (a list of them for a list of pieces).  Views are painted in ascending order, one launch each, plain fp32
+    sums: the same bits from run to run.  Host values (``K``, ``roi``, ``obj_diag``; a ``cam_pose`` on the GPU is copied to the host, one
+    synchronising read, for the camera centre) aside, the call is asynchronous on the current stream and reads nothing back.  No
+    autograd.  CPU meshes raise ``SnrError``."""
+    if blend not in ops.PAINT_BLENDS:
+        raise SnrError(f"blend is one of {ops.PAINT_BLENDS}, got {blend!r}")
+    if int(fill) < 0:
+        raise SnrError(f"fill must not be negative, got {fill}")
+    if facing and normals is None:
+        raise SnrError("facing=True weighs the views by the vertex normals: pass normals (vertex_normals), or facing=False")
+    if tol is not None and not (float(tol) >= 0 and np.isfinite(float(tol))):
+        raise SnrError(f"tol must be finite and not negative, got {tol}")
+    if cull not in (None, "back"):
+        raise SnrError(f"cull is None or 'back', got {cull!r}")
+    if not float(z_near) > 0:
+        raise SnrError(f"z_near must be positive, got {z_near}")
+    _frame_scale(1.0, family)
+    crops = _paint_views(views)
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    mesh = ops.pack_mesh(*_packed(ms))
+    B, dev, nV = len(ms), mesh.verts.device, mesh.verts.shape[0]
+    nrm = None
+    if facing:
+        rows = _per_object_rows(normals, ms, "normals")
+        if any(tuple(n.shape) != (v.shape[0], 3) for n, (v, _) in zip(rows, ms)):
+            raise SnrError(f"normals are (V, 3) per object, got {[tuple(n.shape) for n in rows]}")
+        nrm = (rows[0] if B == 1 else torch.cat(rows)).detach().float().contiguous()
+    fb = None
+    if fallback is not None:
+        rows = _per_object_rows(fallback, ms, "fallback colours")
+        if any(tuple(c.shape) != (v.shape[0], 3) for c, (v, _) in zip(rows, ms)):
+            raise SnrError(f"fallback colours are (V, 3) per object, got {[tuple(c.shape) for c in rows]}")
+        fb = (rows[0] if B == 1 else torch.cat(rows)).detach().float()
+    adj = _adjacency(ms, adjacency)[1] if int(fill) > 0 else None
+    state = ops.paint_state(nV, dev)
+    image_of = torch.zeros(B, dtype=torch.int32, device=dev)
+    for k, (view, (img, mask, (h, w))) in enumerate(zip(views, crops)):
+        m, cam, _ = _view_camera(view["cam_pose"], view["obj_diag"], view["K"], view["roi"], None, family, shapenet_obj_cood, kitti2nusc)
+        cull_sign = torch.sign(_det3(m)).to(torch.int32).to(dev).expand(B).contiguous() if cull == "back" else None
+        _, depth, _, screen = ops.rasterize(mesh, m.unsqueeze(0).expand(B, 3, 4).float().to(dev), cam, image_of, 1, h, w, z_near, cull_sign)
+        centre = to_decoder_frame(torch.as_tensor(view["cam_pose"]).detach().double().cpu()[:3, 3], view["obj_diag"], family,
+                                  shapenet_obj_cood, kitti2nusc).tolist()
+        ops.paint_view(mesh, screen, nrm, img.detach().float().contiguous().to(dev),
+                       None if mask is None else mask.detach().float().reshape(h, w).contiguous().to(dev), depth[0], centre,
+                       0.01 * float(view["obj_diag"]) if tol is None else float(tol), z_near, k, state)
+    colors, filled = ops.paint_finish(state, blend, background)
+    if adj is not None:
+        colors, filled = ops.paint_fill(colors, filled, adj, int(fill))
+    if fb is not None:
+        colors = torch.where((filled < 0)[:, None], fb, colors)
+    weight = state.sum_w if blend == "weighted" else state.best_w
+    out = [Painted(colors[v], weight[v], state.seen[v], state.best[v], filled[v]) for (v,) in _object_slices(mesh.n_verts)]
+    return out[0] if single else out
 
 
 class SceneView(NamedTuple):

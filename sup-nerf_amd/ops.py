@@ -1969,6 +1969,135 @@ def rasterize(mesh, obj_to_cam, camera, image_of_object, n_images, H, W, z_near,
     return raster_resolve(mesh, screen, keys) + (screen,)
 
 
+# ------------------------------------------------------------------------------------ mesh painting
+PAINT_BLENDS = ("weighted", "best")
+PAINT_GRID_THREADS = 2048 * 256      # the threads of one pass of the paint kernels' grid-stride loops (snr_paint.hip: PAINT_MAX_BLOCKS)
+
+
+class PaintState(NamedTuple):
+    """What ``snr_paint_view`` keeps per vertex between the views (include/supnerf_hip.h, "Mesh painting", rule P4)."""
+    sum_rgb: torch.Tensor      # (sum V, 3) fp32: the sum of g c over the views that see the vertex
+    sum_w: torch.Tensor        # (sum V,) fp32: the sum of g
+    seen: torch.Tensor         # (sum V,) int32: how many views see it
+    best_w: torch.Tensor       # (sum V,) fp32: the largest g
+    best: torch.Tensor         # (sum V,) int32: the first view that has it; -1 where none
+    best_rgb: torch.Tensor     # (sum V, 3) fp32: that view's colour
+
+
+def paint_state(n_verts, device) -> PaintState:
+    """The state of ``paint_view`` before the first view: zeros, and ``best`` = -1."""
+    n = int(n_verts)
+    if n < 0:
+        raise SnrError(f"paint_state: n_verts must not be negative, got {n_verts}")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise SnrError("supnerf_amd operators need tensors on the GPU (no CPU fallback)")
+    z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
+    return PaintState(z(n, 3), z(n), z(n, dtype=torch.int32), z(n), torch.full((n,), -1, dtype=torch.int32, device=dev), z(n, 3))
+
+
+def _paint_dense(t, what, shape, dtype=torch.float32):
+    """A buffer the paint kernels read or update where it lies: on the GPU, of this shape and type, contiguous -- nothing is converted."""
+    _need_gpu(t)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+        raise SnrError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got {tuple(t.shape)} {t.dtype}"
+                       f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    return t
+
+
+def _paint_state(state, nV, what):
+    if not isinstance(state, PaintState):
+        raise SnrError(f"{what}: state is what paint_state returns")
+    i32 = torch.int32
+    for name, shape, dtype in (("sum_rgb", (nV, 3), torch.float32), ("sum_w", (nV,), torch.float32), ("seen", (nV,), i32),
+                               ("best_w", (nV,), torch.float32), ("best", (nV,), i32), ("best_rgb", (nV, 3), torch.float32)):
+        _paint_dense(getattr(state, name), f"{what}: state.{name}", shape, dtype)
+    return state
+
+
+def paint_view(mesh, screen, normals, image, mask, depth, centre, tol, z_near, k, state):
+    """One view painted into ``state`` in place (``snr_paint_view``; include/supnerf_hip.h, "Mesh painting", rules P1 - P4).  ``mesh``: the
+    ``PackedMesh``; ``screen`` (sum V, 3): ``raster_project``'s for this view; ``normals`` (sum V, 3) or None (every view weighs 1);
+    ``image`` (H, W, 3), ``mask`` (H, W) or None, ``depth`` (H, W): the view's photograph, its occupancy and ``raster_resolve``'s depth
+    on one pixel grid; ``centre``: the camera centre in the frame of the stored vertices, three host floats; ``tol`` >= 0: how far behind
+    the depth buffer a vertex may lie and still count as seen (camera z); ``k`` >= 0: the view's index.  Views go in ascending ``k`` on
+    one stream.  Every tensor is read where it lies: fp32, contiguous, on the GPU, else ``SnrError``."""
+    nV = mesh.verts.shape[0]
+    _paint_dense(screen, "paint_view: screen", (nV, 3))
+    if normals is not None:
+        _paint_dense(normals, "paint_view: normals", (nV, 3))
+    _need_gpu(image)
+    if image.dim() != 3 or image.shape[2] != 3:
+        raise SnrError(f"paint_view: image must be (H, W, 3), got {tuple(image.shape)}")
+    H, W = int(image.shape[0]), int(image.shape[1])
+    if H * W >= 2 ** 31:
+        raise SnrError(f"paint_view: an image of {H} x {W} pixels: the paint kernels take fewer than 2^31 pixels per view")
+    _paint_dense(image, "paint_view: image", (H, W, 3))
+    _paint_dense(depth, f"paint_view: depth (the image is {H} x {W})", (H, W))
+    if mask is not None:
+        _paint_dense(mask, f"paint_view: mask (the image is {H} x {W})", (H, W))
+    centre = [float(c) for c in centre]
+    tol, z_near, k = float(tol), float(z_near), int(k)
+    if len(centre) != 3:
+        raise SnrError(f"paint_view: centre is three numbers, got {len(centre)}")
+    if not (tol >= 0 and math.isfinite(tol)):
+        raise SnrError(f"paint_view: tol must be finite and not negative, got {tol}")
+    if not z_near > 0:
+        raise SnrError(f"paint_view: z_near must be positive, got {z_near}")
+    if k < 0:
+        raise SnrError(f"paint_view: the view index must not be negative, got {k}")
+    _paint_state(state, nV, "paint_view")
+    dev, i32 = mesh.verts.device, torch.int32
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_paint_view(_ptr(screen), _ptr(mesh.verts), _ptr(normals), nV, _ptr(image), _ptr(mask), _ptr(depth), H, W, *centre,
+                                        tol, z_near, k, _ptr(state.sum_rgb), _ptr(state.sum_w), _ptr(state.seen, i32), _ptr(state.best_w),
+                                        _ptr(state.best, i32), _ptr(state.best_rgb), _stream(dev)), "snr_paint_view")
+    return state
+
+
+def paint_finish(state, blend="weighted", background=0.0):
+    """(colors (sum V, 3) fp32, filled (sum V,) int32) of a ``PaintState`` (``snr_paint_finish``; rule P5): per vertex some view saw the
+    weighted mean of its views (``blend="weighted"``) or the colour of its best view (``"best"``) and filled = 0; ``background`` and -1
+    elsewhere."""
+    if blend not in PAINT_BLENDS:
+        raise SnrError(f"blend is one of {PAINT_BLENDS}, got {blend!r}")
+    if not isinstance(state, PaintState):
+        raise SnrError("paint_finish: state is what paint_state returns")
+    nV = state.seen.shape[0]
+    _paint_state(state, nV, "paint_finish")
+    dev, i32 = state.seen.device, torch.int32
+    colors = torch.empty(nV, 3, device=dev)
+    filled = torch.empty(nV, dtype=i32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().snr_paint_finish(_ptr(state.sum_rgb), _ptr(state.sum_w), _ptr(state.seen, i32), _ptr(state.best_rgb), nV,
+                                          PAINT_BLENDS.index(blend), float(background), _ptr(colors), _ptr(filled, i32), _stream(dev)),
+              "snr_paint_finish")
+    return colors, filled
+
+
+def paint_fill(colors, filled, adjacency, rounds):
+    """``rounds`` Jacobi rounds of rule P6 over a ``MeshAdjacency`` (``snr_paint_fill``): in round r = 1, 2, ... every vertex with
+    ``filled`` < 0 that has a filled neighbour takes the mean of its filled neighbours' colours and ``filled`` = r.  One launch per round
+    between two buffers, no host read; returns new (colors, filled), ``rounds=0`` copies."""
+    rounds = int(rounds)
+    if rounds < 0:
+        raise SnrError(f"paint_fill: rounds must not be negative, got {rounds}")
+    nV = sum(adjacency.n_verts)
+    _paint_dense(colors, "paint_fill: colors", (nV, 3))
+    _paint_dense(filled, "paint_fill: filled", (nV,), torch.int32)
+    dev, i32 = colors.device, torch.int32
+    cur, cur_f = colors.clone(), filled.clone()
+    if rounds == 0 or nV == 0:
+        return cur, cur_f
+    lib, st, csr = _lib.lib(), _stream(dev), _smooth_csr(adjacency)
+    with torch.cuda.device(dev):
+        other, other_f = torch.empty_like(cur), torch.empty_like(cur_f)
+        for r in range(1, rounds + 1):
+            check(lib.snr_paint_fill(_ptr(cur), _ptr(cur_f, i32), *csr, r, _ptr(other), _ptr(other_f, i32), st), "snr_paint_fill")
+            cur, other, cur_f, other_f = other, cur, other_f, cur_f
+    return cur, cur_f
+
+
 # ------------------------------------------------------------------------------------ ray-cast surfaces
 def _ray_shapes(rays_o, rays_d, *per_ray):
     """R of rays_o, rays_d (R, 3) and any number of per-ray (R,) tensors: the sizes the ray kernels index by."""
