@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 24
+#define SNR_ABI_VERSION 25
 
 enum {
     SNR_OK = 0,
@@ -871,6 +871,88 @@ int snr_paint_finish(const float* sum_rgb, const float* sum_w, const int32_t* se
                      float background, float* colors, int32_t* filled, void* stream);
 int snr_paint_fill(const float* colors_in, const int32_t* filled_in, const int64_t* nbr_start, const int32_t* nbr, const int64_t* vert_offset,
                    int64_t n_objects, int64_t n_verts, int64_t n_edges, int round, float* colors_out, int32_t* filled_out, void* stream);
+
+/* Mesh distance: the closest point of a packed triangle mesh to a query point, and area-uniform samples of its surface.  The mesh is the
+ * packed form of "Mesh components" above (verts fp32, object-local int32 faces, vert_offset and face_offset DEVICE arrays).  Queries are
+ * packed the same way: points (sum Q, 3) fp32 with query_offset (n_objects + 1) int64, DEVICE; a query of object b sees the faces of
+ * object b only.  The library is built without fused multiply-adds: all arithmetic of D1 - D3 is float64 on the widened fp32 inputs, one
+ * correctly rounded float64 operation per written operation, in the written order.  tests/nearest_restatement.py restates every rule in
+ * numpy, one function each; the kernels give its bits.
+ *   D1. Point - triangle: the closest point of (a, b, c) to p by the region walk of Ericson (Real-Time Collision Detection, 5.1.5), in
+ *       differences only, so that no rounding error grows with the distance of the object from the origin.  With dot(x, y) = (x0 y0 +
+ *       x1 y1) + x2 y2:  ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;  d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp),
+ *       d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);  vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.  The first
+ *       test that holds decides, in this order (weights w of a, b, c; e = p - closest point):
+ *         vertex a:  d1 <= 0 and d2 <= 0:                                         w = (1, 0, 0),          e = ap;
+ *         vertex b:  d3 >= 0 and d4 <= d3:                                        w = (0, 1, 0),          e = bp;
+ *         edge ab:   vc <= 0, d1 >= 0, d3 <= 0 and d1 - d3 > 0:  t = d1 / (d1 - d3),  w = (1 - t, t, 0),  e = ap - t ab;
+ *         vertex c:  d6 >= 0 and d5 <= d6:                                        w = (0, 0, 1),          e = cp;
+ *         edge ac:   vb <= 0, d2 >= 0, d6 <= 0 and d2 - d6 > 0:  t = d2 / (d2 - d6),  w = (1 - t, 0, t),  e = ap - t ac;
+ *         edge bc:   va <= 0, g = d4 - d3 >= 0, h = d5 - d6 >= 0 and g + h > 0:  t = g / (g + h),  w = (0, 1 - t, t),  e = bp - t (c - b);
+ *         interior:  s = (va + vb) + vc,  v = vb / s,  u = vc / s,  w = ((1 - v) - u, v, u),  e = (ap - v ab) - u ac.
+ *       d^2 = (ex^2 + ey^2) + ez^2.  An edge test also asks for a positive denominator, so no quotient is 0 / 0: a face without area
+ *       (coincident corners; exactly collinear corners in either order) needs no other care and gives the distance to its segment or
+ *       point.  Should rounding still leave s = 0 in the last line, d^2 is not finite; a candidate whose d^2 is NaN or +inf never wins.
+ *   D2. The answer is the brute-force one: over all faces of the query's object the face with the smallest d^2 wins, ties to the lowest
+ *       face index.  A face with an index outside [0, V) is skipped and sets *bad; a face with a vertex coordinate that is not finite is
+ *       skipped.  A query with a non-finite coordinate, or an object without a usable face, gets face -1, weights 0 and d^2 = +inf.  The
+ *       grid below may only change how many faces are tested; it may never change the result.
+ *   D3. The grid.  Object b has cubic cells of edge h = cell[b] > 0 (fp32, widened), anchored at lo = grid_lo[b], the exact fp32 minimum
+ *       of its vertices; grid_hi[b] is their exact maximum (both (n_objects, 3) fp32; 0 for an object without vertices).  Per axis
+ *       n_a = clamp(ceil((hi_a - lo_a) / h), 1, 256) cells; the cell of a coordinate x is clamp(floor((x - lo_a) / h), 0, n_a - 1), so
+ *       border cells reach to infinity outwards.  A face is listed in every cell of the index box spanned by the cells of its component-
+ *       wise minimum and maximum corner.  Cell (cx, cy, cz) of object b has the id cell_offset[b] + (cx n_y + cy) n_z + cz; cell_offset
+ *       (n_objects + 1) int64 = the exclusive scan of n_x n_y n_z, n_cells its last entry.  An object whose h is not positive and finite,
+ *       whose bounds are not finite or whose cell_offset entries do not hold exactly its n_x n_y n_z cells has no usable grid: *bad.
+ *   D4. The search, one thread per query.  c0 = the cell of the query.  For r = 0, 1, ...: visit the cells at Chebyshev distance r from
+ *       c0 that lie inside the grid and test every listed face by D1 and D2 (a face listed in several cells is tested again: harmless).
+ *       After ring r, with t_a = p_a - lo_a:  m = the smallest of t_a - k h over the axes with k = c0_a - r >= 1 and of k h - t_a over
+ *       the axes with k = c0_a + r + 1 <= n_a - 1 -- the distance to the bounding planes of the block [c0 - r, c0 + r] on the sides
+ *       where the grid goes on.  No such side: the search is over.  Otherwise stop iff
+ *           s = m - 2^-40 (E + m) > 0  and  s s > best d^2,        E = the largest hi_a - lo_a of the object.
+ *       Why this cannot change the result: a face not yet tested has no cell in the block, so on some axis all of its vertices fall
+ *       into cells beyond one of those planes; the cell function is monotone, so every point of the face lies beyond the plane up to the
+ *       rounding of (x - lo) / h and of k h, a few 2^-53 of E; the e of D1 is formed from differences whose roundings are a few 2^-53
+ *       of |p - a| <= E + m + the distance found.  The slack 2^-40 (E + m) is 2^12 times all of that, and 2^-16 of the fp32 resolution
+ *       of the inputs, so it costs no measurable extra ring.  The part 2^-40 E covers queries near the object, the part 2^-40 m queries
+ *       far from it, whose roundings grow with their distance and not with E.  A face that only ties the best (equal d^2, lower index)
+ *       is beyond no plane by more than the slack either, so it is still visited.
+ *   D5. Surface samples.  Sample i of the n samples of an object takes three uniforms u (3) float64 in [0, 1) -- an input, as the render
+ *       path takes injected jitter -- and the object's INCLUSIVE cumulative face area cum (F) float64, an input too (the face-area term
+ *       is rule 3 of "Mesh components"; the scan is the caller's).  target = ((double) i + u0) / (double) n * cum[F - 1]; the face is
+ *       the first f with cum[f] > target, or, where rounding leaves none, the first f with cum[f] >= cum[F - 1]: the last face with
+ *       area.  So a face without area is never chosen.  s = sqrt(u1), correctly rounded; weights (1 - s, s (1 - u2), s u2); the point
+ *       is (w0 a + w1 b) + w2 c per coordinate in float64, rounded once to fp32; the weights are rounded to fp32.  The draw is
+ *       stratified: the number of samples on a face differs from n area_f / area by less than 2.  An object with cum[F - 1] not
+ *       positive and finite (or F = 0) gives face -1, weights 0, point 0; so does a chosen face with an index outside [0, V), with *bad.
+ *
+ * snr_nearest_count: count (sum F) int32 = the number of cells of D3 per face; 0 and *bad (device int32, zeroed by the caller) for a face
+ *   with a bad index or a non-finite vertex, or of an object without a usable grid.
+ * snr_nearest_emit: from count_scan (sum F) int64, the caller's EXCLUSIVE scan of those counts, the pairs pair_cell (n_pairs) int64 (global
+ *   cell id) and pair_face (n_pairs) int32 (object-local face), face f's at count_scan[f] on; a slot outside [0, n_pairs) is not written.
+ *   The caller sorts the pairs by cell with one stable sort and finds cell_start (n_cells + 1) int64 by a search over the sorted ids.
+ * snr_nearest_query: face (sum Q) int32 (object-local, -1 for none), weights (sum Q, 3) fp32 and dist2 (sum Q) float64 by D1 - D4.  Every
+ *   index read from a list is range-checked before use: a cell_start pair or a listed face out of range adds nothing.  The object of a
+ *   query is found once, not per candidate face.
+ * snr_surface_sample: points (sum S, 3) fp32, face (sum S) int32 and weights (sum S, 3) fp32 by D5; uniforms (sum S, 3) float64, cum_area
+ *   (sum F) float64 (each object's own inclusive scan), sample_offset (n_objects + 1) int64.
+ * Nothing is allocated, nothing is read back, the caller's stream is used; no atomics except the *bad flag.  A null pointer or a negative
+ * size: SNR_E_ARG; more than 2^38 vertices, faces, queries, samples, cells or pairs in a launch: SNR_E_UNSUPPORTED. */
+int snr_nearest_count(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const float* cell,
+                      const float* grid_lo, const float* grid_hi, const int64_t* cell_offset, int64_t n_objects, int64_t n_verts,
+                      int64_t n_faces, int64_t n_cells, int32_t* count, int32_t* bad, void* stream);
+int snr_nearest_emit(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const float* cell,
+                     const float* grid_lo, const float* grid_hi, const int64_t* cell_offset, const int64_t* count_scan, int64_t n_objects,
+                     int64_t n_verts, int64_t n_faces, int64_t n_cells, int64_t n_pairs, int64_t* pair_cell, int32_t* pair_face,
+                     void* stream);
+int snr_nearest_query(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const float* points,
+                      const int64_t* query_offset, const float* cell, const float* grid_lo, const float* grid_hi, const int64_t* cell_offset,
+                      const int64_t* cell_start, const int32_t* pair_face, int64_t n_objects, int64_t n_verts, int64_t n_faces,
+                      int64_t n_queries, int64_t n_cells, int64_t n_pairs, int32_t* face, float* weights, double* dist2, int32_t* bad,
+                      void* stream);
+int snr_surface_sample(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const double* cum_area,
+                       const double* uniforms, const int64_t* sample_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces,
+                       int64_t n_samples, float* points, int32_t* face, float* weights, int32_t* bad, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Several views of one instance share one shape and one texture code (src/optimizer_nuscenes.py:796-1277): V rendered views, I <= V code

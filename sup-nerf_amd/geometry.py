@@ -41,6 +41,12 @@ After an optimisation or a training run a caller holds one 256-float shape code 
   * ``paint_mesh(mesh, views, normals=...)``: vertex colours from the photographs of an instance's views -- bilinear samples through the
     rasteriser's depth buffer and the occupancy mask, weighed by how squarely each view faces the vertex, the unseen rest filled from its
     neighbours (``ops.paint_view`` / ``paint_finish`` / ``paint_fill``: ``snr_paint_*``; rules restated in tests/paint_restatement.py);
+  * ``closest_point(meshes, points)``: for every query point the closest point of its object's surface -- face, barycentric weights and
+    distance, exact (the brute-force answer, pruned by a uniform grid; ``ops.mesh_nearest_query``: ``snr_nearest_*``), with autograd to
+    the points and the vertices; ``mesh_index(meshes, cell)``: that grid, built once; ``sample_surface(meshes, n)``: stratified
+    area-uniform surface samples (``snr_surface_sample``); ``mesh_distance(a, b)``: mean, RMS and maximum distance in both directions
+    on such samples, Chamfer, Hausdorff and, with a threshold, precision, recall and F-score (rules restated in
+    tests/nearest_restatement.py);
   * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
     ``to_decoder_frame``: its inverse;
   * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
@@ -803,6 +809,194 @@ def laplacian_energy(meshes, adjacency=None):
         count = (adj.degree[v] > 0).sum().clamp(min=1)
         out.append((u[v] ** 2).sum() / count)
     return torch.stack(out)
+
+
+class MeshIndex(NamedTuple):
+    mesh: ops.PackedMesh         # the meshes the index was built over, packed
+    grid: ops.NearestIndex       # the grid of D3: cells, offsets and the sorted face lists
+
+
+class Closest(NamedTuple):
+    point: torch.Tensor          # (Q, 3) fp32: the closest point of the surface; with autograd to the vertices
+    face: torch.Tensor           # (Q,) int32: the face it lies on; -1 where the query has no answer
+    weights: torch.Tensor        # (Q, 3) fp32: its barycentric weights in that face
+    distance: torch.Tensor       # (Q,) fp32: |points - point|; +inf where the query has no answer
+
+
+class SurfaceSamples(NamedTuple):
+    points: torch.Tensor         # (n, 3) fp32
+    face: torch.Tensor           # (n,) int32; -1 for a mesh without area
+    weights: torch.Tensor        # (n, 3) fp32: the barycentric weights of each point in its face
+
+
+class MeshDistance(NamedTuple):
+    """Per object (B,) float64; 0-dim for a single pair.  ``forward`` is from the samples of ``a`` to the surface of ``b``."""
+    forward_mean: torch.Tensor
+    forward_rms: torch.Tensor
+    forward_max: torch.Tensor
+    backward_mean: torch.Tensor
+    backward_rms: torch.Tensor
+    backward_max: torch.Tensor
+    chamfer: torch.Tensor        # forward_mean + backward_mean
+    hausdorff: torch.Tensor      # the larger of the two maxima, on the samples
+    precision: object            # the share of a's samples within ``threshold`` of b; None without a threshold
+    recall: object               # the share of b's samples within ``threshold`` of a
+    fscore: object               # their harmonic mean (0 where both are 0)
+
+
+def _packed_mesh(ms):
+    verts, faces, nvs, nfs = _packed(ms)
+    return ops.pack_mesh(verts, faces, nvs, nfs)
+
+
+def mesh_index(meshes, cell=None) -> MeshIndex:
+    """The search grid of ``closest_point`` over ``meshes`` -- the list ``extract_mesh`` returns, or one (verts, faces) pair -- built once
+    and reusable for any number of queries (include/supnerf_hip.h, "Mesh distance", D3; ``ops.mesh_nearest_index``).  Every object gets
+    cubic cells of edge ``cell`` (a float or one per object), anchored at the minimum of its vertices, at most 256 per axis; every face is
+    listed in the cells its bounding box touches.  ``cell=None``: ``ops.NEAREST_CELL_FACTOR`` times the square root of the object's mean
+    face area, but no less than 1/256 of its largest extent (``ops.mesh_default_cell``; the factor comes from the sweep in DESIGN 4.7.9).  The grid decides only how fast a query is answered, never what
+    the answer is.  One host read (the pair count).  More than ``ops.NEAREST_MAX_PAIRS`` (cell, face) pairs raise ``SnrError`` with the
+    cell size that fits; so do CPU tensors, faces that are not int32, a face index outside its mesh, a non-finite vertex and a ``cell``
+    that is not positive and finite."""
+    ms, _ = _one_or_many(meshes)
+    if not ms:
+        raise SnrError("mesh_index: no meshes")
+    mesh = _packed_mesh(ms)
+    B, dev = len(ms), mesh.verts.device
+    if cell is None:
+        cell = ops.mesh_default_cell(mesh)
+    elif not torch.is_tensor(cell) or not cell.is_cuda:
+        cell_h = torch.as_tensor(cell, dtype=torch.float32).reshape(-1)
+        if not bool(((cell_h > 0) & torch.isfinite(cell_h)).all()):
+            raise SnrError(f"mesh_index: cell must be positive and finite, got {cell_h.tolist()}")
+    return MeshIndex(mesh, ops.mesh_nearest_index(mesh, cell))
+
+
+def _index_for(ms, index, cell=None):
+    if index is None:
+        return mesh_index(ms, cell)
+    if not isinstance(index, MeshIndex) or index.mesh.n_verts != [v.shape[0] for v, _ in ms] or index.mesh.n_faces != [f.shape[0] for _, f in ms]:
+        raise SnrError("index is what mesh_index returned for these meshes")
+    return index
+
+
+def _per_object_points(points, B, single):
+    if torch.is_tensor(points):
+        if B != 1:
+            raise SnrError(f"points are a list of (Q, 3) tensors, one per object: {B} meshes")
+        points = [points]
+    points = list(points)
+    if len(points) != B:
+        raise SnrError(f"{B} meshes but {len(points)} point tensors")
+    for p in points:
+        _gpu(p, "points")
+        if p.dim() != 2 or p.shape[1] != 3:
+            raise SnrError(f"points are (Q, 3) per object, got {tuple(p.shape)}")
+    return points
+
+
+def closest_point(meshes, points, index=None):
+    """For every query point the closest point of its object's surface: ``meshes`` is the list ``extract_mesh`` returns with ``points`` a
+    list of (Q, 3) tensors, one per object, or one (verts, faces) pair with one (Q, 3) tensor.  Returns one ``Closest(point, face,
+    weights, distance)`` per object (a single one for a single pair).  ``index``: what ``mesh_index`` returned for these meshes, to save
+    building it again (and its host read).
+
+    The answer is exact: over all faces of the object the smallest float64 squared distance of Ericson's point-triangle walk, ties to
+    the lowest face index (include/supnerf_hip.h, "Mesh distance"; ``snr_nearest_query``); the grid only prunes, bit for bit.  ``point``
+    = sum_k weights_k verts[faces[face, k]] and ``distance`` = |points - point| are formed in torch, so autograd reaches ``points`` and
+    the vertices (those of ``extract_mesh(..., differentiable=True)`` carry it on to the grid or the shape codes); face and weights are
+    constants of that graph, as in the rasteriser.  When nothing requires grad, ``distance`` is the square root of the kernel's float64
+    squared distance, rounded to fp32.  A query with a non-finite coordinate, and any query of a mesh without a usable face, has face
+    -1, weights 0, point 0 and distance +inf.  CPU tensors raise ``SnrError``."""
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    pts = _per_object_points(points, len(ms), single)
+    index = _index_for(ms, index)
+    nqs = [p.shape[0] for p in pts]
+    packed = pts[0] if len(pts) == 1 else torch.cat([p.float() for p in pts])
+    face, weights, dist2 = ops.mesh_nearest_query(index.mesh, index.grid, packed, nqs)
+    out = []
+    for (v, f), p, (q,) in zip(ms, pts, _object_slices(nqs)):
+        fa, w, d2 = face[q], weights[q], dist2[q]
+        none = fa < 0
+        live = torch.is_grad_enabled() and (p.requires_grad or v.requires_grad)
+        if f.shape[0] and v.shape[0]:
+            corners = v.float()[f.long()[fa.clamp(min=0).long()]]                 # (Q, 3 corners, 3)
+            point = (w[:, :, None] * corners).sum(1)
+        else:
+            point = torch.zeros(p.shape[0], 3, device=p.device)
+        if live:
+            dist = torch.linalg.vector_norm(p.float() - point, dim=1)
+            dist = torch.where(none, torch.full_like(dist, float("inf")), dist)
+        else:
+            dist = torch.sqrt(d2).float()
+        out.append(Closest(point, fa, w, dist))
+    return out[0] if single else out
+
+
+def sample_surface(meshes, n, generator=None):
+    """``n`` points per object spread evenly over the surface of each mesh of ``meshes`` -- the list ``extract_mesh`` returns, or one
+    (verts, faces) pair: one ``SurfaceSamples(points, face, weights)`` per object (a single one for a single pair).  The draw is
+    area-uniform and stratified along the faces (include/supnerf_hip.h, "Mesh distance", D5; ``snr_surface_sample``): the number of samples
+    on a face differs from n area_f / area by less than 2, and a face without area gets none.  The randomness is ``torch.rand`` of
+    (B n, 3) float64 from ``generator`` (on the meshes' device, or a CPU generator), so a seeded generator gives the same samples again.
+    A mesh without area gets face -1 and points 0.  No host read.  CPU tensors and ``n < 0`` raise ``SnrError``."""
+    if int(n) < 0:
+        raise SnrError(f"n must not be negative, got {n}")
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    out = _sample(_packed_mesh(ms), int(n), generator)
+    return out[0] if single else out
+
+
+def _sample(mesh, n, generator):
+    B, dev = len(mesh.n_verts), mesh.verts.device
+    gdev = dev if generator is None else generator.device
+    u = torch.rand(B * n, 3, dtype=torch.float64, device=gdev, generator=generator).to(dev)
+    points, face, weights = ops.mesh_surface_sample(mesh, ops.mesh_cumulative_area(mesh), u, [n] * B)
+    return [SurfaceSamples(points[s], face[s], weights[s]) for (s,) in _object_slices([n] * B)]
+
+
+def mesh_distance(a, b, n=10000, generator=None, threshold=None, index_a=None, index_b=None) -> MeshDistance:
+    """How far apart two surfaces are, object by object: ``a`` and ``b`` are lists of meshes of the same length (or one pair each), paired
+    in order.  ``n`` surface samples are drawn on each side (``sample_surface`` of ``a``, then of ``b``, from ``generator``) and each is
+    taken to the closest point of the OTHER surface (``closest_point``).  Per object and direction the mean, the root mean square and the
+    maximum of those distances; ``chamfer`` = the sum of the two means; ``hausdorff`` = the larger maximum (on the samples: a lower bound
+    of the true Hausdorff distance).  With ``threshold``: ``precision`` = the share of a's samples within it of b, ``recall`` = the share
+    of b's samples within it of a, and their harmonic mean ``fscore`` (a = the reconstruction, b = the truth).  All values are (B,)
+    float64 (0-dim for a single pair).  The sums of d and d^2 go through the fixed-order segmented sum, so the same generator state
+    gives the same bits; nothing is read back beyond the two index builds.  A side without area gives +inf."""
+    if int(n) < 1:
+        raise SnrError(f"n must be positive, got {n}")
+    if threshold is not None and not float(threshold) >= 0:
+        raise SnrError(f"threshold must not be negative, got {threshold}")
+    shape = [(1, True) if isinstance(m, (tuple, list)) and len(m) == 2 and torch.is_tensor(m[0]) else (len(m), False) for m in (a, b)]
+    if shape[0] != shape[1]:
+        raise SnrError(f"mesh_distance pairs the meshes of a and b object by object: got {shape[0][0]} and {shape[1][0]}"
+                       f"{'' if shape[0][1] == shape[1][1] else ' (one pair and one list)'}")
+    ma, single_a = _one_or_many(a)
+    mb, _ = _one_or_many(b)
+    if not ma:
+        raise SnrError("mesh_distance: no meshes")
+    n, B = int(n), len(ma)
+    ia, ib = _index_for(ma, index_a), _index_for(mb, index_b)
+    sa, sb = _sample(ia.mesh, n, generator), _sample(ib.mesh, n, generator)
+    stats = []
+    for samples, index in ((sa, ib), (sb, ia)):
+        pts = torch.cat([s.points for s in samples]) if B > 1 else samples[0].points
+        drawn = torch.cat([s.face for s in samples]) if B > 1 else samples[0].face
+        _, _, d2 = ops.mesh_nearest_query(index.mesh, index.grid, pts, [n] * B)
+        d2 = torch.where(drawn < 0, torch.full_like(d2, float("inf")), d2)       # (a side without area has no samples to measure from)
+        d = torch.sqrt(d2)
+        sum_d, sum_d2 = ops.object_sums(d, d2, [n] * B)
+        within = None if threshold is None else (d.view(B, n) <= float(threshold)).sum(1).double() / n
+        stats.append((sum_d / n, torch.sqrt(sum_d2 / n), d.view(B, n).amax(1), within))
+    (fm, fr, fx, p), (bm, br, bx, r) = stats
+    f = None if p is None else torch.where(p + r > 0, 2 * p * r / (p + r).clamp(min=1e-300), torch.zeros_like(p))
+    out = (fm, fr, fx, bm, br, bx, fm + bm, torch.maximum(fx, bx), p, r, f)
+    return MeshDistance(*[None if t is None else (t[0] if single_a else t) for t in out])
 
 
 def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False, direction=False):

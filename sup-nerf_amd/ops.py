@@ -1735,6 +1735,227 @@ def mesh_simplify(verts, faces, n_verts, n_faces, cell, origin, placement="quadr
     return SimplifiedMesh(out_verts, out_faces, new_n_verts, new_n_faces, vert_map, members, face_index, out_attr)
 
 
+# ------------------------------------------------------------------------------------ mesh distance
+NEAREST_MAX_CELLS = 256         # cells per axis of an object's grid (include/supnerf_hip.h, "Mesh distance", D3)
+NEAREST_MAX_PAIRS = 1 << 26     # (cell, face) pairs of one index: 12 bytes each, sorted once
+NEAREST_CELL_FACTOR = 2.0       # the default cell edge is this times the square root of the object's mean face area
+
+
+class NearestIndex(NamedTuple):
+    """The grid of D3 over a packed mesh: what ``mesh_nearest_query`` walks."""
+    cell: torch.Tensor         # (B,) fp32: the cell edge per object
+    grid_lo: torch.Tensor      # (B, 3) fp32: the exact minimum of each object's vertices (0 without vertices)
+    grid_hi: torch.Tensor      # (B, 3) fp32: their exact maximum
+    cell_offset: torch.Tensor  # (B + 1,) int64 on the device: where each object's cells start
+    cell_start: torch.Tensor   # (n_cells + 1,) int64: cell c's faces at pair_face[cell_start[c] : cell_start[c + 1]]
+    pair_face: torch.Tensor    # (n_pairs,) int32: object-local face indices, ascending within a cell
+    n_cells: int
+    n_pairs: int
+
+
+def mesh_face_areas(mesh: PackedMesh) -> torch.Tensor:
+    """(sum F,) float64: the area term of every face (include/supnerf_hip.h, "Mesh components", rule 3), by ``snr_mesh_face_terms``; 0 for
+    a face with an index outside its object."""
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    dev, nV, nF = verts.device, verts.shape[0], faces.shape[0]
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    area, vol = torch.zeros(nF, dtype=f64, device=dev), torch.empty(nF, dtype=f64, device=dev)
+    if nF:
+        with torch.cuda.device(dev):
+            root = torch.zeros(nV, dtype=i32, device=dev)           # (the volume term's reference vertex; that term is not used)
+            check(_lib.lib().snr_mesh_face_terms(_ptr(verts), _ptr(faces, i32), _ptr(root, i32), None, _ptr(voff, i64), _ptr(foff, i64),
+                                                 len(n_verts), nV, nF, _ptr(area, f64), _ptr(vol, f64), _stream(dev)), "snr_mesh_face_terms")
+    return area
+
+
+def mesh_cumulative_area(mesh: PackedMesh, areas=None) -> torch.Tensor:
+    """(sum F,) float64: per object the INCLUSIVE scan of its face areas (one ``torch.cumsum`` per object): D5's ``cum``."""
+    areas = mesh_face_areas(mesh) if areas is None else areas
+    cum = torch.empty_like(areas)
+    off = _host_offsets(mesh.n_faces)
+    for b in range(len(mesh.n_faces)):
+        if mesh.n_faces[b]:
+            torch.cumsum(areas[off[b]:off[b + 1]], 0, out=cum[off[b]:off[b + 1]])
+    return cum
+
+
+def _nearest_grid(mesh, cell):
+    """(grid_lo, grid_hi (B, 3) fp32, cells per object (B,) int64) of D3 on the device: the same float64 operations as the kernels'."""
+    verts, B, dev = mesh.verts, len(mesh.n_verts), mesh.verts.device
+    lo, hi = torch.zeros(B, 3, device=dev), torch.zeros(B, 3, device=dev)
+    off = _host_offsets(mesh.n_verts)
+    for b in range(B):
+        if mesh.n_verts[b]:
+            lo[b], hi[b] = verts[off[b]:off[b + 1]].amin(0), verts[off[b]:off[b + 1]].amax(0)
+    n = torch.ceil((hi.double() - lo.double()) / cell.double()[:, None])
+    n = torch.where(n >= 1.0, n.clamp(max=float(NEAREST_MAX_CELLS)), torch.ones_like(n)).long()           # (a NaN gives 1)
+    return lo, hi, n.prod(1)
+
+
+def mesh_default_cell(mesh: PackedMesh, factor=NEAREST_CELL_FACTOR) -> torch.Tensor:
+    """(B,) fp32 on the device: the default cell edge of ``geometry.mesh_index`` -- ``factor`` times the square root of the object's mean
+    face area, but no less than 1/256 of its largest extent, below which the 256 cells per axis would no longer cover the object and its
+    border cells, which reach outwards without end, would hold most of the faces.  An object without area gets one cell."""
+    B, dev = len(mesh.n_verts), mesh.verts.device
+    areas = mesh_face_areas(mesh)
+    off = _host_offsets(mesh.n_faces)
+    mean = torch.stack([areas[off[b]:off[b + 1]].mean() if mesh.n_faces[b] else areas.new_zeros(()) for b in range(B)])
+    lo, hi, _ = _nearest_grid(mesh, torch.ones(B, device=dev))
+    base, extent = (float(factor) * torch.sqrt(mean)).float(), (hi - lo).amax(1)
+    whole = torch.where((extent > 0) & torch.isfinite(extent), extent, torch.ones_like(extent))            # one cell
+    return torch.where((base > 0) & torch.isfinite(base), torch.maximum(base, whole / NEAREST_MAX_CELLS), whole)
+
+
+def mesh_nearest_index(mesh: PackedMesh, cell) -> NearestIndex:
+    """The grid of D3 (include/supnerf_hip.h, "Mesh distance") over a packed mesh: ``cell`` (B,) fp32 > 0 on the device, the cell edge per
+    object.  ``snr_nearest_count`` -> one ``torch.cumsum`` -> the one host read (the flag, the pair count and the cell count) ->
+    ``snr_nearest_emit`` -> one stable ``torch.sort`` by cell -> ``torch.searchsorted``.  A face index outside its object, a non-finite
+    vertex and a cell that is not positive and finite raise; so do more than ``NEAREST_MAX_PAIRS`` pairs, with the factor by which to
+    grow the cells."""
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    B, dev = len(n_verts), verts.device
+    nV, nF = verts.shape[0], faces.shape[0]
+    lib, st = _lib.lib(), _stream(dev)
+    i32, i64 = torch.int32, torch.int64
+    cell = _per_object_f32(cell, B, 1, dev, "cell")
+    with torch.cuda.device(dev):
+        lo, hi, cells = _nearest_grid(mesh, cell)
+        coff = torch.zeros(B + 1, dtype=i64, device=dev)
+        torch.cumsum(cells, 0, out=coff[1:])
+        bad = torch.zeros(2, dtype=i32, device=dev)
+        bad[1:] = (~((cell > 0) & torch.isfinite(cell))).any().to(i32)
+        count = torch.zeros(nF, dtype=i32, device=dev)
+        n_cells_bound = min(B * NEAREST_MAX_CELLS ** 3, 1 << 38)    # (the count is on the device still; each object's is checked there)
+        check(lib.snr_nearest_count(_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), _ptr(cell), _ptr(lo), _ptr(hi),
+                                    _ptr(coff, i64), B, nV, nF, n_cells_bound, _ptr(count, i32), _ptr(bad[0:1], i32), st), "snr_nearest_count")
+        scan = torch.cumsum(count, 0, dtype=i64)
+        total = scan[-1:] if nF else torch.zeros(1, dtype=i64, device=dev)
+        host = torch.cat([bad.long(), total, coff[-1:]]).cpu().tolist()                                      # the one host read
+        if host[1]:
+            raise SnrError("mesh_index: cell must be positive and finite")
+        if host[0]:
+            raise SnrError("mesh_index: a face index lies outside its object's vertices, or a vertex is not finite")
+        n_pairs, n_cells = host[2], host[3]
+        if n_pairs > NEAREST_MAX_PAIRS:
+            raise SnrError(f"mesh_index: {n_pairs} (cell, face) pairs exceed the limit of {NEAREST_MAX_PAIRS}; cells "
+                           f"{_nearest_fit(mesh, cell):.3g} times as large would fit")
+        pair_cell = torch.empty(n_pairs, dtype=i64, device=dev)
+        pair_face = torch.empty(n_pairs, dtype=i32, device=dev)
+        first = scan - count                                        # the exclusive scan
+        check(lib.snr_nearest_emit(_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), _ptr(cell), _ptr(lo), _ptr(hi),
+                                   _ptr(coff, i64), _ptr(first, i64), B, nV, nF, n_cells, n_pairs, _ptr(pair_cell, i64),
+                                   _ptr(pair_face, i32), st), "snr_nearest_emit")
+        pair_cell, order = torch.sort(pair_cell, stable=True)
+        cell_start = torch.searchsorted(pair_cell, torch.arange(n_cells + 1, dtype=i64, device=dev))
+    return NearestIndex(cell, lo, hi, coff, cell_start, pair_face[order].contiguous(), n_cells, n_pairs)
+
+
+def _nearest_fit(mesh, cell):
+    """The factor (a power of 1.25) by which to grow ``cell`` so that the pairs fit ``NEAREST_MAX_PAIRS``: counted, not estimated.  Only
+    the error path comes here; each trial is one launch and one host read."""
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    B, dev, i32, i64 = len(n_verts), verts.device, torch.int32, torch.int64
+    factor = 1.0
+    for _ in range(64):
+        factor *= 1.25
+        c = (cell * factor).contiguous()
+        lo, hi, cells = _nearest_grid(mesh, c)
+        coff = torch.zeros(B + 1, dtype=i64, device=dev)
+        torch.cumsum(cells, 0, out=coff[1:])
+        count = torch.zeros(faces.shape[0], dtype=i32, device=dev)
+        bad = torch.zeros(1, dtype=i32, device=dev)
+        check(_lib.lib().snr_nearest_count(_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), _ptr(c), _ptr(lo), _ptr(hi),
+                                           _ptr(coff, i64), B, verts.shape[0], faces.shape[0], min(B * NEAREST_MAX_CELLS ** 3, 1 << 38), _ptr(count, i32),
+                                           _ptr(bad, i32), _stream(dev)), "snr_nearest_count")
+        if int(count.sum(dtype=i64)) <= NEAREST_MAX_PAIRS:
+            break
+    return factor
+
+
+def _packed_counts(counts, B, total, what):
+    counts = [int(c) for c in counts]
+    if len(counts) != B or min(counts + [0]) < 0 or sum(counts) != total:
+        raise SnrError(f"{what}: per-object counts {counts} do not add up to {total} rows for {B} objects")
+    return counts
+
+
+def mesh_nearest_query(mesh: PackedMesh, index: NearestIndex, points, n_queries):
+    """(face (sum Q,) int32, weights (sum Q, 3) fp32, dist2 (sum Q,) float64): per query the closest face of ITS object (object-local
+    index, -1 for none), the barycentric weights of the closest point and the squared distance, by ``snr_nearest_query`` (D1 - D4: the
+    brute-force answer bit for bit, whatever the grid).  ``points`` (sum Q, 3) fp32 object after object, ``n_queries`` the Q per object
+    (a host list).  Nothing is read back: a bad face index that only this launch could notice gives a skipped face."""
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    B, dev = len(n_verts), verts.device
+    _need_gpu(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise SnrError(f"mesh_nearest_query: points are (sum Q, 3), got {tuple(points.shape)}")
+    points = _f32c(points.detach())
+    nQ = points.shape[0]
+    n_queries = _packed_counts(n_queries, B, nQ, "mesh_nearest_query")
+    if tuple(index.cell.shape) != (B,) or index.cell_offset.shape[0] != B + 1 or index.cell_start.shape[0] != index.n_cells + 1:
+        raise SnrError("mesh_nearest_query: this index was not built for this mesh")
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    with torch.cuda.device(dev):
+        qoff = _offsets(n_queries, dev)[1]
+        face = torch.empty(nQ, dtype=i32, device=dev)
+        weights = torch.empty(nQ, 3, device=dev)
+        dist2 = torch.empty(nQ, dtype=f64, device=dev)
+        bad = torch.zeros(1, dtype=i32, device=dev)
+        check(_lib.lib().snr_nearest_query(_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), _ptr(points), _ptr(qoff, i64),
+                                           _ptr(index.cell), _ptr(index.grid_lo), _ptr(index.grid_hi), _ptr(index.cell_offset, i64),
+                                           _ptr(index.cell_start, i64), _ptr(index.pair_face, i32), B, verts.shape[0], faces.shape[0], nQ,
+                                           index.n_cells, index.n_pairs, _ptr(face, i32), _ptr(weights), _ptr(dist2, f64), _ptr(bad, i32),
+                                           _stream(dev)), "snr_nearest_query")
+    return face, weights, dist2
+
+
+def mesh_surface_sample(mesh: PackedMesh, cum, uniforms, n_samples):
+    """(points (sum S, 3) fp32, face (sum S,) int32, weights (sum S, 3) fp32): stratified area-uniform samples by ``snr_surface_sample``
+    (D5) from ``cum`` (sum F,) float64 (``mesh_cumulative_area``) and ``uniforms`` (sum S, 3) float64 in [0, 1); ``n_samples`` the S per
+    object (a host list).  An object without area gets face -1.  Nothing is read back."""
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    B, dev = len(n_verts), verts.device
+    _need_gpu(cum, uniforms)
+    if uniforms.dim() != 2 or uniforms.shape[1] != 3 or uniforms.dtype != torch.float64 or cum.dtype != torch.float64 or \
+            tuple(cum.shape) != (faces.shape[0],):
+        raise SnrError(f"mesh_surface_sample: uniforms are (sum S, 3) float64 and cum is (sum F,) float64, got {tuple(uniforms.shape)} "
+                       f"{uniforms.dtype} and {tuple(cum.shape)} {cum.dtype}")
+    nS = uniforms.shape[0]
+    n_samples = _packed_counts(n_samples, B, nS, "mesh_surface_sample")
+    uniforms, cum = uniforms.contiguous(), cum.contiguous()
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    with torch.cuda.device(dev):
+        soff = _offsets(n_samples, dev)[1]
+        points, weights = torch.empty(nS, 3, device=dev), torch.empty(nS, 3, device=dev)
+        face = torch.empty(nS, dtype=i32, device=dev)
+        bad = torch.zeros(1, dtype=i32, device=dev)
+        check(_lib.lib().snr_surface_sample(_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64), _ptr(cum, f64), _ptr(uniforms, f64),
+                                            _ptr(soff, i64), B, verts.shape[0], faces.shape[0], nS, _ptr(points), _ptr(face, i32), _ptr(weights),
+                                            _ptr(bad, i32), _stream(dev)), "snr_surface_sample")
+    return points, face, weights
+
+
+def object_sums(d, d2, n_per_object):
+    """(sum d, sum d2) (B,) float64 per object of two (sum Q,) float64 lists packed object after object, by ``snr_mesh_segment_sum`` with
+    the objects as segments: the fixed order of include/supnerf_hip.h ("Fixed-order segmented sums"), the same bits from run to run."""
+    _need_gpu(d, d2)
+    dev, B, n = d.device, len(n_per_object), d.shape[0]
+    i64, f64 = torch.int64, torch.float64
+    out_a, out_b = torch.zeros(B, dtype=f64, device=dev), torch.zeros(B, dtype=f64, device=dev)
+    if B == 0 or n == 0:
+        return out_a, out_b
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        seg_start = _offsets(n_per_object, dev)[1]
+        slab_off = torch.zeros(B + 1, dtype=i64, device=dev)
+        torch.cumsum((seg_start[1:] - seg_start[:-1] + (MESH_SLAB - 1)) // MESH_SLAB, 0, out=slab_off[1:])
+        n_slabs = int(lib.snr_segment_slab_bound(B, n))
+        partial = torch.empty(n_slabs, 2, dtype=f64, device=dev)
+        check(lib.snr_mesh_segment_sum(_ptr(d.contiguous(), f64), _ptr(d2.contiguous(), f64), _ptr(seg_start, i64), _ptr(slab_off, i64), B, n,
+                                       _ptr(partial, f64), n_slabs, _ptr(out_a, f64), _ptr(out_b, f64), _stream(dev)), "snr_mesh_segment_sum")
+    return out_a, out_b
+
+
 # ------------------------------------------------------------------------------------ mesh smoothing
 SMOOTH_KEY_BITS = 31            # snr_smooth_edge_keys: (global source index) << 31 | local target index
 SMOOTH_NO_KEY = 2 ** 63 - 1     # a discarded pair
