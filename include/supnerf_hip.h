@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 25
+#define SNR_ABI_VERSION 26
 
 enum {
     SNR_OK = 0,
@@ -953,6 +953,65 @@ int snr_nearest_query(const float* verts, const int32_t* faces, const int64_t* v
 int snr_surface_sample(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const double* cum_area,
                        const double* uniforms, const int64_t* sample_offset, int64_t n_objects, int64_t n_verts, int64_t n_faces,
                        int64_t n_samples, float* points, int32_t* face, float* weights, int32_t* bad, void* stream);
+
+/* Mesh containment: on which side of a packed triangle mesh a point lies -- the integer winding number along +z, the signed number of
+ * faces that the ray from p in direction +z crosses.  The mesh is the packed form of "Mesh components" above, the queries are packed as in
+ * "Mesh distance" (points (sum Q, 3) fp32 with query_offset; a query of object b sees the faces of object b only), and the grid is the one
+ * of "Mesh distance" D3, built by snr_nearest_count / snr_nearest_emit: there is no second index.  The iso rules wind faces counter-
+ * clockwise seen from the low-density side ("Mesh components", rule 3), so for a closed mesh the value is the winding number of p: +1
+ * inside a solid blob, 0 inside a closed cavity of it, 2 where two blobs overlap, 0 outside.  A mesh that the border of the grid cut open
+ * gets the value of these rules and no more.  All arithmetic is float64 on the widened fp32 inputs, one correctly rounded operation per
+ * written operation, in the written order (the library is built without fused multiply-adds); compares of inputs are exact fp32 compares.
+ * tests/inside_restatement.py restates every rule in numpy, one function each; the kernels give its integers.
+ *   W1. Box guard.  Face (a, b, c) can count for p only if  min x <= p_x < max x,  min y <= p_y < max y  and  p_z < max z  over its three
+ *       corners.  The guard is part of the rule, not an optimisation: it is what makes pruning by a grid unable to change the answer (W5).
+ *   W2. Edge side, the same bits from both faces of an edge.  For the directed edge u -> v let (u', v') be the two endpoints ordered
+ *       lexicographically by (x, y):  E = (v'_x - u'_x) (p_y - u'_y) - (v'_y - u'_y) (p_x - u'_x);  s = sign(E); if 0, s = sign(-(v'_y -
+ *       u'_y)); if still 0, s = sign(v'_x - u'_x); if still 0 (a projected edge without length), s = 0.  s is negated if the endpoints
+ *       were swapped.  This takes the query as (p_x + e, p_y + e^2) with e -> 0+: a point exactly under an edge or a vertex belongs to
+ *       exactly one of the faces around it.  For fp32 inputs of comparable magnitude the differences and products are exact in float64,
+ *       so the sign is exact; the canonical order makes the two faces of an edge evaluate the same expression, so they agree on the side
+ *       even where rounding makes it wrong.
+ *   W3. Crossing.  sigma = s(a -> b).  The face's column contains p iff  s(a -> b) = s(b -> c) = s(c -> a) != 0.  sigma = +1: the
+ *       projection is counter-clockwise, the normal has a +z component.  A face without projected area (vertical, or without area at
+ *       all) never counts.
+ *   W4. Ahead.  n = (b - a) x (c - a), each component x1 y2 - x2 y1 as written:  n_x = (b_y - a_y)(c_z - a_z) - (b_z - a_z)(c_y - a_y),
+ *       n_y = (b_z - a_z)(c_x - a_x) - (b_x - a_x)(c_z - a_z),  n_z = (b_x - a_x)(c_y - a_y) - (b_y - a_y)(c_x - a_x).
+ *       t = (n_x (a_x - p_x) + n_y (a_y - p_y)) + n_z (a_z - p_z).  The face is ahead of p iff sigma t > 0: no division.  t = 0 (p on the
+ *       face's plane) is not ahead, so a point on the surface is not under that face.  The face contributes sigma.
+ *   W5. The answer is the brute-force one: winding(p) = the sum over ALL faces of p's object of the contributions, int32.  A face with an
+ *       index outside [0, V) is skipped and sets *bad; a face with a vertex coordinate that is not finite is skipped.  A query with a
+ *       non-finite coordinate, and every query of an object without a usable grid (D3; *bad), gets 0.  Pruning: a thread walks the
+ *       z-column of cells (c_x(p), c_y(p), k), k = c_z(p) .. n_z - 1 -- contiguous entries of cell_start, z being the fastest cell axis
+ *       -- and a face listed in several cells of the column counts ONCE, in cell k = max(c_z(min z of the face), c_z(p)).  Why this
+ *       cannot change the sum: the cell function of D3 is monotone and a face is listed in every cell of the index box of its corner
+ *       cells; so min x <= p_x < max x gives c_x(min x) <= c_x(p) <= c_x(max x), likewise in y, and W1's guard puts every face that can
+ *       count into this column of cells; and p_z < max z gives c_z(p) <= c_z(max z), so the chosen k lies between c_z(min z) and
+ *       c_z(max z): the face is listed there, and there only is it counted.  A face not in the column fails W1 and contributes 0 in the
+ *       brute force too.  The two integer comparisons use the very cell function the lists were built with.
+ *   W6. Lattice form.  For a lattice of n = (n_x, n_y, n_z) points per object, point (i, j, k) is at lat_lo + lat_h index per axis: an
+ *       fp32 multiply, then an fp32 add, rounded separately (the formula of the density lattices, "Geometry").  lat_lo and lat_h are
+ *       (n_objects, 3) fp32 DEVICE arrays; n is shared.  The winding numbers are in the lattice's order (x-major, z fastest) and are THE
+ *       SAME INTEGERS W1 - W5 give for those points.  W2, W3, n and the bracket of W4 do not depend on p_z, so a run of z-points of one
+ *       column does them once per face, walking the column of cells from the cell of its lowest point; per z-point p_z < max z, the last
+ *       multiply-add and the compare remain.
+ *
+ * snr_inside_query: winding (sum Q) int32 by W1 - W5, one thread per query; the mesh, the queries and the grid arrays exactly as
+ *   snr_nearest_query takes them.  *bad (device int32, zeroed by the caller) as W5 says.
+ * snr_inside_lattice: winding (n_objects n_x n_y n_z) int32 by W6; every entry is written, so the caller need not zero it.  One thread
+ *   per 16 consecutive z-points of a column.
+ * Every index read from a list is range-checked before use: a cell_start pair or a listed face out of range adds nothing.  Nothing is
+ * allocated, nothing is read back, the caller's stream is used; no atomics except the *bad flag.  A null pointer or a negative size:
+ * SNR_E_ARG; more than 2^38 vertices, faces, queries, cells, pairs or lattice points (per axis or in all) in a launch:
+ * SNR_E_UNSUPPORTED.  Zero queries, zero objects of a lattice or a lattice without points: SNR_OK without a launch. */
+int snr_inside_query(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const float* points,
+                     const int64_t* query_offset, const float* cell, const float* grid_lo, const float* grid_hi, const int64_t* cell_offset,
+                     const int64_t* cell_start, const int32_t* pair_face, int64_t n_objects, int64_t n_verts, int64_t n_faces,
+                     int64_t n_queries, int64_t n_cells, int64_t n_pairs, int32_t* winding, int32_t* bad, void* stream);
+int snr_inside_lattice(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const float* cell,
+                       const float* grid_lo, const float* grid_hi, const int64_t* cell_offset, const int64_t* cell_start,
+                       const int32_t* pair_face, const float* lat_lo, const float* lat_h, int64_t n_objects, int64_t n_verts, int64_t n_faces,
+                       int64_t n_cells, int64_t n_pairs, int64_t n_x, int64_t n_y, int64_t n_z, int32_t* winding, int32_t* bad, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Several views of one instance share one shape and one texture code (src/optimizer_nuscenes.py:796-1277): V rendered views, I <= V code

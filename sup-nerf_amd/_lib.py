@@ -128,6 +128,10 @@ _SIGS = {
     "snr_nearest_query": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                     _P, _P, _P, _P, _P]),
     "snr_surface_sample": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "snr_inside_query": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                   _P, _P, _P]),
+    "snr_inside_lattice": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int64, _P, _P, _P]),
     "snr_smooth_edge_keys": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "snr_smooth_vertex_flags": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "snr_smooth_step": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_double, _P, _P]),

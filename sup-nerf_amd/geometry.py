@@ -47,6 +47,12 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     area-uniform surface samples (``snr_surface_sample``); ``mesh_distance(a, b)``: mean, RMS and maximum distance in both directions
     on such samples, Chamfer, Hausdorff and, with a threshold, precision, recall and F-score (rules restated in
     tests/nearest_restatement.py);
+  * ``winding_number(meshes, points)``: on which side of its object's surface a point lies -- the integer winding number along +z, exact
+    (the brute-force sum over all faces, pruned by the grid of ``mesh_index``; ``ops.mesh_inside_query``: ``snr_inside_query``);
+    ``contains(meshes, points, rule=...)``: that as a bool; ``signed_distance(meshes, points)``: ``closest_point``'s distance with that
+    sign, one index for both searches; ``voxelize(meshes, resolution, bound)``: the occupancy of a mesh on the lattice ``density_grid``
+    uses (``snr_inside_lattice``); ``occupancy_iou(a, b)`` and ``mesh_iou(a, b, resolution)``: the volumetric intersection over union
+    of two occupancy grids or two meshes, with exact counts (rules restated in tests/inside_restatement.py);
   * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
     ``to_decoder_frame``: its inverse;
   * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
@@ -997,6 +1003,182 @@ def mesh_distance(a, b, n=10000, generator=None, threshold=None, index_a=None, i
     f = None if p is None else torch.where(p + r > 0, 2 * p * r / (p + r).clamp(min=1e-300), torch.zeros_like(p))
     out = (fm, fr, fx, bm, br, bx, fm + bm, torch.maximum(fx, bx), p, r, f)
     return MeshDistance(*[None if t is None else (t[0] if single_a else t) for t in out])
+
+
+class SignedDistance(NamedTuple):
+    distance: torch.Tensor       # (Q,) fp32: closest.distance, negated where the point is contained; +inf where the query has no answer
+    closest: Closest             # what closest_point returns for the same queries
+    winding: torch.Tensor        # (Q,) int32: the winding number the sign was taken from
+
+
+class IoU(NamedTuple):
+    """Per object (B,); 0-dim for a single grid or pair."""
+    iou: torch.Tensor            # float64: intersection / union, 0 where the union is empty
+    intersection: torch.Tensor   # int64: voxels set in both
+    union: torch.Tensor          # int64: voxels set in either
+    count_a: torch.Tensor        # int64: voxels set in a
+    count_b: torch.Tensor        # int64
+
+
+CONTAIN_RULES = ("nonzero", "positive", "odd")
+
+
+def _contained(winding, rule):
+    if rule == "nonzero":
+        return winding != 0
+    if rule == "positive":
+        return winding > 0
+    if rule == "odd":
+        return (winding & 1) != 0
+    raise SnrError(f"rule is one of {CONTAIN_RULES}, got {rule!r}")
+
+
+def _winding(ms, pts, index):
+    nqs = [p.shape[0] for p in pts]
+    packed = pts[0] if len(pts) == 1 else torch.cat([p.detach().float() for p in pts])
+    w = ops.mesh_inside_query(index.mesh, index.grid, packed, nqs)
+    return [w[q] for (q,) in _object_slices(nqs)]
+
+
+def winding_number(meshes, points, index=None):
+    """For every query point the integer winding number of its object's mesh along +z -- the signed number of faces that the ray from the
+    point in direction +z crosses: ``meshes`` is the list ``extract_mesh`` returns with ``points`` a list of (Q, 3) tensors, one per
+    object, or one (verts, faces) pair with one (Q, 3) tensor.  Returns one (Q,) int32 tensor per object (a single one for a single
+    pair).  ``index``: what ``mesh_index`` returned for these meshes -- the grid ``closest_point`` walks serves this search too.
+
+    ``extract_mesh`` winds faces counter-clockwise seen from the low-density side, so for a closed mesh a point inside a solid piece gets
+    +1, a point inside a closed cavity of it 0, a point where two pieces overlap 2, a point outside 0.  The value is exact: the
+    brute-force sum over all faces by the rules of include/supnerf_hip.h ("Mesh containment", W1 - W5; ``snr_inside_query``), which give
+    a point exactly under an edge or a vertex to exactly one face and a point on the surface to the side the rules name (for an
+    axis-parallel box: the half-open box); the grid only prunes.  A mesh that is not closed -- one the border of the grid cut open --
+    gets the value of these rules and no more: ``mesh_adjacency(...).closed`` is the check, and it is not run for the caller.  A query
+    with a non-finite coordinate, and any query of a mesh without faces, gets 0.  No autograd; CPU tensors raise ``SnrError``."""
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    pts = _per_object_points(points, len(ms), single)
+    out = _winding(ms, pts, _index_for(ms, index))
+    return out[0] if single else out
+
+
+def contains(meshes, points, index=None, rule="nonzero"):
+    """Whether each query point lies inside its object's mesh: ``winding_number`` turned into a (Q,) bool tensor per object by ``rule`` --
+    "nonzero" (inside any piece), "positive" (a cavity that overlaps a solid piece cancels it) or "odd" (the parity rule: the overlap of
+    two pieces is outside).  For a closed mesh without overlaps the three agree.  An open mesh gets what ``winding_number`` gives it."""
+    _contained(torch.zeros(0, dtype=torch.int32), rule)
+    w = winding_number(meshes, points, index)
+    return _contained(w, rule) if torch.is_tensor(w) else [_contained(x, rule) for x in w]
+
+
+def signed_distance(meshes, points, index=None, rule="nonzero"):
+    """The signed distance from every query point to its object's surface: one ``SignedDistance(distance, closest, winding)`` per object (a
+    single one for a single pair).  ``closest`` is what ``closest_point`` returns; ``distance`` = ``closest.distance``, negated where
+    ``contains(..., rule)`` holds.  The magnitude carries ``closest_point``'s autograd to the points and the vertices; the sign is a
+    constant of that graph.  One index serves both searches (``index``: what ``mesh_index`` returned, or built here once).  A query
+    without an answer (a non-finite coordinate, a mesh without faces) keeps +inf.  An open mesh gets the sign ``winding_number`` gives."""
+    _contained(torch.zeros(0, dtype=torch.int32), rule)
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    pts = _per_object_points(points, len(ms), single)
+    index = _index_for(ms, index)
+    closest = closest_point(ms, pts, index=index)
+    out = [SignedDistance(torch.where(_contained(w, rule), -c.distance, c.distance), c, w)
+           for c, w in zip(closest, _winding(ms, pts, index))]
+    return out[0] if single else out
+
+
+def _bounds(bound, B, what):
+    """One ``bound`` of ``lattice`` for every object (a tuple), or one per object (a list of B of them)."""
+    if isinstance(bound, list):
+        if len(bound) != B:
+            raise SnrError(f"{what}: {B} meshes but {len(bound)} bounds")
+        return bound
+    return [bound] * B
+
+
+def voxelize(meshes, resolution, bound=(-0.5, 0.5), index=None, rule="nonzero"):
+    """The occupancy of each mesh on ``lattice(resolution, bound)`` -- the lattice ``density_grid`` uses, so ``voxelize(mesh, R) ==
+    (density_grid(model, shapecode, R) > level)`` compares like with like: a (B, nx, ny, nz) bool tensor, (nx, ny, nz) for a single
+    (verts, faces) pair.  ``bound`` is one bound for every object (a tuple, as ``lattice`` takes it) or a list of one per object.  A
+    voxel is set where ``contains(..., rule)`` holds at its lattice point; the winding numbers come from ``snr_inside_lattice``
+    (include/supnerf_hip.h, "Mesh containment", W6), which gives the integers of ``winding_number`` at ``lattice_points`` with the work
+    that does not depend on z done once per face.  An open mesh gets what ``winding_number`` gives it.  No host read beyond the index
+    build; CPU tensors raise ``SnrError``."""
+    _contained(torch.zeros(0, dtype=torch.int32), rule)
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    lats = [lattice(resolution, b) for b in _bounds(bound, len(ms), "voxelize")]
+    index = _index_for(ms, index)
+    lo = torch.tensor([[lat.lo[a] for a in range(3)] for lat in lats], dtype=torch.float32)
+    h = torch.tensor([[lat.h[a] for a in range(3)] for lat in lats], dtype=torch.float32)
+    occ = _contained(ops.mesh_inside_lattice(index.mesh, index.grid, lo, h, [lats[0].n[a] for a in range(3)]), rule)
+    return occ[0] if single else occ
+
+
+def occupancy_iou(a, b) -> IoU:
+    """The volumetric intersection over union of two bool occupancy grids of equal shape, (B, nx, ny, nz) or (nx, ny, nz) -- what
+    ``voxelize`` returns, or ``density_grid(...) > level``: ``IoU(iou, intersection, union, count_a, count_b)`` per object.  The four
+    counts are exact int64; ``iou`` = intersection / union in float64, 0 where the union is empty.  Plain tensor sums on the grids'
+    device."""
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.dtype != torch.bool or b.dtype != torch.bool or a.shape != b.shape or \
+            a.dim() not in (3, 4):
+        raise SnrError("occupancy_iou takes two bool grids of equal shape, (B, nx, ny, nz) or (nx, ny, nz)")
+    dims = (-3, -2, -1)
+    inter, union = (a & b).sum(dims, dtype=torch.int64), (a | b).sum(dims, dtype=torch.int64)
+    iou = torch.where(union > 0, inter.double() / union.clamp(min=1).double(), torch.zeros_like(inter, dtype=torch.float64))
+    return IoU(iou, inter, union, a.sum(dims, dtype=torch.int64), b.sum(dims, dtype=torch.int64))
+
+
+def iou_lattice(box_lo, box_hi, resolution):
+    """(lo, h) (B, 3) fp32 of the lattice ``mesh_iou`` uses over the boxes ``box_lo`` .. ``box_hi`` (B, 3) fp32: the centres of
+    ``resolution``^3 equal boxes.  In fp32, each operation rounded:  h = (box_hi - box_lo) / resolution;  lo = box_lo + h * 0.5;  point i
+    is then lo + h * i (a multiply, then an add), as on every lattice of this module."""
+    h = (box_hi.float() - box_lo.float()) / torch.tensor(float(int(resolution)), dtype=torch.float32, device=box_lo.device)
+    return box_lo.float() + h * 0.5, h
+
+
+def mesh_iou(a, b, resolution=64, bound=None, rule="nonzero", index_a=None, index_b=None) -> IoU:
+    """The volumetric IoU of two meshes, object by object: ``a`` and ``b`` are lists of meshes of the same length (or one pair each),
+    paired in order as ``mesh_distance`` pairs them.  Both are voxelised (``snr_inside_lattice``, ``rule`` as in ``contains``) on one
+    lattice per object: the centres of ``resolution``^3 equal boxes that fill ``bound`` -- one bound as ``lattice`` takes it (a tuple), a
+    list of one per object, or ``None``: per object the union of the two meshes' bounding boxes (the exact fp32 minimum and maximum of
+    their vertices; a mesh without vertices adds nothing).  With the box [lo_box, hi_box], in fp32 with every operation rounded:
+    h = (hi_box - lo_box) / resolution, lo = lo_box + h * 0.5, point i = lo + h * i (``iou_lattice``).  Returns ``occupancy_iou`` of
+    the two grids: exact counts, so the volumes are count * h_x h_y h_z.  Open meshes get what ``winding_number`` gives them.  No host
+    read beyond the index builds."""
+    _contained(torch.zeros(0, dtype=torch.int32), rule)
+    R = int(resolution)
+    if R < 1 or R > MAX_RESOLUTION:
+        raise SnrError(f"resolution must be 1..{MAX_RESOLUTION}, got {resolution}")
+    shape = [(1, True) if isinstance(m, (tuple, list)) and len(m) == 2 and torch.is_tensor(m[0]) else (len(m), False) for m in (a, b)]
+    if shape[0] != shape[1]:
+        raise SnrError(f"mesh_iou pairs the meshes of a and b object by object: got {shape[0][0]} and {shape[1][0]}"
+                       f"{'' if shape[0][1] == shape[1][1] else ' (one pair and one list)'}")
+    ma, single = _one_or_many(a)
+    mb, _ = _one_or_many(b)
+    if not ma:
+        raise SnrError("mesh_iou: no meshes")
+    B = len(ma)
+    ia, ib = _index_for(ma, index_a), _index_for(mb, index_b)
+    dev = ia.mesh.verts.device
+    if bound is None:
+        box_lo, box_hi = [], []
+        for k in range(B):
+            sides = [i.grid for i, ms in ((ia, ma), (ib, mb)) if ms[k][0].shape[0]]
+            box_lo.append(torch.stack([g.grid_lo[k] for g in sides]).amin(0) if sides else torch.zeros(3, device=dev))
+            box_hi.append(torch.stack([g.grid_hi[k] for g in sides]).amax(0) if sides else torch.zeros(3, device=dev))
+        box_lo, box_hi = torch.stack(box_lo), torch.stack(box_hi)
+    else:
+        pairs = [(np.broadcast_to(np.asarray(lo, np.float32), (3,)), np.broadcast_to(np.asarray(hi, np.float32), (3,)))
+                 for lo, hi in _bounds(bound, B, "mesh_iou")]
+        box_lo = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev)
+        box_hi = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
+    lo, h = iou_lattice(box_lo, box_hi, R)
+    grids = [_contained(ops.mesh_inside_lattice(i.mesh, i.grid, lo, h, (R, R, R)), rule) for i in (ia, ib)]
+    out = occupancy_iou(*grids)
+    return IoU(*[t[0] for t in out]) if single else out
 
 
 def to_object_frame(verts, obj_diag, family="a", shapenet_obj_cood=False, kitti2nusc=False, direction=False):

@@ -1956,6 +1956,64 @@ def object_sums(d, d2, n_per_object):
     return out_a, out_b
 
 
+# ------------------------------------------------------------------------------------ mesh containment
+def _inside_args(mesh, index, what):
+    """The pointers and sizes ``snr_inside_query`` and ``snr_inside_lattice`` take for the mesh and its grid (``index``: a
+    ``NearestIndex`` built over this mesh)."""
+    verts, faces, voff, foff, n_verts, n_faces = mesh
+    B = len(n_verts)
+    if not isinstance(index, NearestIndex) or tuple(index.cell.shape) != (B,) or index.cell_offset.shape[0] != B + 1 or \
+            index.cell_start.shape[0] != index.n_cells + 1:
+        raise SnrError(f"{what}: this index was not built for this mesh")
+    i32, i64 = torch.int32, torch.int64
+    grid = (_ptr(index.cell), _ptr(index.grid_lo), _ptr(index.grid_hi), _ptr(index.cell_offset, i64), _ptr(index.cell_start, i64),
+            _ptr(index.pair_face, i32))
+    return (_ptr(verts), _ptr(faces, i32), _ptr(voff, i64), _ptr(foff, i64)), grid, (B, verts.shape[0], faces.shape[0])
+
+
+def mesh_inside_query(mesh: PackedMesh, index: NearestIndex, points, n_queries):
+    """winding (sum Q,) int32: per query the integer winding number along +z of ITS object's mesh, by ``snr_inside_query``
+    (include/supnerf_hip.h, "Mesh containment", W1 - W5: the brute-force integers, whatever the grid).  ``points`` (sum Q, 3) fp32 object
+    after object, ``n_queries`` the Q per object (a host list), ``index`` what ``mesh_nearest_index`` built over ``mesh``.  Nothing is read
+    back: a bad face index that only this launch could notice gives a skipped face."""
+    dev = mesh.verts.device
+    _need_gpu(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise SnrError(f"mesh_inside_query: points are (sum Q, 3), got {tuple(points.shape)}")
+    m, g, (B, nV, nF) = _inside_args(mesh, index, "mesh_inside_query")
+    points = _f32c(points.detach())
+    nQ = points.shape[0]
+    n_queries = _packed_counts(n_queries, B, nQ, "mesh_inside_query")
+    i32, i64 = torch.int32, torch.int64
+    with torch.cuda.device(dev):
+        qoff = _offsets(n_queries, dev)[1]
+        winding = torch.empty(nQ, dtype=i32, device=dev)
+        bad = torch.zeros(1, dtype=i32, device=dev)
+        check(_lib.lib().snr_inside_query(*m, _ptr(points), _ptr(qoff, i64), *g, B, nV, nF, nQ, index.n_cells, index.n_pairs,
+                                          _ptr(winding, i32), _ptr(bad, i32), _stream(dev)), "snr_inside_query")
+    return winding
+
+
+def mesh_inside_lattice(mesh: PackedMesh, index: NearestIndex, lat_lo, lat_h, n):
+    """winding (B, nx, ny, nz) int32: the winding numbers of ``mesh_inside_query`` at the points lat_lo + lat_h (i, j, k) of one lattice
+    per object (an fp32 multiply, then an fp32 add: the points of ``geometry.lattice_points``), by ``snr_inside_lattice`` (W6: the same
+    integers, the work that does not depend on z done once per face and run of 16 z-points).  ``lat_lo`` and ``lat_h`` are (B, 3) fp32
+    (or 3 numbers for every object), ``n`` = (nx, ny, nz) shared by the objects.  Nothing is read back."""
+    dev = mesh.verts.device
+    m, g, (B, nV, nF) = _inside_args(mesh, index, "mesh_inside_lattice")
+    n = tuple(int(x) for x in n)
+    if len(n) != 3 or min(n) < 1:
+        raise SnrError(f"mesh_inside_lattice: n is three positive point counts, got {n}")
+    lat_lo, lat_h = _per_object_f32(lat_lo, B, 3, dev, "lat_lo"), _per_object_f32(lat_h, B, 3, dev, "lat_h")
+    i32 = torch.int32
+    with torch.cuda.device(dev):
+        winding = torch.empty((B,) + n, dtype=i32, device=dev)
+        bad = torch.zeros(1, dtype=i32, device=dev)
+        check(_lib.lib().snr_inside_lattice(*m, *g, _ptr(lat_lo), _ptr(lat_h), B, nV, nF, index.n_cells, index.n_pairs, n[0], n[1], n[2],
+                                            _ptr(winding, i32), _ptr(bad, i32), _stream(dev)), "snr_inside_lattice")
+    return winding
+
+
 # ------------------------------------------------------------------------------------ mesh smoothing
 SMOOTH_KEY_BITS = 31            # snr_smooth_edge_keys: (global source index) << 31 | local target index
 SMOOTH_NO_KEY = 2 ** 63 - 1     # a discarded pair
