@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SNR_ABI_VERSION 26
+#define SNR_ABI_VERSION 27
 
 enum {
     SNR_OK = 0,
@@ -1012,6 +1012,89 @@ int snr_inside_lattice(const float* verts, const int32_t* faces, const int64_t* 
                        const float* grid_lo, const float* grid_hi, const int64_t* cell_offset, const int64_t* cell_start,
                        const int32_t* pair_face, const float* lat_lo, const float* lat_h, int64_t n_objects, int64_t n_verts, int64_t n_faces,
                        int64_t n_cells, int64_t n_pairs, int64_t n_x, int64_t n_y, int64_t n_z, int32_t* winding, int32_t* bad, void* stream);
+
+/* Mesh ray casting: where a ray hits a packed triangle mesh first, and how many faces it crosses.  The mesh is the packed form of "Mesh
+ * components" above; rays are packed as the queries of "Mesh distance" are (rays_o and rays_d (sum N, 3) fp32 with ray_offset (n_objects +
+ * 1) int64, DEVICE; t_min and t_max (sum N) fp32; a ray of object b sees the faces of object b only), and the grid is the one of "Mesh
+ * distance" D3, built by snr_nearest_count / snr_nearest_emit: there is no second index.  All arithmetic is float64 on the widened fp32
+ * inputs, one correctly rounded operation per written operation, in the written order (the library is built without fused multiply-adds).
+ * tests/raycast_restatement.py restates every rule in numpy, one function each; the kernels give its integers, its t bit for bit in
+ * float64 and its weights bit for bit in fp32.
+ *   R1. Ray frame (Woop, Benthin, Wald 2013, "Watertight ray/triangle intersection").  The ray is o + t d; d need not be unit, t is in
+ *       units of |d|.  kz = the axis of the largest |d| (ties to the lowest axis); kx, ky = the next two axes cyclically, swapped when
+ *       d[kz] < 0, so that winding is kept.  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].  Per vertex v:  A = v - o;
+ *       x' = A[kx] - Sx A[kz],  y' = A[ky] - Sy A[kz],  z' = Sz A[kz].  In (x', y', z') the ray is the z' axis and z' is its parameter.
+ *       A ray with a non-finite component of o or d, or with d = 0, hits nothing and crosses nothing.
+ *   R2. Edge side, the same bits from both faces of an edge: W2's construction on the projected corners, with the query at the origin.
+ *       For the directed edge u -> v let (u', v') be the two endpoints ordered lexicographically by (x', y'):
+ *       E = (v'_y - u'_y) u'_x - (v'_x - u'_x) u'_y  (W2's E with p = 0);  s = sign(E); if 0, s = sign(-(v'_y - u'_y)); if still 0,
+ *       s = sign(v'_x - u'_x); if still 0, s = 0.  s AND E are negated if the endpoints were swapped.  This takes the ray through
+ *       (e, e^2) of its own (x', y') plane with e -> 0+.  A shared vertex gives identical (x', y', z') in both faces, because the inputs
+ *       and the operations are the same; so both faces of an edge evaluate the same expression, and a ray through a shared edge or
+ *       vertex of a closed mesh crosses exactly one of the faces around it.
+ *   R3. Crossing.  The ray's line crosses face (a, b, c) iff  s(a -> b) = s(b -> c) = s(c -> a) = sigma != 0.  A face seen edge-on or
+ *       without area never counts.  sigma = -1 is FRONT-facing: the projection is clockwise seen against the ray, d . n < 0 with n =
+ *       (b - a) x (c - a), the ray enters through the face.  sigma = +1 is back-facing: d . n > 0, the ray leaves through it (W3's
+ *       sigma for d = +z).
+ *   R4. Depth and weights.  U = E(b -> c), V = E(c -> a), W = E(a -> b), the values of the edges opposite a, b and c;  det = (U + V) +
+ *       W;  t = ((U z'_a + V z'_b) + W z'_c) / det: the one division of a face, made after R3.  The weights of (a, b, c) are (U, V, W) /
+ *       det, rounded to fp32.  The hit counts iff t_min < t < t_max, both strict (fp32 bounds, widened; t_max = +inf is allowed; a NaN
+ *       t or bound never counts).  So a ray that starts on a face does not hit that face at t_min = 0: W4's "on the plane is not ahead".
+ *   R5. The answers are the brute-force ones over ALL faces of the ray's object.  First hit: the counting face with the smallest t,
+ *       ties to the lowest face index; face (int32, object-local, -1 for none), t (float64, +inf for none), weights (fp32, 0 for none),
+ *       side (int8: +1 front, -1 back, 0 none).  cull = 0 keeps all faces, 1 drops back-facing faces, 2 drops front-facing faces,
+ *       before the minimum is taken.  Crossings: signed (int32) = the sum of sigma over the counting faces (+1 where the ray leaves, -1
+ *       where it enters), total (int32) = their number.  For a closed mesh wound as the iso rules wind it, signed of a ray to infinity
+ *       is the winding number of its origin, in any direction, for an origin off the surface.  A face with an index outside [0, V) is
+ *       skipped and sets *bad; a face with a vertex coordinate that is not finite is skipped; every ray of an object without a usable
+ *       grid (D3; *bad) gets no hit and zero crossings: the treatment of D2 and W5.
+ *   R6. Pruning, which may never change R5's answer.  With lo, hi and E the object's bounds and largest extent (D3) and m = the largest
+ *       over the axes of lo_a - o_a, o_a - hi_a and 0, the slack is  s = 2^-40 (E + m)  and, as a parameter,  s_t = s / |d[kz]|.
+ *       Clip:  [t_a, t_b] = [t_min, t_max] cut per axis with d_a != 0 to the parameters of lo_a - s and hi_a + s; an axis with d_a = 0
+ *       and o_a outside [lo_a - s, hi_a + s], or t_a > t_b: the ray visits no cell.  Walk: slab k of cells along kz, from the cell of
+ *       o[kz] + t_a d[kz] to that of o[kz] + t_b d[kz].  Its parameters: t_n, t_f of its near and far plane lo[kz] + k h; the interval
+ *       [max(t_a, t_n - s_t), min(t_b, t_f + s_t)], with t_a for the first and t_b for the last slab (border cells reach outwards
+ *       without end), and for the first hit cut at best t + s_t.  The other two coordinates at the interval's two ends span their
+ *       range over it, the ray being linear; widened by s and taken through the cell function it gives the rectangle [i0, i1] x
+ *       [j0, j1] of cells, kx outer, both ascending; kz is the dominant axis, so it is 2 x 2 cells at most but for the slack.  Every
+ *       listed face of every cell of it is tested (again, if listed in several: harmless for the minimum).  First hit: stop after a
+ *       slab once best t < t_f - s_t.  Crossings: a face counts ONCE, in slab  clamp(clamp(c_kz(o[kz] + t d[kz]), c_kz(min), c_kz(max)),
+ *       the walk's slabs)  -- the slab of its hit, kept within the slabs that list the face -- and there in cell (max(i0, c_kx(min)),
+ *       max(j0, c_ky(min))), the first cell of the rectangle that lists it (min, max: the face's corner extremes; c: D3's cell
+ *       function, the one the lists were built with; W5's max(c_z(min z), c_z(p)) is the model).
+ *       Why this cannot change the result: with lambda = (U, V, W) / det -- all of one sign, so a convex combination, whatever the
+ *       roundings -- t is the combination of the z'_i, the ray's parameters of the corners' kz coordinates, and the hit point o + t d
+ *       is the combination of the corners up to the roundings of R1's x', y' (a few 2^-53 of |v - o| <= E + m) and of U, V, W (a few
+ *       2^-53 of the squared size of the projected face, over det).  So the hit point lies in the face's bounding box up to those, the
+ *       box lies within the bounds, and a ray that misses the widened bounds has no hit; the cell function is monotone and a face is
+ *       listed in every cell of the index box of its corner cells, so the cell of a point within s of the box lies within that index
+ *       box when the point's coordinates are widened by s: the slab that holds parameter t visits a cell that lists the face.  A face
+ *       not yet met when the first walk stops has its hit beyond the far plane less the slack, so a larger t; one that ties is within
+ *       best t + s_t and is still met.  The slack is 2^12 times the roundings of well-conditioned faces and 2^-16 of the fp32
+ *       resolution of the inputs.  The division by det is the one place where rounding can grow: a face as large as the whole object
+ *       seen at less than 2^-9 rad from edge-on can exceed the slack; the rules give such a face the t of R4 in the brute force, and
+ *       the walk may then differ.  Extracted meshes have faces of a cell of the lattice, where the bound is 2^-9 rad times face size
+ *       over E.
+ *
+ * snr_raycast_first: face (sum N) int32, t (sum N) float64, weights (sum N, 3) fp32 and side (sum N) int8 by R1 - R6.
+ * snr_raycast_crossings: signed_count and total (sum N) int32 by R1 - R6.
+ * Both take the mesh and the grid arrays exactly as snr_nearest_query takes them, run one thread per ray and find the object of a ray
+ * once; every index read from a list is range-checked before use (a cell_start pair or a listed face out of range adds nothing); every
+ * output entry is written.  Nothing is allocated, nothing is read back, the caller's stream is used; no atomics except the *bad flag
+ * (device int32, zeroed by the caller).  A null pointer, a negative size or a cull outside {0, 1, 2}: SNR_E_ARG; more than 2^38 vertices,
+ * faces, rays, cells or pairs: SNR_E_UNSUPPORTED.  Zero rays: SNR_OK without a launch.  With zero faces and zero pairs the mesh and list
+ * pointers may be null. */
+int snr_raycast_first(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset, const float* rays_o,
+                      const float* rays_d, const int64_t* ray_offset, const float* t_min, const float* t_max, const float* cell,
+                      const float* grid_lo, const float* grid_hi, const int64_t* cell_offset, const int64_t* cell_start,
+                      const int32_t* pair_face, int64_t n_objects, int64_t n_verts, int64_t n_faces, int64_t n_rays, int64_t n_cells,
+                      int64_t n_pairs, int cull, int32_t* face, double* t, float* weights, int8_t* side, int32_t* bad, void* stream);
+int snr_raycast_crossings(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* face_offset,
+                          const float* rays_o, const float* rays_d, const int64_t* ray_offset, const float* t_min, const float* t_max,
+                          const float* cell, const float* grid_lo, const float* grid_hi, const int64_t* cell_offset,
+                          const int64_t* cell_start, const int32_t* pair_face, int64_t n_objects, int64_t n_verts, int64_t n_faces,
+                          int64_t n_rays, int64_t n_cells, int64_t n_pairs, int32_t* signed_count, int32_t* total, int32_t* bad,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Several views of one instance share one shape and one texture code (src/optimizer_nuscenes.py:796-1277): V rendered views, I <= V code

@@ -132,6 +132,8 @@ _SIGS = {
                                    _P, _P, _P]),
     "snr_inside_lattice": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                      C.c_int64, C.c_int64, _P, _P, _P]),
+    "snr_raycast_first": (C.c_int, [_P] * 15 + [C.c_int64] * 6 + [C.c_int, _P, _P, _P, _P, _P, _P]),
+    "snr_raycast_crossings": (C.c_int, [_P] * 15 + [C.c_int64] * 6 + [_P, _P, _P, _P]),
     "snr_smooth_edge_keys": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "snr_smooth_vertex_flags": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "snr_smooth_step": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_double, _P, _P]),

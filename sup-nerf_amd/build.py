@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsupnerf_hip.so")
 STAMP = os.path.join(HERE, ".libsupnerf_hip.stamp")
-SOURCES = ["snr_aux.hip", "snr_loss.hip", "snr_loop.hip", "snr_wgrad.hip", "snr_mlp.hip", "snr_mlp16.hip", "snr_mlp16_bwd.hip", "snr_mlp_bwd.hip", "snr_bf16.hip", "snr_decoder.hip", "snr_iso.hip", "snr_band.hip", "snr_iso_grad.hip", "snr_ray.hip", "snr_mesh.hip", "snr_simplify.hip", "snr_nearest.hip", "snr_inside.hip", "snr_smooth.hip", "snr_raster.hip", "snr_paint.hip", "snr_scene_bwd.hip", "snr_scene_rows.hip", "snr_views.hip", "snr_cross.hip"]
+SOURCES = ["snr_aux.hip", "snr_loss.hip", "snr_loop.hip", "snr_wgrad.hip", "snr_mlp.hip", "snr_mlp16.hip", "snr_mlp16_bwd.hip", "snr_mlp_bwd.hip", "snr_bf16.hip", "snr_decoder.hip", "snr_iso.hip", "snr_band.hip", "snr_iso_grad.hip", "snr_ray.hip", "snr_mesh.hip", "snr_simplify.hip", "snr_nearest.hip", "snr_inside.hip", "snr_raycast.hip", "snr_smooth.hip", "snr_raster.hip", "snr_paint.hip", "snr_scene_bwd.hip", "snr_scene_rows.hip", "snr_views.hip", "snr_cross.hip"]
 HEADERS = ["snr_layout.h", "snr_device.hpp", "snr_host.hpp", "snr_mlp_core.hpp", "snr_mlp16_core.hpp", "snr_grid.hpp", "snr_packed_mesh.hpp", "snr_nearest_grid.hpp", "snr_scene_merge.hpp", os.path.join("..", "..", "include", "supnerf_hip.h")]
 EXPORTS = "exports.map"        # linker version script: the library exports the C ABI (snr_*) and no other symbol
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -53,6 +53,13 @@ After an optimisation or a training run a caller holds one 256-float shape code 
     sign, one index for both searches; ``voxelize(meshes, resolution, bound)``: the occupancy of a mesh on the lattice ``density_grid``
     uses (``snr_inside_lattice``); ``occupancy_iou(a, b)`` and ``mesh_iou(a, b, resolution)``: the volumetric intersection over union
     of two occupancy grids or two meshes, with exact counts (rules restated in tests/inside_restatement.py);
+  * ``ray_mesh(meshes, rays_o, rays_d)``: where each ray hits its object's mesh first -- depth, face, barycentric weights, side, point
+    and normal (``MeshHits``), exact (the brute-force answer over all faces, pruned by the grid of ``mesh_index``;
+    ``ops.mesh_raycast_first``: ``snr_raycast_first``), with autograd to the rays and the vertices; ``ray_crossings(meshes, rays_o,
+    rays_d)``: the signed and the total number of faces a ray crosses (``snr_raycast_crossings``); ``visible(meshes, points, eye)``:
+    whether the segment from a point to an eye crosses no face; ``mesh_depth(mesh, cam_pose, obj_diag, K, roi)``: the mesh twin of
+    ``surface_depth``, metric depth on a camera grid or at listed pixels with autograd to the pose and the vertices (rules restated in
+    tests/raycast_restatement.py);
   * ``to_object_frame(verts, obj_diag, family)``: decoder coordinates back to the object's metric frame (``direction=True``: normals);
     ``to_decoder_frame``: its inverse;
   * ``write_ply(path, verts, faces, normals=None, colors=None)``: binary little-endian PLY (host code).
@@ -1609,6 +1616,196 @@ def surface_depth(model, cam_pose, obj_diag, K, roi, shapecode, *, level, im_sz=
     hits = ray_surface(model, o, d, near / scale, far / scale, shapecode, level=level, n_samples=n_samples, refine=refine)
     normal = to_object_frame(hits.normal, obj_diag, family, shapenet_obj_cood, kitti2nusc, direction=True)
     return RayHits((hits.depth * scale).view(shape), hits.state.view(shape), normal.view(*shape, 3), (hits.width * scale).view(shape))
+
+
+class MeshHits(NamedTuple):
+    t: torch.Tensor          # (N,) fp32: the ray parameter of the first hit (units of |rays_d|); +inf on a miss
+    face: torch.Tensor       # (N,) int32: the face that was hit, local to the object; -1 on a miss
+    weights: torch.Tensor    # (N, 3) fp32: the barycentric weights of the hit in that face; 0 on a miss
+    side: torch.Tensor       # (N,) int8: +1 the face was hit from its front (d . n < 0), -1 from its back, 0 on a miss
+    point: torch.Tensor      # (N, 3) fp32: rays_o + t rays_d; +inf on a miss
+    normal: torch.Tensor     # (N, 3) fp32: the unit geometric normal of the face; 0 on a miss
+
+
+RAY_CULL = {None: 0, "back": 1, "front": 2}
+
+
+def _ray_cull(cull):
+    if cull not in RAY_CULL:
+        raise SnrError(f"cull is None, 'back' or 'front', got {cull!r}")
+    return RAY_CULL[cull]
+
+
+def _mesh_count(meshes):
+    """How many meshes the caller passed -- 1 for a single (verts, faces) pair -- before anything else about them is checked."""
+    single = isinstance(meshes, (tuple, list)) and len(meshes) == 2 and torch.is_tensor(meshes[0])
+    return 1 if single else len(meshes)
+
+
+def _per_object_rays(rays_o, rays_d, B, names=("rays_o", "rays_d")):
+    """Per-object lists of (N, 3) origins and directions: one tensor each with one mesh, else one per object."""
+    if torch.is_tensor(rays_o) != torch.is_tensor(rays_d):
+        raise SnrError(f"{names[0]} and {names[1]} are both tensors or both lists with one tensor per object")
+    if torch.is_tensor(rays_o):
+        if B != 1:
+            raise SnrError(f"rays are lists of (N, 3) tensors, one per object: {B} meshes")
+        rays_o, rays_d = [rays_o], [rays_d]
+    rays_o, rays_d = list(rays_o), list(rays_d)
+    if len(rays_o) != B or len(rays_d) != B:
+        raise SnrError(f"{B} meshes but {len(rays_o)} {names[0]} and {len(rays_d)} {names[1]} tensors")
+    for o, d in zip(rays_o, rays_d):
+        if o.dim() != 2 or o.shape[1] != 3 or tuple(d.shape) != tuple(o.shape):
+            raise SnrError(f"{names[0]} and {names[1]} are (N, 3) per object, got {tuple(o.shape)} and {tuple(d.shape)}")
+        _gpu(o, names[0]), _gpu(d, names[1])
+    return rays_o, rays_d
+
+
+def _ray_bounds(v, what, ns, dev):
+    """t_min / t_max packed over the objects (sum N,) fp32: a float or a 0-dim tensor for every ray, a (N,) tensor with one mesh, or a
+    list with one of those per object."""
+    per = list(v) if isinstance(v, (list, tuple)) else [v] * len(ns)
+    if len(per) != len(ns):
+        raise SnrError(f"{what}: {len(ns)} meshes but {len(per)} values")
+    parts = [_ray_bound(x, what, (n,), dev) for x, n in zip(per, ns)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def _ray_cast(ms, os_, ds, t_min, t_max, index, cull=None):
+    """The packed kernel call of ``ray_mesh`` / ``visible`` (``cull`` a number) or of ``ray_crossings`` (``cull=None``), cut per object."""
+    ns = [o.shape[0] for o in os_]
+    dev = os_[0].device
+    o = os_[0] if len(os_) == 1 else torch.cat([x.detach().float() for x in os_])
+    d = ds[0] if len(ds) == 1 else torch.cat([x.detach().float() for x in ds])
+    lo, hi = _ray_bounds(t_min, "t_min", ns, dev), _ray_bounds(t_max, "t_max", ns, dev)
+    if cull is None:
+        out = ops.mesh_raycast_crossings(index.mesh, index.grid, o, d, lo, hi, ns)
+    else:
+        out = ops.mesh_raycast_first(index.mesh, index.grid, o, d, lo, hi, ns, cull)
+    return [tuple(x[q] for x in out) for (q,) in _object_slices(ns)]
+
+
+def ray_mesh(meshes, rays_o, rays_d, *, t_min=0.0, t_max=float("inf"), cull=None, index=None, face_forward=False):
+    """Where each ray rays_o + t rays_d hits its object's mesh first, t_min < t < t_max: ``meshes`` is the list ``extract_mesh`` returns
+    with ``rays_o`` and ``rays_d`` lists of (N, 3) tensors, one per object, or one (verts, faces) pair with one tensor each.  The rays
+    need not start at a camera and ``rays_d`` need not be unit (t is in units of |rays_d|).  ``t_min`` / ``t_max``: floats, 0-dim tensors
+    or per-ray (N,) tensors (with several meshes also a list, one entry per object).  ``cull``: None, "back" (faces seen from behind are
+    passed through) or "front".  ``index``: what ``mesh_index`` returned for these meshes.  Returns one ``MeshHits(t, face, weights, side,
+    point, normal)`` per object (a single one for a single pair).
+
+    The answer is exact: over all faces of the object the watertight ray/triangle test of Woop, Benthin and Wald in float64, the
+    smallest t, ties to the lowest face index (include/supnerf_hip.h, "Mesh ray casting", R1 - R6; ``snr_raycast_first``); the grid only
+    prunes, bit for bit.  A ray through a shared edge or vertex hits exactly one of the faces around it; a ray that starts on a face
+    does not hit that face at ``t_min = 0``.  ``normal`` is the unit geometric normal (b - a) x (c - a) of the hit face, turned to face
+    the ray only with ``face_forward=True``.  Face, weights and side are constants of the graph.  When grad mode is on and ``rays_o``,
+    ``rays_d`` or the vertices require grad, ``t`` is formed again in torch from the chosen face as n . (a - o) / (n . d), so autograd
+    reaches the rays and the vertices (those of ``extract_mesh(..., differentiable=True)`` carry it on to the shape codes); misses get
+    exactly zero.  Otherwise ``t`` is the kernel's float64 value rounded once to fp32.  A mesh cut open by the border of the grid is cast
+    as it is: a ray through the opening hits what lies behind it or nothing, and ``side`` = -1 tells a hit from inside.  A ray with a
+    non-finite component or a zero direction, and any ray of a mesh without faces, misses.  CPU tensors raise ``SnrError``."""
+    c = _ray_cull(cull)
+    os_, ds = _per_object_rays(rays_o, rays_d, _mesh_count(meshes))
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    index = _index_for(ms, index)
+    out = []
+    for (v, f), o, d, (fa, t64, w, side) in zip(ms, os_, ds, _ray_cast(ms, os_, ds, t_min, t_max, index, c)):
+        hit = fa >= 0
+        live = torch.is_grad_enabled() and (o.requires_grad or d.requires_grad or v.requires_grad)
+        o, d = o.float(), d.float()
+        if f.shape[0] and v.shape[0]:
+            a, b, cc = v.float()[f.long()[fa.clamp(min=0).long()]].unbind(1)
+            n = torch.linalg.cross(b - a, cc - a)
+        else:
+            a = n = torch.zeros_like(o)
+        if live:
+            nd = torch.where(hit, (n * d).sum(1), torch.ones_like(t64, dtype=torch.float32))
+            t = torch.where(hit, (n * (a - o)).sum(1) / nd, torch.full_like(nd, float("inf")))
+        else:
+            t = t64.float()
+        inf3 = torch.full_like(o, float("inf"))
+        point = torch.where(hit[:, None], o + torch.where(hit, t, torch.zeros_like(t))[:, None] * d, inf3)
+        normal = torch.nn.functional.normalize(n, dim=1)
+        if face_forward:
+            normal = torch.where((side < 0)[:, None], -normal, normal)
+        normal = torch.where(hit[:, None], normal, torch.zeros_like(normal))
+        out.append(MeshHits(t, fa, w, side, point, normal))
+    return out[0] if single else out
+
+
+def ray_crossings(meshes, rays_o, rays_d, *, t_min=0.0, t_max=float("inf"), index=None):
+    """The faces each ray rays_o + t rays_d crosses with t_min < t < t_max: ``(signed, total)``, (N,) int32 each, per object (lists with
+    several meshes, as ``ray_mesh`` takes them).  ``signed`` counts +1 where the ray leaves through a face and -1 where it enters,
+    ``total`` counts both as 1.  For a closed mesh wound as ``extract_mesh`` winds it, ``signed`` of a ray to infinity is the winding
+    number of its origin, in any direction (``winding_number`` is the case +z); ``total`` is its parity check.  Exact as ``ray_mesh``
+    is (R1 - R6; ``snr_raycast_crossings``): a ray through a shared edge or vertex crosses exactly one of the faces around it.  A mesh
+    cut open by the border of the grid gets the counts of these rules and no more.  No autograd; CPU tensors raise ``SnrError``."""
+    os_, ds = _per_object_rays(rays_o, rays_d, _mesh_count(meshes))
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    out = _ray_cast(ms, os_, ds, t_min, t_max, _index_for(ms, index))
+    return out[0] if single else out
+
+
+def visible(meshes, points, eye, *, offset=0.0, index=None):
+    """Whether each point sees ``eye``: a (N,) bool tensor per object, true where no face of the object's mesh is crossed on the open
+    segment from the point to the eye.  ``points``: (N, 3) per object as ``closest_point`` takes them; ``eye``: (3,), or (N, 3) with one
+    row per point (with several meshes also a list, one entry per object).  It is one first-hit call of ``ray_mesh``'s kernel with
+    d = eye - p and t in (offset, 1): ``offset`` is in units of the segment's length (0.01 skips the first hundredth of the way) and
+    lifts the start off a noisy surface.  At ``offset = 0`` a point that lies on the surface -- a vertex, say -- is not hidden by its own
+    faces, because a ray that starts on a face does not hit that face (R4); a vertex on the silhouette is hidden or not by the edge rule
+    R2, the same from run to run.  No autograd; CPU tensors raise ``SnrError``."""
+    ms, single = _one_or_many(meshes)
+    if not ms:
+        return []
+    pts = _per_object_points(points, len(ms), single)
+    eyes = list(eye) if isinstance(eye, (list, tuple)) else [eye] * len(ms)
+    if len(eyes) != len(ms):
+        raise SnrError(f"{len(ms)} meshes but {len(eyes)} eyes")
+    ds = []
+    for p, e in zip(pts, eyes):
+        e = _gpu(e, "eye")
+        if tuple(e.shape) not in ((3,), tuple(p.shape)):
+            raise SnrError(f"eye is (3,) or one row per point {tuple(p.shape)}, got {tuple(e.shape)}")
+        ds.append((e.detach().float() - p.detach().float()).contiguous())
+    pts = [p.detach() for p in pts]
+    out = [r[0] < 0 for r in _ray_cast(ms, pts, ds, float(offset), 1.0, _index_for(ms, index), 0)]
+    return out[0] if single else out
+
+
+def mesh_depth(meshes, cam_pose, obj_diag, K, roi, *, im_sz=None, pixels=None, cull="back", family="a", shapenet_obj_cood=False,
+               kitti2nusc=False, index=None):
+    """One object's decoder-frame mesh (a (verts, faces) pair) as a camera sees it, in metric units: the mesh twin of ``surface_depth``.
+    ``ray_mesh`` on the very rays ``surface_depth`` casts -- ``utils.get_rays`` (a grid over ``roi``, ``im_sz`` x ``im_sz`` steps or one
+    per pixel) or ``utils.get_rays_specified`` (``pixels = (x_vec, y_vec)`` in image coordinates: lidar returns), taken to the decoder
+    frame with ``to_decoder_frame`` -- from the camera centre to infinity.  ``cam_pose``: the camera in the object's frame (3, 4), on
+    the GPU.  Returns ``(depth, hits)``: depth in metres along the unit view direction, +inf where the pixel sees no face, and
+    ``MeshHits`` with ``point`` and ``normal`` in the object's metric frame (``to_object_frame``), shaped (H, W[, 3]) for a grid and
+    (n[, 3]) for listed pixels.  Unlike ``mesh_view`` nothing is snapped to a pixel grid: the depth is that of the exact ray.  Gradients
+    reach ``cam_pose`` through the ray operators and the vertices through ``ray_mesh``."""
+    scale = _frame_scale(obj_diag, family)
+    _ray_cull(cull)
+    if _mesh_count(meshes) != 1 or not torch.is_tensor(meshes[0]):
+        raise SnrError("mesh_depth takes one (verts, faces) pair: the mesh of the object the camera pose belongs to")
+    ms, _ = _one_or_many(meshes)
+    _gpu(cam_pose, "cam_pose")
+    if pixels is not None:
+        rays_o, viewdir = U.get_rays_specified(K, cam_pose, pixels[0], pixels[1])
+        shape = (rays_o.shape[0],)
+    else:
+        steps = None if im_sz is None else [int(im_sz), int(im_sz)]
+        rays_o, viewdir = U.get_rays(K, cam_pose, roi, uv_steps=steps)
+        x0, y0, x1, y1 = [int(v) for v in roi]
+        shape = (int(im_sz), int(im_sz)) if im_sz is not None else (y1 - y0, x1 - x0)
+    o = to_decoder_frame(rays_o, obj_diag, family, shapenet_obj_cood, kitti2nusc).reshape(-1, 3)
+    d = to_decoder_frame(viewdir, obj_diag, family, shapenet_obj_cood, kitti2nusc, direction=True).reshape(-1, 3)
+    h = ray_mesh(ms[0], o, d, cull=cull, index=index)
+    point = to_object_frame(h.point, obj_diag, family, shapenet_obj_cood, kitti2nusc)
+    normal = to_object_frame(h.normal, obj_diag, family, shapenet_obj_cood, kitti2nusc, direction=True)
+    hits = MeshHits(h.t.view(shape), h.face.view(shape), h.weights.view(*shape, 3), h.side.view(shape), point.view(*shape, 3),
+                    normal.view(*shape, 3))
+    return (h.t * scale).view(shape), hits
 
 
 def quantize_colors(colors):

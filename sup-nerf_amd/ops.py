@@ -2014,6 +2014,62 @@ def mesh_inside_lattice(mesh: PackedMesh, index: NearestIndex, lat_lo, lat_h, n)
     return winding
 
 
+# ------------------------------------------------------------------------------------ mesh ray casting
+def _raycast_rays(mesh, index, rays_o, rays_d, t_min, t_max, n_rays, what):
+    """The leading arguments of the C calls of ``mesh_raycast_first`` / ``mesh_raycast_crossings`` from the checked ray arrays, the ray
+    count, and the dense arrays those pointers name (the caller holds them until its launch is enqueued)."""
+    _need_gpu(rays_o, rays_d, t_min, t_max)
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
+        raise SnrError(f"{what}: rays_o and rays_d are (sum N, 3), got {tuple(rays_o.shape)} and {tuple(rays_d.shape)}")
+    nR = rays_o.shape[0]
+    if tuple(t_min.shape) != (nR,) or tuple(t_max.shape) != (nR,):
+        raise SnrError(f"{what}: t_min and t_max are (sum N,), got {tuple(t_min.shape)} and {tuple(t_max.shape)} for {nR} rays")
+    m, g, (B, nV, nF) = _inside_args(mesh, index, what)
+    n_rays = _packed_counts(n_rays, B, nR, what)
+    rays = [_f32c(x.detach()) for x in (rays_o, rays_d, t_min, t_max)]
+    roff = _offsets(n_rays, rays_o.device)[1]
+    args = (*m, _ptr(rays[0]), _ptr(rays[1]), _ptr(roff, torch.int64), _ptr(rays[2]), _ptr(rays[3]), *g, B, nV, nF, nR, index.n_cells,
+            index.n_pairs)
+    return args, nR, (rays, roff)
+
+
+def mesh_raycast_first(mesh: PackedMesh, index: NearestIndex, rays_o, rays_d, t_min, t_max, n_rays, cull=0):
+    """(face (sum N,) int32, t (sum N,) float64, weights (sum N, 3) fp32, side (sum N,) int8): per ray o + t d the first face of ITS
+    object's mesh that it hits with t_min < t < t_max (object-local index, -1 for none; t = +inf for none), the barycentric weights of
+    the hit and the side it was hit from (+1 front, -1 back, 0 none), by ``snr_raycast_first`` (include/supnerf_hip.h, "Mesh ray casting",
+    R1 - R6: the brute-force answer bit for bit, whatever the grid).  ``rays_o`` and ``rays_d`` (sum N, 3) fp32 object after object,
+    ``t_min`` and ``t_max`` (sum N,) fp32, ``n_rays`` the N per object (a host list), ``index`` what ``mesh_nearest_index`` built over
+    ``mesh``; ``cull``: 0 none, 1 drops back-facing faces, 2 front-facing ones.  Nothing is read back."""
+    if cull not in (0, 1, 2):
+        raise SnrError(f"mesh_raycast_first: cull is 0 (none), 1 (back) or 2 (front), got {cull!r}")
+    dev = mesh.verts.device
+    with torch.cuda.device(dev):
+        args, nR, keep = _raycast_rays(mesh, index, rays_o, rays_d, t_min, t_max, n_rays, "mesh_raycast_first")
+        face = torch.empty(nR, dtype=torch.int32, device=dev)
+        t = torch.empty(nR, dtype=torch.float64, device=dev)
+        weights = torch.empty(nR, 3, device=dev)
+        side = torch.empty(nR, dtype=torch.int8, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        check(_lib.lib().snr_raycast_first(*args, int(cull), _ptr(face, torch.int32), _ptr(t, torch.float64), _ptr(weights),
+                                           _ptr(side, torch.int8), _ptr(bad, torch.int32), _stream(dev)), "snr_raycast_first")
+    return face, t, weights, side
+
+
+def mesh_raycast_crossings(mesh: PackedMesh, index: NearestIndex, rays_o, rays_d, t_min, t_max, n_rays):
+    """(signed (sum N,) int32, total (sum N,) int32): per ray the faces of ITS object's mesh that it crosses with t_min < t < t_max --
+    +1 where it leaves through the face, -1 where it enters, and their number -- by ``snr_raycast_crossings`` (R1 - R6: the brute-force
+    integers, whatever the grid).  The arguments are those of ``mesh_raycast_first``.  Nothing is read back."""
+    dev = mesh.verts.device
+    with torch.cuda.device(dev):
+        args, nR, keep = _raycast_rays(mesh, index, rays_o, rays_d, t_min, t_max, n_rays, "mesh_raycast_crossings")
+        signed = torch.empty(nR, dtype=torch.int32, device=dev)
+        total = torch.empty(nR, dtype=torch.int32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        check(_lib.lib().snr_raycast_crossings(*args, _ptr(signed, torch.int32), _ptr(total, torch.int32), _ptr(bad, torch.int32),
+                                               _stream(dev)), "snr_raycast_crossings")
+    return signed, total
+
+
 # ------------------------------------------------------------------------------------ mesh smoothing
 SMOOTH_KEY_BITS = 31            # snr_smooth_edge_keys: (global source index) << 31 | local target index
 SMOOTH_NO_KEY = 2 ** 63 - 1     # a discarded pair
